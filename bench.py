@@ -32,7 +32,15 @@ The JSON line also carries
   cpu_baseline   the CPU oracle (C port of the reference's easa.py) timed on this box's host cores on the
                  same 64 MiB document (one core) and over the documents of configs[2] (all cores)
 
-Launch:  python bench.py [--gpus N --steps K --warmup W]      (N > 1 without WORLD_SIZE in the environment: bench.py
+A plain run sets up, warms up, times the K steps and prints the line with the figures of the timed steps alone (value,
+ms_per_step, step/build/score times, the build's path; multi_gpu's step_local_ms / allgather_ms at N > 1).  Everything
+above that takes runs of its own -- the profiling pass and `roofline`, `roofline_score`, the first-build, host-resident and
+raw-text legs, the worst case, the config2 / config5 legs, `cpu_baseline`, the in-process leg at N > 1 and
+bench_detail.json -- is measured with --full (--full-line implies it).  --dump-outputs DIR writes what the timed path
+computed in its last step (the score table, samples of the index tables), see dump_outputs().
+
+Launch:  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
+                                                              (N > 1 without WORLD_SIZE in the environment: bench.py
                                                                starts its N ranks itself, as child processes)
          python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
@@ -76,12 +84,20 @@ def parse():
                          "then carries multi_gpu.scaling_efficiency = value / (N x base)")
     ap.add_argument("--full-line", action="store_true",
                     help="print the whole record (what bench_detail.json holds) as the last line instead of the driver's compact "
-                         "one: the A/B scripts under tools/ read per-kernel tables off it")
+                         "one: the A/B scripts under tools/ read per-kernel tables off it.  Implies --full")
     ap.add_argument("--no-in-process", action="store_true",
                     help="N > 1: skip the leg that runs the same shards through the in-process device group on rank 0")
     ap.add_argument("--cpu-sample-mib", type=float, default=64.0,
                     help="size of the CPU-baseline document (64 = the bench document itself, about 15 s of one core)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline: profiling pass and roofline, the other legs and "
+                         "configurations, the CPU baseline, bench_detail.json (the --no-* options trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    args.full = args.full or args.full_line
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))      # (never returns: the ranks are child processes)
     return args
@@ -325,22 +341,23 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    # Untimed profiling pass: EVERY kernel bracketed by HIP events on the library's stream -- the per-kernel
-    # breakdown and the name of the dominant kernel.  (Two events per launch cost the stream time, about 10 % of
-    # a 2 ms step with ~30 launches: that does not belong into the timed region.)
-    profile_steps = max(1, min(args.steps, 3))
-    index.profile_enable(True)
-    fence()
-    for _ in range(profile_steps):
-        step()
-    fence()
-    prof = index.profile_report()
-    index.profile_enable(False)
-    dom_name = max(prof.items(), key=lambda kv: kv[1][1])[0]
-    # Timed region: exactly args.steps steps; only the dominant kernel's launches are bracketed (its average
-    # launch duration, live, over the timed region -- `roofline`).
-    index.profile_only(dom_name)
-    index.profile_enable(True)
+    if args.full:
+        # Untimed profiling pass: EVERY kernel bracketed by HIP events on the library's stream -- the per-kernel
+        # breakdown and the name of the dominant kernel.  (Two events per launch cost the stream time, about 10 % of
+        # a 2 ms step with ~30 launches: that does not belong into the timed region.)
+        profile_steps = max(1, min(args.steps, 3))
+        index.profile_enable(True)
+        fence()
+        for _ in range(profile_steps):
+            step()
+        fence()
+        prof = index.profile_report()
+        index.profile_enable(False)
+        dom_name = max(prof.items(), key=lambda kv: kv[1][1])[0]
+        # Timed region: exactly args.steps steps; only the dominant kernel's launches are bracketed (its average
+        # launch duration, live, over the timed region -- `roofline`).
+        index.profile_only(dom_name)
+        index.profile_enable(True)
     build_ms, score_ms = [], []
     fence()
     local_s[0] = 0.0
@@ -355,9 +372,13 @@ def main():
         score_ms.append(index.last_score_ms)
     fence()
     elapsed = time.perf_counter() - t0
-    prof_timed = index.profile_report()
-    index.profile_enable(False)
-    index.profile_only(None)
+    if args.full:
+        prof_timed = index.profile_report()
+        index.profile_enable(False)
+        index.profile_only(None)
+    if rank == 0 and args.dump_outputs:
+        # (before anything else runs on the index: the arrays of the last timed step)
+        dump_outputs(args.dump_outputs, index, full_table if use_dist else local_block, D)
     step_local_ms = local_s[0] * 1e3 / args.steps
     allgather_ms = sum(a.elapsed_time(b) for a, b in gather_events) / args.steps if gather_events else 0.0
     rccl_world = None
@@ -372,28 +393,6 @@ def main():
         ms_per_step = elapsed * 1e3 / args.steps
         value = world * n_bytes / (elapsed / args.steps)
         default_shape = (D, doc_mib, K, args.mode, args.corpus) == (1, 64.0, 1000, "text", "words") and not args.duplicate_docs
-        zipf_shape = (D, doc_mib, K, args.mode, args.corpus) == (100, 1.0, 1000, "text", "zipf") and not args.duplicate_docs
-        config2_shape = (D, doc_mib, K, args.mode, args.corpus) == (256, 1.0, 10000, "text", "words") and not args.duplicate_docs
-        # (the counters were collected on these workloads: tools/profile_round.sh, profile_zipf.sh, profile_config2.sh)
-        traffic_file = ("traffic.json" if default_shape else "traffic_zipf.json" if zipf_shape else
-                        "traffic_config2.json" if config2_shape else None)
-        traffic_meta = {}
-        traffic = load_traffic(traffic_file, traffic_meta) if traffic_file else {}
-        roofline, by_kernel, per_step = roofline_of(prof, info, n, D, profile_steps, traffic)
-        live = prof_timed.get(dom_name)
-        if live and live[0]:                             # the dominant kernel as measured inside the timed region
-            roofline["launches_per_step"] = live[0] // args.steps
-            roofline["avg_launch_ms"] = live[1] / live[0]
-            b = kernel_bytes(dom_name, info, n, D)
-            if b is not None:
-                roofline["achieved"] = b * args.steps / (live[1] * 1e-3) / 1e9
-                roofline["frac"] = roofline["achieved"] / HBM_PEAK_GBS
-            roofline["avg_launch_ms_profiling_pass"] = prof[dom_name][1] / prof[dom_name][0]
-        roofline["rocprof_hbm_fraction"] = hbm_fraction(prof, traffic)
-        roofline["traffic_commit"] = traffic_meta.get("commit")
-        roofline["traffic_source"] = ("profiles/%s: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of an earlier run of this "
-                                      "workload (tools/profile_*.sh + summarize_profiles.py), committed with the code -- not "
-                                      "measured by this run" % traffic_file) if traffic_file else None
         out = {
             "metric": "corpus chars/sec (SA+annotation build + keyphrase score table)",
             "value": value, "unit": "chars/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -417,12 +416,36 @@ def main():
             "dc3_levels": info["dc3_levels"], "dc3_levels_resolved": info["dc3_levels_resolved"],
             "dc3_refine_rounds": info["refine_rounds"], "window_sorted": info["window_sorted"],
             "radix_passes": info["radix_passes"], "variable_length_keys": info.get("ht_keys", 0), "segmented_sort": info.get("seg_sort", 0),
-            "roofline": roofline, "roofline_by_kernel": by_kernel, "kernels_ms_per_step": per_step,
-            "kernel_launches_per_step": {k: v[0] // profile_steps for k, v in sorted(prof.items(), key=lambda kv: -kv[1][1])},
-            "profiling_pass": "%d untimed step(s) with every kernel bracketed: roofline_by_kernel, kernels_ms_per_step, "
-                              "rocprof_hbm_fraction; the timed steps bracket the dominant kernel only" % profile_steps,
             "lds_sorted": info.get("lds_sorted", 0),
         }
+        if args.full:
+            zipf_shape = (D, doc_mib, K, args.mode, args.corpus) == (100, 1.0, 1000, "text", "zipf") and not args.duplicate_docs
+            config2_shape = (D, doc_mib, K, args.mode, args.corpus) == (256, 1.0, 10000, "text", "words") and not args.duplicate_docs
+            # (the counters were collected on these workloads: tools/profile_round.sh, profile_zipf.sh, profile_config2.sh)
+            traffic_file = ("traffic.json" if default_shape else "traffic_zipf.json" if zipf_shape else
+                            "traffic_config2.json" if config2_shape else None)
+            traffic_meta = {}
+            traffic = load_traffic(traffic_file, traffic_meta) if traffic_file else {}
+            roofline, by_kernel, per_step = roofline_of(prof, info, n, D, profile_steps, traffic)
+            live = prof_timed.get(dom_name)
+            if live and live[0]:                             # the dominant kernel as measured inside the timed region
+                roofline["launches_per_step"] = live[0] // args.steps
+                roofline["avg_launch_ms"] = live[1] / live[0]
+                b = kernel_bytes(dom_name, info, n, D)
+                if b is not None:
+                    roofline["achieved"] = b * args.steps / (live[1] * 1e-3) / 1e9
+                    roofline["frac"] = roofline["achieved"] / HBM_PEAK_GBS
+                roofline["avg_launch_ms_profiling_pass"] = prof[dom_name][1] / prof[dom_name][0]
+            roofline["rocprof_hbm_fraction"] = hbm_fraction(prof, traffic)
+            roofline["traffic_commit"] = traffic_meta.get("commit")
+            roofline["traffic_source"] = ("profiles/%s: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of an earlier run of this "
+                                          "workload (tools/profile_*.sh + summarize_profiles.py), committed with the code -- not "
+                                          "measured by this run" % traffic_file) if traffic_file else None
+            out.update({
+                "roofline": roofline, "roofline_by_kernel": by_kernel, "kernels_ms_per_step": per_step,
+                "kernel_launches_per_step": {k: v[0] // profile_steps for k, v in sorted(prof.items(), key=lambda kv: -kv[1][1])},
+                "profiling_pass": "%d untimed step(s) with every kernel bracketed: roofline_by_kernel, kernels_ms_per_step, "
+                                  "rocprof_hbm_fraction; the timed steps bracket the dominant kernel only" % profile_steps})
         if use_dist:
             # Multi-GPU accounting (the driver computes scaling efficiency itself from `value` at N = 1, 2, 4, 8 -- the
             # same-shape N = 1 base of this line is the `config2` leg of the N = 1 line, see below): the rank-local
@@ -440,13 +463,13 @@ def main():
         else:
             out["scaling_base_note"] = ("--gpus N > 1 runs BASELINE configs[3]'s per-GPU shape (256 x 1 MiB documents, 10000 "
                                         "keyphrases per rank): its single-GPU base is this line's config2.value, not value")
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             out.update(first_build_leg(hip_backend, torch, local_rank, d_symbols, n, doc_offsets, n_strings, q_symbols,
                                        q_offsets, local_block, not args.denormalized, n_bytes))
         if world == 1:
             out["value_note"] = ("value = steady state: the timed steps rebuild the same collection on one handle (guesses "
                                  "from the build before always hold); value_first_build = a fresh handle's first build")
-        if not args.no_extras:
+        if args.full and not args.no_extras:
             out.update(extras(index, prof, args, symbols, doc_offsets, n_strings, q_offsets, K, D, d_symbols))
             if "child_tables_ms" in out:
                 # the reference's constructor also fills the child tables (easa.py:16-24); here they are built on first request
@@ -458,7 +481,7 @@ def main():
             out["value_from_host"] = n_bytes / (host_step_ms * 1e-3)
             out["value_from_host_note"] = ("input bytes / (east_hip_build wall -- the median of twelve calls, the upload from pageable "
                                            "memory included -- + score call); value itself starts from symbols resident in HBM")
-        if world == 1 and not args.no_config2 and default_shape:
+        if args.full and world == 1 and not args.no_config2 and default_shape:
             out["from_text"] = from_text_leg(hip_backend, synthetic, local_rank)
             ft = out["from_text"].get("ascii_64MiB")
             if ft:
@@ -469,9 +492,9 @@ def main():
             out["config2"] = config2_leg(args, hip_backend, synthetic, torch, dev, local_rank)
             out["config5"] = config5_leg(args, hip_backend, synthetic, torch, dev, local_rank)
             out["config5_prose"] = config5_prose_leg(hip_backend, synthetic, torch, dev, local_rank)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, synthetic)
-    if use_dist and not args.no_in_process:
+    if args.full and use_dist and not args.no_in_process:
         # The path `east -g N` takes by default is not the one timed above (one process per GPU, torch.distributed) but the
         # library's in-process group: one host thread per device, ncclCommInitAll, one grouped ncclAllGather (csrc/multi.h).
         # Every rank gives its device memory back and waits on a CPU-side (gloo) barrier -- an NCCL barrier would keep a
@@ -507,7 +530,7 @@ def main():
         except OSError:
             pass
         sys.stdout.flush()
-        detail_path = write_detail(out)
+        detail_path = write_detail(out) if args.full else None
         print(json.dumps(out) if args.full_line else compact_line(out, detail_path), flush=True)
 
 
@@ -566,16 +589,17 @@ def compact_line(out, detail_path=None):
     line["vs_baseline"] = out.get("vs_baseline")
     line.update(_pick(out, ("dtype", "data", "config", "step_ms_min", "step_ms_median", "step_ms_max", "build_ms", "score_ms",
                             "keyphrase_scores_per_s")))
-    roof = out.get("roofline") or {}
-    r = _pick(roof, ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "launches_per_step", "avg_launch_ms",
-                     "algorithmic_bytes_per_launch", "share_of_kernel_time", "traffic_commit"))
-    if "traffic" not in r:
-        r["traffic"] = None
-    if isinstance(roof.get("next"), dict):
-        r["next"] = _pick(roof["next"], ("kernel", "launches_per_step", "avg_launch_ms", "achieved", "frac", "traffic"))
-    if isinstance(roof.get("rocprof_hbm_fraction"), dict):
-        r["rocprof_hbm_fraction"] = _pick(roof["rocprof_hbm_fraction"], ("GBps", "frac", "kernels"))
-    line["roofline"] = r
+    roof = out.get("roofline")
+    if isinstance(roof, dict):                           # (a --full run)
+        r = _pick(roof, ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "launches_per_step", "avg_launch_ms",
+                         "algorithmic_bytes_per_launch", "share_of_kernel_time", "traffic_commit"))
+        if "traffic" not in r:
+            r["traffic"] = None
+        if isinstance(roof.get("next"), dict):
+            r["next"] = _pick(roof["next"], ("kernel", "launches_per_step", "avg_launch_ms", "achieved", "frac", "traffic"))
+        if isinstance(roof.get("rocprof_hbm_fraction"), dict):
+            r["rocprof_hbm_fraction"] = _pick(roof["rocprof_hbm_fraction"], ("GBps", "frac", "kernels"))
+        line["roofline"] = r
     if isinstance(out.get("roofline_score"), dict):
         line["roofline_score"] = _pick(out["roofline_score"], ("kernel", "avg_launch_ms", "algorithmic_bytes_per_launch",
                                                                "achieved", "frac"))
@@ -639,6 +663,33 @@ def write_detail(out):
         except OSError:
             pass
     return written
+
+
+DUMP_SCORE_ENTRIES = 1 << 21          # --dump-outputs: the score table whole up to 16 MB, else a sample of this many scores
+DUMP_TABLE_ENTRIES = 1 << 19          # ... and of each index table per dumped document (3 tables x 3 documents: 36 MB)
+
+
+def _sample(a, limit, seed):
+    """`a` whole (and in its shape) if it has at most `limit` entries, else the entries of the flattened array at up to
+    `limit` sorted, distinct positions drawn with a fixed seed: the same positions for the same shape on every run."""
+    a = np.asarray(a)
+    if a.size <= limit:
+        return a
+    return a.reshape(-1)[np.unique(np.random.default_rng(seed).integers(0, a.size, size=limit))]
+
+
+def dump_outputs(path, index, table, n_docs):
+    """--dump-outputs DIR: what the timed path computed in its last step, as float64 .npy files (64 MB at most), for
+    comparing two builds output for output.  scores.npy: the K x D table of the step (at N > 1 the all-gathered one);
+    suftab / lcptab / anntab.npy: the index tables of the first, the middle and the last document, one after the other
+    (document-local positions; a document of more than DUMP_TABLE_ENTRIES symbols contributes a seeded sample)."""
+    os.makedirs(path, exist_ok=True)
+    scores = table.cpu().numpy()
+    np.save(os.path.join(path, "scores.npy"), _sample(scores, DUMP_SCORE_ENTRIES, 20240).astype(np.float64))
+    docs = sorted({0, n_docs // 2, n_docs - 1})
+    for k, name in enumerate(("suftab", "lcptab", "anntab")):
+        parts = [_sample(index.tables(d, names=(name,))[name], DUMP_TABLE_ENTRIES, 20240 + 16 * d + k) for d in docs]
+        np.save(os.path.join(path, name + ".npy"), np.concatenate(parts).astype(np.float64))
 
 
 def in_process_child(args, world, D, doc_mib, K, limit_s=600):

@@ -21,8 +21,11 @@ Files written (tests/golden/):
                         plane letter): tables + scores of strings collections, and a keyphrase table over raw texts
   traversal_synonyms.json  pre-/post-order lcp-interval traversals (easa.py:38-85) and synonym-expanded
                         scores (easa.py:27-34, relevance.py:51-53, applications.py:43-52) with a stub synonimizer
+  reference_fuzz.json.gz  the differential fuzz (gzip): 595 random small collections, every table, easa scores with suffix
+                        scores and the ast_linear score per query
 """
 import glob
+import gzip
 import json
 import os
 import random
@@ -418,6 +421,45 @@ def gen_high_text():
     write("high_text.json", {"cases": cases, "table": d})
 
 
+def gen_reference_fuzz(seed=77, iters=120):
+    """The differential fuzz of tests/test_oracle_vs_reference.py, recorded: random small collections over five
+    alphabets (the same draws, in the same order, as the live comparison the test once ran), each with its string, every
+    table and, per query, the easa scores with their suffix scores and the ast_linear score, normalized and denormalized."""
+    rng = random.Random(seed)
+    cases = []
+    for alpha in ["AB", "ABC", "ABCDEFGH", "AB C", "ABCDEFGHIJKLMNOPQRSTUVWXYZ"]:
+        for _ in range(iters):
+            m = rng.randint(1, 6)
+            strings = ["".join(rng.choice(alpha) for _ in range(rng.randint(0, 12))) for _ in range(m)]
+            if sum(map(len, strings)) + m < 2:
+                continue
+            ref = base.AST.get_ast(strings, "easa")
+            lin = base.AST.get_ast(strings, "ast_linear")
+            d = {"strings": strings, "string": [ord(c) for c in ref.string]}
+            for name in ["suftab", "lcptab", "childtab_up", "childtab_down", "childtab_next_l_index", "anntab"]:
+                d[name] = ints(getattr(ref, name))
+            d["queries"] = []
+            for _ in range(4):
+                q = "".join(rng.choice(alpha + "Z") for _ in range(rng.randint(1, 10)))
+                qq = q.replace(" ", "")
+                if not qq:
+                    continue
+                rec = {"query": q, "score": [], "linear": [], "suffix": []}
+                for norm in (True, False):
+                    r = ref.score(q, normalized=norm, return_suffix_scores=True)
+                    assert sorted(r[1]) == sorted(qq[i:] for i in range(len(qq))), (strings, q)
+                    rec["score"].append(float(r[0]))
+                    rec["linear"].append(float(lin.score(q, normalized=norm)))
+                    rec["suffix"].append([float(r[1][qq[i:]]) for i in range(len(qq))])
+                d["queries"].append(rec)
+            cases.append(d)
+    path = os.path.join(OUT, "reference_fuzz.json.gz")
+    text = json.dumps({"seed": seed, "iters": iters, "cases": cases}, ensure_ascii=False, separators=(",", ":")) + "\n"
+    with open(path, "wb") as f:                         # (gzip, mtime 0: the same bytes on every run)
+        f.write(gzip.compress(text.encode("utf-8"), mtime=0))
+    print("wrote", path, os.path.getsize(path), "bytes")
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     gen_readme()
@@ -430,3 +472,4 @@ if __name__ == "__main__":
     gen_prose_like()
     gen_traversal_synonyms()
     gen_high_text()
+    gen_reference_fuzz()

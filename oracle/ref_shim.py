@@ -7,10 +7,8 @@ disk: sources are read in place, refactored in memory and exec'd.
 
 This module only works in the build container (where /root/reference is
 mounted).  It is used by
-  * oracle/gen_golden.py      -- to generate tests/golden/*.json
-  * tests/test_oracle_vs_reference.py (auto-skipped when the reference is
-    absent, e.g. on the GPU box)
-and by nothing else.  The product package never imports it.
+  * oracle/gen_golden.py      -- to generate the fixtures under tests/golden/
+and by nothing else (the tests read those fixtures only).  The product package never imports it.
 """
 import importlib.abc
 import importlib.machinery

@@ -54,8 +54,10 @@ def test_bench_distributed_line_on_one_gpu(tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", EAST_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1",
                MASTER_PORT=str(29700 + os.getpid() % 200), RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
     env.pop("EAST_HIP_DEVICE", None)
+    # (--full: the roofline and the in-process leg checked below are measured by a full run only)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--docs", "8",
-           "--doc-mib", "0.25", "--keyphrases", "200", "--no-cpu-baseline", "--no-extras", "--no-config2", "--base-value", "1e9"]
+           "--doc-mib", "0.25", "--keyphrases", "200", "--full", "--no-cpu-baseline", "--no-extras", "--no-config2",
+           "--base-value", "1e9"]
     done = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert done.returncode == 0, done.stderr.decode(errors="replace")[-4000:]
     line = [ln for ln in done.stdout.decode().splitlines() if ln.startswith("{")][-1]
@@ -76,6 +78,40 @@ def test_bench_distributed_line_on_one_gpu(tmp_path):
     assert ip["gather"] == "rccl" and ip["rccl_ranks"] == 1 and ip["shards"] == [8] and ip["step_ms"] > 0 and ip["value"] > 0
     assert out["config"]["all_gather_bytes_per_rank"] == 200 * 8 * 8
     assert out["roofline"]["kernel"] and out["roofline"]["peak"] == 8000.0
+
+
+@pytest.mark.parametrize("collective", [False, True])
+def test_bench_plain_run_dumps_its_last_step(tmp_path, collective):
+    """A plain bench.py run (no --full) times exactly --steps steps, prints the headline line without the legs of a full
+    run and, with --dump-outputs, writes the last step's score table (at N > 1: the all-gathered one; here the collective
+    path with a single rank) and the index tables of the first, middle and last document as float64 .npy files."""
+    import json
+    if _device_count() < 1:
+        pytest.skip("no GPU")
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    if collective:
+        env.update(EAST_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(29500 + os.getpid() % 200),
+                   RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
+    env.pop("EAST_HIP_DEVICE", None)
+    out_dir = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--docs", "8",
+           "--doc-mib", "0.25", "--keyphrases", "200", "--dump-outputs", str(out_dir)]
+    done = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert done.returncode == 0, done.stderr.decode(errors="replace")[-4000:]
+    out = json.loads(done.stdout.decode().splitlines()[-1])
+    assert out["steps"] == 4 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert all(k in out for k in ("metric", "unit", "higher_is_better", "dtype"))
+    assert not {"roofline", "cpu_baseline", "config2", "detail"} & set(out)
+    assert ("multi_gpu" in out) == collective and "in_process" not in out.get("multi_gpu", {})
+    scores = np.load(str(out_dir / "scores.npy"))
+    assert scores.dtype == np.float64 and scores.shape == (200, 8)
+    assert np.all(np.isfinite(scores)) and scores.min() >= 0 and scores.max() <= 1 and scores.max() > 0
+    n = out["config"]["symbols_per_gpu"]
+    tables = {name: np.load(str(out_dir / (name + ".npy"))) for name in ("suftab", "lcptab", "anntab")}
+    # three documents of about n / 8 symbols each, whole (below the sampling threshold)
+    assert all(t.dtype == np.float64 and t.shape == tables["suftab"].shape for t in tables.values())
+    assert 3 * (n // 8) * 0.9 < tables["suftab"].size < 3 * (n // 8) * 1.1
+    assert np.all(tables["suftab"] >= 0) and np.all(tables["suftab"] == np.round(tables["suftab"]))
 
 
 @pytest.mark.parametrize("world", [1, 2])

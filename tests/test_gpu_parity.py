@@ -1069,15 +1069,43 @@ def test_long_repeats_in_large_groups(hip, oracle, case):
             assert np.array_equal(t[name], getattr(o, name)), (name, d)
 
 
+# word-wise re-spellings of a-z in accented Latin, Greek and Cyrillic letters (all below the terminator base U+0A00)
+_RESPELL = [str.maketrans("abcdefghijklmnopqrstuvwxyz", t) for t in
+            ("\u00e1\u0180\u00e7\u0111\u00e9\u0192\u011f\u0125\u00ed\u0135\u0137\u0142m\u00f1\u00f3\u01a5q\u0155\u015f\u0163\u00fav\u0175x\u00fd\u017e",
+             "\u03b1\u03b2\u03c8\u03b4\u03b5\u03c6\u03b3\u03b7\u03b9\u03be\u03ba\u03bb\u03bc\u03bd\u03bf\u03c0\u03b8\u03c1\u03c3\u03c4\u03c5\u03c9\u03c2\u03c7\u03c5\u03b6",
+             "\u0430\u0431\u0446\u0434\u0435\u0444\u0433\u0445\u0438\u0439\u043a\u043b\u043c\u043d\u043e\u043f\u044f\u0440\u0441\u0442\u0443\u0436\u0432\u044c\u044b\u0437")]
+
+
+def _prose_stand_in(n_bytes, seed=31):
+    """Natural-language text of about n_bytes (UTF-8) for the real-prose cases, made from what the repository holds: the
+    order-3 character model of east/synthetic.py (English letter statistics, digits, punctuation, capitals), one word in
+    eight respelt in accented Latin, Greek or Cyrillic letters (a mixed alphabet of about a hundred symbols, as in
+    documentation written in many languages), and passages of a few KB that recur throughout (boilerplate repeated
+    across files).  The same bytes on every machine."""
+    from east import synthetic
+    rng = np.random.default_rng(seed)
+    words = b"".join(synthetic.prose_like_texts(rng, 8, n_bytes // 8)).decode("ascii").split(" ")
+    pick = rng.random(len(words))
+    for k, table in enumerate(_RESPELL):
+        for i in np.flatnonzero((pick >= k / 24.0) & (pick < (k + 1) / 24.0)):
+            words[i] = words[i].translate(table)
+    text = " ".join(words)
+    passages = [text[int(s):int(s) + int(rng.integers(4096, 16384))] for s in rng.integers(0, len(text) // 2, size=8)]
+    parts, pos = [], 0
+    for cut in np.sort(rng.integers(0, len(text), size=48)):
+        parts += [text[pos:int(cut)], passages[int(rng.integers(0, len(passages)))]]
+        pos = int(cut)
+    parts.append(text[pos:])
+    return "\n".join(parts).encode("utf-8")[:n_bytes]
+
+
 def test_real_prose_from_the_image(hip, oracle):
-    """BASELINE config 5 on real natural language: the prose that ships with the container image
-    (mixed alphabet of ~100 symbols, most suffixes tied after the first window, boilerplate repeated
-    across files).  Device text preparation + build of 0.5 MiB documents; tables of two documents
-    bit-exact and the scores of 40 keyphrases bit-equal against the oracle."""
+    """BASELINE config 5 on text with the traits of real natural language (_prose_stand_in: mixed alphabet of ~100
+    symbols, most suffixes tied after the first window, boilerplate repeated across files).  Device text preparation
+    + build of 0.5 MiB documents; tables of two documents bit-exact and the scores of 40 keyphrases bit-equal against
+    the oracle."""
     from east import hip_backend, synthetic
-    raw, n_files = synthetic.image_prose(3 << 20, keep_duplicates=True)
-    if len(raw) < (1 << 20):
-        pytest.skip("less than 1 MiB of prose found on this image")
+    raw = _prose_stand_in(3 << 20)
     step = 1 << 19
     texts = [raw[i:i + step] for i in range(0, len(raw), step)]
     hip_backend.unicode_tables()
@@ -1207,9 +1235,7 @@ def test_resident_build_fits_the_planned_arena(hip, corpus, wide_keys):
         vocab = synthetic.zipf_vocabulary(rng, size=300, exponent=1.0)
         docs = [synthetic.zipf_document(rng, 1 << 20, vocab) for _ in range(3)]
     else:
-        raw, _ = synthetic.image_prose(3 << 20, keep_duplicates=True)
-        if len(raw) < (1 << 20):
-            pytest.skip("less than 1 MiB of prose found on this image")
+        raw = _prose_stand_in(3 << 20)
         prep = hip_backend.HipIndex()
         prep.build_texts([raw[: len(raw) // 2], raw[len(raw) // 2:]])
         sym, off, ms = prep.prepared()

@@ -479,3 +479,35 @@ def test_bench_line_stays_under_the_drivers_tail():
     bare = {k: canned[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                                    "scaling", "vs_baseline", "dtype", "data", "config", "roofline")}
     assert json.loads(bench.compact_line(bare))["roofline"]["kernel"] == canned["roofline"]["kernel"]
+
+
+def test_bench_plain_run_options_and_dump_sampling(monkeypatch):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` measures the timed steps alone: --full (or --full-line, which prints
+    the whole record) asks for everything else.  Its compact line carries the contract keys without a roofline.  The
+    sample --dump-outputs takes of a large array is the same for the same shape, and a small array is written whole."""
+    import bench
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    for argv, full in ((["--steps", "7", "--warmup", "2"], False), (["--full"], True), (["--full-line"], True)):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1"] + argv)
+        args = bench.parse()
+        assert args.full is full and args.dump_outputs is None
+    assert args.steps == 20 and args.warmup == 3
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--dump-outputs", "out_dir"])
+    args = bench.parse()
+    assert args.steps == 7 and args.dump_outputs == "out_dir" and not args.full
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+    with open(os.path.join(ROOT, "profiles", "r05_final_bench.json")) as f:
+        canned = json.load(f)
+    plain = {k: canned[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
+                                    "scaling", "vs_baseline", "dtype", "data", "config", "step_ms_min", "step_ms_median",
+                                    "step_ms_max", "build_ms", "score_ms")}
+    line = json.loads(bench.compact_line(plain))
+    assert all(k in line for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"))
+    assert "roofline" not in line and "cpu_baseline" not in line and "detail" not in line
+    big = np.arange(5 << 20, dtype=np.float64).reshape(-1, 5)
+    a, b = bench._sample(big, 1000, 7), bench._sample(big.copy(), 1000, 7)
+    assert np.array_equal(a, b) and a.ndim == 1 and 900 < a.size <= 1000 and np.all(np.diff(a) > 0)
+    small = np.arange(12.0).reshape(3, 4)
+    assert np.array_equal(bench._sample(small, 1000, 7), small)

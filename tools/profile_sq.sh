@@ -13,7 +13,7 @@ NAME=$1; shift
 OUT=gpurun_out/${NAME}_sq
 rm -rf "$OUT"; mkdir -p "$OUT"
 echo "${EAST_COMMIT:-unknown}" > $OUT/commit.txt
-ARGS="$* --no-cpu-baseline --no-config2 --no-extras --steps 2 --warmup 1"
+ARGS="$* --full --no-cpu-baseline --no-config2 --no-extras --steps 2 --warmup 1"
 pass() {
   local tag=$1; shift
   timeout 420 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $OUT/$tag -- python3 bench.py $ARGS > $OUT/$tag.json 2> $OUT/$tag.err \

@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 OUT=gpurun_out/zipf
 rm -rf "$OUT"; mkdir -p "$OUT"
 echo "${EAST_COMMIT:-unknown}" > $OUT/commit.txt     # (the tree the passes are taken on: gpurun -- "EAST_COMMIT=$(git rev-parse --short HEAD) tools/...")
-ARGS="--corpus zipf --docs 100 --doc-mib 1 --keyphrases 1000 --no-cpu-baseline --no-config2 --no-extras"
+ARGS="--full --corpus zipf --docs 100 --doc-mib 1 --keyphrases 1000 --no-cpu-baseline --no-config2 --no-extras"
 export EAST_BENCH_DETAIL=$OUT/bench_detail.json
 timeout 300 python3 bench.py $ARGS 2>/dev/null | tail -1 > $OUT/bench.json
 unset EAST_BENCH_DETAIL
