@@ -5,7 +5,8 @@ import this module; the product package never does.
 
 `OracleEASA(strings)` mirrors the attributes and `score()` of the reference's
 EnhancedAnnotatedSuffixArray (east/asts/easa.py:12-36) on top of the C
-restatement.
+restatement.  `check_tables()` and `score_table_fast()` check a built index in
+linear time (easa_linear.c), for inputs the faithful port is too slow for.
 """
 import ctypes
 import os
@@ -20,13 +21,15 @@ TERMINATOR_START = 0x0A00  # east/consts.py:23-24
 _lib = None
 
 
+_SOURCES = ("easa_oracle.c", "easa_linear.c", "Makefile")
+
+
 def build(force=False):
     """Compile libeasa_oracle.so with gcc (a few hundred ms)."""
-    src = os.path.join(_HERE, "easa_oracle.c")
     if "EASA_ORACLE_LIBRARY" in os.environ:
         return _LIB_PATH
     if force or not os.path.exists(_LIB_PATH) or \
-            os.path.getmtime(_LIB_PATH) < os.path.getmtime(src):
+            os.path.getmtime(_LIB_PATH) < max(os.path.getmtime(os.path.join(_HERE, f)) for f in _SOURCES):
         subprocess.check_call(["make", "-s", "-C", _HERE, "libeasa_oracle.so"])
     return _LIB_PATH
 
@@ -51,6 +54,10 @@ def lib():
         L.easa_score_fast.argtypes = [u32p, i64, i64, i64p, u32p, i64, ctypes.c_int,
                                       dblp, i64p, intp]
         L.easa_score_fast.restype = ctypes.c_double
+        L.lin_check_tables.argtypes = [u32p, i64p, i64p, i64, i64p, i64p, ctypes.c_int] + [i64p] * 5 + [i64p]
+        L.lin_check_tables.restype = ctypes.c_int
+        L.lin_score_table.argtypes = [u32p, i64p, i64p, i64, i64p, u32p, i64p, i64, ctypes.c_int, dblp, dblp, i64p]
+        L.lin_score_table.restype = ctypes.c_int
         _lib = L
     return _lib
 
@@ -149,6 +156,83 @@ class OracleEASA(object):
             r, suf = self.score_symbols(qs, normalized, fast, want_suffix=True)
             return r, {q[i:]: float(suf[i]) for i in range(len(q))}
         return self.score_symbols(qs, normalized, fast)
+
+
+# ---- linear-time checkers (easa_linear.c) ----------------------------------------
+CHECKED_TABLES = ("suftab", "lcptab", "anntab", "childtab_up", "childtab_down", "childtab_next_l_index", "left")
+
+
+class TableMismatch(AssertionError):
+    """A table that disagrees with its definition: `doc`, `table` and the lowest failing `rank`."""
+
+    def __init__(self, doc, table, rank):
+        AssertionError.__init__(self, "document %d: %s wrong at rank %d" % (doc, table, rank))
+        self.doc, self.table, self.rank = doc, table, rank
+
+
+def _offsets(symbols, doc_offsets, n_strings):
+    sym = np.ascontiguousarray(symbols, dtype=np.uint32)
+    off = np.ascontiguousarray(doc_offsets, dtype=np.int64)
+    ms = np.ascontiguousarray(n_strings, dtype=np.int64)
+    assert off.ndim == 1 and off.size == ms.size + 1 and off[0] == 0 and off[-1] == sym.size and (np.diff(off) > 0).all()
+    return sym, off, ms
+
+
+def check_tables(symbols, doc_offsets, n_strings, tables, verified_lcptab=None):
+    """Check the tables of the documents symbols[doc_offsets[d]:doc_offsets[d + 1]] (n_strings[d] strings each)
+    against their definitions in O(n): `tables` maps names of CHECKED_TABLES ("left": what lcp_interval_lefts returns)
+    to arrays over all the documents, in document-local numbering.  suftab is checked by the rank-pair condition,
+    lcptab by Kasai from it, the rest from lcptab: whatever is given after suftab needs suftab and lcptab -- or an
+    lcp table checked before, as `verified_lcptab` (then `tables` holds none of the two).  Raises TableMismatch with
+    the lowest failing document, its first failing table and the lowest failing rank there."""
+    sym, off, ms = _offsets(symbols, doc_offsets, n_strings)
+    unknown = set(tables) - set(CHECKED_TABLES)
+    assert not unknown, unknown
+    if verified_lcptab is None:
+        assert "suftab" in tables and (len(tables) == 1 or "lcptab" in tables), "the later checks build on suftab and lcptab"
+    else:
+        assert "suftab" not in tables and "lcptab" not in tables
+        tables = dict(tables, lcptab=verified_lcptab)
+    keep = []
+    ptrs = []
+    for name in CHECKED_TABLES:
+        if name in tables:
+            a = np.ascontiguousarray(tables[name], dtype=np.int64)
+            assert a.shape == sym.shape, (name, a.shape, sym.shape)
+            keep.append(a)
+            ptrs.append(_p(a, ctypes.c_int64))
+        else:
+            ptrs.append(None)
+    fail = np.zeros(3, np.int64)
+    rc = lib().lin_check_tables(_p(sym, ctypes.c_uint32), _p(off, ctypes.c_int64), _p(ms, ctypes.c_int64),
+                                ms.size, ptrs[0], ptrs[1], int(verified_lcptab is not None), *ptrs[2:],
+                                _p(fail, ctypes.c_int64))
+    if rc < 0:
+        raise MemoryError("lin_check_tables")
+    if rc:
+        raise TableMismatch(int(fail[0]), CHECKED_TABLES[int(fail[1])], int(fail[2]))
+
+
+def score_table_fast(symbols, doc_offsets, n_strings, suftab, q_symbols, q_offsets, normalized=True,
+                     want_suffix=False):
+    """easa_score_fast of K queries in D documents in one call (at most 16 threads): a (K, D) table like
+    HipIndex.score_table, and with want_suffix the per-suffix results as a (D, q_offsets[-1]) array."""
+    sym, off, ms = _offsets(symbols, doc_offsets, n_strings)
+    sa = np.ascontiguousarray(suftab, dtype=np.int64)
+    q = np.ascontiguousarray(q_symbols, dtype=np.uint32)
+    qo = np.ascontiguousarray(q_offsets, dtype=np.int64)
+    assert sa.shape == sym.shape and qo[0] == 0 and qo[-1] == q.size
+    K, D = qo.size - 1, ms.size
+    out = np.zeros((K, D), np.float64)
+    suf = np.zeros((D, int(qo[-1])), np.float64) if want_suffix else None
+    empty = ctypes.c_int64(0)
+    lib().lin_score_table(_p(sym, ctypes.c_uint32), _p(off, ctypes.c_int64), _p(ms, ctypes.c_int64), D,
+                          _p(sa, ctypes.c_int64), _p(q, ctypes.c_uint32), _p(qo, ctypes.c_int64), K,
+                          int(bool(normalized)), _p(out, ctypes.c_double),
+                          _p(suf, ctypes.c_double) if want_suffix else None, ctypes.byref(empty))
+    if empty.value:
+        raise ZeroDivisionError("float division by zero")  # easa.py:134 on an empty query
+    return (out, suf) if want_suffix else out
 
 
 # ---- closed forms (SURVEY.md Appendix A.2), numpy, small inputs only ----------

@@ -285,8 +285,8 @@ def test_group_shards_with_repetitive_documents_share_the_chip(hip, oracle):
     persistent kernel whose workgroups must all be resident at once (csrc/persist_rounds.h): two such launches from two
     threads must not share the chip half resident each -- the library holds a process-wide lock from the launch to the
     read-back.  Four logical shards on device 0, every document the reference's worst-case shape (identical strings) or
-    copies of a passage: tables of sampled documents array_equal to the oracle, the score table equal to a single
-    handle's."""
+    copies of a passage: tables of sampled documents array_equal to the oracle, every document's tables checked in full
+    against their definitions, the score table equal to a single handle's and to the batched interval walk."""
     from east import hip_backend, synthetic
     rng = np.random.default_rng(4242)
     docs = []
@@ -312,4 +312,11 @@ def test_group_shards_with_repetitive_documents_share_the_chip(hip, oracle):
         t = shard.tables(local)
         for name in TABLES:
             assert np.array_equal(t[name], getattr(o, name)), (name, d)
+    # every document: the group's tables checked in full against their definitions, its score table equal to the batched
+    # interval walk over them (normalized and -d)
+    t = {name: np.concatenate([group.locate(d)[0].tables(group.locate(d)[1], names=(name,))[name] for d in range(len(docs))])
+         for name in TABLES}
+    oracle.check_tables(sym, off, ms, t)
+    for norm in (True, False):
+        assert np.array_equal(group.score_table(qs, qo, norm), oracle.score_table_fast(sym, off, ms, t["suftab"], qs, qo, norm)), norm
     group.close()

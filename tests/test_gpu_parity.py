@@ -454,40 +454,57 @@ def test_sixteen_copies_of_a_passage_in_one_string(hip, oracle, request):
         assert table[k, 0] == o.score_symbols(qs[qo[k]:qo[k + 1]], True, fast=True), k
 
 
-def _check_easa_properties(sym, m, t, spot=4000):
-    """Size-independent properties that pin SA and LCP completely: sa is a permutation; for every
-    rank r the two neighbouring suffixes agree on exactly lcp[r] symbols and the next symbol of the
-    left one is smaller (=> sorted, and lcp exact).  anntab: root n-m, interval widths."""
-    n = sym.size
-    sa, lcp, ann = t["suftab"], t["lcptab"], t["anntab"]
-    assert np.array_equal(np.sort(sa), np.arange(n))
-    assert lcp[0] == 0 and int(lcp.min()) >= 0
-    a, b, h = sa[:-1], sa[1:], lcp[1:]
-    pad = np.concatenate([sym.astype(np.int64), [-1] * 4])
-    assert (pad[a + h] < pad[b + h]).all()                       # first differing symbol orders them
-    for off in range(int(h.max())):                              # and everything before it agrees
-        sel = h > off
-        assert (pad[a[sel] + off] == pad[b[sel] + off]).all()
-    assert int(ann[0]) == n - m
-    first = np.flatnonzero(ann[1:] > 0) + 1
-    assert (lcp[first] > 0).all()
-    rng = np.random.default_rng(1)
-    for i in rng.integers(1, n, size=spot).tolist():             # spot-check against plain scans
-        v = lcp[i]
-        p = i - 1
-        while lcp[p] > v:
-            p -= 1                                               # previous value <= v
-        if v == 0 or lcp[p] == v:
-            assert ann[i] == 0                                   # not the first l-index of its interval
-        else:
-            j = i + 1
-            while j < n and lcp[j] >= v:
-                j += 1
-            assert ann[i] == j - p                               # interval width = NSV - PSV
+def _assert_scores(got, want, what):
+    if not np.array_equal(got, want):
+        bad = np.argwhere(got != want)[0]
+        raise AssertionError("%s: %r differs at %s: %r, want %r" % (what, got.shape, tuple(bad), got[tuple(bad)],
+                                                                    want[tuple(bad)]))
 
 
-def test_64mib_document_properties(hip, request, suffix_sort_path):
-    """BASELINE configs[1] at full size (64 MiB, text mode): property checks + score sanity."""
+def _check_index(oracle, index, sym, off, ms, names=TABLES, left=True, scores=None, group=1 << 25):
+    """Every document of a build checked in full against the definitions of its tables (oracle.check_tables, linear time:
+    the suffix array by the rank-pair condition, LCP by Kasai from it, anntab, child tables and the lcp-interval lefts
+    from LCP), the documents read back and checked in runs of about `group` symbols.  `scores`: (q_symbols, q_offsets,
+    {normalized: score table, or (table, per-suffix results) as score_table(want_suffix=True) gives them}[, rows]) --
+    the given rows (default: all) of every document equal to the batched interval walk (easa_score_fast), bit for bit."""
+    off = np.asarray(off, np.int64)
+    ms = np.asarray(ms, np.int64)
+    if scores is not None:
+        qs, qo, got = scores[:3]
+        rows = np.arange(qo.size - 1) if len(scores) < 4 else np.asarray(scores[3])
+        sub = [qs[qo[k]:qo[k + 1]] for k in rows]
+        sub_qs, sub_qo = np.concatenate(sub), np.concatenate([[0], np.cumsum([q.size for q in sub])])
+    d0 = 0
+    while d0 < ms.size:
+        d1 = d0 + 1
+        while d1 < ms.size and off[d1 + 1] - off[d0] <= group:
+            d1 += 1
+        t = {}
+        for name in names:                                       # (one table at a time: int32 read-back, int64 copy)
+            t[name] = np.concatenate([index.tables(d, names=(name,))[name] for d in range(d0, d1)])
+        if left:
+            t["left"] = np.concatenate([index.lcp_interval_lefts(d) for d in range(d0, d1)])
+        s, loc = sym[off[d0]:off[d1]], off[d0:d1 + 1] - off[d0]
+        try:
+            oracle.check_tables(s, loc, ms[d0:d1], t)
+        except oracle.TableMismatch as e:
+            raise oracle.TableMismatch(e.doc + d0, e.table, e.rank)
+        if scores is not None:
+            for norm, g in got.items():
+                table, suf = g if isinstance(g, tuple) else (g, None)
+                want = oracle.score_table_fast(s, loc, ms[d0:d1], t["suftab"], sub_qs, sub_qo, norm,
+                                               want_suffix=suf is not None)
+                if suf is not None:
+                    want, want_suf = want
+                    _assert_scores(suf[d0:d1], want_suf, "per-suffix scores of documents %d.. (%s)" % (d0, norm))
+                _assert_scores(table[rows, d0:d1], want, "scores of documents %d.. (%s)" % (d0, norm))
+        del t
+        d0 = d1
+
+
+def test_64mib_document_properties(hip, oracle, request, suffix_sort_path):
+    """BASELINE configs[1] at full size (64 MiB, text mode): all six tables and the lcp-interval lefts checked in full
+    against their definitions, the 1 000 keyphrases bit-equal to the interval walk, normalized and -d."""
     if "_seg" in suffix_sort_path:
         pytest.skip("one document: nothing to segment (the same build as the path without _seg)")
     _three_paths(request, "window_sort_unfused", "window_sort_ht", "window_sort_ht_unfused")
@@ -496,10 +513,9 @@ def test_64mib_document_properties(hip, request, suffix_sort_path):
     _, sym, m = synthetic.word_stream_document(rng, 64 << 20, want_text=False)
     index = hip_backend.HipIndex()
     index.build(sym, np.array([0, sym.size]), np.array([m]))
-    t = index.tables(0, names=("suftab", "lcptab", "anntab"))
-    _check_easa_properties(sym, m, t)
     qs, qo = synthetic.keyphrases(rng, sym, 1000)
     table = index.score_table(qs, qo, True)
+    _check_index(oracle, index, sym, [0, sym.size], [m], scores=(qs, qo, {True: table, False: index.score_table(qs, qo, False)}))
     assert table.shape == (1000, 1) and (table >= 0).all() and (table <= 1).all()
     assert (table[0::2] > 0).all()                               # keyphrases copied from the text match
     # idempotence: rebuilding and rescoring gives the same bits
@@ -531,9 +547,10 @@ def test_256_documents_batched_equals_individual(hip):
 
 def test_config2_256_documents_10000_keyphrases_vs_oracle(hip, oracle, request, suffix_sort_path):
     """BASELINE configs[2] at its full size: 256 word-stream documents of 1 MiB (text mode) and
-    10 000 keyphrases in ONE batched build + ONE score call.  Every document: the properties that
-    pin SA / LCP / annotation completely; 8 sampled documents: all six tables array_equal to the
-    oracle and all 10 000 scores bit-equal, normalized and denormalized (applications.py:43-52)."""
+    10 000 keyphrases in ONE batched build + ONE score call.  Every document: all six tables and the lcp-interval
+    lefts checked in full against their definitions, every tenth keyphrase bit-equal to the interval walk; 8 sampled
+    documents: all six tables array_equal to the oracle and all 10 000 scores bit-equal, normalized and denormalized
+    (applications.py:43-52)."""
     # (by its size this shard takes the segmented sort on every window-sort path: the `_seg` paths would repeat the others --
     # one of them runs with the document number in the keys instead, the other two are skipped at this size)
     if suffix_sort_path in ("window_sort_seg_unfused", "window_sort_seg_ht"):
@@ -553,10 +570,7 @@ def test_config2_256_documents_10000_keyphrases_vs_oracle(hip, oracle, request, 
     qs, qo = synthetic.keyphrases(rng, sym, 10000)
     tables = {norm: index.score_table(qs, qo, norm) for norm in (True, False)}
     assert tables[True].shape == (10000, 256)
-    assert (tables[True] >= 0).all() and (tables[True] <= 1).all()
-    for d in range(256):
-        t = index.tables(d, names=("suftab", "lcptab", "anntab"))
-        _check_easa_properties(docs[d][0], docs[d][1], t, spot=150)
+    _check_index(oracle, index, sym, off, ms, scores=(qs, qo, tables, np.arange(0, 10000, 10)))
     sampled = [0, 1, 37, 100, 128, 199, 254, 255]
     for d in sampled:
         o = oracle.OracleEASA(symbols=docs[d][0], n_strings=docs[d][1])
@@ -1257,8 +1271,9 @@ def test_resident_build_fits_the_planned_arena(hip, corpus, wide_keys):
 def test_config5_zipf_100_documents_full_size(hip, oracle, request, suffix_sort_path):
     """BASELINE config 5 stand-in at its full size (enwik8 is not available offline): 100 natural-language-like
     documents of 1 MiB (Zipf vocabulary, 94 M symbols, tie-refinement rounds), one batched build.  Every document:
-    the properties that pin SA / LCP / annotation; 6 sampled documents: tables and 400 scores, normalized and
-    -d denormalized, bit-equal to the oracle (the oracle itself is pinned to ast_linear on the zipf_docs fixture)."""
+    all six tables and the lcp-interval lefts checked in full against their definitions, the 400 scores bit-equal to
+    the interval walk, normalized and -d; 6 sampled documents: tables array_equal to the oracle, scores bit-equal to its
+    walks (the oracle itself is pinned to ast_linear on the zipf_docs fixture)."""
     # (by its size this shard takes the segmented sort on every window-sort path: the `_seg` paths would repeat the others --
     # one of them runs with the document number in the keys instead, the other two are skipped at this size)
     if suffix_sort_path in ("window_sort_seg_unfused", "window_sort_seg_ht"):
@@ -1276,9 +1291,7 @@ def test_config5_zipf_100_documents_full_size(hip, oracle, request, suffix_sort_
     index.build(sym, off, np.array([d[1] for d in docs], dtype=np.int32))
     qs, qo = synthetic.keyphrases(rng, sym, 400)
     tables = {norm: index.score_table(qs, qo, norm) for norm in (True, False)}
-    for d in range(100):
-        t = index.tables(d, names=("suftab", "lcptab", "anntab"))
-        _check_easa_properties(docs[d][0], docs[d][1], t, spot=150)
+    _check_index(oracle, index, sym, off, [d[1] for d in docs], scores=(qs, qo, tables))
     for d in (0, 17, 42, 63, 98, 99):
         o = oracle.OracleEASA(symbols=docs[d][0], n_strings=docs[d][1])
         t = index.tables(d)
@@ -1413,6 +1426,46 @@ def test_repetitive_inputs_lcp_beyond_the_direct_cap(hip, oracle, case):
     q = docs[0][0][:40]
     qs, qo = hip_backend.pack_queries([q])
     assert index.score_table(qs, qo, True)[0, 0] == oracle.OracleEASA(docs[0]).score(q)
+    sym = np.concatenate(parts)
+    qs, qo = _repeat_keyphrases(parts[0][parts[0] < 0x0A00])
+    tables = {norm: index.score_table(qs, qo, norm, want_suffix=True) for norm in (True, False)}
+    _check_index(oracle, index, sym, np.concatenate([[0], np.cumsum([p.size for p in parts])]), [len(sc) for sc in docs],
+                 scores=(qs, qo, tables))
+
+
+def _long_repeat_body(case, n, rng):
+    if case in ("one_symbol", "one_letter"):
+        return np.full(n, 65, np.uint32)
+    if case == "period3":
+        return np.resize(np.array([65, 66, 67], np.uint32), n)
+    if case == "fibonacci":
+        a, b = np.array([65], np.uint32), np.array([65, 66], np.uint32)
+        while b.size < n:
+            a, b = b, np.concatenate([b, a])
+        return b[:n]
+    return np.tile(rng.integers(65, 91, size=n // 16, dtype=np.uint32), 16)
+
+
+def _repeat_keyphrases(body):
+    """About 50 keyphrases for a text of long repeats: windows of the text of 1, 2, 3, 64 and 512 symbols (runs of the
+    repeat), the same windows broken on their last symbol and in the middle, an absent symbol alone and after a match,
+    and a window of 300 symbols -- longer than a workgroup (the reduction-kernel fallback of csrc/score.h)."""
+    alphabet = np.unique(body)
+
+    def other(c):                                               # another symbol of the text (one letter: an absent one)
+        return alphabet[(np.searchsorted(alphabet, c) + 1) % alphabet.size] if alphabet.size > 1 else np.uint32(66)
+    qs = []
+    for length in (1, 2, 3, 64, 512):
+        for start in (0, 1, 2, body.size // 2 + 1):
+            w = body[start:start + length]
+            qs.append(w)
+            if length > 1:
+                qs.append(np.concatenate([w[:-1], [other(w[-1])]]))
+            if length > 2:
+                qs.append(np.concatenate([w[:length // 2], [other(w[length // 2])], w[length // 2 + 1:]]))
+    qs += [np.array([0x05D0]), np.concatenate([body[:5], [0x05D0]]), body[7:307]]
+    qs = [np.asarray(q, np.uint32) for q in qs]
+    return np.concatenate(qs), np.concatenate([[0], np.cumsum([q.size for q in qs])]).astype(np.int64)
 
 
 @pytest.mark.parametrize("case", ["one_symbol", "period3", "fibonacci", "sixteen_copies"])
@@ -1420,24 +1473,15 @@ def test_long_repeats_at_four_million_symbols(hip, oracle, request, case):
     """Repetitive inputs at a size where a quadratic step shows (a blocked Kasai walk took 0.16 s here and 0.8 s at 16 M;
     the finishing pass now goes by the irreducible-LCP lemma, csrc/tables.h): 4 Mi symbols of one letter, of a period of
     three, a Fibonacci string, 16 copies of a passage -- suffix array and LCP table array_equal to the oracle's DC3 + Kasai
-    (the reference's annotation pass, and with it the full oracle, is quadratic on such trees: minutes at 1 M), annotation
-    table by its closed form on sampled ranks; and the build stays within a bound."""
+    (the reference's annotation pass, and with it the full oracle, is quadratic on such trees: minutes at 1 M), all six
+    tables and the lcp-interval lefts checked in full against their definitions, ~50 keyphrases of runs and broken runs
+    bit-equal to the interval walk with their per-suffix results, normalized and -d; and the build stays within a bound."""
     _only_paths(request, "window_sort", "dc3_only")
     import time
     from east import hip_backend
     n = 1 << 22
     rng = np.random.default_rng(7)
-    if case == "one_symbol":
-        body = np.full(n, 65, np.uint32)
-    elif case == "period3":
-        body = np.resize(np.array([65, 66, 67], np.uint32), n)
-    elif case == "fibonacci":
-        a, b = np.array([65], np.uint32), np.array([65, 66], np.uint32)
-        while b.size < n:
-            a, b = b, np.concatenate([b, a])
-        body = b[:n]
-    else:
-        body = np.tile(rng.integers(65, 91, size=n // 16, dtype=np.uint32), 16)
+    body = _long_repeat_body(case, n, rng)
     sym = np.concatenate([body, [0x0A00]]).astype(np.uint32)
     index = hip_backend.HipIndex()
     index.build(sym, np.array([0, sym.size]), np.array([1]))
@@ -1447,20 +1491,57 @@ def test_long_repeats_at_four_million_symbols(hip, oracle, request, case):
     o = oracle.OracleEASA(symbols=sym, n_strings=1, tables=False)
     t = index.tables(0, names=("suftab", "lcptab", "anntab"))
     assert np.array_equal(t["suftab"], o.suftab) and np.array_equal(t["lcptab"], o.lcptab)
-    lcp, ann = t["lcptab"], t["anntab"]
-    assert int(ann[0]) == sym.size - 1
-    checked = 0
-    for i in rng.integers(1, sym.size, size=400).tolist():     # anntab[k] = NSV(k) - PSV(k) at first l-indices, 0 elsewhere
-        v, p, j = lcp[i], i - 1, i + 1
-        while p > 0 and lcp[p] > v and i - p < 20000:
-            p -= 1
-        while j < sym.size and lcp[j] >= v and j - i < 20000:
-            j += 1
-        if i - p >= 20000 or j - i >= 20000:
-            continue                                           # (an interval too wide for a plain scan)
-        checked += 1
-        assert ann[i] == (0 if v == 0 or lcp[p] == v else j - p), (case, i)
-    assert checked > 0 or case in ("one_symbol", "period3")
+    assert int(t["anntab"][0]) == sym.size - 1
+    del t, o
+    qs, qo = _repeat_keyphrases(body)
+    tables = {norm: index.score_table(qs, qo, norm, want_suffix=True) for norm in (True, False)}
+    _check_index(oracle, index, sym, [0, sym.size], [1], scores=(qs, qo, tables))
+
+
+@pytest.mark.parametrize("case", ["one_letter", "period3", "fibonacci"])
+def test_long_repeats_at_sixteen_mi_symbols(hip, oracle, request, case):
+    """The 16 Mi inputs of tools/long_repeat_profile.py, whose doubling rounds go launch by launch (fewer group-number
+    bits, short first attempts, no direct comparisons once long repeats are known: DESIGN 5.6), each as one string: the
+    suffix array by the rank-pair condition (no DC3 oracle at this size), LCP by Kasai, the other tables and the
+    lcp-interval lefts from it, all in full; the keyphrases of runs and broken runs bit-equal to the interval walk."""
+    _only_paths(request, "window_sort", "dc3_only")
+    from east import hip_backend
+    body = _long_repeat_body(case, 16 << 20, None)
+    sym = np.concatenate([body, [0x0A00]]).astype(np.uint32)
+    index = hip_backend.HipIndex()
+    index.build(sym, np.array([0, sym.size]), np.array([1]))
+    qs, qo = _repeat_keyphrases(body)
+    tables = {norm: index.score_table(qs, qo, norm, want_suffix=True) for norm in (True, False)}
+    _check_index(oracle, index, sym, [0, sym.size], [1], scores=(qs, qo, tables))
+
+
+def test_long_repeats_in_one_batched_build(hip, oracle, suffix_sort_path):
+    """Long repeats next to each other and next to ordinary text in ONE build, so that the segmented first-level sort
+    (the `_seg` paths) and domains of mixed documents meet them: 2 Mi of one letter, a 2 Mi Fibonacci string, a period
+    of three cut into eight strings at cuts off the period, the reference's worst case (100 identical strings of 10^4),
+    1 Mi of word stream.  Every table of every document and the lcp-interval lefts checked in full against their
+    definitions; keyphrases of runs and of the word stream bit-equal to the interval walk, with per-suffix results."""
+    from east import hip_backend, synthetic
+    rng = np.random.default_rng(5150)
+    period = np.resize(np.array([65, 66, 67], np.uint32), 1 << 20)
+    cuts = np.sort(rng.choice(np.arange(1, period.size), size=7, replace=False))
+    docs = [(np.concatenate([_long_repeat_body("one_letter", 2 << 20, None), [0x0A00]]).astype(np.uint32), 1),
+            (np.concatenate([_long_repeat_body("fibonacci", 2 << 20, None), [0x0A00]]).astype(np.uint32), 1),
+            (np.concatenate([np.concatenate([p, [0x0A00 + i]]) for i, p in enumerate(np.split(period, cuts))]).astype(np.uint32), 8),
+            synthetic.worst_case_collection(rng, 100, 10 ** 4),
+            synthetic.word_stream_document(rng, 1 << 20, want_text=False)[1:]]
+    sym = np.concatenate([d[0] for d in docs])
+    off = np.concatenate([[0], np.cumsum([d[0].size for d in docs])]).astype(np.int64)
+    ms = np.array([d[1] for d in docs], dtype=np.int32)
+    index = hip_backend.HipIndex()
+    index.build(sym, off, ms)
+    assert index.info()["n_docs"] == 5
+    qa, oa = _repeat_keyphrases(docs[1][0][:-1])
+    qb, ob = synthetic.keyphrases(rng, docs[4][0], 20)
+    qs, qo = np.concatenate([qa, qb]), np.concatenate([oa, ob[1:] + oa[-1]])
+    tables = {norm: index.score_table(qs, qo, norm, want_suffix=True) for norm in (True, False)}
+    assert (tables[True][0][:, 0] > 0).any() and (tables[True][0][:, 4] > 0).any()
+    _check_index(oracle, index, sym, off, ms, scores=(qs, qo, tables))
 
 
 def test_host_symbols_go_up_as_16_bit_words(hip, oracle, request):
@@ -2075,13 +2156,16 @@ def test_score_path_variants(hip, oracle, mode):
         assert lib.east_hip_debug_set_score_path(1) == 0
 
 
-def test_half_gib_symbols(hip, request, suffix_sort_path):
-    """Maximum-size leg: one document of 2^29 symbols (a quarter of the 2^31 index range; 20 GB arena).
-    Checked through size-independent properties: permutation checksums, and on 2 M sampled ranks
-    the exact LCP plus the order of the first differing symbol."""
+def test_half_gib_symbols(hip, oracle, request, record_property, suffix_sort_path):
+    """Maximum-size leg: one document of 2^29 symbols (a quarter of the 2^31 index range; 20 GB arena), checked in full
+    in linear time: the suffix array by the rank-pair condition, LCP by Kasai, the annotation table; on window_sort also
+    the three child tables (computed on the device at their first read) and the lcp-interval lefts; 100 scores bit-equal
+    to the interval walk, normalized and -d.  Host memory: the tables are read one or two at a time, the checkers' scratch is
+    int32 (peak RSS recorded as the test's `peak_rss_gib` property)."""
     if "_seg" in suffix_sort_path:
         pytest.skip("one document: nothing to segment (the same build as the path without _seg)")
     _three_paths(request, "window_sort_unfused", "window_sort_ht", "window_sort_ht_unfused")
+    import resource
     from east import hip_backend, synthetic
     n = 1 << 29
     rng = np.random.default_rng(29)
@@ -2090,18 +2174,20 @@ def test_half_gib_symbols(hip, request, suffix_sort_path):
     index.build(sym, np.array([0, n]), np.array([m]))
     info = index.info()
     assert info["n_total"] == n and (info["dc3_levels"] >= 1 or info["window_sorted"] == 1)
-    t = index.tables(0, names=("suftab", "lcptab"))
-    sa, lcp = t["suftab"], t["lcptab"]
-    assert int(sa.sum()) == n * (n - 1) // 2
-    squares = int((sa.astype(np.uint64) * sa.astype(np.uint64)).sum(dtype=np.uint64))      # mod 2^64
-    assert squares == ((n - 1) * n * (2 * n - 1) // 6) % (1 << 64)
-    r = np.sort(rng.integers(1, n, size=2_000_000))
-    a, b, h = sa[r - 1], sa[r], lcp[r]
-    pad = np.concatenate([sym.astype(np.int64), np.full(64, -1, dtype=np.int64)])
-    assert (pad[a + h] < pad[b + h]).all()
-    for off in range(int(h.max())):
-        sel = h > off
-        assert (pad[a[sel] + off] == pad[b[sel] + off]).all()
+    t = {}
+    for name in ("suftab", "lcptab", "anntab"):                 # (one at a time: int32 read-back, int64 copy)
+        t[name] = index.tables(0, names=(name,))[name]
+    oracle.check_tables(sym, [0, n], [m], t)
+    del t["anntab"]
     qs, qo = synthetic.keyphrases(rng, sym[: 1 << 20], 100)
-    table = index.score_table(qs, qo, True)
-    assert (table >= 0).all() and (table <= 1).all() and (table[0::2] > 0).all()
+    for norm in (True, False):
+        table = index.score_table(qs, qo, norm)
+        _assert_scores(table, oracle.score_table_fast(sym, [0, n], [m], t["suftab"], qs, qo, norm), "scores (%s)" % norm)
+        assert (table[0::2] > 0).all()
+    del t["suftab"]
+    if _raw_path(request) == "window_sort":                     # (two at a time on the checked lcp table; two passes run at once)
+        oracle.check_tables(sym, [0, n], [m], {name: index.tables(0, names=(name,))[name]
+                                               for name in ("childtab_up", "childtab_down")}, verified_lcptab=t["lcptab"])
+        oracle.check_tables(sym, [0, n], [m], {"childtab_next_l_index": index.tables(0, names=("childtab_next_l_index",))[
+            "childtab_next_l_index"], "left": index.lcp_interval_lefts(0)}, verified_lcptab=t["lcptab"])
+    record_property("peak_rss_gib", resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 2.0 ** 20)

@@ -49,6 +49,50 @@ try:
     raise SystemExit("U+0001 accepted")
 except ValueError:
     pass
+# the linear-time checkers (easa_linear.c): the fixture cases and deep trees in one multi-document call, corruptions of
+# every table, and the batched score walk with its per-suffix output
+names = ("suftab", "lcptab", "anntab", "childtab_up", "childtab_down", "childtab_next_l_index")
+a, b = np.array([65], np.uint32), np.array([65, 66], np.uint32)
+while b.size < 3000:
+    a, b = b, np.concatenate([b, a])
+inputs = [(easa_oracle.make_symbols(c["strings"]), len(c["strings"])) for c in cases]
+inputs += [(np.concatenate([body, [0x0A00]]).astype(np.uint32), 1) for body in
+           (np.full(3000, 65, np.uint32), np.resize(np.array([65, 66, 67], np.uint32), 3000), b[:3000])]
+parts = []
+for sym, m in inputs:
+    o = easa_oracle.OracleEASA(symbols=sym, n_strings=m)
+    t = {k: getattr(o, k) for k in names}
+    left = np.full(sym.size, -1, np.int64)
+    for k in np.flatnonzero(o.anntab[1:] > 0) + 1:
+        p = k - 1
+        while o.lcptab[p] >= o.lcptab[k]:
+            p -= 1
+        left[k] = p
+    t["left"] = left
+    parts.append(t)
+sym = np.concatenate([s for s, _ in inputs])
+off = np.concatenate([[0], np.cumsum([s.size for s, _ in inputs])])
+ms = np.array([m for _, m in inputs])
+tables = {k: np.concatenate([t[k] for t in parts]) for k in parts[0]}
+easa_oracle.check_tables(sym, off, ms, tables)
+for k in tables:
+    for r in (int(off[-4]) + 1, int(off[-1]) - 1):
+        bad = dict(tables)
+        bad[k] = tables[k].copy()
+        bad[k][r] += 1
+        try:
+            easa_oracle.check_tables(sym, off, ms, bad)
+            raise SystemExit("corrupt %%s accepted" %% k)
+        except easa_oracle.TableMismatch:
+            pass
+qs = np.array([65, 66, 65, 65, 66, 67, 65] + [65] * 300, np.uint32)
+qo = np.array([0, 3, 7, 307])
+for norm in (True, False):
+    got, suf = easa_oracle.score_table_fast(sym, off, ms, tables["suftab"], qs, qo, norm, want_suffix=True)
+    for d in (0, len(ms) - 1):
+        o = easa_oracle.OracleEASA(symbols=sym[off[d]:off[d + 1]], n_strings=ms[d], tables=False)
+        for k in range(3):
+            assert got[k, d] == o.score_symbols(qs[qo[k]:qo[k + 1]], norm, fast=True)
 print("oracle under sanitizers: %%d fixture cases" %% n)
 """
 
