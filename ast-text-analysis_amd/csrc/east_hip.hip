@@ -513,7 +513,11 @@ struct east_hip_index {
     i64 prep_n = 0;
     std::vector<i64> prep_doc_off;
     std::vector<int32_t> prep_n_strings;
+    // the cosine measure's term index (cosine.h; own allocations, made by the first east_hip_cosine_build_texts)
+    struct CosState *cos = nullptr;
 };
+static void cos_reset(east_hip_index *h);
+static void cos_destroy(east_hip_index *h);
 
 struct SpecAbort {};             // a speculative build cannot go on: build_common starts over with the read-backs in place
 
@@ -1792,6 +1796,77 @@ static bool prepare_texts_streamed(east_hip_index *h, Ctx &ctx, const uint8_t *b
     return high == 0;
 }
 
+// The caller's Unicode tables (290 KB) stay on the device between calls (own allocation): they are uploaded again only
+// when their content changes -- a 64-bit hash over all of them, taken while the text is on its way.  With them go the two
+// 256-entry tables of the byte-wise fast path (class and upper-cased code point of a byte that is a code point of its own).
+struct TpDevTables {
+    TpTables t;
+    const uint8_t *cls256;     // the 256-entry tables of the byte-wise fast path
+    const u32 *up256;
+};
+static TpDevTables tp_upload_tables(east_hip_index *h, const uint8_t *cp_class, const u32 *cp_upper, const u32 *word_hi,
+                                    const u32 *digit_hi, const u32 *hi_upper_from, const u32 *hi_upper_to, int32_t n_hi_upper)
+{
+    const size_t tb_class = 0, tb_upper = tb_class + TP_TEXT_LIMIT, tb_word = tb_upper + (size_t)TP_TEXT_LIMIT * 4,
+                 tb_digit = tb_word + (size_t)TP_WORD_HI_WORDS * 4, tb_from = tb_digit + (size_t)TP_WORD_HI_WORDS * 4,
+                 tb_to = tb_from + ((size_t)n_hi_upper + 1) * 4, tb_cls256 = tb_to + ((size_t)n_hi_upper + 1) * 4,
+                 tb_up256 = tb_cls256 + 256, tb_total = tb_up256 + 1024;
+    {
+        u64 hash = 0x9E3779B97F4A7C15ull ^ (u64)n_hi_upper;
+        auto mix = [&](const void *p, size_t bytes) {
+            const u64 *q = (const u64 *)p;
+            for (size_t i = 0; i < bytes / 8; i++) hash = (hash ^ q[i]) * 0x100000001B3ull + (hash >> 29);
+        };
+        mix(cp_class, TP_TEXT_LIMIT); mix(cp_upper, (size_t)TP_TEXT_LIMIT * 4); mix(word_hi, (size_t)TP_WORD_HI_WORDS * 4);
+        mix(digit_hi, (size_t)TP_WORD_HI_WORDS * 4);
+        for (int32_t q = 0; q < n_hi_upper; q++) hash = (hash ^ (((u64)hi_upper_from[q] << 32) | hi_upper_to[q])) * 0x100000001B3ull + (hash >> 29);
+        if (!h->tp_tables || h->tp_tables_bytes < tb_total || h->tp_tables_hash != hash) {
+            if (h->tp_tables_bytes < tb_total) {
+                HIP_CHECK(hipStreamSynchronize(h->stream));
+                if (h->tp_tables) HIP_CHECK(hipFree(h->tp_tables));
+                h->tp_tables = nullptr;
+                h->tp_tables_bytes = 0;
+                void *p = nullptr;
+                if (hipMalloc(&p, tb_total) != hipSuccess) east_throw(EAST_HIP_ERR_OOM, "hipMalloc of the Unicode tables failed");
+                h->tp_tables = (char *)p;
+                h->tp_tables_bytes = tb_total;
+            }
+            h->tp_host_tables.resize(256 + 1024);
+            uint8_t *cls256 = h->tp_host_tables.data();
+            u32 *up256 = reinterpret_cast<u32 *>(h->tp_host_tables.data() + 256);
+            for (u32 x = 0; x < 256; x++) {              // (as tp_decode_kernel: upper first, then the class of the result)
+                u32 cp = x < 0x80u ? cp_upper[x] : TP_REPLACEMENT;
+                if (cp >= TP_TEXT_LIMIT) {
+                    for (int32_t q = 0; q < n_hi_upper; q++)
+                        if (hi_upper_from[q] == cp) { cp = hi_upper_to[q]; break; }
+                }
+                u32 cls;
+                if (cp < TP_TEXT_LIMIT) cls = cp_class[cp];
+                else { const u32 k = cp - TP_TEXT_LIMIT; cls = ((word_hi[k >> 5] >> (k & 31u)) & 1u) | (((digit_hi[k >> 5] >> (k & 31u)) & 1u) << 1); }
+                cls256[x] = (uint8_t)cls;
+                up256[x] = cp;
+            }
+            char *t = h->tp_tables;
+            HIP_CHECK(hipMemcpyAsync(t + tb_class, cp_class, TP_TEXT_LIMIT, hipMemcpyHostToDevice, h->stream));
+            HIP_CHECK(hipMemcpyAsync(t + tb_upper, cp_upper, (size_t)TP_TEXT_LIMIT * 4, hipMemcpyHostToDevice, h->stream));
+            HIP_CHECK(hipMemcpyAsync(t + tb_word, word_hi, (size_t)TP_WORD_HI_WORDS * 4, hipMemcpyHostToDevice, h->stream));
+            HIP_CHECK(hipMemcpyAsync(t + tb_digit, digit_hi, (size_t)TP_WORD_HI_WORDS * 4, hipMemcpyHostToDevice, h->stream));
+            if (n_hi_upper) {
+                HIP_CHECK(hipMemcpyAsync(t + tb_from, hi_upper_from, (size_t)n_hi_upper * 4, hipMemcpyHostToDevice, h->stream));
+                HIP_CHECK(hipMemcpyAsync(t + tb_to, hi_upper_to, (size_t)n_hi_upper * 4, hipMemcpyHostToDevice, h->stream));
+            }
+            HIP_CHECK(hipMemcpyAsync(t + tb_cls256, cls256, 256, hipMemcpyHostToDevice, h->stream));
+            HIP_CHECK(hipMemcpyAsync(t + tb_up256, up256, 1024, hipMemcpyHostToDevice, h->stream));
+            h->tp_tables_hash = hash;                   // (the read-back below waits for the stream: the host buffers are the caller's / the handle's)
+        }
+    }
+    const uint8_t *d_class = (const uint8_t *)(h->tp_tables + tb_class), *d_cls256 = (const uint8_t *)(h->tp_tables + tb_cls256);
+    const u32 *d_upper = (const u32 *)(h->tp_tables + tb_upper), *d_word_hi = (const u32 *)(h->tp_tables + tb_word),
+              *d_digit_hi = (const u32 *)(h->tp_tables + tb_digit), *d_hi_from = (const u32 *)(h->tp_tables + tb_from),
+              *d_hi_to = (const u32 *)(h->tp_tables + tb_to), *d_up256 = (const u32 *)(h->tp_tables + tb_up256);
+    return TpDevTables{TpTables{d_class, d_upper, d_word_hi, d_digit_hi, d_hi_from, d_hi_to, (u32)n_hi_upper}, d_cls256, d_up256};
+}
+
 // bytes: the texts concatenated, each followed by one 0xFF byte (host pointer).
 // (texts != nullptr: the texts lie apart in host memory -- text d = texts[d], text_offsets as if they were
 // concatenated with their separators; they are uploaded one by one and never joined on the host)
@@ -1863,68 +1938,11 @@ static void build_from_texts(east_hip_index *h, const uint8_t *bytes, i64 n_byte
     };
     if (!stream_chunk) upload_all();
     HIP_CHECK(hipMemcpyAsync(d_text_off, off32.data(), off32.size() * 4, hipMemcpyHostToDevice, h->stream));
-    // The caller's Unicode tables (290 KB) stay on the device between calls (own allocation): they are uploaded again only
-    // when their content changes -- a 64-bit hash over all of them, taken while the text is on its way.  With them go the two
-    // 256-entry tables of the byte-wise fast path (class and upper-cased code point of a byte that is a code point of its own).
-    const size_t tb_class = 0, tb_upper = tb_class + TP_TEXT_LIMIT, tb_word = tb_upper + (size_t)TP_TEXT_LIMIT * 4,
-                 tb_digit = tb_word + (size_t)TP_WORD_HI_WORDS * 4, tb_from = tb_digit + (size_t)TP_WORD_HI_WORDS * 4,
-                 tb_to = tb_from + ((size_t)n_hi_upper + 1) * 4, tb_cls256 = tb_to + ((size_t)n_hi_upper + 1) * 4,
-                 tb_up256 = tb_cls256 + 256, tb_total = tb_up256 + 1024;
-    {
-        u64 hash = 0x9E3779B97F4A7C15ull ^ (u64)n_hi_upper;
-        auto mix = [&](const void *p, size_t bytes) {
-            const u64 *q = (const u64 *)p;
-            for (size_t i = 0; i < bytes / 8; i++) hash = (hash ^ q[i]) * 0x100000001B3ull + (hash >> 29);
-        };
-        mix(cp_class, TP_TEXT_LIMIT); mix(cp_upper, (size_t)TP_TEXT_LIMIT * 4); mix(word_hi, (size_t)TP_WORD_HI_WORDS * 4);
-        mix(digit_hi, (size_t)TP_WORD_HI_WORDS * 4);
-        for (int32_t q = 0; q < n_hi_upper; q++) hash = (hash ^ (((u64)hi_upper_from[q] << 32) | hi_upper_to[q])) * 0x100000001B3ull + (hash >> 29);
-        if (!h->tp_tables || h->tp_tables_bytes < tb_total || h->tp_tables_hash != hash) {
-            if (h->tp_tables_bytes < tb_total) {
-                HIP_CHECK(hipStreamSynchronize(h->stream));
-                if (h->tp_tables) HIP_CHECK(hipFree(h->tp_tables));
-                h->tp_tables = nullptr;
-                h->tp_tables_bytes = 0;
-                void *p = nullptr;
-                if (hipMalloc(&p, tb_total) != hipSuccess) east_throw(EAST_HIP_ERR_OOM, "hipMalloc of the Unicode tables failed");
-                h->tp_tables = (char *)p;
-                h->tp_tables_bytes = tb_total;
-            }
-            h->tp_host_tables.resize(256 + 1024);
-            uint8_t *cls256 = h->tp_host_tables.data();
-            u32 *up256 = reinterpret_cast<u32 *>(h->tp_host_tables.data() + 256);
-            for (u32 x = 0; x < 256; x++) {              // (as tp_decode_kernel: upper first, then the class of the result)
-                u32 cp = x < 0x80u ? cp_upper[x] : TP_REPLACEMENT;
-                if (cp >= TP_TEXT_LIMIT) {
-                    for (int32_t q = 0; q < n_hi_upper; q++)
-                        if (hi_upper_from[q] == cp) { cp = hi_upper_to[q]; break; }
-                }
-                u32 cls;
-                if (cp < TP_TEXT_LIMIT) cls = cp_class[cp];
-                else { const u32 k = cp - TP_TEXT_LIMIT; cls = ((word_hi[k >> 5] >> (k & 31u)) & 1u) | (((digit_hi[k >> 5] >> (k & 31u)) & 1u) << 1); }
-                cls256[x] = (uint8_t)cls;
-                up256[x] = cp;
-            }
-            char *t = h->tp_tables;
-            HIP_CHECK(hipMemcpyAsync(t + tb_class, cp_class, TP_TEXT_LIMIT, hipMemcpyHostToDevice, h->stream));
-            HIP_CHECK(hipMemcpyAsync(t + tb_upper, cp_upper, (size_t)TP_TEXT_LIMIT * 4, hipMemcpyHostToDevice, h->stream));
-            HIP_CHECK(hipMemcpyAsync(t + tb_word, word_hi, (size_t)TP_WORD_HI_WORDS * 4, hipMemcpyHostToDevice, h->stream));
-            HIP_CHECK(hipMemcpyAsync(t + tb_digit, digit_hi, (size_t)TP_WORD_HI_WORDS * 4, hipMemcpyHostToDevice, h->stream));
-            if (n_hi_upper) {
-                HIP_CHECK(hipMemcpyAsync(t + tb_from, hi_upper_from, (size_t)n_hi_upper * 4, hipMemcpyHostToDevice, h->stream));
-                HIP_CHECK(hipMemcpyAsync(t + tb_to, hi_upper_to, (size_t)n_hi_upper * 4, hipMemcpyHostToDevice, h->stream));
-            }
-            HIP_CHECK(hipMemcpyAsync(t + tb_cls256, cls256, 256, hipMemcpyHostToDevice, h->stream));
-            HIP_CHECK(hipMemcpyAsync(t + tb_up256, up256, 1024, hipMemcpyHostToDevice, h->stream));
-            h->tp_tables_hash = hash;                   // (the read-back below waits for the stream: the host buffers are the caller's / the handle's)
-        }
-    }
-    const uint8_t *d_class = (const uint8_t *)(h->tp_tables + tb_class), *d_cls256 = (const uint8_t *)(h->tp_tables + tb_cls256);
-    const u32 *d_upper = (const u32 *)(h->tp_tables + tb_upper), *d_word_hi = (const u32 *)(h->tp_tables + tb_word),
-              *d_digit_hi = (const u32 *)(h->tp_tables + tb_digit), *d_hi_from = (const u32 *)(h->tp_tables + tb_from),
-              *d_hi_to = (const u32 *)(h->tp_tables + tb_to), *d_up256 = (const u32 *)(h->tp_tables + tb_up256);
+    const TpDevTables tb = tp_upload_tables(h, cp_class, cp_upper, word_hi, digit_hi, hi_upper_from, hi_upper_to, n_hi_upper);
+    const uint8_t *d_cls256 = tb.cls256;
+    const u32 *d_up256 = tb.up256;
     HIP_CHECK(hipMemsetAsync(d_high, 0, 4, h->stream));
-    const TpTables tables{d_class, d_upper, d_word_hi, d_digit_hi, d_hi_from, d_hi_to, (u32)n_hi_upper};
+    const TpTables tables = tb.t;
     if (stream_chunk) {
         std::vector<u32> s_off, s_m;
         const size_t mark = ar.mark();
@@ -2363,6 +2381,7 @@ void east_hip_destroy(east_hip_handle_t h)
     (void)hipGetDevice(&cur);
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
+    cos_destroy(h);
     if (h->arena.base) (void)hipFree(h->arena.base);
     if (h->q_buf) (void)hipFree(h->q_buf);
     if (h->kg) (void)hipFree(h->kg);
@@ -2622,6 +2641,7 @@ int east_hip_reset(east_hip_handle_t h)
         if (h->q_cap > keep) { (void)hipFree(h->q_buf); h->q_buf = nullptr; h->q_cap = 0; }
         if (h->kg_cap > keep) { (void)hipFree(h->kg); h->kg = nullptr; h->kg_cap = 0; }
         if (h->prep_cap > keep) { (void)hipFree(h->prep_sym); h->prep_sym = nullptr; h->prep_cap = 0; }
+        cos_reset(h);
     });
 }
 
@@ -2964,3 +2984,5 @@ int east_hip_debug_suffix_array(int device, const uint32_t *symbols, int64_t n, 
 // ---- several devices in one process ------------------------------------------------------------------
 #include "multi.h"
 #include "format.h"
+// ---- the cosine relevance measure ------------------------------------------------------------------
+#include "cosine.h"

@@ -35,7 +35,7 @@ RelevanceMeasure = _Group(AST="AST", COSINE="cosine")
 # -a option of the CLI / second argument of AST.get_ast; "easa_hip" names the MI355X backend explicitly
 ASTAlgorithm = _Group(EASA="easa", AST_LINEAR="ast_linear", AST_NAIVE="ast_naive", EASA_HIP="easa_hip")
 
-# -w / -v options (cosine measure only; kept so that option parsing stays compatible)
+# -w / -v options of the cosine measure (relevance.CosineRelevanceMeasure)
 TermWeighting = _Group(TF="tf", TF_IDF="tf-idf")
 VectorSpace = _Group(WORDS="words", STEMS="stems", LEMMATA="lemmata")
 

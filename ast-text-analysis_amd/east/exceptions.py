@@ -49,3 +49,24 @@ class SymbolOutOfDomainException(EastException):
 class HipBackendError(EastException):
     """New: the MI355X backend is unavailable or failed.  There is no CPU fallback."""
     msg_fmt = "HIP backend error: %(reason)s"
+
+
+class NoSuchVectorSpace(NotFoundException):
+    """New: -v / CosineRelevanceMeasure(vector_space=...) is none of consts.VectorSpace."""
+    msg_fmt = "There is no vector space with name `%(name)s` (use 'words' or 'stems')."
+
+
+class NoSuchTermWeighting(NotFoundException):
+    """New: -w / CosineRelevanceMeasure(term_weighting=...) is none of consts.TermWeighting."""
+    msg_fmt = "There is no term weighting with name `%(name)s` (use 'tf' or 'tf-idf')."
+
+
+class LemmataUnavailableException(EastException):
+    """New: the reference declares the 'lemmata' vector space and raises when it is used (relevance.py:98-100)."""
+    msg_fmt = "The 'lemmata' vector space has no implementation (nor has the reference's): use '-v words' or '-v stems'."
+
+
+class StemmerUnavailableException(EastException):
+    """New: the 'stems' vector space needs a stemmer; the default is nltk's Snowball stemmer (relevance.py:7, 67-68)."""
+    msg_fmt = ("The 'stems' vector space needs nltk's Snowball stemmer, and nltk is not installed: "
+               "use '-v words' (or pass a stemmer to CosineRelevanceMeasure).")

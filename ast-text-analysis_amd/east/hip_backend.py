@@ -101,6 +101,19 @@ SIGNATURES = {
     "east_hip_profile_enable": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "east_hip_profile_only": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
     "east_hip_profile_report": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int64]),
+    "east_hip_cosine_build_texts": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int64, _c_i64p, ctypes.c_int32,
+                                                   ctypes.POINTER(ctypes.c_uint8), _c_u32p, _c_u32p, _c_u32p, _c_u32p,
+                                                   _c_u32p, ctypes.c_int32, _c_u32p, _c_i64p, ctypes.c_int32]),
+    "east_hip_cosine_build_texts_v": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_char_p), _c_i64p, ctypes.c_int32,
+                                                     ctypes.POINTER(ctypes.c_uint8), _c_u32p, _c_u32p, _c_u32p, _c_u32p,
+                                                     _c_u32p, ctypes.c_int32, _c_u32p, _c_i64p, ctypes.c_int32]),
+    "east_hip_cosine_info": (ctypes.c_int, [ctypes.c_void_p, _c_i64p, ctypes.c_int32]),
+    "east_hip_cosine_get_terms": (ctypes.c_int, [ctypes.c_void_p, _c_i64p, _c_u32p, _c_i64p]),
+    "east_hip_cosine_set_classes": (ctypes.c_int, [ctypes.c_void_p, _c_i32p, ctypes.c_int32]),
+    "east_hip_cosine_lookup": (ctypes.c_int, [ctypes.c_void_p, _c_u32p, _c_i64p, ctypes.c_int32, _c_i32p]),
+    "east_hip_cosine_score_table": (ctypes.c_int, [ctypes.c_void_p, _c_i32p, _c_i64p, ctypes.c_int64, ctypes.c_int32,
+                                                   ctypes.c_int32, _c_dblp]),
+    "east_hip_debug_set_term_hash_bits": (ctypes.c_int, [ctypes.c_int]),
 }
 
 BUILD_INFO_FIELDS = ("n_total", "n_docs", "n_strings", "sigma_text", "bits_level0", "dc3_levels", "arena_bytes",
@@ -108,6 +121,8 @@ BUILD_INFO_FIELDS = ("n_total", "n_docs", "n_strings", "sigma_text", "bits_level
                      "radix_passes_u32", "radix_elements_u32", "radix_passes_u64", "radix_elements_u64",
                      "dc3_levels_resolved", "merge_elements", "refine_rounds", "window_sorted", "lds_sorted",
                      "fused_finish", "first_kept", "first_n", "ht_keys", "seg_sort", "narrow_upload", "persist_rounds")
+COSINE_INFO_FIELDS = ("built", "n_docs", "kept_tokens", "words", "terms", "classes", "postings", "hash_attempts", "build_us",
+                      "score_us")
 
 _lib = None
 
@@ -218,6 +233,34 @@ def _drain_pool():
 atexit.register(_drain_pool)
 
 
+def _raw_texts(texts):
+    return [t if isinstance(t, bytes) else t.encode("utf-8", errors="surrogatepass") for t in texts]
+
+
+def _table_args():
+    """unicode_tables() as the arguments of east_hip_build_texts[_v] / east_hip_cosine_build_texts[_v]."""
+    cls, upper, word_hi, digit_hi, hi_from, hi_to = unicode_tables()
+    return (_ptr(cls, ctypes.POINTER(ctypes.c_uint8)), _ptr(upper, _c_u32p), _ptr(word_hi, _c_u32p),
+            _ptr(digit_hi, _c_u32p), _ptr(hi_from, _c_u32p), _ptr(hi_to, _c_u32p), hi_from.size)
+
+
+def _join_free(raw):
+    """Whether texts go to the device one by one (the _v entry points) rather than joined into one blob."""
+    total = sum(len(t) for t in raw)
+    # (... through the pinned ring only while a text averages JOIN_FREE_RING_MIN_MEAN bytes: half a million one-line
+    # texts cost more as a ctypes pointer array than the one b"".join they would save)
+    return (len(raw) <= JOIN_FREE_MAX_TEXTS and total >= JOIN_FREE_MIN_BYTES) or \
+        (len(raw) <= JOIN_FREE_RING_MAX_TEXTS and total >= JOIN_FREE_RING_BYTES and total >= JOIN_FREE_RING_MIN_MEAN * len(raw))
+
+
+def _joined(raw):
+    """Every text followed by one 0xFF, in a single copy, and the D + 1 offsets."""
+    blob = b"\xff".join(raw + [b""])
+    offsets = np.zeros(len(raw) + 1, dtype=np.int64)
+    np.cumsum([len(t) + 1 for t in raw], out=offsets[1:])
+    return blob, offsets
+
+
 class HipIndex(object):
     """One device-resident batch of annotated suffix arrays (an AST shard)."""
 
@@ -298,25 +341,16 @@ class HipIndex(object):
     def build_texts(self, texts):
         """Text preparation + build on the device.  texts: list of bytes (UTF-8, decoded with
         errors='replace' semantics) or str."""
-        raw = [t if isinstance(t, bytes) else t.encode("utf-8", errors="surrogatepass") for t in texts]
-        cls, upper, word_hi, digit_hi, hi_from, hi_to = unicode_tables()
-        tables = (_ptr(cls, ctypes.POINTER(ctypes.c_uint8)), _ptr(upper, _c_u32p), _ptr(word_hi, _c_u32p),
-                  _ptr(digit_hi, _c_u32p), _ptr(hi_from, _c_u32p), _ptr(hi_to, _c_u32p), hi_from.size)
-        total = sum(len(t) for t in raw)
-        # (... through the pinned ring only while a text averages JOIN_FREE_RING_MIN_MEAN bytes: half a million one-line
-        # texts cost more as a ctypes pointer array than the one b"".join they would save)
-        if (len(raw) <= JOIN_FREE_MAX_TEXTS and total >= JOIN_FREE_MIN_BYTES) or \
-                (len(raw) <= JOIN_FREE_RING_MAX_TEXTS and total >= JOIN_FREE_RING_BYTES and
-                 total >= JOIN_FREE_RING_MIN_MEAN * len(raw)):
+        raw = _raw_texts(texts)
+        tables = _table_args()
+        if _join_free(raw):
             # a few large texts: uploaded one by one straight out of their bytes objects (joining 64 MiB costs
             # more host time than the device needs for the whole build)
             ptrs = (ctypes.c_char_p * len(raw))(*raw)
             lengths = np.array([len(t) for t in raw], dtype=np.int64)
             _check(self._lib.east_hip_build_texts_v(self._h, ptrs, _ptr(lengths, _c_i64p), len(raw), *tables))
         else:
-            blob = b"\xff".join(raw + [b""])    # every text followed by one 0xFF, in a single copy
-            offsets = np.zeros(len(raw) + 1, dtype=np.int64)
-            np.cumsum([len(t) + 1 for t in raw], out=offsets[1:])
+            blob, offsets = _joined(raw)
             _check(self._lib.east_hip_build_texts(self._h, blob, len(blob), _ptr(offsets, _c_i64p), len(raw), *tables))
         self.n_docs = len(raw)
         self._host_symbols = None
@@ -446,6 +480,85 @@ class HipIndex(object):
         return float(self._lib.east_hip_last_score_ms(self._h))
 
 
+class HipCosineIndex(object):
+    """The cosine measure's term index (include/east_hip.h, "The cosine relevance measure"): the postings (term, document,
+    count) of a whole collection, built on the device from raw texts.  It lives in the handle of a HipIndex: its own one
+    (device choice and handle pool as HipIndex) unless `index` is given -- then it shares that handle, whose EASA index it
+    leaves alone, and closing is the owner's business."""
+
+    def __init__(self, device=None, index=None):
+        self._owner = index is None
+        self.index = HipIndex(device) if index is None else index
+        self._lib = self.index._lib
+        self.device = self.index.device
+        self.n_docs = 0
+        self.n_terms = 0
+
+    @property
+    def _h(self):
+        return self.index._h
+
+    def close(self):
+        if self._owner:
+            self.index.close()
+
+    def build_texts(self, texts, stopwords=()):
+        """texts: bytes (UTF-8, decoded with errors='replace') or str; stopwords: upper-cased words."""
+        raw = _raw_texts(texts)
+        sw_cps, sw_off = pack_words(list(stopwords))
+        args = _table_args() + (_ptr(sw_cps, _c_u32p), _ptr(sw_off, _c_i64p), sw_off.size - 1)
+        if _join_free(raw):
+            ptrs = (ctypes.c_char_p * len(raw))(*raw)
+            lengths = np.array([len(t) for t in raw], dtype=np.int64)
+            _check(self._lib.east_hip_cosine_build_texts_v(self._h, ptrs, _ptr(lengths, _c_i64p), len(raw), *args))
+        else:
+            blob, offsets = _joined(raw)
+            _check(self._lib.east_hip_cosine_build_texts(self._h, blob, len(blob), _ptr(offsets, _c_i64p), len(raw), *args))
+        self.n_docs = len(raw)
+        self.n_terms = self.info()["terms"]
+
+    def info(self):
+        buf = np.zeros(len(COSINE_INFO_FIELDS), dtype=np.int64)
+        _check(self._lib.east_hip_cosine_info(self._h, _ptr(buf, _c_i64p), buf.size))
+        return dict(zip(COSINE_INFO_FIELDS, (int(x) for x in buf)))
+
+    def terms(self):
+        """The terms in id order (first occurrence in the collection)."""
+        n = ctypes.c_int64(0)
+        _check(self._lib.east_hip_cosine_get_terms(self._h, None, None, ctypes.byref(n)))
+        offsets = np.zeros(self.n_terms + 1, dtype=np.int64)
+        cps = np.zeros(max(n.value, 1), dtype=np.uint32)
+        _check(self._lib.east_hip_cosine_get_terms(self._h, _ptr(offsets, _c_i64p), _ptr(cps, _c_u32p), ctypes.byref(n)))
+        text = cps[:n.value].astype("<u4").tobytes().decode("utf-32-le", errors="surrogatepass")
+        return [text[offsets[t]:offsets[t + 1]] for t in range(self.n_terms)]
+
+    def set_classes(self, term_class, n_classes):
+        """The vector space of classes of terms (stems): term_class[t], classes numbered by their smallest term id;
+        n_classes = 0 goes back to the terms."""
+        tc = np.ascontiguousarray(term_class, dtype=np.int32)
+        _check(self._lib.east_hip_cosine_set_classes(self._h, _ptr(tc, _c_i32p) if n_classes else None, int(n_classes)))
+
+    def lookup(self, words):
+        """[prepared word] -> int32 term ids, -1 for a word that is not a term."""
+        out = np.full(len(words), -1, dtype=np.int32)
+        if words:
+            cps, offsets = pack_words(words)
+            _check(self._lib.east_hip_cosine_lookup(self._h, _ptr(cps, _c_u32p), _ptr(offsets, _c_i64p), len(words),
+                                                    _ptr(out, _c_i32p)))
+        return out
+
+    def score_table(self, q_ids, q_offsets, tfidf=True):
+        """K x D cosine scores: q_ids[q_offsets[k]:q_offsets[k + 1]] = the kept tokens of query k as ids of the vector
+        space, -1 outside it."""
+        q_ids = np.ascontiguousarray(q_ids, dtype=np.int32)
+        q_offsets = np.ascontiguousarray(q_offsets, dtype=np.int64)
+        K = q_offsets.size - 1
+        out = np.empty((K, self.n_docs), dtype=np.float64)
+        _check(self._lib.east_hip_cosine_score_table(self._h, _ptr(q_ids, _c_i32p), _ptr(q_offsets, _c_i64p), q_ids.size, K,
+                                                     1 if tfidf else 0, _ptr(out, _c_dblp)))
+        return out
+
+
 class HipGroup(object):
     """One collection over several devices in this process: a shard of documents -- one HipIndex -- per device, driven
     by the library's own host threads, the K x D_local score blocks assembled by one all-gather (RCCL between distinct
@@ -565,6 +678,14 @@ def format_table(scores, kp_order, text_order, kp_names, text_names, kind):
     if n < 0:
         raise exceptions.HipBackendError(reason="table formatter: %d" % n)
     return buf.raw[:n].decode("utf-8", "surrogatepass")
+
+
+def pack_words(words):
+    """[str] -> (code points uint32, offsets int64)."""
+    cps = np.frombuffer("".join(words).encode("utf-32-le", errors="surrogatepass"), dtype="<u4").astype(np.uint32)
+    offsets = np.zeros(len(words) + 1, dtype=np.int64)
+    np.cumsum([len(w) for w in words], out=offsets[1:])
+    return cps, offsets
 
 
 def pack_queries(queries, keep_spaces=False):

@@ -5,6 +5,9 @@ README.rst:27-63; the shipped reference main crashes with a NameError, SURVEY.md
     east [-s ast] [-a easa|easa_hip|ast_linear|ast_naive] [-d] [-f xml|csv] \\
          keyphrases table <keyphrases file> <directory with .txt files | single file>
     east [-c confidence] [-r relevance] [-p support] [-f edges|gml] keyphrases graph <keyphrases file> <texts>
+    east -s cosine [-w tf|tf-idf] [-v stems|words] keyphrases table|graph ...
+        the cosine measure (relevance.CosineRelevanceMeasure) on one device; `-v stems` (the default) needs nltk's
+        Snowball stemmer, and without nltk's stopword list no stopwords are removed (said on stderr)
 
 Several GPUs (one process per GPU, documents sharded over the ranks, one RCCL all-gather of the score blocks --
 east/parallel.py; the reference's loops relevance.py:41-53 / applications.py:43-52 are what is sharded):
@@ -62,11 +65,20 @@ def main(argv=None, measure_factory=None):
     opt_list = opts                                         # (as given: repeated options, empty values)
     opts = dict(opts)
     world, rank = _world()
+    cosine = opts.get("-s", "").lower() == consts.RelevanceMeasure.COSINE
+    if world > 1 and cosine:
+        if rank == 0:
+            print("Relevance measure 'cosine' runs on one device: a launcher with WORLD_SIZE=%d is not supported." % world)
+        return 1
     if world == 1:
         try:
             n_ranks = int(opts.get("-g", os.environ.get("EAST_HIP_DEVICES", "1")))
         except ValueError:
             print("Invalid number of GPUs: '%s'." % opts.get("-g", os.environ.get("EAST_HIP_DEVICES")))
+            return 1
+        if n_ranks > 1 and cosine:
+            # (several devices would need an all-reduce of the document frequencies)
+            print("Relevance measure 'cosine' runs on one device: -g %d is not supported." % n_ranks)
             return 1
         if n_ranks > 1 and os.environ.get("EAST_HIP_MULTI", "threads") != "process":
             # the default: N devices in THIS process (one AST shard and one host thread of the library per device, one
@@ -139,12 +151,18 @@ def _main(opts, args, world, measure_factory):
             texts[os.path.basename(filename)[:-4]] = _read(filename)
 
     measure_name = opts["-s"]
-    if measure_name.lower() != "ast":
-        print("Relevance measure '%s' is not available in the MI355X build (only 'ast')." % measure_name)
+    cosine = measure_name.lower() == consts.RelevanceMeasure.COSINE
+    if measure_name.lower() != "ast" and not cosine:
+        print("Relevance measure '%s' is not available (use 'ast' or 'cosine')." % measure_name)
         return 1
     if "-y" in opts:
         print("Synonym extraction (-y) needs the external Tomita parser and is not available.")
         return 1
+    if cosine:
+        if distributed:
+            print("Relevance measure 'cosine' runs on one device: the collective path is not supported.")
+            return 1
+        return _run_cosine(subcommand, keyphrases, texts, opts)
 
     group_up = False
     try:
@@ -179,6 +197,20 @@ def _main(opts, args, world, measure_factory):
         if group_up:
             import torch.distributed as dist
             dist.destroy_process_group()
+
+
+def _run_cosine(subcommand, keyphrases, texts, opts):
+    """-s cosine with its -w / -v options (reference main.py:95-98, relevance.py:58-62); bad values, -v lemmata and a
+    missing stemmer end here with one line, before anything touches the device."""
+    try:
+        measure = relevance.CosineRelevanceMeasure(opts.get("-v", consts.VectorSpace.STEMS),
+                                                   opts.get("-w", consts.TermWeighting.TF_IDF))
+        if measure.stopwords_source == "none":
+            sys.stderr.write("nltk's English stopword list is not available: no stopwords are removed.\n")
+        return _run(subcommand, keyphrases, texts, measure, opts)
+    except exceptions.EastException as e:
+        print(e)
+        return 1
 
 
 def _run(subcommand, keyphrases, texts, similarity_measure, opts):

@@ -1,11 +1,11 @@
 # -*- coding: utf-8 -*-
-"""Relevance measures (reference east/relevance.py:16-53, AST half).
+"""Relevance measures (reference east/relevance.py:16-168).
 
-ASTRelevanceMeasure keeps the reference surface (set_text_collection /
-relevance) and adds the batched path the GPU needs: ONE build call for the whole
-text collection (the documents become one device-resident shard of annotated
-suffix arrays) and `relevance_table`, ONE score call for all keyphrases.
-CosineRelevanceMeasure is a different method and out of scope.
+Both keep the reference surface (set_text_collection / relevance) and add the batched path the GPU needs: ONE build
+call for the whole text collection and `relevance_table`, ONE score call for all keyphrases.
+ASTRelevanceMeasure: the documents become one device-resident shard of annotated suffix arrays.
+CosineRelevanceMeasure (`-s cosine`): the documents become one device-resident term index -- postings (term, document,
+count) -- and a keyphrase is scored against every document by walking the posting lists of its terms.
 """
 import itertools
 import os
@@ -276,3 +276,106 @@ class MultiDeviceASTRelevanceMeasure(ASTRelevanceMeasure):
             raise ZeroDivisionError("float division by zero")
         qs, qo = hip_backend.pack_queries(queries)
         return self.group.score_table(qs, qo, self.normalized)
+
+
+def default_stopwords():
+    """nltk's English stopword list, upper-cased (utils.py:41-46), or None where nltk or its corpus is not there."""
+    try:
+        from nltk.corpus import stopwords
+        return frozenset(utils.prepare_text(word) for word in stopwords.words("english"))
+    except (ImportError, LookupError):
+        return None
+
+
+class CosineRelevanceMeasure(RelevanceMeasure):
+    """relevance.py:56-168: the cosine between a document's and a keyphrase's term vectors.
+
+    Tokens are tokenize_and_filter's (utils.py:41-46): [\\w']+ over the prepared text, at least 3 code points, not a
+    stopword.  The terms are the tokens (`words`) or their stems (`stems`); a document's weights are
+    tf = count / max(n_d, 1), times idf = 1 + ln(D / df) under `tf-idf`; the keyphrase's are count / max(its kept
+    tokens, 1) over the terms of the collection.  The index is built on the device (hip_backend.HipCosineIndex); the
+    keyphrases' few tokens are prepared here.
+
+    stopwords: None = nltk's English list where nltk is installed, else none (`stopwords_source` says which: "nltk",
+    "none", "given"); or any words, upper-cased here.  `stopwords` holds the set that is used.
+    stemmer: anything with .stem(str) -> str; None = nltk's SnowballStemmer(language) for `stems` -- without nltk
+    StemmerUnavailableException, at once, before any device work.
+    """
+
+    def __init__(self, vector_space=consts.VectorSpace.STEMS, term_weighting=consts.TermWeighting.TF_IDF, device=None,
+                 stopwords=None, stemmer=None):
+        super(CosineRelevanceMeasure, self).__init__()
+        if vector_space == consts.VectorSpace.LEMMATA:
+            raise exceptions.LemmataUnavailableException()
+        if vector_space not in consts.VectorSpace:
+            raise exceptions.NoSuchVectorSpace(name=vector_space)
+        if term_weighting not in consts.TermWeighting:
+            raise exceptions.NoSuchTermWeighting(name=term_weighting)
+        self._snowball = None
+        if vector_space == consts.VectorSpace.STEMS and stemmer is None:
+            try:
+                from nltk.stem import snowball
+            except ImportError:
+                raise exceptions.StemmerUnavailableException()
+            self._snowball = snowball
+        self.vector_space = vector_space
+        self.term_weighting = term_weighting
+        self.device = device
+        self.stemmer = stemmer
+        if stopwords is None:
+            found = default_stopwords()
+            self.stopwords = found if found is not None else frozenset()
+            self.stopwords_source = "nltk" if found is not None else "none"
+        else:
+            self.stopwords = frozenset(utils.prepare_text(word) for word in stopwords)
+            self.stopwords_source = "given"
+        self.index = None
+        self._stem_class = None
+        self._row = (None, None)
+
+    def set_text_collection(self, texts, language=consts.Language.ENGLISH):
+        texts = list(texts)
+        self.texts = texts
+        self.language = language
+        if self._snowball is not None:
+            self.stemmer = self._snowball.SnowballStemmer(language)
+        if self.index is None:
+            self.index = hip_backend.HipCosineIndex(self.device)
+        self.index.build_texts(texts, sorted(self.stopwords))
+        self._stem_class = None
+        if self.vector_space == consts.VectorSpace.STEMS:
+            # every distinct term stemmed once; a class per stem, numbered by its smallest term id
+            classes = {}
+            term_class = [classes.setdefault(self.stemmer.stem(term), len(classes)) for term in self.index.terms()]
+            self.index.set_classes(term_class, len(classes))
+            self._stem_class = classes
+        self._row = (None, None)
+
+    def _query_terms(self, query):
+        """The kept tokens of a prepared keyphrase (tokenize_and_filter), stemmed in the `stems` space."""
+        tokens = [t for t in utils.tokenize(query) if len(t) >= 3 and t not in self.stopwords]
+        if self.vector_space == consts.VectorSpace.STEMS:
+            return [self.stemmer.stem(t) for t in tokens]
+        return tokens
+
+    def relevance_table(self, prepared_keyphrases, synonimizer=None):
+        """K prepared keyphrases -> K x D float64 array of scores (relevance.py:150-168 for every pair).  The synonimizer
+        is accepted and ignored, as the reference does."""
+        per_query = [self._query_terms(q) for q in prepared_keyphrases]
+        offsets = np.zeros(len(per_query) + 1, dtype=np.int64)
+        np.cumsum([len(q) for q in per_query], out=offsets[1:])
+        flat = [t for q in per_query for t in q]
+        if self._stem_class is not None:
+            ids = [self._stem_class.get(t, -1) for t in flat]
+        else:
+            distinct = list(dict.fromkeys(flat))
+            where = dict(zip(distinct, self.index.lookup(distinct).tolist()))
+            ids = [where[t] for t in flat]
+        return self.index.score_table(np.array(ids, dtype=np.int32), offsets,
+                                      self.term_weighting == consts.TermWeighting.TF_IDF)
+
+    def relevance(self, keyphrase, text, synonimizer=None):
+        """relevance.py:150-168: the score of a prepared keyphrase in text number `text` (one row is cached)."""
+        if self._row[0] != keyphrase:
+            self._row = (keyphrase, self.relevance_table([keyphrase])[0])
+        return float(self._row[1][text])

@@ -234,6 +234,48 @@ int east_hip_get_lcp_intervals(east_hip_handle_t h, int32_t doc, int32_t *left);
 int east_hip_score_probes(east_hip_handle_t h, int normalized, int64_t *probes);
 
 /*
+ * The cosine relevance measure (`east -s cosine`): replaces CosineRelevanceMeasure (east/relevance.py:56-168) with the
+ * token filter it uses, tokenize_and_filter (east/utils.py:31-46).  A term index of the whole collection lives in the
+ * handle beside the EASA index: a cosine build never disturbs an EASA index and the other way round; east_hip_reset
+ * forgets both.  (How: csrc/cosine.h)
+ *
+ * east_hip_cosine_build_texts[_v]  set_text_collection (relevance.py:65-83): the texts and the Unicode tables as for
+ *     east_hip_build_texts[_v] (utf-8 with errors='replace', upper case 1:1, [\w']+ tokens).  A token is kept when it
+ *     has at least 3 code points -- no isdigit filter and no U+0A00 limit: every script is plain terms -- and is not
+ *     one of the n_stop stopwords (code points, already upper-cased; stop_offsets: n_stop + 1 offsets into stop_cps).
+ *     The terms are the distinct kept words numbered by first occurrence in the collection; the index holds the postings
+ *     (term, document, count) and n_d, the kept tokens of every document.
+ * east_hip_cosine_info  out[0..9]: built, documents, kept tokens (stopwords included), distinct words (stopwords
+ *     included), terms V, classes (0 while the terms are the vector space), postings of the vector space, hash attempts
+ *     of the build, device time of the last build and of the last score call in microseconds (-1: none).
+ * east_hip_cosine_get_terms  the terms in id order: V + 1 offsets in code points and the code points (each pointer
+ *     nullable; *n_cps = the number of code points).
+ * east_hip_cosine_set_classes  the vector space of stems (relevance.py:86-97): term_class[t] = the class of term t, the
+ *     classes numbered by the smallest term id in each; the postings are re-keyed by class and their counts merged.
+ *     n_classes = 0 goes back to the terms.
+ * east_hip_cosine_lookup  words (code points, prepared) -> term ids, -1 for a word that is not a term (a stopword is none).
+ * east_hip_cosine_score_table  relevance() (relevance.py:150-168) for K keyphrases x every document:
+ *     q_ids[q_offsets[k] .. q_offsets[k + 1]) = the kept tokens of keyphrase k as ids of the vector space (term ids, or
+ *     class ids after east_hip_cosine_set_classes), -1 for a token outside it (it still counts in the query's length);
+ *     q_len = q_offsets[K].  weighting: 0 = tf, 1 = tf-idf.  out: K x D doubles, row-major, the layout of
+ *     east_hip_score_table.  score = dot(w_d, q) / (|w_d| |q|), the norm of an all-zero vector being 1.
+ */
+int east_hip_cosine_build_texts(east_hip_handle_t h, const uint8_t *bytes, int64_t n_bytes, const int64_t *text_offsets,
+                                int32_t n_docs, const uint8_t *cp_class, const uint32_t *cp_upper, const uint32_t *word_hi,
+                                const uint32_t *digit_hi, const uint32_t *hi_upper_from, const uint32_t *hi_upper_to,
+                                int32_t n_hi_upper, const uint32_t *stop_cps, const int64_t *stop_offsets, int32_t n_stop);
+int east_hip_cosine_build_texts_v(east_hip_handle_t h, const uint8_t *const *texts, const int64_t *lengths, int32_t n_docs,
+                                  const uint8_t *cp_class, const uint32_t *cp_upper, const uint32_t *word_hi,
+                                  const uint32_t *digit_hi, const uint32_t *hi_upper_from, const uint32_t *hi_upper_to,
+                                  int32_t n_hi_upper, const uint32_t *stop_cps, const int64_t *stop_offsets, int32_t n_stop);
+int east_hip_cosine_info(east_hip_handle_t h, int64_t *out, int32_t cap);
+int east_hip_cosine_get_terms(east_hip_handle_t h, int64_t *offsets, uint32_t *cps, int64_t *n_cps);
+int east_hip_cosine_set_classes(east_hip_handle_t h, const int32_t *term_class, int32_t n_classes);
+int east_hip_cosine_lookup(east_hip_handle_t h, const uint32_t *cps, const int64_t *offsets, int32_t n_words, int32_t *ids);
+int east_hip_cosine_score_table(east_hip_handle_t h, const int32_t *q_ids, const int64_t *q_offsets, int64_t q_len,
+                                int32_t n_keyphrases, int32_t weighting, double *out);
+
+/*
  * Several devices in one process ("single-process/8-device fits the one-process CLI best").
  * Every document is an independent AST (east/relevance.py:41-46) and every (keyphrase, document) score is independent
  * (east/applications.py:43-52): a GROUP shards a collection at document granularity -- contiguous blocks of documents
@@ -386,6 +428,10 @@ int east_hip_debug_set_text_stream(int64_t chunk_bytes);
  * a few host threads into a ring of pinned memory and go up slot by slot.  mode -1 (default): four or more texts of less
  * than 8 MiB on average; 0: never; 1: always.  slot_bytes: size of a ring slot (0: the default, 8 MiB). */
 int east_hip_debug_set_text_ring(int mode, int64_t slot_bytes);
+/* Test knob: the FIRST hash attempt of every cosine build keeps only the low `bits` bits of the term hashes (1 .. 61; 0 =
+ * all 61, the default), so that different words collide, the verification finds it and the build starts over with the
+ * next seed (east_hip_cosine_info: hash attempts).  The index does not depend on it. */
+int east_hip_debug_set_term_hash_bits(int bits);
 /* Host only (needs no device): the order-preserving variable-length code csrc/ht_code.h makes for n symbols (in their
  * order) with the given weights -- code[i] = the len[i] bits of symbol i's code word, right-aligned.  EAST_HIP_ERR_DOMAIN
  * if no code with word lengths in [3, 12] exists for them (n < 8, n > 256). */
