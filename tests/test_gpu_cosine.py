@@ -7,6 +7,7 @@ from contextlib import redirect_stdout
 import numpy as np
 import pytest
 
+import cosine_exact as cx
 from conftest import load_golden, word_stream
 from test_cosine_host import ToyStemmer, assert_scores, case_texts, restate
 
@@ -168,9 +169,35 @@ def _member(sorted_keys, x):
     return found & (pos < sorted_keys.size), pos
 
 
-def configs2_restatement(texts, kps, sample_docs):
+def configs2_exact(parts, n_docs, sample_docs):
+    """The exact model of cosine_exact.py (integers exact, ln / sqrt / the quotient at 50 digits, one rounding) on the
+    integer word codes of configs2_restatement: {d: (scores of every keyphrase in document d, its postings)}."""
+    uniq, df_keys, df, per_kp = parts["uniq"], parts["df_keys"], parts["df"], parts["per_kp"]
+    idf = {}
+    out = {}
+    for d in sample_docs:
+        u, cnt = uniq[d]
+        dfs = df[np.searchsorted(df_keys, u)]
+        squares = np.bincount(dfs, cnt.astype(np.float64) ** 2)              # (integers below 2^53: exact)
+        for f in np.flatnonzero(squares).tolist():
+            idf.setdefault(f, 1 + cx.MP.log(cx.MP.mpf(n_docs) / f))
+        rad = sum((int(squares[f]) * idf[f] ** 2 for f in np.flatnonzero(squares).tolist()), cx.MP.mpf(0))
+        scores = np.zeros(len(per_kp))
+        for k, (codes, c) in enumerate(per_kp):
+            in_vocab, _ = _member(df_keys, codes)
+            hit, pos = _member(u, codes)
+            if hit.any():
+                num = sum((int(c[i]) * int(cnt[pos[i]]) * idf[int(dfs[pos[i]])] for i in np.flatnonzero(hit).tolist()), cx.MP.mpf(0))
+                q2 = int((c[in_vocab].astype(np.int64) ** 2).sum())
+                scores[k] = float(num / cx.MP.sqrt(rad * q2))
+        out[d] = (scores, int(u.size))
+    return out
+
+
+def configs2_restatement(texts, kps, sample_docs, parts=None):
     """The restatement of test_cosine_host for word-stream text, on integer word codes: (shared[k, d] = keyphrase k and
-    document d share a term, {d: scores of every keyphrase in the sampled document d})."""
+    document d share a term, {d: scores of every keyphrase in the sampled document d}).  `parts`: a dict that receives
+    the integer structures (configs2_exact, the counts of east_hip_cosine_info)."""
     D, K = len(texts), len(kps)
     codes = [_word_codes(t) for t in texts]
     uniq = [np.unique(c, return_counts=True) for c in codes]
@@ -196,6 +223,9 @@ def configs2_restatement(texts, kps, sample_docs):
         hit, pos = _member(u, distinct)
         dot = np.bincount(owner, np.where(hit, w[np.minimum(pos, u.size - 1)] * qv, 0.0), minlength=K)
         scores[d] = dot / (norm * qn)
+    if parts is not None:
+        parts.update(uniq=uniq, df_keys=df_keys, df=df, per_kp=per_kp, q_len=q_len, kept_tokens=sum(int(c.size) for c in codes),
+                     terms=int(df_keys.size), postings=sum(int(u.size) for u, _ in uniq))
     return shared, scores
 
 
@@ -223,7 +253,11 @@ def test_configs2_shape_against_the_restatement(hip):
     assert table.shape == (K, D)
 
     sample = (0, 37, 128, 255)
-    shared, scores = configs2_restatement(texts, kps, sample)
+    parts = {}
+    shared, scores = configs2_restatement(texts, kps, sample, parts)
+    info = m.index.info()                                            # the counts, from the integer codes
+    assert (info["n_docs"], info["kept_tokens"], info["words"], info["terms"], info["postings"], info["classes"]) == \
+        (D, parts["kept_tokens"], parts["terms"], parts["terms"], parts["postings"], 0)
     assert ((table >= 0.0) & (table <= 1.0 + 1e-12)).all()
     assert np.array_equal(table > 0.0, shared)
     assert shared.any() and not shared.all()
@@ -231,6 +265,8 @@ def test_configs2_shape_against_the_restatement(hip):
         want = scores[d]
         assert np.abs(table[:, d] - want).max() <= 1e-12
         assert np.array_equal(table[:, d] == 0.0, want == 0.0)
+    for d, (exact, p_d) in configs2_exact(parts, D, sample).items():      # ... and the relative bound of DESIGN.md 9
+        cx.check_scores(table[:, [d]], exact[:, None], [p_d], parts["q_len"])
 
 
 def test_one_text_of_a_single_huge_token(hip):
