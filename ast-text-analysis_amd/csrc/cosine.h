@@ -594,6 +594,9 @@ struct CosState {
     u32 *run_term = nullptr, *term_off = nullptr, *term_len = nullptr, *tcp = nullptr, *n_d = nullptr;
     CosUnits terms, cls;
     float build_ms = -1.f, score_ms = -1.f;
+    double *table = nullptr;                              // the last score call's K x D table, where it lies in `score` (graph.h reads it there)
+    u32 table_K = 0;
+    bool table_valid = false;
     CosBuf *bufs[8] = {&text, &work, &index, &term_text, &classes, &score, &terms.weights, &cls.weights};
 };
 
@@ -662,6 +665,7 @@ static void cos_build(east_hip_index *h, const uint8_t *bytes, i64 n_bytes64, co
     if (!h->cos) h->cos = new CosState();
     CosState &c = *h->cos;
     c.built = c.use_classes = false;
+    c.table_valid = false;
     c.terms.w_valid[0] = c.terms.w_valid[1] = c.cls.w_valid[0] = c.cls.w_valid[1] = false;
     const u32 N = (u32)n_bytes64, D = (u32)n_docs;
     Stats stats;
@@ -979,7 +983,7 @@ static void cos_score(east_hip_index *h, const int32_t *q_ids, const i64 *q_offs
                       double *out)
 {
     CosState &c = cos_built(h);
-    if (K < 0 || weighting < 0 || weighting > 1 || (K > 0 && (!q_offsets || !out))) east_throw(EAST_HIP_ERR_INVALID, "bad score arguments");
+    if (K < 0 || weighting < 0 || weighting > 1 || (K > 0 && !q_offsets)) east_throw(EAST_HIP_ERR_INVALID, "bad score arguments");
     if (K == 0) return;
     if (q_offsets[0] != 0 || q_offsets[K] != q_len || q_len < 0 || q_len >= (i64)0x7FFFFFF0 || (q_len > 0 && !q_ids))
         east_throw(EAST_HIP_ERR_INVALID, "q_offsets must start at 0 and end at q_len");
@@ -993,6 +997,7 @@ static void cos_score(east_hip_index *h, const int32_t *q_ids, const i64 *q_offs
         if (q_ids[i] < -1 || (q_ids[i] >= 0 && (u32)q_ids[i] >= U.n_units))
             east_throw(EAST_HIP_ERR_INVALID, "a query id is neither -1 nor a unit of the vector space");
     use_device(h);
+    c.table_valid = false;
     const u32 D = c.n_docs, total = (u32)q_len;
     const size_t b_ids = cos_align(((size_t)total + 1) * 4), b_off = cos_align(((size_t)K + 1) * 4),
                  b_qw = cos_align(((size_t)total + 1) * 8), table = (size_t)K * D * 8;
@@ -1021,9 +1026,12 @@ static void cos_score(east_hip_index *h, const int32_t *q_ids, const i64 *q_offs
     LAUNCH(ctx, cos_score_kernel, std::min<u32>((u32)K, 1u << 16), (const int32_t *)d_ids, (const u32 *)d_off, (const double *)d_qw,
            (u32)K, (const u32 *)U.unit_off, (const u32 *)U.post_doc, (const double *)w, (const double *)norm, D, d_out);
     HIP_CHECK(hipEventRecord(h->ev1, h->stream));
-    HIP_CHECK(hipMemcpyAsync(out, d_out, table, hipMemcpyDeviceToHost, h->stream));
+    if (out) HIP_CHECK(hipMemcpyAsync(out, d_out, table, hipMemcpyDeviceToHost, h->stream));     // (null: the table stays on the device, graph.h)
     HIP_CHECK(hipStreamSynchronize(h->stream));
     U.w_valid[weighting] = true;
+    c.table = d_out;
+    c.table_K = (u32)K;
+    c.table_valid = true;
     HIP_CHECK(hipEventElapsedTime(&c.score_ms, h->ev0, h->ev1));
 }
 
@@ -1032,6 +1040,7 @@ static void cos_reset(east_hip_index *h)
     CosState *c = h->cos;
     if (!c) return;
     c->built = c->use_classes = false;
+    c->table_valid = false;
     c->terms.w_valid[0] = c->terms.w_valid[1] = c->cls.w_valid[0] = c->cls.w_valid[1] = false;
     c->build_ms = c->score_ms = -1.f;
     for (CosBuf *b : c->bufs)                               // (a recycled handle keeps small buffers only, as east_hip_reset does)

@@ -515,9 +515,16 @@ struct east_hip_index {
     std::vector<int32_t> prep_n_strings;
     // the cosine measure's term index (cosine.h; own allocations, made by the first east_hip_cosine_build_texts)
     struct CosState *cos = nullptr;
+    // the AST score table of the resident keyphrases (h->table) holds the scores of the index as it stands: set by the score
+    // walk, withdrawn by every build and every new set of keyphrases (the keyphrase graph reads it where it lies, graph.h)
+    bool table_scored = false;
+    // the keyphrase graph (graph.h; own allocations, made by the first east_hip_graph_build_*)
+    struct GraphState *graph = nullptr;
 };
 static void cos_reset(east_hip_index *h);
 static void cos_destroy(east_hip_index *h);
+static void graph_reset(east_hip_index *h);
+static void graph_destroy(east_hip_index *h);
 
 struct SpecAbort {};             // a speculative build cannot go on: build_common starts over with the read-backs in place
 
@@ -980,6 +987,7 @@ static void ensure_arena(east_hip_index *h, size_t bytes)
     h->arena.base = nullptr;
     h->arena.cap = 0;
     h->built = false;
+    h->table_scored = false;
     void *p = nullptr;
     hipError_t e = hipMalloc(&p, bytes);
     if (e != hipSuccess) {
@@ -1241,6 +1249,7 @@ static void build_common(east_hip_index *h, const u32 *sym, bool sym_on_host, i6
     check_build_args(n_total, doc_offsets, n_strings, n_docs);
     use_device(h);
     h->built = false;
+    h->table_scored = false;
     const Knobs kn = knobs_snapshot();                   // (the test knobs of this call, from its sizing run to its last launch)
     const u32 n = (u32)n_total;
     // (host symbols of the reference encoding go up as 16-bit words where that pays: upload_symbols_narrow)
@@ -1890,6 +1899,7 @@ static void build_from_texts(east_hip_index *h, const uint8_t *bytes, i64 n_byte
     }
     use_device(h);
     h->built = false;
+    h->table_scored = false;
     const u32 n_bytes = (u32)n_bytes64, D = (u32)n_docs;
     const size_t arena_before = h->arena.cap;
     size_t arena_need = (size_t)n_bytes * 46 + (size_t)D * 96 + (8u << 20);
@@ -2095,6 +2105,7 @@ static void set_keyphrases(east_hip_index *h, const u32 *q_symbols, const i64 *q
     if (S >= (i64)0x7FFFFFF0 || (i64)n_kp * h->n_docs >= ((i64)1 << 40))
         east_throw(EAST_HIP_ERR_INVALID, "keyphrase set too large");
     use_device(h);
+    h->table_scored = false;
     const u32 n_q = (u32)S;
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const Knobs kn = knobs_snapshot();
@@ -2300,6 +2311,7 @@ static void score_resident(east_hip_index *h, int normalized, unsigned long long
                                      hipMemcpyDeviceToHost, h->stream));
     }
     HIP_CHECK(hipEventRecord(h->ev1, h->stream));
+    h->table_scored = true;
 }
 
 // ------------------------------------------------------------------ C ABI --
@@ -2382,6 +2394,7 @@ void east_hip_destroy(east_hip_handle_t h)
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     cos_destroy(h);
+    graph_destroy(h);
     if (h->arena.base) (void)hipFree(h->arena.base);
     if (h->q_buf) (void)hipFree(h->q_buf);
     if (h->kg) (void)hipFree(h->kg);
@@ -2619,6 +2632,7 @@ int east_hip_reset(east_hip_handle_t h)
         use_device(h);
         HIP_CHECK(hipStreamSynchronize(h->stream));
         h->built = false;
+    h->table_scored = false;
         h->n = 0;
         h->n_docs = 0;
         h->n_kp = 0;
@@ -2642,6 +2656,7 @@ int east_hip_reset(east_hip_handle_t h)
         if (h->kg_cap > keep) { (void)hipFree(h->kg); h->kg = nullptr; h->kg_cap = 0; }
         if (h->prep_cap > keep) { (void)hipFree(h->prep_sym); h->prep_sym = nullptr; h->prep_cap = 0; }
         cos_reset(h);
+        graph_reset(h);
     });
 }
 
@@ -2986,3 +3001,4 @@ int east_hip_debug_suffix_array(int device, const uint32_t *symbols, int64_t n, 
 #include "format.h"
 // ---- the cosine relevance measure ------------------------------------------------------------------
 #include "cosine.h"
+#include "graph.h"

@@ -1,6 +1,7 @@
 # -*- coding: utf-8 -*-
 """keyphrases_table / keyphrases_graph (reference east/applications.py:11-149)."""
 
+import os
 from collections.abc import Mapping
 
 import numpy as np
@@ -112,6 +113,111 @@ def keyphrases_table(keyphrases, texts, similarity_measure=None, synonimizer=Non
     return res
 
 
+class KeyphraseGraph(object):
+    """The keyphrase graph (applications.py:59-149) as arrays, the way ScoreTable is the table as an array: at BASELINE
+    configs[2] a graph holds 10^5 .. 10^7 edges, the device writes them in well under a millisecond and a dict per edge
+    costs seconds.  `keyphrases` is the input list (a node's id is its position in it); `support[p]` the number of texts
+    position p occurs in (-1 for a position that is not a node where the graph was taken from a dict, which does not say);
+    `node_ids` the positions that are nodes, in order; per edge, in the reference's order (sources in list order, a source's
+    targets in list order), `edge_source` and `edge_target` (positions) and `edge_confidence` (float64).  Compares equal
+    to the reference's dict with the same content; `.to_dict()` gives that dict."""
+
+    __hash__ = None
+
+    def __init__(self, keyphrases, support, node_ids, edge_source, edge_target, edge_confidence, referral_confidence,
+                 relevance_threshold, support_threshold):
+        self.keyphrases = list(keyphrases)
+        self.support = np.asarray(support)
+        self.node_ids = np.asarray(node_ids)
+        self.edge_source, self.edge_target = np.asarray(edge_source), np.asarray(edge_target)
+        self.edge_confidence = np.asarray(edge_confidence, dtype=np.float64)
+        self.referral_confidence, self.relevance_threshold = referral_confidence, relevance_threshold
+        self.support_threshold = support_threshold
+
+    @classmethod
+    def from_dict(cls, keyphrases, graph):
+        """The reference's dict (what keyphrases_graph returns) as arrays."""
+        support = np.full(len(keyphrases), -1, dtype=np.int64)
+        node_ids = np.array([node["id"] for node in graph["nodes"]], dtype=np.int64)
+        support[node_ids] = [node["support"] for node in graph["nodes"]]
+        edges = graph["edges"]
+        return cls(keyphrases, support, node_ids, np.array([e["source"] for e in edges], dtype=np.int64),
+                   np.array([e["target"] for e in edges], dtype=np.int64),
+                   np.array([e["confidence"] for e in edges], dtype=np.float64), graph["referral_confidence"],
+                   graph["relevance_threshold"], graph["support_threshold"])
+
+    @classmethod
+    def from_device(cls, keyphrases, found, referral_confidence, relevance_threshold, support_threshold):
+        """The arrays the device built (hip_backend.GraphArrays) as a graph over the keyphrase list.  The confidence is
+        float(shared) / max(len(source_texts), 1) (applications.py:137), the same correctly rounded division, once per edge."""
+        confidence = found.edge_shared.astype(np.float64) / np.maximum(found.support[found.edge_source], 1).astype(np.float64)
+        return cls(keyphrases, found.support, found.kept, found.edge_source, found.edge_target, confidence,
+                   referral_confidence, relevance_threshold, support_threshold)
+
+    def to_dict(self):
+        """The reference's own return type: {"nodes": [...], "edges": [...], the three thresholds}, plain Python values."""
+        nodes = [{"id": position, "label": self.keyphrases[position], "support": support}
+                 for position, support in zip(self.node_ids.tolist(), self.support[self.node_ids].tolist())]
+        edges = [{"source": source, "target": target, "confidence": confidence}
+                 for source, target, confidence in zip(self.edge_source.tolist(), self.edge_target.tolist(),
+                                                       self.edge_confidence.tolist())]
+        return {"nodes": nodes, "edges": edges, "referral_confidence": self.referral_confidence,
+                "relevance_threshold": self.relevance_threshold, "support_threshold": self.support_threshold}
+
+    def __eq__(self, other):
+        if isinstance(other, KeyphraseGraph):
+            other = other.to_dict()
+        if not isinstance(other, dict):
+            return NotImplemented
+        return self.to_dict() == other
+
+    def __ne__(self, other):
+        result = self.__eq__(other)
+        return result if result is NotImplemented else not result
+
+
+def _device_graph_applies(measure, texts, synonimizer):
+    """Whether keyphrases_graph builds the graph on the device: the measure scores into a table that stays there
+    (`relevance_graph`; None counts as absent: the measures over several devices or ranks), no synonimizer, distinct
+    text titles, and EAST_HIP_GRAPH is not `host` (the precedent: EAST_HIP_TEXT_PREP=host)."""
+    titles = list(texts.keys())
+    return (getattr(measure, "relevance_graph", None) is not None and not synonimizer
+            and len(set(titles)) == len(titles) and os.environ.get("EAST_HIP_GRAPH", "device") != "host")
+
+
+def _graph_on_device(keyphrases, texts, referral_confidence, relevance_threshold, support_threshold, measure, language):
+    """keyphrases_graph with its main loop on the device: the keyphrases are scored as keyphrases_table scores them
+    (empty ones skipped, duplicates collapsed: a keyphrase listed twice is two nodes over one row), the K x D table stays
+    where the device wrote it, and the nodes and edges come back as arrays (csrc/graph.h).  None: no keyphrase to score
+    (the host path says what the reference says then)."""
+    keyphrases = list(keyphrases)
+    wanted = [kp for kp in dict.fromkeys(keyphrases) if kp]              # applications.py:44-45
+    if not wanted:
+        return None
+    measure.set_text_collection(list(texts.values()), language)
+    row_of = {kp: k for k, kp in enumerate(wanted)}
+    rows = np.array([row_of[kp] for kp in keyphrases], dtype=np.int32)   # (an empty keyphrase: KeyError, as table[""] raises)
+    found = measure.relevance_graph([utils.prepare_text(kp) for kp in wanted], rows, referral_confidence,
+                                    relevance_threshold, support_threshold)
+    return KeyphraseGraph.from_device(keyphrases, found, referral_confidence, relevance_threshold, support_threshold)
+
+
+def keyphrases_graph_arrays(keyphrases, texts, referral_confidence=0.6, relevance_threshold=0.25,
+                            support_threshold=1, similarity_measure=None, synonimizer=None,
+                            language=consts.Language.ENGLISH):
+    """keyphrases_graph with the graph as arrays: a KeyphraseGraph (`.to_dict()` gives what keyphrases_graph returns; the
+    formatters take it as it is).  Built on the device where keyphrases_graph builds it there; elsewhere the host path's
+    dict, wrapped, so that a caller gets one type."""
+    measure = similarity_measure or relevance.ASTRelevanceMeasure()
+    if _device_graph_applies(measure, texts, synonimizer):
+        graph = _graph_on_device(keyphrases, texts, referral_confidence, relevance_threshold, support_threshold, measure,
+                                 language)
+        if graph is not None:
+            return graph
+    return KeyphraseGraph.from_dict(keyphrases, keyphrases_graph(keyphrases, texts, referral_confidence, relevance_threshold,
+                                                                 support_threshold, measure, synonimizer, language))
+
+
 def keyphrases_graph(keyphrases, texts, referral_confidence=0.6, relevance_threshold=0.25,
                      support_threshold=1, similarity_measure=None, synonimizer=None,
                      language=consts.Language.ENGLISH):
@@ -125,8 +231,17 @@ def keyphrases_graph(keyphrases, texts, referral_confidence=0.6, relevance_thres
     :returns: {"nodes": [{"id", "label", "support"}], "edges": [{"source", "target", "confidence"}],
                "referral_confidence", "relevance_threshold", "support_threshold"}; node ids are the
                positions of the keyphrases in the input list.
+
+    The main loop runs on the device, from the score table where the score call left it (_graph_on_device), when the
+    measure has `relevance_graph`, no synonimizer is given, the text titles are distinct and EAST_HIP_GRAPH is not `host`;
+    in every other case on the host, below.  The graph is the same either way.
     """
     measure = similarity_measure or relevance.ASTRelevanceMeasure()
+    if _device_graph_applies(measure, texts, synonimizer):
+        graph = _graph_on_device(keyphrases, texts, referral_confidence, relevance_threshold, support_threshold, measure,
+                                 language)
+        if graph is not None:
+            return graph.to_dict()
     table = keyphrases_table(keyphrases, texts, measure, synonimizer, language)
 
     if isinstance(table, ScoreTable) and len(set(table.text_titles)) == len(table.text_titles):

@@ -88,8 +88,44 @@ def format_graph(graph, format):
     return renderers[format](graph)
 
 
+def _as_arrays(graph):
+    """The graph if it is a KeyphraseGraph (applications.py), else None."""
+    from east import applications
+    return graph if isinstance(graph, applications.KeyphraseGraph) else None
+
+
+def _edges_from_arrays(graph):
+    """graph2edges off the arrays: the edges of a source are one stretch of the edge arrays, so a line is made per stretch
+    (a label listed twice gathers its stretches in the line of its first appearance, as the dict form does)."""
+    import numpy as np
+    labels, source, target = graph.keyphrases, graph.edge_source, graph.edge_target.tolist()
+    starts = np.flatnonzero(np.diff(source)) + 1 if len(source) else np.zeros(0, dtype=np.int64)
+    bounds = [0] + starts.tolist() + [len(source)]
+    targets = {}
+    for a, b in zip(bounds[:-1], bounds[1:]):
+        if b > a:
+            targets.setdefault(labels[int(source[a])], []).extend(map(labels.__getitem__, target[a:b]))
+    return "".join("%s -> %s\n" % (label, ", ".join(found)) for label, found in targets.items())
+
+
+def _gml_from_arrays(graph):
+    """graph2gml off the arrays: one format per node and per edge, no dict in between."""
+    out = ["graph", "[", "  directed 1",
+           "  referral_confidence %.2f" % graph.referral_confidence,
+           "  relevance_threshold %.2f" % graph.relevance_threshold,
+           "  support_threshold %i" % graph.support_threshold]
+    out += ['  node\n  [\n    id %i\n    label "%s"\n  ]' % (position, graph.keyphrases[position])
+            for position in graph.node_ids.tolist()]
+    out += ["  edge\n  [\n    source %i\n    target %i\n    confidence %.2f\n  ]" % edge
+            for edge in zip(graph.edge_source.tolist(), graph.edge_target.tolist(), graph.edge_confidence.tolist())]
+    out.append("]")
+    return "\n".join(out) + "\n"
+
+
 def graph2edges(graph):
     """One line per source node: `label -> label, label`, in order of first appearance."""
+    if _as_arrays(graph) is not None:
+        return _edges_from_arrays(graph)
     label_of = dict((node["id"], node["label"]) for node in graph["nodes"])
     targets = {}
     for edge in graph["edges"]:
@@ -99,6 +135,8 @@ def graph2edges(graph):
 
 def graph2gml(graph):
     """Graph Modelling Language: header with the three thresholds, a node block per node, an edge block per edge."""
+    if _as_arrays(graph) is not None:
+        return _gml_from_arrays(graph)
     out = ["graph", "[", "  directed 1",
            "  referral_confidence %.2f" % graph["referral_confidence"],
            "  relevance_threshold %.2f" % graph["relevance_threshold"],

@@ -114,6 +114,12 @@ SIGNATURES = {
     "east_hip_cosine_score_table": (ctypes.c_int, [ctypes.c_void_p, _c_i32p, _c_i64p, ctypes.c_int64, ctypes.c_int32,
                                                    ctypes.c_int32, _c_dblp]),
     "east_hip_debug_set_term_hash_bits": (ctypes.c_int, [ctypes.c_int]),
+    "east_hip_graph_build_resident": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _c_i32p, ctypes.c_int64, ctypes.c_double,
+                                                     ctypes.c_double, ctypes.c_double, _c_i64p]),
+    "east_hip_graph_build_host": (ctypes.c_int, [ctypes.c_void_p, _c_dblp, ctypes.c_int32, ctypes.c_int32, _c_i32p,
+                                                 ctypes.c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _c_i64p]),
+    "east_hip_graph_fetch": (ctypes.c_int, [ctypes.c_void_p] + [_c_i32p] * 5),
+    "east_hip_last_graph_ms": (ctypes.c_double, [ctypes.c_void_p]),
 }
 
 BUILD_INFO_FIELDS = ("n_total", "n_docs", "n_strings", "sigma_text", "bits_level0", "dc3_levels", "arena_bytes",
@@ -123,6 +129,8 @@ BUILD_INFO_FIELDS = ("n_total", "n_docs", "n_strings", "sigma_text", "bits_level
                      "fused_finish", "first_kept", "first_n", "ht_keys", "seg_sort", "narrow_upload", "persist_rounds")
 COSINE_INFO_FIELDS = ("built", "n_docs", "kept_tokens", "words", "terms", "classes", "postings", "hash_attempts", "build_us",
                       "score_us")
+
+GRAPH_SOURCE_AST, GRAPH_SOURCE_COSINE, GRAPH_SOURCE_UPLOADED = 0, 1, 2      # east_hip_graph_build_resident: which resident table
 
 _lib = None
 
@@ -259,6 +267,38 @@ def _joined(raw):
     offsets = np.zeros(len(raw) + 1, dtype=np.int64)
     np.cumsum([len(t) + 1 for t in raw], out=offsets[1:])
     return blob, offsets
+
+
+class GraphArrays(object):
+    """A keyphrase graph as the device built it (include/east_hip.h, "The keyphrase graph"): `support` per node position,
+    `kept` = the node positions in order, and per edge -- in the order of applications.py:111-141 -- `edge_source`,
+    `edge_target` (positions) and `edge_shared` (texts that hold both); all int32."""
+
+    __slots__ = ("support", "kept", "edge_source", "edge_target", "edge_shared")
+
+    def __init__(self, support, kept, edge_source, edge_target, edge_shared):
+        self.support, self.kept = support, kept
+        self.edge_source, self.edge_target, self.edge_shared = edge_source, edge_target, edge_shared
+
+
+def _graph_build(lib, h, source, table, rows, relevance_threshold, support_threshold, referral_confidence):
+    """east_hip_graph_build_resident (table None) / _host, then east_hip_graph_fetch."""
+    rows = np.ascontiguousarray(rows, dtype=np.int32)
+    counts = np.zeros(2, dtype=np.int64)
+    thresholds = (float(relevance_threshold), float(support_threshold), float(referral_confidence))
+    if table is None:
+        _check(lib.east_hip_graph_build_resident(h, int(source), _ptr(rows, _c_i32p), rows.size, *thresholds,
+                                                 _ptr(counts, _c_i64p)))
+    else:
+        table = np.ascontiguousarray(table, dtype=np.float64)
+        if table.ndim != 2:
+            raise exceptions.HipBackendError(reason="the score table of a keyphrase graph is a K x D array")
+        _check(lib.east_hip_graph_build_host(h, _ptr(table, _c_dblp), table.shape[0], table.shape[1], _ptr(rows, _c_i32p),
+                                             rows.size, *thresholds, _ptr(counts, _c_i64p)))
+    out = GraphArrays(np.empty(rows.size, dtype=np.int32), np.empty(int(counts[0]), dtype=np.int32),
+                      *(np.empty(int(counts[1]), dtype=np.int32) for _ in range(3)))
+    _check(lib.east_hip_graph_fetch(h, *(_ptr(getattr(out, name), _c_i32p) for name in GraphArrays.__slots__)))
+    return out
 
 
 class HipIndex(object):
@@ -479,6 +519,27 @@ class HipIndex(object):
     def last_score_ms(self):
         return float(self._lib.east_hip_last_score_ms(self._h))
 
+    # -- keyphrase graph -------------------------------------------------------
+    def graph(self, rows, relevance_threshold, support_threshold, referral_confidence):
+        """The keyphrase graph of the score table the last score call left on the device (rows[p] = the table row of node
+        position p) -> GraphArrays."""
+        return _graph_build(self._lib, self._h, GRAPH_SOURCE_AST, None, rows, relevance_threshold, support_threshold,
+                            referral_confidence)
+
+    def graph_from_table(self, table, rows, relevance_threshold, support_threshold, referral_confidence):
+        """The same from a K x D host array, which is uploaded first (tables from elsewhere, tests)."""
+        return _graph_build(self._lib, self._h, None, table, rows, relevance_threshold, support_threshold,
+                            referral_confidence)
+
+    def graph_from_uploaded(self, rows, relevance_threshold, support_threshold, referral_confidence):
+        """Another graph of the table graph_from_table left on the device: no upload."""
+        return _graph_build(self._lib, self._h, GRAPH_SOURCE_UPLOADED, None, rows, relevance_threshold, support_threshold,
+                            referral_confidence)
+
+    @property
+    def last_graph_ms(self):
+        return float(self._lib.east_hip_last_graph_ms(self._h))
+
 
 class HipCosineIndex(object):
     """The cosine measure's term index (include/east_hip.h, "The cosine relevance measure"): the postings (term, document,
@@ -547,16 +608,25 @@ class HipCosineIndex(object):
                                                     _ptr(out, _c_i32p)))
         return out
 
-    def score_table(self, q_ids, q_offsets, tfidf=True):
+    def score_table(self, q_ids, q_offsets, tfidf=True, fetch=True):
         """K x D cosine scores: q_ids[q_offsets[k]:q_offsets[k + 1]] = the kept tokens of query k as ids of the vector
-        space, -1 outside it."""
+        space, -1 outside it.  fetch=False: the table stays on the device (for graph()), nothing is returned."""
         q_ids = np.ascontiguousarray(q_ids, dtype=np.int32)
         q_offsets = np.ascontiguousarray(q_offsets, dtype=np.int64)
         K = q_offsets.size - 1
-        out = np.empty((K, self.n_docs), dtype=np.float64)
+        out = np.empty((K, self.n_docs), dtype=np.float64) if fetch else None
         _check(self._lib.east_hip_cosine_score_table(self._h, _ptr(q_ids, _c_i32p), _ptr(q_offsets, _c_i64p), q_ids.size, K,
-                                                     1 if tfidf else 0, _ptr(out, _c_dblp)))
+                                                     1 if tfidf else 0, _ptr(out, _c_dblp) if fetch else None))
         return out
+
+    def graph(self, rows, relevance_threshold, support_threshold, referral_confidence):
+        """The keyphrase graph of the table the last score_table left on the device -> GraphArrays (HipIndex.graph)."""
+        return _graph_build(self._lib, self._h, GRAPH_SOURCE_COSINE, None, rows, relevance_threshold, support_threshold,
+                            referral_confidence)
+
+    @property
+    def last_graph_ms(self):
+        return float(self._lib.east_hip_last_graph_ms(self._h))
 
 
 class HipGroup(object):

@@ -227,8 +227,9 @@ def _run(subcommand, keyphrases, texts, similarity_measure, opts):
         opts.setdefault("-c", "0.6")    # referral confidence
         opts.setdefault("-r", "0.25")   # relevance threshold of the matching score
         opts.setdefault("-p", "1")      # support threshold for graph nodes
-        graph = applications.keyphrases_graph(keyphrases, texts, float(opts["-c"]), float(opts["-r"]),
-                                              float(opts["-p"]), similarity_measure, None, opts["-l"])
+        # (the graph as arrays: the formatters write it from them, no dict per edge)
+        graph = applications.keyphrases_graph_arrays(keyphrases, texts, float(opts["-c"]), float(opts["-r"]),
+                                                     float(opts["-p"]), similarity_measure, None, opts["-l"])
         graph_format = opts.get("-f", "edges").lower()
         try:
             print(formatting.format_graph(graph, graph_format))

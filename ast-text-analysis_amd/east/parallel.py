@@ -101,6 +101,8 @@ class DistributedASTRelevanceMeasure(relevance.ASTRelevanceMeasure):
         # logic can be exercised on CPU (gloo) with a stand-in scorer
         self._factory = measure_factory or (lambda: relevance.ASTRelevanceMeasure(ast_algorithm, normalized, self.gpu))
 
+    relevance_graph = None       # (every rank holds a block of the table: keyphrases_graph keeps its host path)
+
     def _on_gpu(self):
         import torch.distributed as dist
         return dist.get_backend(self.group) == "nccl"

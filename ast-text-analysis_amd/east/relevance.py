@@ -207,6 +207,19 @@ class ASTRelevanceMeasure(RelevanceMeasure):
         qs, qo = hip_backend.pack_queries(queries)
         return self.index.score_table(qs, qo, self.normalized)
 
+    # HOT LOOP C (applications.py:59-149) on the device, from the table the score call leaves there
+    def relevance_graph(self, prepared_keyphrases, rows, referral_confidence, relevance_threshold, support_threshold):
+        """The keyphrase graph of K prepared keyphrases: they are scored as relevance_table scores them, the K x D table
+        stays on the device and the graph is built from it there.  rows[p] = the keyphrase (0 .. K - 1) of node position
+        p.  -> hip_backend.GraphArrays."""
+        queries = [kp.replace(" ", "") for kp in prepared_keyphrases]
+        if not all(queries):
+            raise ZeroDivisionError("float division by zero")
+        qs, qo = hip_backend.pack_queries(queries)
+        self.index.set_keyphrases(qs, qo)
+        self.index.score_resident(self.normalized)
+        return self.index.graph(rows, relevance_threshold, support_threshold, referral_confidence)
+
 
 class MultiDeviceASTRelevanceMeasure(ASTRelevanceMeasure):
     """ASTRelevanceMeasure over several GPUs of this process (`east -g N`): the documents are sharded over the devices --
@@ -222,6 +235,8 @@ class MultiDeviceASTRelevanceMeasure(ASTRelevanceMeasure):
         self.devices = [int(d) for d in spelled.split(",")] if spelled and isinstance(devices, int) else devices
         self.group = None
         self._shards = []
+
+    relevance_graph = None       # (the table is spread over the devices: keyphrases_graph keeps its host path)
 
     def _after_build(self, n_docs):
         self._shards = []
@@ -361,6 +376,15 @@ class CosineRelevanceMeasure(RelevanceMeasure):
     def relevance_table(self, prepared_keyphrases, synonimizer=None):
         """K prepared keyphrases -> K x D float64 array of scores (relevance.py:150-168 for every pair).  The synonimizer
         is accepted and ignored, as the reference does."""
+        return self._score(prepared_keyphrases, True)
+
+    def relevance_graph(self, prepared_keyphrases, rows, referral_confidence, relevance_threshold, support_threshold):
+        """The keyphrase graph of K prepared keyphrases (ASTRelevanceMeasure.relevance_graph): the query ids are prepared
+        as relevance_table prepares them, the table stays on the device."""
+        self._score(prepared_keyphrases, False)
+        return self.index.graph(rows, relevance_threshold, support_threshold, referral_confidence)
+
+    def _score(self, prepared_keyphrases, fetch):
         per_query = [self._query_terms(q) for q in prepared_keyphrases]
         offsets = np.zeros(len(per_query) + 1, dtype=np.int64)
         np.cumsum([len(q) for q in per_query], out=offsets[1:])
@@ -372,7 +396,7 @@ class CosineRelevanceMeasure(RelevanceMeasure):
             where = dict(zip(distinct, self.index.lookup(distinct).tolist()))
             ids = [where[t] for t in flat]
         return self.index.score_table(np.array(ids, dtype=np.int32), offsets,
-                                      self.term_weighting == consts.TermWeighting.TF_IDF)
+                                      self.term_weighting == consts.TermWeighting.TF_IDF, fetch)
 
     def relevance(self, keyphrase, text, synonimizer=None):
         """relevance.py:150-168: the score of a prepared keyphrase in text number `text` (one row is cached)."""

@@ -259,3 +259,22 @@ def prose_like_texts(rng, n_docs, doc_bytes, chain=256):
     flat[cap[rng.random(cap.size) < 0.08]] -= 32
     docs = text.reshape(n_docs, per_doc * chain)[:, :doc_bytes]
     return [bytes(row) for row in docs]
+
+
+def topic_score_table(rng, n_keyphrases, n_docs, n_topics=40, p_in=0.7, p_out=0.004):
+    """A K x D score table with the structure a keyphrase graph lives on (tools/graph_bench.py, the gpu tests of
+    csrc/graph.h): every document and every keyphrase has one of n_topics topics; a keyphrase occurs in a document of
+    its own topic with probability p_in and in any other with p_out.  An occurrence scores in [0.3, 1), anything else
+    in [0, 0.2): at relevance_threshold 0.25 the occurrences are exactly the planted ones.  With the defaults and
+    referral_confidence 0.6, 10 000 x 256 gives about a million edges -- keyphrases of one topic refer to each other."""
+    doc_topic = rng.integers(0, n_topics, size=n_docs)
+    kp_topic = rng.integers(0, n_topics, size=n_keyphrases)
+    scores = np.empty((n_keyphrases, n_docs), dtype=np.float64)
+    step = max(1, (1 << 22) // max(n_docs, 1))                 # (a block of rows at a time: no K x D temporaries beside the table)
+    for a in range(0, n_keyphrases, step):
+        same = kp_topic[a:a + step, None] == doc_topic[None, :]
+        u = rng.random(same.shape)
+        hit = u < np.where(same, p_in, p_out)
+        v = rng.random(same.shape)
+        scores[a:a + step] = np.where(hit, 0.3 + 0.7 * v, 0.2 * v)
+    return scores

@@ -258,7 +258,8 @@ int east_hip_score_probes(east_hip_handle_t h, int normalized, int64_t *probes);
  *     q_ids[q_offsets[k] .. q_offsets[k + 1]) = the kept tokens of keyphrase k as ids of the vector space (term ids, or
  *     class ids after east_hip_cosine_set_classes), -1 for a token outside it (it still counts in the query's length);
  *     q_len = q_offsets[K].  weighting: 0 = tf, 1 = tf-idf.  out: K x D doubles, row-major, the layout of
- *     east_hip_score_table.  score = dot(w_d, q) / (|w_d| |q|), the norm of an all-zero vector being 1.
+ *     east_hip_score_table.  score = dot(w_d, q) / (|w_d| |q|), the norm of an all-zero vector being 1.  out may be
+ *     null: the table then stays on the device only, where the keyphrase graph reads it (below).
  */
 int east_hip_cosine_build_texts(east_hip_handle_t h, const uint8_t *bytes, int64_t n_bytes, const int64_t *text_offsets,
                                 int32_t n_docs, const uint8_t *cp_class, const uint32_t *cp_upper, const uint32_t *word_hi,
@@ -274,6 +275,46 @@ int east_hip_cosine_set_classes(east_hip_handle_t h, const int32_t *term_class, 
 int east_hip_cosine_lookup(east_hip_handle_t h, const uint32_t *cps, const int64_t *offsets, int32_t n_words, int32_t *ids);
 int east_hip_cosine_score_table(east_hip_handle_t h, const int32_t *q_ids, const int64_t *q_offsets, int64_t q_len,
                                 int32_t n_keyphrases, int32_t weighting, double *out);
+
+/*
+ * The keyphrase graph (`east keyphrases graph`): the main loop of keyphrases_graph (east/applications.py:59-149) on the
+ * device, from a K x D score table that is already there.  A keyphrase occurs in a text when score >= relevance_threshold
+ * (a NaN score never does, -0.0 >= 0.0 does); its support is the number of such texts; the nodes are the positions p of
+ * the keyphrase list with (double)support >= support_threshold (applications.py:103-109); for every ordered pair of
+ * nodes (A, B), A != B, in list order, the edge A -> B exists when (double)shared / (double)max(support_A, 1) >=
+ * referral_confidence (applications.py:111-141: one correctly rounded IEEE division, as Python's).  (How: csrc/graph.h,
+ * DESIGN.md 10.)
+ *
+ * rows[p] = the table row of node position p, 0 <= rows[p] < K (a keyphrase listed twice names the same row twice);
+ * n_positions = the length of the keyphrase list.  out[0] = the kept nodes, out[1] = the edges (64 bits: nothing is cut
+ * short; an edge buffer the device cannot hold is EAST_HIP_ERR_OOM with the number of edges in the message).
+ * The build call on the RESIDENT table takes it where the last score call of the handle left it -- no score crosses the
+ * link: source EAST_HIP_GRAPH_SOURCE_AST = the table of the resident keyphrases (the last score call of the AST
+ * index, asynchronous ones included: the graph is queued behind it); EAST_HIP_GRAPH_SOURCE_COSINE = the table of the last
+ * cosine score call; EAST_HIP_GRAPH_SOURCE_UPLOADED = the copy the last build call on a host table left on the device
+ * (further graphs of one table from elsewhere, at other thresholds, without another upload).  EAST_HIP_ERR_NOT_BUILT where
+ * no such table is there (no score call since the last build or since the keyphrases were set).  The build call on a HOST
+ * table uploads K x D doubles, row-major, first.
+ * The fetch call gives the last graph (each pointer nullable): support[n_positions], kept[out[0]] = the node positions in
+ * order, and per edge, in the order of applications.py:111-141 (sources in list order, a source's targets in list order),
+ * source position, target position and the number of shared texts -- confidence = shared / max(support[source], 1).
+ * Two builds of the same input give the same bytes (no atomic decides an order).  The graph's buffers are the handle's
+ * own -- neither the EASA arena nor the cosine buffers --; the reset call releases them, destroying the handle too.
+ * Device time of the last graph build in milliseconds (events on the handle's stream around the build, its two
+ * read-backs -- kept nodes, edges -- included), -1 when there is none.
+ */
+#define EAST_HIP_GRAPH_SOURCE_AST 0
+#define EAST_HIP_GRAPH_SOURCE_COSINE 1
+#define EAST_HIP_GRAPH_SOURCE_UPLOADED 2
+int east_hip_graph_build_resident(east_hip_handle_t h, int32_t source, const int32_t *rows, int64_t n_positions,
+                                  double relevance_threshold, double support_threshold, double referral_confidence,
+                                  int64_t *out);
+int east_hip_graph_build_host(east_hip_handle_t h, const double *table, int32_t n_keyphrases, int32_t n_docs,
+                              const int32_t *rows, int64_t n_positions, double relevance_threshold, double support_threshold,
+                              double referral_confidence, int64_t *out);
+int east_hip_graph_fetch(east_hip_handle_t h, int32_t *support, int32_t *kept, int32_t *edge_source, int32_t *edge_target,
+                         int32_t *edge_shared);
+double east_hip_last_graph_ms(east_hip_handle_t h);
 
 /*
  * Several devices in one process ("single-process/8-device fits the one-process CLI best").
