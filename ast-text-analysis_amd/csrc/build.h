@@ -1,0 +1,624 @@
+// build.h -- the build of the enhanced annotated suffix array: build_impl queues it (or, dry, sizes its arena),
+// build_common is the driver behind every build entry point.
+#pragma once
+#include "dc3.h"
+#include "score.h"
+#include "tables.h"
+#include "upload.h"
+#include <chrono>
+
+static bool kgram_reserve(east_hip_index *h, u64 bins, u32 n_docs);      // (score_host.h: the build marks the score walk's k-gram tables)
+
+// min pyramid over the LCP table and the annotation table: the streaming pass decides all but the widest
+// intervals and writes pyramid level 1 on the way, the upper levels follow, then the listed wide ones
+static void annotate(east_hip_index *h, Ctx &ctx)
+{
+    const Pyramid &pyr = h->pyr;
+    const u32 n = pyr.len[0];
+    Arena &ar = *ctx.arena;
+    const size_t mark = ar.mark();
+    const u32 n_tiles = ceil_div_u32(n, ANN_TILE);
+    u32 *wide_list = ar.alloc<u32>((size_t)n_tiles * ANN_TILE);       // every tile has its own stretch
+    u32 *wide_count = ar.alloc<u32>(n_tiles);
+    const bool has_lvl1 = pyr.levels > 1;                // (a table of at most 16 entries has no level 1)
+    LAUNCH(ctx, ann_stream_kernel, n_tiles, pyr.ptr[0], (const u32 *)h->doc_off, (const u32 *)h->n_strings,
+           h->build_docs, n, h->ann, has_lvl1 ? (u32 *)pyr.ptr[1] : (u32 *)nullptr, has_lvl1 ? pyr.len[1] : 0u,
+           has_lvl1 ? pyr_padded(pyr.len[1]) : 0u, wide_list, wide_count, h->lcp);
+    // the levels above: one launch each while they are large, the top of the pyramid in a single one
+    int l = 2;
+    for (; l < pyr.levels && pyr.len[l] > PYR_TOP; l++)
+        LAUNCH(ctx, pyramid_level_kernel, ceil_div_u32(pyr_padded(pyr.len[l]), BLOCK), pyr.ptr[l - 1], pyr.len[l],
+               pyr_padded(pyr.len[l]), (u32 *)pyr.ptr[l]);
+    if (l < pyr.levels) LAUNCH(ctx, pyramid_top_kernel, 1, pyr, l);
+    LAUNCH(ctx, ann_wide_kernel, ceil_div_u32(n_tiles, BLOCK / ANN_WIDE_SLOTS), pyr, n, n_tiles, (const u32 *)wide_list,
+           (const u32 *)wide_count, h->ann);
+    ar.release(mark);
+}
+
+// symbol counts of the byte stream (the weights of the variable-length code, ht_code.h): 16 bytes per thread and step,
+// per-lane-class counters in LDS
+__global__ __launch_bounds__(BLOCK) void byte_hist_kernel(const uint8_t *__restrict__ s8, u32 n, u32 *__restrict__ counts)
+{
+    __shared__ u32 bins[4][256];
+    for (int c = 0; c < 4; c++) bins[c][threadIdx.x] = 0;
+    __syncthreads();
+    u32 *mine = bins[threadIdx.x & 3u];
+    for (u64 i = ((u64)blockIdx.x * BLOCK + threadIdx.x) * 16u; i < n; i += (u64)gridDim.x * BLOCK * 16u) {
+        const uint4 x = *reinterpret_cast<const uint4 *>(s8 + i);          // (the stream is padded to 16 bytes behind n)
+        const u32 wds[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+        for (int q = 0; q < 16; q++)
+            if (i + q < n) atomicAdd(&mine[(wds[q >> 2] >> ((q & 3) * 8)) & 0xFFu], 1u);
+    }
+    __syncthreads();
+    const u32 t = bins[0][threadIdx.x] + bins[1][threadIdx.x] + bins[2][threadIdx.x] + bins[3][threadIdx.x];
+    if (t) atomicAdd(&counts[threadIdx.x], t);
+}
+
+// The variable-length code of this build's text (ht_code.h), for the window sort to use if it pays: made from the symbol
+// counts on a build that waits for the device anyway, taken over from the build before on a speculative one (same
+// alphabet -- any alphabetic code orders correctly, a stale one is merely less compact).
+static void prepare_ht_code(east_hip_index *h, Ctx &ctx, u32 n, u32 sigma_t, u32 m_total)
+{
+    ctx.ht_max_len = 0;
+    if (ctx.dry || !h->use_s8 || !ctx.knobs.window_sort || ctx.knobs.ht_mode == 0) return;
+    if (ctx.spec) {
+        if (!h->ht_valid || h->ht_sigma != sigma_t) {
+            // (no code from the build before.  Forced -- the tests -- the build starts over with its read-backs in place and makes one)
+            if (ctx.knobs.ht_mode == 1 && sigma_t + 1 >= 8 && n >= 64) throw SpecAbort();
+            return;
+        }
+    } else {
+        h->ht_valid = false;
+        // (an alphabet of at most 5 bits -- letters only -- has nothing to gain: at best a fraction of a symbol per key)
+        if (sigma_t + 1 < 8 || (ctx.knobs.ht_mode != 1 && (bit_width_u32(sigma_t + 1) < 6 || n < 65536)) || n < 64) return;
+        Arena &ar = *ctx.arena;
+        const size_t mark = ar.mark();
+        u32 *d_counts = ar.alloc<u32>(256);
+        HIP_CHECK(hipMemsetAsync(d_counts, 0, 256 * sizeof(u32), ctx.stream));
+        LAUNCH(ctx, byte_hist_kernel, std::min<u32>(ceil_div_u32(n, BLOCK * 16), 2048), (const uint8_t *)h->s8, n, d_counts);
+        u32 h_counts[256];
+        HIP_CHECK(hipMemcpyAsync(h_counts, d_counts, sizeof(h_counts), hipMemcpyDeviceToHost, ctx.stream));
+        HIP_CHECK(sync_stream(ctx.stream));
+        ar.release(mark);
+        std::vector<u64> counts(256);
+        for (int c = 0; c < 256; c++) counts[c] = h_counts[c];
+        std::vector<u32> enc;
+        std::vector<uint16_t> dec;
+        double mean_len = 0.0;
+        if (!ht_make_tables(counts, sigma_t, m_total, enc, dec, &mean_len)) return;
+        if (!h->ht_tab.try_ensure(256 * 4 + HT_DEC_SIZE * 2)) return;
+        // (pageable host buffers: the copies are staged before the calls return)
+        HIP_CHECK(hipMemcpyAsync(h->ht_tab.p, enc.data(), 256 * 4, hipMemcpyHostToDevice, ctx.stream));
+        HIP_CHECK(hipMemcpyAsync(h->ht_tab.p + 256 * 4, dec.data(), HT_DEC_SIZE * 2, hipMemcpyHostToDevice, ctx.stream));
+        HIP_CHECK(sync_stream(ctx.stream));
+        int longest = 0;
+        for (u32 c = 0; c < 256; c++) longest = std::max(longest, (int)(enc[c] & 0xFFu));
+        h->ht_valid = true;
+        h->ht_sigma = sigma_t;
+        h->ht_max_len = longest;
+        h->ht_mean_len = mean_len;
+        if (g_trace) fprintf(stderr, "[east_hip] variable-length code: %u symbols, %.2f bits per symbol on average, longest code word %d\n",
+                             sigma_t + 1, mean_len, longest);
+    }
+    ctx.ht_enc = h->ht_tab.as<const u32>();
+    ctx.ht_dec = (const uint16_t *)(h->ht_tab.p + 256 * 4);
+    ctx.ht_max_len = h->ht_max_len;
+    ctx.ht_mean_len = h->ht_mean_len;
+}
+
+// The build proper.  With ctx.dry it only measures the arena high-water mark
+// (worst case: widest keys, recursion to the bottom).
+static void build_impl(east_hip_index *h, Ctx &ctx, const u32 *d_sym, u32 n, u32 n_docs,
+                       const i64 *doc_offsets, const int32_t *n_strings, u32 spec_sigma = 0, bool tagged = false)
+{
+    Arena &ar = *ctx.arena;
+    ar.release(0);
+    // ---- persistent arrays --------------------------------------------------
+    h->s = ar.alloc<u32>((size_t)n + 3);
+    h->s8 = ar.alloc<uint8_t>((size_t)n + 64);           // (16 zero bytes behind the stream; comparisons look up to 32 bytes ahead)
+    h->sa = ar.alloc<u32>(n);
+    h->lcp = ar.alloc<u32>(pyr_padded(n));
+    h->ann = ar.alloc<u32>(n);
+    h->up = ar.alloc<u32>(n);
+    h->down = ar.alloc<u32>(n);
+    h->next = ar.alloc<u32>(n);
+    h->doc_off = ar.alloc<u32>((size_t)n_docs + 1);
+    h->n_strings = ar.alloc<u32>(n_docs);
+    h->code_map = ar.alloc<u32>(TEXT_SYMBOLS + FLAG_WORDS + PRESENT_WORDS + 1 + LCP_BUDGET_SLOTS);   // + the flag words (FLAG_*) + the presence bitmap and its status word + the budget of deep LCP comparisons
+    h->hi_bits = tagged ? ar.alloc<u32>(HI_WORDS) : nullptr;
+    h->hi_rank = tagged ? ar.alloc<u32>(HI_WORDS) : nullptr;
+    Pyramid pyr;
+    pyr.levels = 1;
+    pyr.ptr[0] = h->lcp;
+    pyr.len[0] = n;
+    while (pyr.len[pyr.levels - 1] > PYR_FAN) {
+        if (pyr.levels >= PYR_MAX_LEVELS) east_throw(EAST_HIP_ERR_INTERNAL, "pyramid too deep");
+        const u32 len = ceil_div_u32(pyr.len[pyr.levels - 1], PYR_FAN);
+        pyr.ptr[pyr.levels] = ar.alloc<u32>(pyr_padded(len));
+        pyr.len[pyr.levels] = len;
+        pyr.levels++;
+    }
+    h->pyr = pyr;
+    h->build_docs = n_docs;
+
+    // ---- host-side small tables ---------------------------------------------
+    std::vector<u32> off32((size_t)n_docs + 1), m32(n_docs);
+    u32 longest_doc = ctx.dry ? n : 0;                    // (sizing run: as if one document held everything)
+    if (!ctx.dry) {
+        for (u32 d = 0; d <= n_docs; d++) off32[d] = (u32)doc_offsets[d];
+        for (u32 d = 0; d < n_docs; d++) longest_doc = std::max(longest_doc, off32[d + 1] - off32[d]);
+        for (u32 d = 0; d < n_docs; d++) m32[d] = (u32)n_strings[d];
+        HIP_CHECK(hipMemcpyAsync(h->doc_off, off32.data(), off32.size() * 4, hipMemcpyHostToDevice, ctx.stream));
+        HIP_CHECK(hipMemcpyAsync(h->n_strings, m32.data(), m32.size() * 4, hipMemcpyHostToDevice, ctx.stream));
+    }
+
+    const u32 gn = ceil_div_u32(n, BLOCK);
+    u32 sigma_t = TEXT_SYMBOLS - 1, m_total = n;          // dry-run worst case
+    u32 sigma_hi = tagged ? HI_SYMBOLS : 0;
+    u32 *flags = h->code_map + TEXT_SYMBOLS;              // flag words behind the code map
+    u32 *capped = flags + FLAG_CAPPED, *status = flags + FLAG_STATUS;
+    u32 *present = flags + FLAG_WORDS;                    // PRESENT_WORDS + 1 (status word): zeroed in the same fill
+    if (!ctx.dry) HIP_CHECK(hipMemsetAsync(flags, 0, (FLAG_WORDS + PRESENT_WORDS + 1 + LCP_BUDGET_SLOTS) * sizeof(u32), ctx.stream));
+    // (deep LCP comparisons -- beyond LCP_SOFT_CAP symbols -- this build may make: n / 256, see common.h)
+    ctx.lcp_budget.slots = ctx.dry ? nullptr : present + PRESENT_WORDS + 1;
+    ctx.lcp_budget.per_slot = std::max<u32>(n / 256u / LCP_BUDGET_SLOTS, 4u);
+    ctx.spec_out = flags + FLAG_KEEP;
+    ctx.zeroed_word = ctx.dry ? nullptr : flags + FLAG_PLACE_FAIL;
+    ctx.kg_bad = ctx.dry ? nullptr : flags + FLAG_KG_BAD;
+    {
+        // ---- alphabet, dense remap ---------------------------------------------
+        const size_t mark = ar.mark();
+        u32 *term_ex = ar.alloc<u32>((size_t)n + 1);      // wide-alphabet path only
+        const int vec = ((uintptr_t)d_sym & 15u) == 0;
+        const bool fused = ctx.spec && vec && h->guess.p;     // (the bytes come out of the same pass, through the last build's map)
+        if (fused) LAUNCH(ctx, presence_remap_kernel, std::min<u32>(gn, 2048), d_sym, n, h->guess.as<const u32>(), present, h->s8);
+        else LAUNCH(ctx, presence_kernel, std::min<u32>(gn, 2048), d_sym, n, vec, present);
+        LAUNCH(ctx, validate_last_symbol_kernel, ceil_div_u32(n_docs, BLOCK), d_sym, (const u32 *)h->doc_off, n_docs,
+               (u32)tagged, present + PRESENT_WORDS);
+        if (tagged) {
+            if (!ctx.dry) HIP_CHECK(hipMemsetAsync(h->hi_bits, 0, HI_WORDS * 4, ctx.stream));
+            LAUNCH_BLOCK(ctx, presence_hi_kernel, std::min<u32>(ceil_div_u32(n, PRESENCE_HI_THREADS), 256), PRESENCE_HI_THREADS,
+                         d_sym, n, h->hi_bits, status);
+            LAUNCH(ctx, hi_rank_kernel, 1, (const u32 *)h->hi_bits, h->hi_rank, flags);
+        }
+        LAUNCH(ctx, codemap_kernel, 1, (const u32 *)present, ctx.spec ? spec_sigma : 0xFFFFFFFFu, h->code_map, flags, h->guess.as<u32>(),
+               (int)fused);
+        ctx.sample_n = 0;
+        ctx.rep_n = ctx.rep_dup = 0;
+        bool sample_plans = false;                          // the sample is large enough to plan the window and the fused finish from
+        if (!ctx.dry && !ctx.spec && !tagged && n >= 1024u) {
+            // the planning sample: the middle of the longest document (read back together with the alphabet)
+            u32 dl = 0;
+            for (u32 d = 1; d < n_docs; d++)
+                if (off32[d + 1] - off32[d] > off32[dl + 1] - off32[dl]) dl = d;
+            const u32 len = off32[dl + 1] - off32[dl], cnt = std::min<u32>(SAMPLE_N, len);
+            // (many short documents: a sample of a few dozen suffixes decides nothing -- no sample, the uniform estimates.
+            // A small input's sample -- 512 suffixes or more -- only answers "is this text repetitive?": the reference's
+            // worst-case collection at n = 300, 30 K symbols, took 3.7 ms through the endgame's direct ordering of its
+            // groups of 100 and takes 0.6 through the persistent rounds, window_sort.h)
+            sample_plans = n >= 4 * SAMPLE_N && cnt >= SAMPLE_N / 4;
+            if (cnt >= 512u)
+                LAUNCH_BLOCK(ctx, sample_prefix_kernel, SAMPLE_MAX_L, SAMPLE_THREADS, d_sym, n, off32[dl] + (len - cnt) / 2, cnt,
+                             flags + FLAG_SAMPLE);
+        }
+        if (!ctx.dry) {
+            if (ctx.spec) {
+                sigma_t = spec_sigma;                        // (checked on the device; found out at the end of the build)
+            } else {
+                u32 hf[FLAG_WORDS];
+                HIP_CHECK(hipMemcpyAsync(hf, flags, sizeof(hf), hipMemcpyDeviceToHost, ctx.stream));
+                HIP_CHECK(sync_stream(ctx.stream));
+                if (hf[FLAG_STATUS] & STATUS_NO_TERMINATOR)
+                    east_throw(EAST_HIP_ERR_DOMAIN, tagged ? "a document does not end in a (tagged) string terminator"
+                                                           : "a document does not end in a string terminator (>= U+0A00)");
+                if (hf[FLAG_STATUS] & STATUS_BAD_SYMBOL)
+                    east_throw(EAST_HIP_ERR_DOMAIN, "a symbol is neither a tagged terminator nor a code point < U+110000");
+                sigma_t = hf[FLAG_SIGMA];
+                sigma_hi = tagged ? hf[FLAG_SIGMA_HI] : 0;
+                ctx.sample_n = hf[FLAG_SAMPLE + 2 * SAMPLE_MAX_L];
+                for (int l = 1; l <= SAMPLE_MAX_L; l++) {
+                    ctx.sample_dup2[l] = hf[FLAG_SAMPLE + 2 * (l - 1)];
+                    ctx.sample_dup4[l] = hf[FLAG_SAMPLE + 2 * (l - 1) + 1];
+                }
+                ctx.rep_n = ctx.sample_n;
+                ctx.rep_dup = ctx.sample_dup4[SAMPLE_MAX_L];
+                if (!sample_plans) ctx.sample_n = 0;          // (too small to plan from)
+                if (g_trace && ctx.sample_n) {
+                    fprintf(stderr, "[east_hip] sample of %u suffixes, shared prefixes (>= 2 / >= 4 of the sample) by length:", ctx.sample_n);
+                    for (int l = 1; l <= SAMPLE_MAX_L; l++) fprintf(stderr, " %d: %u/%u", l, ctx.sample_dup2[l], ctx.sample_dup4[l]);
+                    fprintf(stderr, "\n");
+                }
+            }
+            m_total = 0;
+            for (u32 d = 0; d < n_docs; d++) m_total += (u32)n_strings[d];     // checked after the build
+            h->use_s8 = sigma_t + sigma_hi <= 254;
+        }
+        sigma_t += sigma_hi;                                  // one text alphabet, the high code points above the low ones
+        if (sigma_hi && h->use_s8 && !ctx.dry) {
+            LAUNCH(ctx, remap_hi_kernel, ceil_div_u32((u64)n + 16, BLOCK), d_sym, (const u32 *)nullptr,
+                   (const u32 *)h->code_map, (const u32 *)h->hi_bits, (const u32 *)h->hi_rank, sigma_t - sigma_hi, sigma_t, n,
+                   (u32 *)nullptr, h->s8);
+        } else if (fused) {
+            // (done)
+        } else if (h->use_s8 && !ctx.dry) {
+            LAUNCH(ctx, remap_bytes_kernel, ceil_div_u32((u64)n + 16, BLOCK * 16), d_sym, (const u32 *)h->code_map, n,
+                   vec, h->s8);
+        } else {
+            // wide alphabets: dense u32 codes, terminators numbered globally by a scan
+            device_scan<TermIn, false>(ctx, TermIn{d_sym, n, (u32)tagged}, n + 1, term_ex);
+            if (sigma_hi)
+                LAUNCH(ctx, remap_hi_kernel, ceil_div_u32((u64)n + 16, BLOCK), d_sym, (const u32 *)term_ex,
+                       (const u32 *)h->code_map, (const u32 *)h->hi_bits, (const u32 *)h->hi_rank, sigma_t - sigma_hi, sigma_t, n,
+                       h->s, (uint8_t *)nullptr);
+            else
+                LAUNCH(ctx, remap_kernel, ceil_div_u32((u64)n + 16, BLOCK), d_sym, (const u32 *)term_ex,
+                       (const u32 *)h->code_map, sigma_t, n, h->s, (uint8_t *)nullptr);
+        }
+        ar.release(mark);
+    }
+    const u32 sigma = sigma_t + m_total;
+    const u32 term_first = sigma_t + 1u;
+    h->sigma_hi = ctx.dry ? 0u : sigma_hi;
+    h->sigma_t = sigma_t;
+    h->m_total = m_total;
+    h->bits0 = bit_width_u32(sigma);
+
+    // ---- suffix array of the whole shard, then partition by document -------------
+    // Text first goes through the window sort over all suffixes -- with several documents the keys carry
+    // the document number on top, so that every document's tables come out side by side --; DC3 is the
+    // bounded-work fallback (several documents: one suffix sort of the whole shard, then a stable
+    // partition by document).
+    bool window_sorted = false;
+    const int doc_bits = n_docs > 1 ? bit_width_u32(n_docs - 1) : 0;
+    h->kg_marked = false;
+    prepare_ht_code(h, ctx, n, sigma_t, m_total);
+    if ((h->use_s8 || ctx.dry) && ctx.knobs.window_sort) {       // (the sizing run prices it with 64-bit keys)
+        DocKey docs;
+        if (n_docs > 1) { docs.doc_off = h->doc_off; docs.n_docs = n_docs; docs.bits = doc_bits; docs.h_doc_off = ctx.dry ? nullptr : off32.data(); }
+        // the score walk's k-gram tables are marked off the sorted keys on the way (KgMark): as many levels
+        // as a table of at most twice a document's size (and 1 GiB in all) has room for
+        KgMark km;
+        if (!ctx.dry && n_docs <= 65535 && !getenv("EAST_HIP_NO_KG_MARKS")) {     // (the variable: experiments -- the score side then builds its tables itself)
+            km.A = sigma_t + 2;
+            u64 bins = 1;
+            while (km.k < KGRAM_KEYS_MAX_K && bins * km.A <= KGRAM_KEYS_MAX_BINS && bins * km.A <= 2 * ((u64)n / n_docs) + 4096 &&
+                   (bins * km.A + 1) * n_docs * 8 <= ((u64)1 << 31)) {
+                bins *= km.A;
+                km.k++;
+            }
+            if (km.k > 0 && kgram_reserve(h, bins, n_docs)) {
+                km.kg = h->kg.as<u32>();
+                km.doc_off = h->doc_off;
+                km.n_docs = n_docs;
+                // (the pair layout: the level above the last in a table of its own, behind the 8-byte entries)
+                // (... where the score table has many columns: with a handful of long documents the 8-byte marks cost the
+                // build more than the few thousand walks of a score call get back; forced by the test knob)
+                if (ctx.knobs.kg_pairs && (n_docs >= 16 || ctx.knobs.kg_pairs_forced)) km.kg3 = km.kg + 2 * (size_t)(bins + 1) * n_docs;
+                h->kg3 = km.kg3;
+                h->kg_up = km.kg3 ? km.kg3 + (size_t)(bins / km.A + 1) * n_docs : nullptr;
+            } else {
+                km.k = 0;
+            }
+        }
+        window_sorted = window_suffix_sort(ctx, h->s8, n, sigma_t + 1, h->sa, h->lcp, capped, docs, longest_doc,
+                                           km.k > 0 ? &km : nullptr);
+        if (window_sorted && km.k > 0) {                 // (km.k is 0 if the sort did not mark: small inputs)
+            h->kg_marked = true;
+            h->kg_pairs = km.pairs != 0;
+            h->kg_k = km.k;
+            h->kg_A = km.A;
+            h->kg_bins = km.bins;
+        }
+    }
+    ctx.stats->window_sorted = window_sorted;
+    if (ctx.spec && !window_sorted) throw SpecAbort();   // (DC3 is not written to survive a wrong guess of the alphabet)
+    // on the byte stream the LCP table comes with the suffix array: from the window keys, or (one
+    // document) out of the level-0 merge of DC3
+    const bool fused_lcp = h->use_s8 && (window_sorted || n_docs == 1);
+    if (window_sorted) {
+        ctx.stats->levels = 0;
+    } else if (n_docs == 1) {
+        ctx.stats->levels = dc3_suffix_array(ctx, h->s, n, sigma, h->sa, 0, term_first, h->use_s8 ? h->s8 : nullptr,
+                                             fused_lcp ? h->lcp : nullptr, capped);
+    } else {
+        // the suffix array of the whole shard lands in vals[0]; the partition is a stable radix sort of
+        // (document, suffix) pairs whose last pass writes into h->sa (pass i reads buffers [i % 2], writes the others)
+        const size_t mark_sa = ar.mark();
+        SortBufs<u32> sb;
+        const int last = radix_pass_count(doc_bits) & 1;
+        for (int k = 0; k < 2; k++) { sb.keys[k] = ar.alloc<u32>((size_t)n + 4); sb.vals[k] = k == last ? h->sa : ar.alloc<u32>((size_t)n + 4); }
+        u32 *sa_whole = sb.vals[0];
+        ctx.stats->levels = dc3_suffix_array(ctx, h->s, n, sigma, sa_whole, 0, term_first, h->use_s8 ? h->s8 : nullptr);
+        if (n_docs <= DOC_LDS_MAX) {
+            LAUNCH(ctx, doc_keys_lds_kernel, ceil_div_u32(n, BLOCK * 4), (const u32 *)sa_whole, (const u32 *)h->doc_off, n_docs,
+                   n, sb.keys[0]);
+        } else {
+            const int shift = std::max(0, bit_width_u32(n) - 20);
+            const u32 n_coarse = (u32)(((u64)n >> shift) + 1);
+            u32 *coarse = ar.alloc<u32>(n_coarse);
+            LAUNCH(ctx, doc_coarse_kernel, ceil_div_u32(n_coarse, BLOCK), (const u32 *)h->doc_off, n_docs, n, shift,
+                   n_coarse, coarse);
+            LAUNCH(ctx, doc_keys_kernel, ceil_div_u32(n, BLOCK * 4), (const u32 *)sa_whole, (const u32 *)h->doc_off,
+                   (const u32 *)coarse, shift, n, sb.keys[0]);
+        }
+        const int r = radix_sort_pairs<u32>(ctx, sb, n, doc_bits);
+        if (sb.vals[r] != h->sa) east_throw(EAST_HIP_ERR_INTERNAL, "document partition ended in the wrong buffer");
+        ar.release(mark_sa);
+    }
+
+    // n_strings against the terminators actually present (read back at the end of the build)
+    if (h->use_s8)
+        LAUNCH_NAMED(ctx, "validate_n_strings_kernel", (validate_n_strings_kernel<uint8_t>), ceil_div_u32(n_docs, WAVES_PER_BLOCK),
+                     (const uint8_t *)h->s8, 0xFFu, (const u32 *)h->sa, (const u32 *)h->doc_off,
+                     (const u32 *)h->n_strings, n_docs, status);
+    else
+        LAUNCH_NAMED(ctx, "validate_n_strings_kernel", (validate_n_strings_kernel<u32>), ceil_div_u32(n_docs, WAVES_PER_BLOCK),
+                     (const u32 *)h->s, sigma_t + 1u, (const u32 *)h->sa, (const u32 *)h->doc_off,
+                     (const u32 *)h->n_strings, n_docs, status);
+
+    // ---- LCP, min pyramid, annotation + child tables ------------------------------
+    {
+        const size_t mark = ar.mark();
+        u32 *rank = ctx.dry ? ar.alloc<u32>(n) : nullptr;       // only allocated for real when needed
+        if (fused_lcp) {
+            // (the table's padding up to a multiple of 16 is written by ann_stream_kernel)
+        } else if (h->use_s8) {
+            LAUNCH(ctx, lcp8_kernel, ceil_div_u32(pyr_padded(n), BLOCK), (const uint8_t *)h->s8, (const u32 *)h->sa,
+                   n, h->lcp, capped, ctx.lcp_budget);
+        } else {
+            LAUNCH(ctx, lcp_kernel, ceil_div_u32(pyr_padded(n), BLOCK), (const u32 *)h->s, (const u32 *)h->sa,
+                   n, h->lcp, capped, ctx.lcp_budget);
+        }
+        if (n_docs > 1)
+            LAUNCH(ctx, lcp_doc_starts_kernel, ceil_div_u32(n_docs, BLOCK), (const u32 *)h->doc_off, n_docs, h->lcp);
+        (void)rank;
+        ar.release(mark);
+    }
+    // (comparisons that hit the cap -- a repetitive input -- are found out about at the end of the build,
+    // together with the status word: build_common then finishes those ranks and redoes the two steps below)
+    annotate(h, ctx);
+    h->kg_built = false;
+    h->child_built = false;      // childtab_up / down / next_l_index: built on first east_hip_get_tables request
+}
+
+// A repetitive input: the ranks whose direct comparison was capped are finished with the Kasai carry
+// over the text (blocked, O(n + marked work)), then pyramid and annotation are built again.
+static void finish_capped_lcp(east_hip_index *h, Ctx &ctx)
+{
+    Arena &ar = *ctx.arena;
+    const u32 n = h->pyr.len[0];
+    const size_t mark = ar.mark();
+    const u32 gn = ceil_div_u32(n, BLOCK);
+    u32 *rank = ar.alloc<u32>(n), *count = ar.alloc<u32>(n), *apos = ar.alloc<u32>(n);
+    u32 *list = ar.alloc<u32>(n), *long_list = ar.alloc<u32>(n), *counters = ar.alloc<u32>(2);
+    uint8_t *anchor = ar.alloc<uint8_t>((size_t)n + 16);
+    const void *sym = h->use_s8 ? (const void *)h->s8 : (const void *)h->s;
+    HIP_CHECK(hipMemsetAsync(counters, 0, 2 * sizeof(u32), ctx.stream));
+    LAUNCH(ctx, inverse_sa_kernel, gn, (const u32 *)h->sa, n, rank);
+    // (tables.h, "finishing pass for unfinished LCP entries": classify, compare the irreducible positions, fill the rest)
+    if (h->use_s8) {
+        LAUNCH(ctx, (lcp_phi_classify_kernel<true>), gn, sym, (const u32 *)h->sa, (const u32 *)rank, (const u32 *)h->lcp, n, anchor, list, counters);
+        LAUNCH(ctx, (lcp_phi_compare_kernel<true>), std::min<u32>(ceil_div_u32(n, WAVES_PER_BLOCK), 8192u), sym, (const u32 *)h->sa, (const u32 *)rank, (const u32 *)list,
+               (const u32 *)counters, n, h->lcp, long_list, counters + 1);
+        LAUNCH_BLOCK(ctx, (lcp_phi_long_kernel<true>), 512, PHI_LONG_THREADS, sym, (const u32 *)h->sa, (const u32 *)rank, (const u32 *)long_list,
+                     (const u32 *)(counters + 1), n, h->lcp);
+    } else {
+        LAUNCH(ctx, (lcp_phi_classify_kernel<false>), gn, sym, (const u32 *)h->sa, (const u32 *)rank, (const u32 *)h->lcp, n, anchor, list, counters);
+        LAUNCH(ctx, (lcp_phi_compare_kernel<false>), std::min<u32>(ceil_div_u32(n, WAVES_PER_BLOCK), 8192u), sym, (const u32 *)h->sa, (const u32 *)rank, (const u32 *)list,
+               (const u32 *)counters, n, h->lcp, long_list, counters + 1);
+        LAUNCH_BLOCK(ctx, (lcp_phi_long_kernel<false>), 512, PHI_LONG_THREADS, sym, (const u32 *)h->sa, (const u32 *)rank, (const u32 *)long_list,
+                     (const u32 *)(counters + 1), n, h->lcp);
+    }
+    device_scan<U8In, true>(ctx, U8In{anchor}, n, count);
+    LAUNCH(ctx, lcp_phi_anchors_kernel, gn, (const uint8_t *)anchor, (const u32 *)count, n, apos);
+    LAUNCH(ctx, lcp_phi_fill_kernel, gn, (const uint8_t *)anchor, (const u32 *)count, (const u32 *)apos, (const u32 *)rank, n, h->lcp);
+    ar.release(mark);
+    annotate(h, ctx);
+}
+
+static size_t plan_arena_bytes(u32 n, u32 n_docs, bool lean = false, bool tagged = false, const Knobs *knobs = nullptr)
+{
+    // (a tagged stream is priced both ways: as the byte stream it becomes when its alphabet is small -- the window
+    // sort with its rounds, which the sizing run of the widest alphabet never enters -- and as dense u32 codes)
+    size_t high = 0;
+    for (int t = 0; t <= (tagged ? 1 : 0); t++) {
+        east_hip_index tmp;
+        Arena dry;
+        dry.dry = true;
+        Stats st;
+        Ctx ctx;
+        if (knobs) ctx.knobs = *knobs;
+        ctx.arena = &dry;
+        ctx.dry = true;
+        ctx.lean = lean;
+        ctx.stats = &st;
+        build_impl(&tmp, ctx, nullptr, n, n_docs, nullptr, nullptr, 0, t == 1);
+        high = std::max(high, dry.high + (tagged ? 2 * (size_t)HI_WORDS * 4 + 1024 : 0));
+    }
+    return high + (1u << 20);
+}
+
+static void ensure_arena(east_hip_index *h, size_t bytes)
+{
+    if (h->arena.cap >= bytes) return;
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    if (h->arena.base) HIP_CHECK(hipFree(h->arena.base));
+    h->arena.base = nullptr;
+    h->arena.cap = 0;
+    h->built = false;
+    h->table_scored = false;
+    void *p = nullptr;
+    hipError_t e = hipMalloc(&p, bytes);
+    if (e != hipSuccess) {
+        char b[160];
+        snprintf(b, sizeof(b), "hipMalloc of the %.2f GiB build arena failed: %s", bytes / 1073741824.0,
+                 hipGetErrorString(e));
+        east_throw(EAST_HIP_ERR_OOM, b);
+    }
+    h->arena.base = (char *)p;
+    h->arena.cap = bytes;
+}
+
+static void check_build_args(i64 n_total, const i64 *doc_offsets, const int32_t *n_strings, int32_t n_docs)
+{
+    if (n_docs < 1 || !doc_offsets || !n_strings) east_throw(EAST_HIP_ERR_INVALID, "n_docs < 1 or null offsets");
+    if (n_total < 1 || n_total >= (i64)0x7FFFFFF0) east_throw(EAST_HIP_ERR_INVALID, "n_total must be in [1, 2^31-16)");
+    if (doc_offsets[0] != 0 || doc_offsets[n_docs] != n_total)
+        east_throw(EAST_HIP_ERR_INVALID, "doc_offsets must start at 0 and end at n_total");
+    for (int32_t d = 0; d < n_docs; d++) {
+        if (doc_offsets[d + 1] <= doc_offsets[d]) east_throw(EAST_HIP_ERR_INVALID, "empty document (the reference raises EmptyStringsCollectionException)");
+        if (n_strings[d] < 1 || n_strings[d] > doc_offsets[d + 1] - doc_offsets[d])
+            east_throw(EAST_HIP_ERR_INVALID, "n_strings[d] must be in [1, n_d]");
+    }
+}
+
+static void build_common(east_hip_index *h, const u32 *sym, bool sym_on_host, i64 n_total, const i64 *doc_offsets,
+                         const int32_t *n_strings, int32_t n_docs, bool tagged)
+{
+    if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
+    if (!sym) east_throw(EAST_HIP_ERR_INVALID, "null symbols");
+    check_build_args(n_total, doc_offsets, n_strings, n_docs);
+    use_device(h);
+    h->built = false;
+    h->table_scored = false;
+    const Knobs kn = knobs_snapshot();                   // (the test knobs of this call, from its sizing run to its last launch)
+    const u32 n = (u32)n_total;
+    // (host symbols of the reference encoding go up as 16-bit words where that pays: upload_symbols_narrow)
+    ring_adopt(h, false);
+    const bool narrow_shape = sym_on_host && !tagged && n >= SYM_NARROW_MIN && getenv("EAST_HIP_NO_SYMBOL_NARROW") == nullptr;
+    if (narrow_shape && !h->ring) {
+        // The first host-resident build of this size pins the ring in line (3-5 ms, once per handle) and goes up narrowed
+        // already: until round 6 it took the plain copy, left the pinning to a background thread, and the call behind it
+        // -- arriving while that thread was still at work -- took the plain copy again (6.9, 6.7, then 3.5 ms a call).
+        ring_adopt(h, true);                                // (a background pin under way: its ring)
+        (void)ring_pin_now(h);                              // (no ring: the plain copy)
+    }
+    const bool narrow = narrow_shape && h->ring != nullptr;
+    const size_t narrow_bytes = narrow_shape ? (((size_t)n + 8) * 2 + 255) & ~(size_t)255 : 0;    // (also while the ring is still being pinned: the arena is sized once)
+    const size_t staging_bytes = (sym_on_host ? ((size_t)n * 4 + 255) & ~(size_t)255 : 0) + narrow_bytes;
+    if (h->plan_n != n || h->plan_docs != (u32)n_docs || h->plan_epoch != kn.plan_epoch || h->plan_tagged != tagged) {     // (the sizing run costs host time: remembered per shape)
+        h->plan_bytes = plan_arena_bytes(n, (u32)n_docs, false, tagged, &kn);
+        h->plan_tagged = tagged;
+        h->plan_n = n;
+        h->plan_docs = (u32)n_docs;
+        h->plan_epoch = kn.plan_epoch;
+    }
+    size_t need = h->plan_bytes + staging_bytes;
+    bool lean = kn.force_lean;
+    if (!lean && need > h->arena.cap) {
+        // the tie-refinement rounds are the largest consumer: when they do not fit next to what else
+        // lives on the device, build without them (heavy ties then take the DC3 recursion)
+        size_t free_b = 0, total_b = 0;
+        HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+        lean = need > (size_t)(0.92 * (double)(free_b + h->arena.cap));
+    }
+    if (lean) need = plan_arena_bytes(n, (u32)n_docs, true, tagged, &kn) + staging_bytes;
+    u32 *staging = nullptr;
+    {
+        const size_t cap_before = h->arena.cap;
+        const auto t_a = std::chrono::steady_clock::now();
+        ensure_arena(h, need);
+        if (g_trace && h->arena.cap != cap_before)
+            fprintf(stderr, "[east_hip] build: arena grown to %.2f GiB in %.2f ms\n", h->arena.cap / 1073741824.0,
+                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_a).count());
+    }
+    if (sym_on_host) {   // raw symbols are staged at the top of the arena
+        staging = (u32 *)(h->arena.base + (h->arena.cap - (((size_t)n * 4 + 255) & ~(size_t)255)));
+        int went = 0;
+        if (narrow) {
+            // bytes first where the text may fit them (the first 64 Ki symbols say: word text does, Cyrillic does not); a
+            // symbol that does not fit further on starts the upload over with 16-bit words, for this call and the handle's later ones
+            static const bool no_bytes = getenv("EAST_HIP_NO_SYMBOL_BYTES") != nullptr;
+            bool bytes = !no_bytes && !h->bytes_refused;
+            for (u32 i = 0; bytes && i < std::min<u32>(n, 65536u); i++) bytes = sym[i] < 0xFFu || sym[i] >= TEXT_SYMBOLS;
+            if (bytes && upload_symbols_narrow<uint8_t>(h, sym, n, staging, (uint8_t *)((char *)staging - narrow_bytes))) went = 2;
+            else {
+                if (bytes) h->bytes_refused = true;
+                (void)upload_symbols_narrow<uint16_t>(h, sym, n, staging, (uint16_t *)((char *)staging - narrow_bytes));
+                went = 1;
+            }
+        } else HIP_CHECK(hipMemcpyAsync(staging, sym, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+        h->narrow_upload = went;
+        sym = staging;
+    } else h->narrow_upload = 0;
+    h->stats = Stats();
+    h->arena.high = 0;
+    Ctx ctx = handle_ctx(h, &h->arena, &h->stats);
+    ctx.knobs = kn;
+    ctx.lean = lean;
+    // The build is queued WITHOUT waiting for the device wherever the previous build on this handle says what
+    // to expect (alphabet size, no large tie groups): one read-back at the end finds out whether it was
+    // right.  If not -- or on a handle's first build -- the build runs with its read-backs in place.
+    u32 flags[FLAG_WORDS] = {0};
+    auto run = [&](bool spec, bool spec_rounds) -> bool {
+        ctx.spec = spec;
+        ctx.spec_rounds = spec && spec_rounds;
+        ctx.plan_wide = spec ? h->plan_wide : -1;        // (a build that waits for the alphabet plans from its own sample)
+        ctx.plan_fused = spec ? h->plan_fused : -1;
+        ctx.plan_ht = spec ? h->plan_ht : -1;
+        ctx.plan_persist = spec ? h->plan_persist : -1;
+        try {
+            build_impl(h, ctx, sym, n, (u32)n_docs, doc_offsets, n_strings, h->hint_sigma, tagged);
+        } catch (const SpecAbort &) {
+            HIP_CHECK(hipStreamSynchronize(h->stream));
+            return false;
+        } catch (const EastError &) {
+            if (!spec) throw;                            // (whatever a wrong guess ran into: the build is repeated without guesses)
+            (void)hipStreamSynchronize(h->stream);
+            return false;
+        }
+        HIP_CHECK(hipEventRecord(h->ev1, h->stream));
+        HIP_CHECK(hipMemcpyAsync(flags, h->code_map + TEXT_SYMBOLS, sizeof(flags), hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(sync_stream(h->stream));
+        return true;
+    };
+    HIP_CHECK(hipEventRecord(h->ev0, h->stream));
+    // (the alphabet is guessed whenever the last build took the window sort; that no tie group is large only if it found none)
+    const bool speculate = kn.speculate && kn.window_sort && h->hint_valid && h->hint_window && h->hint_sigma <= 254 && !tagged;
+    const bool spec_rounds = speculate && h->hint_no_rounds;
+    const bool went_through = run(speculate, spec_rounds);
+    if (speculate && (!went_through || (flags[FLAG_STATUS] & STATUS_SIGMA_GUESS) ||
+                      (spec_rounds && (flags[FLAG_KEEP] || flags[FLAG_FAIL])))) {
+        if (g_trace) fprintf(stderr, "[east_hip] speculative build guessed wrong: building again\n");
+        h->stats = Stats();
+        run(false, false);
+    }
+    const u32 status = flags[FLAG_STATUS];
+    if (status & STATUS_NO_TERMINATOR)
+        east_throw(EAST_HIP_ERR_DOMAIN, "a document does not end in a string terminator (>= U+0A00)");
+    if (flags[FLAG_CAPPED] && !(status & STATUS_N_STRINGS)) {
+        finish_capped_lcp(h, ctx);
+        HIP_CHECK(hipEventRecord(h->ev1, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+    }
+    if (status & STATUS_N_STRINGS)
+        east_throw(EAST_HIP_ERR_DOMAIN, tagged ? "n_strings does not match the tagged terminators found in a document"
+                                               : "n_strings does not match the terminators found in a document "
+                                                 "(text symbols must be < U+0A00 unless the terminators are tagged)");
+    if (flags[FLAG_KG_BAD]) h->kg_marked = false;    // (the score side then builds its k-gram tables itself)
+    h->hint_valid = !tagged || h->sigma_hi == 0;
+    h->hint_sigma = h->sigma_t;
+    h->hint_window = h->stats.window_sorted != 0;
+    h->plan_wide = h->stats.window_sorted ? ctx.did_wide : -1;
+    // (hardly anything tied behind the wide window -- another kind of text on the same handle: back to the estimate)
+    if (ctx.did_wide && h->stats.first_n > 0 && h->stats.first_kept * 50 < h->stats.first_n) h->plan_wide = -1;
+    h->plan_fused = h->stats.window_sorted ? ctx.did_fused : -1;
+    h->plan_ht = h->stats.window_sorted ? ctx.did_ht : -1;
+    h->plan_persist = h->stats.window_sorted ? ctx.did_persist : -1;
+    // (the same for the fused finish: it handed more than a few per cent of the suffixes to the rounds, or the separate
+    // placement pass left next to nothing -- another kind of text than the plan was made for: the next build decides anew)
+    if (h->stats.first_n > 0 && ((ctx.did_fused && h->stats.first_kept * 20 > h->stats.first_n) ||
+                                 (!ctx.did_fused && h->stats.first_kept * 50 < h->stats.first_n)))
+        h->plan_fused = -1;
+    h->hint_no_rounds = h->stats.window_sorted && h->stats.refine_rounds == 0 && !h->stats.long_repeats;
+    h->prof.collect();
+    HIP_CHECK(hipEventElapsedTime(&h->last_build_ms, h->ev0, h->ev1));
+    h->n = n;
+    if (h->n_docs != (u32)n_docs) h->n_kp = 0;       // resident keyphrase scratch is sized per n_docs
+    h->n_docs = (u32)n_docs;
+    h->h_doc_off.assign(doc_offsets, doc_offsets + n_docs + 1);
+    h->h_n_strings.assign(n_strings, n_strings + n_docs);
+    h->built = true;
+    ring_pin_later(h);
+}

@@ -85,6 +85,44 @@ struct Arena {
     template <class T> T *alloc(size_t count) { return (T *)alloc_bytes(count * sizeof(T)); }
 };
 
+// A device allocation of its own that belongs to a handle (or to its cosine / graph state) and grows on demand: what is
+// in it is lost when it grows.  drain: a stream whose queued work may still use the old allocation, waited for before it
+// is freed.
+struct DevBuf {
+    char *p = nullptr;
+    size_t cap = 0;
+    bool try_ensure(size_t bytes, hipStream_t drain = nullptr)      // false: no memory -- the buffer is left empty
+    {
+        if (bytes <= cap) return true;
+        if (drain) HIP_CHECK(hipStreamSynchronize(drain));
+        release();
+        void *q = nullptr;
+        if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); return false; }
+        p = (char *)q;
+        cap = bytes;
+        return true;
+    }
+    void ensure(size_t bytes, const char *what, hipStream_t drain = nullptr)
+    {
+        if (!try_ensure(bytes, drain))
+            east_throw(EAST_HIP_ERR_OOM, "hipMalloc of " + std::to_string(bytes) + " bytes for " + what + " failed");
+    }
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    template <class T> T *as() const { return (T *)p; }
+    Arena arena() const
+    {
+        Arena a;
+        a.base = p;
+        a.cap = cap;
+        return a;
+    }
+};
+
 struct Stats {
     i64 levels = 0, levels_resolved = 0, refine_rounds = 0, window_sorted = 0, merge_elems = 0, radix_passes = 0, radix_elems = 0, radix_elem_bytes = 0;
     i64 radix_elems_u32 = 0, radix_elems_u64 = 0, radix_passes_u32 = 0, radix_passes_u64 = 0;
@@ -208,7 +246,7 @@ struct Ctx {
     Arena *arena = nullptr;
     bool dry = false;
     bool lean = false;          // no tie-refinement rounds (their buffers did not fit the device)
-    // Speculative build (east_hip.hip, build_common): the host does not wait for the device where the previous
+    // Speculative build (build.h, build_common): the host does not wait for the device where the previous
     // build on the handle tells it what to expect -- the size of the text alphabet, "no suffix is left in a
     // large tie group after the placement pass".  The device checks both and the one read-back at the
     // end of the build finds out; a wrong guess costs a second, non-speculative build.

@@ -539,44 +539,13 @@ __global__ __launch_bounds__(BLOCK) void cos_score_kernel(const int32_t *__restr
 }
 
 // ============================================================================================================ host ==
-// A device allocation of the cosine state, grown on demand.  Every buffer is the handle's own: a cosine build never
-// touches the EASA index's arena.
-struct CosBuf {
-    char *p = nullptr;
-    size_t cap = 0;
-    void ensure(size_t bytes)
-    {
-        if (bytes <= cap) return;
-        release();
-        void *q = nullptr;
-        if (hipMalloc(&q, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            east_throw(EAST_HIP_ERR_OOM, "hipMalloc of the cosine index failed");
-        }
-        p = (char *)q;
-        cap = bytes;
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    Arena arena() const
-    {
-        Arena a;
-        a.base = p;
-        a.cap = cap;
-        return a;
-    }
-};
-
+// The cosine state's device buffers are the handle's own (DevBuf): a cosine build never touches the EASA index's arena.
 // a vector space the scores are taken in: the terms, or classes of terms (the stems)
 struct CosUnits {
     u32 n_units = 0, P = 0;
     u32 *unit_off = nullptr, *post_doc = nullptr, *post_unit = nullptr, *post_cnt = nullptr;
     u32 *inv_perm = nullptr, *doc_off = nullptr;        // a posting's place in document order; per document its range there
-    CosBuf weights;                                       // per weighting (0 tf, 1 tf-idf): P weights and D norms, made on first use
+    DevBuf weights;                                       // per weighting (0 tf, 1 tf-idf): P weights and D norms, made on first use
     bool w_valid[2] = {false, false};
 };
 
@@ -584,12 +553,12 @@ struct CosState {
     bool built = false, use_classes = false;
     u32 n_docs = 0, n_kept = 0, n_runs = 0, V = 0, attempts = 0;
     u64 B = 0, mask = 0;                                  // hash base and mask of the attempt that passed the verification
-    CosBuf text;             // scratch: bytes, code points, tokens (after the build: the scratch of the weights)
-    CosBuf work;             // scratch: the term sort and what goes with it (after the build: classes, look-ups)
-    CosBuf index;            // what stays: runs, the terms' places, per-document lengths, the terms' postings
-    CosBuf term_text;        // the terms' code points
-    CosBuf classes;          // the classes' postings
-    CosBuf score;            // the last score call's queries and table
+    DevBuf text;             // scratch: bytes, code points, tokens (after the build: the scratch of the weights)
+    DevBuf work;             // scratch: the term sort and what goes with it (after the build: classes, look-ups)
+    DevBuf index;            // what stays: runs, the terms' places, per-document lengths, the terms' postings
+    DevBuf term_text;        // the terms' code points
+    DevBuf classes;          // the classes' postings
+    DevBuf score;            // the last score call's queries and table
     u64 *run_key = nullptr;
     u32 *run_term = nullptr, *term_off = nullptr, *term_len = nullptr, *tcp = nullptr, *n_d = nullptr;
     CosUnits terms, cls;
@@ -597,18 +566,8 @@ struct CosState {
     double *table = nullptr;                              // the last score call's K x D table, where it lies in `score` (graph.h reads it there)
     u32 table_K = 0;
     bool table_valid = false;
-    CosBuf *bufs[8] = {&text, &work, &index, &term_text, &classes, &score, &terms.weights, &cls.weights};
+    DevBuf *bufs[8] = {&text, &work, &index, &term_text, &classes, &score, &terms.weights, &cls.weights};
 };
-
-static Ctx cos_ctx(east_hip_index *h, Arena *arena, Stats *stats)
-{
-    Ctx ctx;
-    ctx.stream = h->stream;
-    ctx.arena = arena;
-    ctx.stats = stats;           // (not the handle's: east_hip_build_info describes the EASA build)
-    ctx.prof = &h->prof;
-    return ctx;
-}
 
 static CosState &cos_built(east_hip_index *h)
 {
@@ -672,9 +631,9 @@ static void cos_build(east_hip_index *h, const uint8_t *bytes, i64 n_bytes64, co
 
     // ---- bytes -> code points -> tokens (at most one token per two code points, plus one)
     const size_t n_tok_max = (size_t)N / 2 + 2;
-    c.text.ensure((size_t)N * 6 + n_tok_max * 20 + (size_t)N / 32 + (size_t)D * 16 + ((size_t)1 << 20));
+    c.text.ensure((size_t)N * 6 + n_tok_max * 20 + (size_t)N / 32 + (size_t)D * 16 + ((size_t)1 << 20), "the cosine index");
     Arena a1 = c.text.arena();
-    Ctx ctx = cos_ctx(h, &a1, &stats);
+    Ctx ctx = handle_ctx(h, &a1, &stats);
     HIP_CHECK(hipEventRecord(h->ev0, h->stream));
     uint8_t *d_bytes = a1.alloc<uint8_t>((size_t)N + 32);
     u32 *d_text_off = a1.alloc<u32>((size_t)D + 1);
@@ -729,7 +688,7 @@ static void cos_build(east_hip_index *h, const uint8_t *bytes, i64 n_bytes64, co
 
     // ---- what stays (runs, terms and postings are at most as many as the kept tokens)
     const size_t K1 = (size_t)n_kept + 2;
-    c.index.ensure(K1 * 48 + (size_t)D * 12 + ((size_t)1 << 16));
+    c.index.ensure(K1 * 48 + (size_t)D * 12 + ((size_t)1 << 16), "the cosine index");
     Arena ai = c.index.arena();
     c.run_key = ai.alloc<u64>(K1);
     c.run_term = ai.alloc<u32>(K1);
@@ -746,7 +705,7 @@ static void cos_build(east_hip_index *h, const uint8_t *bytes, i64 n_bytes64, co
 
     // ---- the kept tokens and their pieces
     const size_t n_pc_max = (size_t)n_kept + n_cp / COS_PIECE + 2;
-    c.work.ensure(K1 * 160 + n_pc_max * 12 + ((size_t)n_stop_cps + 3 * (size_t)n_stop) * 4 + ((size_t)4 << 20));
+    c.work.ensure(K1 * 160 + n_pc_max * 12 + ((size_t)n_stop_cps + 3 * (size_t)n_stop) * 4 + ((size_t)4 << 20), "the cosine index");
     Arena a2 = c.work.arena();
     ctx.arena = &a2;
     u32 *kstart = a2.alloc<u32>(K1), *klen = a2.alloc<u32>(K1), *kdoc = a2.alloc<u32>(K1), *npc = a2.alloc<u32>(K1),
@@ -865,7 +824,7 @@ static void cos_build(east_hip_index *h, const uint8_t *bytes, i64 n_bytes64, co
     u32 n_tcp = 0;
     HIP_CHECK(hipMemcpyAsync(&n_tcp, c.term_off + V, 4, hipMemcpyDeviceToHost, h->stream));
     HIP_CHECK(hipStreamSynchronize(h->stream));
-    c.term_text.ensure(((size_t)n_tcp + 1) * 4);
+    c.term_text.ensure(((size_t)n_tcp + 1) * 4, "the cosine index");
     c.tcp = (u32 *)c.term_text.p;
     if (V)
         LAUNCH(ctx, cos_term_text_kernel, ceil_div_u32(V, WAVES_PER_BLOCK), (const u32 *)cpu, (const u32 *)term_run,
@@ -901,7 +860,7 @@ static void cos_set_classes(east_hip_index *h, const int32_t *term_class, int32_
     c.use_classes = false;
     U.w_valid[0] = U.w_valid[1] = false;
     const size_t K1 = (size_t)std::max(P, C) + 2;
-    c.classes.ensure(K1 * 24 + (size_t)D * 4 + ((size_t)1 << 16));
+    c.classes.ensure(K1 * 24 + (size_t)D * 4 + ((size_t)1 << 16), "the cosine index");
     Arena ac = c.classes.arena();
     U.unit_off = ac.alloc<u32>(K1);
     U.post_doc = ac.alloc<u32>(K1);
@@ -910,9 +869,9 @@ static void cos_set_classes(east_hip_index *h, const int32_t *term_class, int32_
     U.inv_perm = ac.alloc<u32>(K1);
     U.doc_off = ac.alloc<u32>((size_t)D + 1);
     Stats stats;
-    c.work.ensure(cos_align(((size_t)c.V + 1) * 4) + ((size_t)P + 2) * 64 + ((size_t)4 << 20));
+    c.work.ensure(cos_align(((size_t)c.V + 1) * 4) + ((size_t)P + 2) * 64 + ((size_t)4 << 20), "the cosine index");
     Arena a = c.work.arena();
-    Ctx ctx = cos_ctx(h, &a, &stats);
+    Ctx ctx = handle_ctx(h, &a, &stats);
     u32 *d_tc = a.alloc<u32>((size_t)c.V + 1);
     SortBufs<u64> sb;
     for (int k = 0; k < 2; k++) { sb.keys[k] = a.alloc<u64>((size_t)P + 1); sb.vals[k] = a.alloc<u32>((size_t)P + 1); }
@@ -953,9 +912,9 @@ static void cos_lookup(east_hip_index *h, const u32 *cps, const i64 *offsets, in
     }
     use_device(h);
     Stats stats;
-    c.work.ensure(cos_align(((size_t)n_cps + 1) * 4) + cos_align(((size_t)n_words + 1) * 4) * 2 + 4096);
+    c.work.ensure(cos_align(((size_t)n_cps + 1) * 4) + cos_align(((size_t)n_words + 1) * 4) * 2 + 4096, "the cosine index");
     Arena a = c.work.arena();
-    Ctx ctx = cos_ctx(h, &a, &stats);
+    Ctx ctx = handle_ctx(h, &a, &stats);
     u32 *d_w = a.alloc<u32>((size_t)n_cps + 1), *d_off = a.alloc<u32>((size_t)n_words + 1);
     int32_t *d_out = a.alloc<int32_t>((size_t)n_words + 1);
     if (n_cps) HIP_CHECK(hipMemcpyAsync(d_w, cps, (size_t)n_cps * 4, hipMemcpyHostToDevice, h->stream));
@@ -973,7 +932,7 @@ static void cos_weight_ptrs(CosUnits &U, u32 D, int wt, double **w, double **nor
     const size_t wb = cos_align(((size_t)U.P + 1) * 8), nb = cos_align(((size_t)D + 1) * 8);
     if (U.weights.cap < 2 * (wb + nb)) {
         U.w_valid[0] = U.w_valid[1] = false;
-        U.weights.ensure(2 * (wb + nb));
+        U.weights.ensure(2 * (wb + nb), "the cosine index");
     }
     *w = (double *)(U.weights.p + wt * (wb + nb));
     *norm = (double *)(U.weights.p + wt * (wb + nb) + wb);
@@ -1001,7 +960,7 @@ static void cos_score(east_hip_index *h, const int32_t *q_ids, const i64 *q_offs
     const u32 D = c.n_docs, total = (u32)q_len;
     const size_t b_ids = cos_align(((size_t)total + 1) * 4), b_off = cos_align(((size_t)K + 1) * 4),
                  b_qw = cos_align(((size_t)total + 1) * 8), table = (size_t)K * D * 8;
-    c.score.ensure(b_ids + b_off + b_qw + table);
+    c.score.ensure(b_ids + b_off + b_qw + table, "the cosine index");
     int32_t *d_ids = (int32_t *)c.score.p;
     u32 *d_off = (u32 *)(c.score.p + b_ids);
     double *d_qw = (double *)(c.score.p + b_ids + b_off), *d_out = (double *)(c.score.p + b_ids + b_off + b_qw);
@@ -1009,7 +968,7 @@ static void cos_score(east_hip_index *h, const int32_t *q_ids, const i64 *q_offs
     cos_weight_ptrs(U, D, weighting, &w, &norm);
     Stats stats;
     Arena a = c.text.arena();             // (the build's first scratch: 6 bytes and more per byte of text, P <= bytes / 4)
-    Ctx ctx = cos_ctx(h, &a, &stats);
+    Ctx ctx = handle_ctx(h, &a, &stats);
     HIP_CHECK(hipEventRecord(h->ev0, h->stream));
     if (!U.w_valid[weighting]) {
         double *sq = a.alloc<double>((size_t)U.P + 1);
@@ -1043,14 +1002,14 @@ static void cos_reset(east_hip_index *h)
     c->table_valid = false;
     c->terms.w_valid[0] = c->terms.w_valid[1] = c->cls.w_valid[0] = c->cls.w_valid[1] = false;
     c->build_ms = c->score_ms = -1.f;
-    for (CosBuf *b : c->bufs)                               // (a recycled handle keeps small buffers only, as east_hip_reset does)
+    for (DevBuf *b : c->bufs)                               // (a recycled handle keeps small buffers only, as east_hip_reset does)
         if (b->cap > ((size_t)64 << 20)) b->release();
 }
 
 static void cos_destroy(east_hip_index *h)
 {
     if (!h->cos) return;
-    for (CosBuf *b : h->cos->bufs) b->release();
+    for (DevBuf *b : h->cos->bufs) b->release();
     delete h->cos;
     h->cos = nullptr;
 }

@@ -1,0 +1,251 @@
+// debug_api.h -- the debug ABI of include/east_hip.h: the test knobs and the kernel-level test entry points.
+#pragma once
+
+struct DebugScope {
+    hipStream_t stream = nullptr;
+    Arena arena;
+    Stats stats;
+    Ctx ctx;
+    DebugScope(int device, size_t bytes)
+    {
+        int c = 0;
+        if (hipGetDeviceCount(&c) != hipSuccess || c <= 0)
+            east_throw(EAST_HIP_ERR_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
+        if (device < 0 || device >= c) east_throw(EAST_HIP_ERR_NO_DEVICE, "device ordinal out of range");
+        use_device_ordinal(device);
+        HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        void *p = nullptr;
+        HIP_CHECK(hipMalloc(&p, bytes));
+        arena.base = (char *)p;
+        arena.cap = bytes;
+        ctx.stream = stream;
+        ctx.arena = &arena;
+        ctx.stats = &stats;
+    }
+    ~DebugScope()
+    {
+        if (stream) (void)hipStreamSynchronize(stream);
+        if (arena.base) (void)hipFree(arena.base);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+template <class K> static void debug_sort(int device, K *keys, u32 *vals, i64 n, int bits)
+{
+    if (n < 0 || n >= (i64)0x7FFFFFF0 || !keys || !vals || bits < 1 || bits > (int)sizeof(K) * 8)
+        east_throw(EAST_HIP_ERR_INVALID, "bad radix sort arguments");
+    if (n == 0) return;
+    DebugScope sc(device, (size_t)n * (sizeof(K) + 4) * 2 + (40u << 20));
+    SortBufs<K> sb;
+    for (int k = 0; k < 2; k++) { sb.keys[k] = sc.arena.alloc<K>(n); sb.vals[k] = sc.arena.alloc<u32>(n); }
+    HIP_CHECK(hipMemcpyAsync(sb.keys[0], keys, (size_t)n * sizeof(K), hipMemcpyHostToDevice, sc.stream));
+    HIP_CHECK(hipMemcpyAsync(sb.vals[0], vals, (size_t)n * 4, hipMemcpyHostToDevice, sc.stream));
+    const int r = radix_sort_pairs<K>(sc.ctx, sb, (u32)n, bits);
+    HIP_CHECK(hipMemcpyAsync(keys, sb.keys[r], (size_t)n * sizeof(K), hipMemcpyDeviceToHost, sc.stream));
+    HIP_CHECK(hipMemcpyAsync(vals, sb.vals[r], (size_t)n * 4, hipMemcpyDeviceToHost, sc.stream));
+    HIP_CHECK(hipStreamSynchronize(sc.stream));
+}
+
+extern "C" {
+
+int east_hip_debug_set_rank_bucket_bytes(int64_t bytes)
+{
+    if (bytes < 0) return EAST_HIP_ERR_INVALID;
+    knobs_update([&](Knobs &k) { k.rank_bucket_bytes = (size_t)bytes; k.plan_epoch++; });
+    return EAST_HIP_OK;
+}
+
+int east_hip_debug_set_window_sort(int enabled)
+{
+    // 0: DC3 only; 1: the default; 2: lean (no refinement rounds); 3: 64-bit window keys; 4 / 5: as 1 / 3 without the
+    // fused finish (every radix pass global, then lvl0_place_kernel)
+    knobs_update([&](Knobs &k) {
+    k.window_sort = enabled != 0;
+    k.force_lean = enabled == 2;
+    k.force_wide_keys = enabled == 3 || enabled == 5;
+    k.fused_finish = enabled != 4 && enabled != 5 && enabled != 9 && getenv("EAST_HIP_NO_FUSED_FINISH") == nullptr;
+    k.force_fused = enabled == 6 || getenv("EAST_HIP_FORCE_FUSED") != nullptr;                        // 6: as 1, the fused finish whatever the plan says (skewed text through it)
+    // 7: as 1, first-level keys of variable-length code words wherever a code can be made (ht_code.h); 9: the same
+    // without the fused finish; 8: as 1 without such keys
+    k.ht_mode = enabled == 7 || enabled == 9 ? 1 : enabled == 8 ? 0 : env_int("EAST_HIP_HT", -1);
+    k.plan_epoch++;
+    });
+    return EAST_HIP_OK;
+}
+
+int east_hip_debug_set_segmented_sort(int mode)
+{
+    // -1: the default (by size: a few large documents); 0: never (the document number is a key digit); 1: wherever it
+    // can be done (2 .. RS_SEG_MAX_DOCS documents of any size)
+    knobs_update([&](Knobs &k) { k.seg_mode = mode < 0 ? env_int("EAST_HIP_SEG", -1) : (mode != 0); k.plan_epoch++; });
+    return EAST_HIP_OK;
+}
+
+int east_hip_debug_alphabetic_code(const uint64_t *weights, int32_t n, uint32_t *code, int32_t *len)
+{
+    // host only: the order-preserving variable-length code of csrc/ht_code.h for n symbols with the given weights
+    if (!weights || !code || !len || n < 1) return EAST_HIP_ERR_INVALID;
+    std::vector<u64> w(weights, weights + n);
+    std::vector<u32> c;
+    std::vector<int> l;
+    if (!ht_build_code(w, c, l)) return EAST_HIP_ERR_DOMAIN;
+    for (int i = 0; i < n; i++) { code[i] = c[i]; len[i] = l[i]; }
+    return EAST_HIP_OK;
+}
+
+int east_hip_debug_narrow_symbols(const uint32_t *symbols, int64_t n, uint16_t *out, int vector)
+{
+    // host only: what upload_symbols_narrow's host threads do to a stretch of symbols on its way into the pinned ring
+    // (vector != 0: the AVX2 form where the CPU has it; 0: the plain loop)
+    if (!symbols || !out || n < 0) return EAST_HIP_ERR_INVALID;
+    if (vector) narrow_symbols(symbols, out, (size_t)n);
+    else
+        for (int64_t i = 0; i < n; i++) out[i] = symbols[i] < TEXT_SYMBOLS ? (uint16_t)symbols[i] : (uint16_t)SYM_TERMINATOR16;
+    return vector && g_have_avx2 ? 1 : EAST_HIP_OK;
+}
+
+int east_hip_debug_narrow_symbols8(const uint32_t *symbols, int64_t n, uint8_t *out, int vector)
+{
+    // host only, as above: the narrowing to bytes.  Returns 1 when every symbol fitted (text below 0xFF, terminators from
+    // U+0A00 on), 0 when one did not, + 2 when the AVX2 form ran
+    if (!symbols || !out || n < 0) return EAST_HIP_ERR_INVALID;
+    bool ok = true;
+    if (vector) ok = narrow_symbols8(symbols, out, (size_t)n);
+    else
+        for (int64_t i = 0; i < n; i++) { const u32 c = symbols[i]; ok &= !(c >= 0xFFu && c < TEXT_SYMBOLS); out[i] = c < 0xFFu ? (uint8_t)c : (uint8_t)0xFFu; }
+    return (ok ? 1 : 0) + (vector && g_have_avx2 ? 2 : 0);
+}
+
+int east_hip_debug_set_lds_rounds(int enabled)
+{
+    // 0: every round through the global sort; 1: the default (in-LDS rounds that also classify the next domain, small
+    // domains finished by one persistent launch); 2: in-LDS rounds with the stand-alone classification pass, launch by
+    // launch; 3: as 1, launch by launch (no persistent kernel)
+    knobs_update([&](Knobs &k) {
+        k.lds_rounds = enabled != 0;
+        k.fused_classify = enabled != 2 && getenv("EAST_HIP_NO_FUSED_CLASSIFY") == nullptr;
+        k.persist = enabled == 1 && getenv("EAST_HIP_NO_PERSIST") == nullptr;
+    });
+    return EAST_HIP_OK;
+}
+
+int east_hip_debug_set_persist(int force_large, int max_workgroups)
+{
+    // the persistent rounds (persist_rounds.h): force_large != 0 -- the large form (tiles' state in global memory, several
+    // tiles per workgroup) also where the resident form would do; max_workgroups > 0 -- a grid of at most that many
+    // workgroups (0: what the device holds).  (0, 0) = the default.
+    knobs_update([&](Knobs &k) {
+        k.persist_force_large = force_large != 0;
+        k.persist_max_wgs = max_workgroups > 0 ? max_workgroups : 0;
+    });
+    return EAST_HIP_OK;
+}
+
+int east_hip_debug_set_score_scratch(int64_t bytes)
+{
+    knobs_update([&](Knobs &k) { k.score_scratch_bytes = bytes > 0 ? (size_t)bytes : SCORE_SCRATCH_BYTES; });
+    return EAST_HIP_OK;
+}
+
+int east_hip_debug_set_score_grid(int64_t workgroups)
+{
+    // workgroups a launch of the score walk may have when the sums run inside it (0 or less: the default, 2^22)
+    knobs_update([&](Knobs &k) { k.score_grid_blocks = workgroups > 0 ? (u64)std::min<int64_t>(workgroups, (int64_t)1 << 23) : SCORE_GRID_BLOCKS; });
+    return EAST_HIP_OK;
+}
+
+int east_hip_debug_set_text_ring(int mode, int64_t slot_bytes)
+{
+    // mode -1: separate texts go up through the pinned ring when there are four or more of less than 8 MiB on average
+    // (and the preparation is streamed); 0: never; 1: whenever the texts lie apart.  slot_bytes: size of a ring slot
+    // (0 or less: the default, 8 MiB; at most that)
+    knobs_update([&](Knobs &k) {
+        k.tp_ring = mode;
+        k.tp_ring_slot = slot_bytes > 0 ? (size_t)std::min<int64_t>(slot_bytes, (int64_t)TP_RING_SLOT) : TP_RING_SLOT;
+    });
+    return EAST_HIP_OK;
+}
+
+int east_hip_debug_set_text_stream(int64_t chunk_bytes)
+{
+    // -1: the default (inputs of 8 MiB or more go up and are prepared in about five chunks); 0: the raw text goes up and
+    // is prepared in one piece; > 0: always in chunks of about that many bytes
+    knobs_update([&](Knobs &k) { k.tp_stream = chunk_bytes; });
+    return EAST_HIP_OK;
+}
+
+int east_hip_debug_set_score_path(int mode)
+{
+    // 1: the default; 0: the walk as rounds 1-3 ran it -- one filled k-gram table of 4-byte entries, per-suffix results in
+    // HBM and a reduction kernel; 2: pair tables, separate reduction; 3: filled table, the sums inside the walk.
+    // (takes effect with the next build / the next set of keyphrases)
+    knobs_update([&](Knobs &k) {
+        k.kg_pairs = mode == 1 || mode == 2 || mode == 4 || mode == 5;
+        k.kg_pairs_forced = mode == 4;                  // 4: as 1, the pair tables also for collections of fewer than 16 documents
+        k.score_fused = mode == 1 || mode == 3 || mode == 4 || mode == 5;
+        k.score_endgame = mode == 5 ? 0 : 1;                 // 5: as 1, binary search down to the last suffix (no register endgame)
+    });
+    return EAST_HIP_OK;
+}
+
+int east_hip_debug_set_speculation(int enabled)
+{
+    knobs_update([&](Knobs &k) { k.speculate = enabled != 0; });
+    return EAST_HIP_OK;
+}
+
+int east_hip_debug_radix_sort_u64(int device, uint64_t *keys, uint32_t *vals, int64_t n, int bits)
+{
+    return guarded([&] { debug_sort<u64>(device, keys, vals, n, bits); });
+}
+
+int east_hip_debug_radix_sort_u32(int device, uint32_t *keys, uint32_t *vals, int64_t n, int bits)
+{
+    return guarded([&] { debug_sort<u32>(device, keys, vals, n, bits); });
+}
+
+int east_hip_debug_exclusive_scan(int device, const uint32_t *in, uint32_t *out, int64_t n)
+{
+    return guarded([&] {
+        if (n < 0 || n >= (i64)0x7FFFFFF0 || !in || !out) east_throw(EAST_HIP_ERR_INVALID, "bad scan arguments");
+        if (n == 0) return;
+        DebugScope sc(device, (size_t)n * 8 + (size_t)ceil_div_u32(n, SCAN_TILE) * 16 + (8u << 20));
+        u32 *d_in = sc.arena.alloc<u32>(n), *d_out = sc.arena.alloc<u32>(n);
+        HIP_CHECK(hipMemcpyAsync(d_in, in, (size_t)n * 4, hipMemcpyHostToDevice, sc.stream));
+        device_scan<ArrIn, false>(sc.ctx, ArrIn{d_in}, (u32)n, d_out);
+        HIP_CHECK(hipMemcpyAsync(out, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, sc.stream));
+        HIP_CHECK(hipStreamSynchronize(sc.stream));
+    });
+}
+
+int east_hip_debug_suffix_array(int device, const uint32_t *symbols, int64_t n, uint32_t sigma, int32_t *sa_out,
+                                int32_t *levels_out)
+{
+    return guarded([&] {
+        if (n < 1 || n >= (i64)0x7FFFFFF0 || !symbols || !sa_out || sigma < 1)
+            east_throw(EAST_HIP_ERR_INVALID, "bad suffix array arguments");
+        for (i64 i = 0; i < n; i++)
+            if (symbols[i] < 1 || symbols[i] > sigma) east_throw(EAST_HIP_ERR_INVALID, "symbol outside [1, sigma]");
+        // measure the arena with the same code path, then run it
+        Arena dry;
+        dry.dry = true;
+        Stats st;
+        Ctx dctx;
+        dctx.arena = &dry;
+        dctx.dry = true;
+        dctx.stats = &st;
+        (void)dry.alloc<u32>((size_t)n + 3);
+        (void)dry.alloc<u32>(n);
+        dc3_suffix_array(dctx, nullptr, (u32)n, (u32)std::max<i64>(n, sigma), nullptr);
+        DebugScope sc(device, dry.high + (8u << 20));
+        u32 *s = sc.arena.alloc<u32>((size_t)n + 3), *sa = sc.arena.alloc<u32>(n);
+        HIP_CHECK(hipMemsetAsync(s + n, 0, 12, sc.stream));
+        HIP_CHECK(hipMemcpyAsync(s, symbols, (size_t)n * 4, hipMemcpyHostToDevice, sc.stream));
+        const int levels = dc3_suffix_array(sc.ctx, s, (u32)n, sigma, sa);
+        HIP_CHECK(hipMemcpyAsync(sa_out, sa, (size_t)n * 4, hipMemcpyDeviceToHost, sc.stream));
+        HIP_CHECK(hipStreamSynchronize(sc.stream));
+        if (levels_out) *levels_out = levels;
+    });
+}
+
+}  // extern "C"

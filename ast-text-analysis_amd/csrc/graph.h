@@ -201,50 +201,18 @@ __global__ __launch_bounds__(BLOCK) void graph_row_base_kernel(const u32 *__rest
 
 // ============================================================================================================ host ==
 // The graph's device buffers belong to the handle and to nothing else: not the EASA arena, not the cosine buffers.
-struct GraphBuf {
-    char *p = nullptr;
-    size_t cap = 0;
-    void ensure(size_t bytes, const char *what, i64 count)
-    {
-        if (bytes <= cap) return;
-        release();
-        void *q = nullptr;
-        if (hipMalloc(&q, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            char msg[256];
-            snprintf(msg, sizeof(msg), "keyphrase graph: no device memory for %lld %s (%zu bytes)", (long long)count, what, bytes);
-            east_throw(EAST_HIP_ERR_OOM, msg);
-        }
-        p = (char *)q;
-        cap = bytes;
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    Arena arena() const
-    {
-        Arena a;
-        a.base = p;
-        a.cap = cap;
-        return a;
-    }
-};
-
 struct GraphState {
     bool valid = false;
     u32 n = 0, M = 0;                       // node positions, kept nodes
     i64 E = 0;                              // edges
-    GraphBuf table;                         // a host table's copy (east_hip_graph_build_host), table_K x table_D while it is whole
+    DevBuf table;                           // a host table's copy (east_hip_graph_build_host), table_K x table_D while it is whole
     u32 table_K = 0, table_D = 0;
-    GraphBuf nodes, pairs, edges;
+    DevBuf nodes, pairs, edges;
     u32 *support = nullptr, *kept = nullptr;
     int32_t *e_src = nullptr, *e_dst = nullptr, *e_shared = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     float ms = -1.f;
-    GraphBuf *bufs[4] = {&table, &nodes, &pairs, &edges};
+    DevBuf *bufs[4] = {&table, &nodes, &pairs, &edges};
 };
 
 static GraphState &graph_state(east_hip_index *h)
@@ -285,15 +253,12 @@ static void graph_build(east_hip_index *h, const double *d_table, u32 K, u32 D, 
     g.n = n;
     g.M = 0;
     g.E = 0;
-    Ctx ctx;
-    ctx.stream = h->stream;
-    ctx.prof = &h->prof;
     Stats stats;
-    ctx.stats = &stats;
+    Ctx ctx = handle_ctx(h, nullptr, &stats);
     HIP_CHECK(hipEventRecord(g.ev0, h->stream));
     if (n) {
         const size_t n1 = (size_t)n + 1;
-        g.nodes.ensure(n1 * 20 + (size_t)n * W * 8 + ((size_t)ceil_div_u32(n1, SCAN_TILE) + 1) * 8 + 16 * 256, "node positions", n);
+        g.nodes.ensure(n1 * 20 + (size_t)n * W * 8 + ((size_t)ceil_div_u32(n1, SCAN_TILE) + 1) * 8 + 16 * 256, "the keyphrase graph's node positions");
         Arena a = g.nodes.arena();
         ctx.arena = &a;
         g.support = a.alloc<u32>(n1);
@@ -318,7 +283,7 @@ static void graph_build(east_hip_index *h, const double *d_table, u32 K, u32 D, 
                 east_throw(EAST_HIP_ERR_INVALID, msg);
             }
             g.pairs.ensure((size_t)M * W * 8 + (size_t)M * 12 + n_cnt * 4 + ((size_t)ceil_div_u32(n_cnt, SCAN_TILE) + 1) * 8 + 16 * 256,
-                           "nodes", M);
+                           "the keyphrase graph's nodes");
             Arena b = g.pairs.arena();
             ctx.arena = &b;
             u64 *cbits = b.alloc<u64>((size_t)M * W), *row_base = b.alloc<u64>((size_t)M + 1);
@@ -335,7 +300,7 @@ static void graph_build(east_hip_index *h, const double *d_table, u32 K, u32 D, 
             HIP_CHECK(hipStreamSynchronize(h->stream));
             if (E) {
                 const size_t eb = (((size_t)E * 4) + 255) & ~(size_t)255;
-                g.edges.ensure(eb * 3, "edges", (i64)E);
+                g.edges.ensure(eb * 3, "the keyphrase graph's edges");
                 g.e_src = (int32_t *)g.edges.p;
                 g.e_dst = (int32_t *)(g.edges.p + eb);
                 g.e_shared = (int32_t *)(g.edges.p + 2 * eb);
@@ -361,7 +326,7 @@ static void graph_reset(east_hip_index *h)
     g->E = 0;
     g->ms = -1.f;
     g->table_K = g->table_D = 0;
-    for (GraphBuf *b : g->bufs) b->release();
+    for (DevBuf *b : g->bufs) b->release();
 }
 
 static void graph_destroy(east_hip_index *h)
@@ -414,7 +379,7 @@ int east_hip_graph_build_host(east_hip_handle_t h, const double *table, int32_t 
         g.valid = false;
         g.table_K = g.table_D = 0;
         const size_t bytes = (size_t)n_keyphrases * (size_t)n_docs * 8;
-        g.table.ensure(bytes, "scores", (i64)n_keyphrases * n_docs);
+        g.table.ensure(bytes, "the keyphrase graph's score table");
         HIP_CHECK(hipMemcpyAsync(g.table.p, table, bytes, hipMemcpyHostToDevice, h->stream));
         HIP_CHECK(hipStreamSynchronize(h->stream));
         g.table_K = (u32)n_keyphrases;

@@ -1,0 +1,129 @@
+// handle.h -- what an east_hip_handle_t points to, and the helpers every host driver needs.
+#pragma once
+#include "common.h"
+#include "tables.h"
+#include <atomic>
+#include <thread>
+
+struct east_hip_index {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    Arena arena;
+    Stats stats;
+    Profiler prof;
+    bool built = false, child_built = false;
+    u32 n = 0, n_docs = 0, sigma_t = 0, m_total = 0;
+    u32 sigma_hi = 0;            // text code points >= U+0A00 present (tagged encoding only): the top sigma_hi codes of the text alphabet
+    u32 *hi_bits = nullptr, *hi_rank = nullptr;      // presence bitmap over [U+0A00, U+110000) and its rank directory
+    DevBuf guess;                // code map + presence bitmap of the last build (own allocation): what a speculative build starts from
+    bool tagged_input = false;   // east_hip_set_symbol_encoding: the symbol entry points take the tagged encoding
+    bool prep_tagged = false;    // the prepared symbols (east_hip_build_texts) are in the tagged encoding
+    int bits0 = 0;
+    std::vector<i64> h_doc_off;
+    std::vector<u32> h_n_strings;
+    // persistent device arrays (inside the arena)
+    uint8_t *s8 = nullptr;
+    bool use_s8 = false;
+    u32 *s = nullptr, *sa = nullptr, *lcp = nullptr, *ann = nullptr, *up = nullptr, *down = nullptr,
+        *next = nullptr, *doc_off = nullptr, *n_strings = nullptr, *code_map = nullptr;
+    Pyramid pyr;
+    u32 build_docs = 0;          // documents of the build in progress (h->n_docs is set when it has succeeded)
+    // what the last successful build found, the guesses of the next (speculative) one
+    bool hint_valid = false, hint_no_rounds = false, hint_window = false;
+    int plan_wide = -1, plan_fused = -1;   // what the last build's window sort did (wide first window, fused finish): a speculative build does the same
+    int plan_ht = -1;                      // ... (first-level keys of variable-length code words)
+    int plan_persist = -1;                 // ... (the first domain went straight to the persistent rounds)
+    // the order-preserving variable-length code of the last build that made one (ht_code.h): device tables (own
+    // allocation: 256 x u32 enc, 4096 x u16 dec), valid for text with ht_sigma text symbols
+    DevBuf ht_tab;
+    bool ht_valid = false;
+    u32 ht_sigma = 0;
+    int ht_max_len = 0;
+    double ht_mean_len = 0.0;
+    u32 hint_sigma = 0;
+    u32 plan_n = 0, plan_docs = 0, plan_epoch = 0;
+    bool plan_tagged = false;   // shape of the last sizing run (and test-knob epoch), its result
+    size_t plan_bytes = 0;
+    // keyphrases + score scratch (own allocation, grown on demand)
+    DevBuf q_buf;
+    u32 n_kp = 0, n_q = 0, score_chunk = 0;     // score_chunk: documents per stretch the scratch was sized for
+    u32 *q_raw = nullptr, *q_code = nullptr, *q_end = nullptr, *q_off = nullptr, *group_off = nullptr;
+    u32 *q_blk = nullptr;        // whole keyphrases per workgroup of the score walk: [q_blk[i], q_blk[i + 1]), n_blk of them
+    u32 n_blk = 0;               // (0: a keyphrase is longer than a workgroup -- the walk writes per-suffix results, a second kernel sums)
+    double *suffix = nullptr, *table = nullptr, *table_g = nullptr;
+    // k-gram bucket tables for the score walk (own allocation, rebuilt after every build)
+    DevBuf kg;
+    int kg_k = 0;
+    u32 kg_A = 0, kg_bins = 0;
+    bool kg_built = false;
+    bool kg_marked = false;      // the bucket starts were written by the build (off the window keys): only the fill is due
+    bool kg_pairs = false;       // ... in the pair layout (score.h: KgTables); kg3 = the table of the levels above the last,
+    u32 *kg3 = nullptr, *kg_up = nullptr;        // kg_up = the small tables of the levels above kg3's own
+    u32 kg_up_stride = 0;
+    float last_build_ms = -1.f, last_score_ms = -1.f, last_prep_ms = -1.f;
+    // the caller's Unicode tables of the device text preparation (own allocation, re-uploaded when their hash changes)
+    DevBuf tp_tables;
+    u64 tp_tables_hash = 0;
+    std::vector<uint8_t> tp_host_tables;
+    // the streamed text preparation: a copy stream of its own and one event per chunk
+    hipStream_t copy_stream = nullptr;     // (created with the handle: creating a stream costs milliseconds)
+    std::vector<hipEvent_t> copy_events;
+    // ... and a ring of pinned host memory through which MANY separate texts go up (tp_upload_through_ring): allocated on
+    // first use, kept with the handle
+    char *ring = nullptr;
+    std::vector<hipEvent_t> ring_events;
+    std::thread ring_alloc;                 // pins the ring in the background after a first call that went without it
+    std::atomic<char *> ring_pending{nullptr};
+    std::atomic<bool> ring_done{false};     // the background thread is through (with or without a ring): it can be joined without waiting
+    int narrow_upload = 0;                  // the last build's host symbols went up as 16-bit words (1) / as bytes (2) (east_hip_build_info [25])
+    bool bytes_refused = false;             // a text symbol of 0xFF .. 0x9FF was met on the way up as bytes: this handle's later uploads take 16 bits at once
+    bool ring_wanted = false;               // (the call under way would have taken the ring: pin it once the call is over --
+                                            // while it runs, the pinning and the call's own copies fight over the runtime's locks)
+    // symbols prepared on the device by east_hip_build_texts (own allocation)
+    DevBuf prep_sym;
+    i64 prep_n = 0;
+    std::vector<i64> prep_doc_off;
+    std::vector<int32_t> prep_n_strings;
+    // the cosine measure's term index (cosine.h; own allocations, made by the first east_hip_cosine_build_texts)
+    struct CosState *cos = nullptr;
+    // the AST score table of the resident keyphrases (h->table) holds the scores of the index as it stands: set by the score
+    // walk, withdrawn by every build and every new set of keyphrases (the keyphrase graph reads it where it lies, graph.h)
+    bool table_scored = false;
+    // the keyphrase graph (graph.h; own allocations, made by the first east_hip_graph_build_*)
+    struct GraphState *graph = nullptr;
+    // the handle's own device allocations besides the arena: east_hip_destroy frees them, east_hip_reset the large ones
+    DevBuf *bufs[6] = {&guess, &ht_tab, &q_buf, &kg, &tp_tables, &prep_sym};
+};
+static void cos_reset(east_hip_index *h);
+static void cos_destroy(east_hip_index *h);
+static void graph_reset(east_hip_index *h);
+static void graph_destroy(east_hip_index *h);
+
+struct SpecAbort {};             // a speculative build cannot go on: build_common starts over with the read-backs in place
+
+// Every entry point runs on the handle's device and puts the calling thread's current device back on the way
+// out (a caller that also drives torch or other HIP code on another GPU must not find its device changed).
+static thread_local int g_saved_device = -1;
+static void use_device_ordinal(int device)
+{
+    int cur = -1;
+    if (g_saved_device < 0 && hipGetDevice(&cur) == hipSuccess && cur != device) g_saved_device = cur;
+    HIP_CHECK(hipSetDevice(device));
+}
+static void use_device(east_hip_index *h) { use_device_ordinal(h->device); }
+static void restore_device()
+{
+    if (g_saved_device >= 0) { (void)hipSetDevice(g_saved_device); g_saved_device = -1; }
+}
+
+// a launch context on the handle's stream, timed by its profiler (arena, stats: what the caller's launches need of them)
+static Ctx handle_ctx(east_hip_index *h, Arena *arena = nullptr, Stats *stats = nullptr)
+{
+    Ctx ctx;
+    ctx.stream = h->stream;
+    ctx.arena = arena;
+    ctx.stats = stats;
+    ctx.prof = &h->prof;
+    return ctx;
+}

@@ -62,11 +62,9 @@ struct east_hip_group {
     bool built = false;
     // assembly buffers: per shard the padded block (K x widest) and the gathered blocks (G x K x widest), on the first
     // shard's device also the K x D table and the shard bounds
-    struct Buf { double *send = nullptr, *recv = nullptr; size_t send_cap = 0, recv_cap = 0; };
+    struct Buf { DevBuf send, recv; };
     std::vector<Buf> buf;
-    double *packed = nullptr;
-    size_t packed_cap = 0;
-    u32 *d_first = nullptr;
+    DevBuf packed, d_first;
     std::vector<hipEvent_t> done;               // per shard: its block is in place (copy path)
     RcclApi rccl;
     std::vector<void *> comms;
@@ -152,18 +150,6 @@ __global__ __launch_bounds__(BLOCK) void group_pack_kernel(const double *__restr
     out[i] = recv[((u64)s * K + k) * width + (d - first[s])];
 }
 
-static void grow(double *&p, size_t &cap, size_t bytes)
-{
-    if (bytes <= cap) return;
-    if (p) HIP_CHECK(hipFree(p));
-    p = nullptr;
-    cap = 0;
-    void *q = nullptr;
-    if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); east_throw(EAST_HIP_ERR_OOM, "hipMalloc of the score blocks of a group failed"); }
-    p = (double *)q;
-    cap = bytes;
-}
-
 // RCCL where every shard has a device of its own (EAST_HIP_GROUP_GATHER=copy / rccl overrides), copies otherwise
 static int decide_gather_mode(east_hip_group *g)
 {
@@ -209,15 +195,9 @@ static void group_destroy(east_hip_group *g)
         if (!g->shard[s]) continue;
         (void)hipSetDevice(g->devices[s]);
         if (g->shard[s]->stream) (void)hipStreamSynchronize(g->shard[s]->stream);
-        if (s < g->buf.size()) {
-            if (g->buf[s].send) (void)hipFree(g->buf[s].send);
-            if (g->buf[s].recv) (void)hipFree(g->buf[s].recv);
-        }
+        if (s < g->buf.size()) { g->buf[s].send.release(); g->buf[s].recv.release(); }
         if (s < g->done.size() && g->done[s]) (void)hipEventDestroy(g->done[s]);
-        if (s == 0) {
-            if (g->packed) (void)hipFree(g->packed);
-            if (g->d_first) (void)hipFree(g->d_first);
-        }
+        if (s == 0) { g->packed.release(); g->d_first.release(); }
         east_hip_destroy(g->shard[s]);
     }
     if (cur >= 0) (void)hipSetDevice(cur);
@@ -236,15 +216,15 @@ static void group_allgather(east_hip_group *g, u32 K)
     on_every_shard(g, [&](int s) {
         east_hip_index *h = g->shard[s];
         use_device(h);
-        grow(g->buf[s].send, g->buf[s].send_cap, block);
-        if (mode == 1 || s == 0) grow(g->buf[s].recv, g->buf[s].recv_cap, block * G);
+        g->buf[s].send.ensure(block, "the score blocks of a group");
+        if (mode == 1 || s == 0) g->buf[s].recv.ensure(block * G, "the score blocks of a group");
         const u32 Ds = (u32)(g->first_doc[s + 1] - g->first_doc[s]);
         if (Ds) {
             hipLaunchKernelGGL(group_pad_kernel, dim3(ceil_div_u32((u64)K * width, BLOCK)), dim3(BLOCK), 0, h->stream,
-                               (const double *)h->table, K, Ds, width, g->buf[s].send);
+                               (const double *)h->table, K, Ds, width, g->buf[s].send.as<double>());
             HIP_CHECK(hipGetLastError());
         } else {
-            HIP_CHECK(hipMemsetAsync(g->buf[s].send, 0, block, h->stream));
+            HIP_CHECK(hipMemsetAsync(g->buf[s].send.p, 0, block, h->stream));
         }
     });
     east_hip_index *h0 = g->shard[0];
@@ -257,7 +237,7 @@ static void group_allgather(east_hip_group *g, u32 K)
         for (u32 s = 0; s < G && rc == 0 && dev_rc == hipSuccess; s++) {
             dev_rc = hipSetDevice(g->devices[s]);
             if (dev_rc == hipSuccess)
-                rc = g->rccl.all_gather(g->buf[s].send, g->buf[s].recv, (size_t)K * width, EAST_NCCL_DOUBLE, g->comms[s], g->shard[s]->stream);
+                rc = g->rccl.all_gather(g->buf[s].send.p, g->buf[s].recv.p, (size_t)K * width, EAST_NCCL_DOUBLE, g->comms[s], g->shard[s]->stream);
         }
         if (opened) {
             const int rc_end = g->rccl.group_end();
@@ -278,9 +258,9 @@ static void group_allgather(east_hip_group *g, u32 K)
         for (u32 s = 0; s < G; s++) {
             HIP_CHECK(hipSetDevice(g->devices[s]));
             if (g->devices[s] == g->devices[0])
-                HIP_CHECK(hipMemcpyAsync(g->buf[0].recv + (size_t)s * K * width, g->buf[s].send, block, hipMemcpyDeviceToDevice, g->shard[s]->stream));
+                HIP_CHECK(hipMemcpyAsync(g->buf[0].recv.as<double>() + (size_t)s * K * width, g->buf[s].send.p, block, hipMemcpyDeviceToDevice, g->shard[s]->stream));
             else
-                HIP_CHECK(hipMemcpyPeerAsync(g->buf[0].recv + (size_t)s * K * width, g->devices[0], g->buf[s].send, g->devices[s], block,
+                HIP_CHECK(hipMemcpyPeerAsync(g->buf[0].recv.as<double>() + (size_t)s * K * width, g->devices[0], g->buf[s].send.p, g->devices[s], block,
                                              g->shard[s]->stream));
             if (s > 0) HIP_CHECK(hipEventRecord(g->done[s], g->shard[s]->stream));
         }
@@ -288,11 +268,11 @@ static void group_allgather(east_hip_group *g, u32 K)
         for (u32 s = 1; s < G; s++) HIP_CHECK(hipStreamWaitEvent(h0->stream, g->done[s], 0));
     }
     HIP_CHECK(hipSetDevice(g->devices[0]));
-    grow(g->packed, g->packed_cap, (size_t)K * D * 8);
+    g->packed.ensure((size_t)K * D * 8, "the score table of a group");
     std::vector<u32> first(g->first_doc.begin(), g->first_doc.end());
-    HIP_CHECK(hipMemcpyAsync(g->d_first, first.data(), first.size() * 4, hipMemcpyHostToDevice, h0->stream));
+    HIP_CHECK(hipMemcpyAsync(g->d_first.p, first.data(), first.size() * 4, hipMemcpyHostToDevice, h0->stream));
     hipLaunchKernelGGL(group_pack_kernel, dim3(ceil_div_u32((u64)K * D, BLOCK)), dim3(BLOCK), 0, h0->stream,
-                       (const double *)g->buf[0].recv, (const u32 *)g->d_first, G, K, D, width, g->packed);
+                       g->buf[0].recv.as<const double>(), g->d_first.as<const u32>(), G, K, D, width, g->packed.as<double>());
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(h0->stream));         // (also covers `first`)
     if (mode == 1)                                        // the other shards' part of the collective
@@ -322,9 +302,7 @@ int east_hip_group_create(const int32_t *devices, int32_t n_shards, east_hip_gro
                 HIP_CHECK(hipEventCreateWithFlags(&g->done[s], hipEventDisableTiming));
             }
             use_device_ordinal(devices[0]);
-            void *p = nullptr;
-            HIP_CHECK(hipMalloc(&p, ((size_t)n_shards + 1) * 4));
-            g->d_first = (u32 *)p;
+            g->d_first.ensure(((size_t)n_shards + 1) * 4, "the shard bounds of a group");
         } catch (...) {
             group_destroy(g);
             throw;
@@ -440,7 +418,7 @@ int east_hip_score_table_multi(east_hip_group_t g, const uint32_t *q_symbols, co
         const auto t1 = std::chrono::steady_clock::now();
         group_allgather(g, (u32)n_keyphrases);
         HIP_CHECK(hipSetDevice(g->devices[0]));
-        HIP_CHECK(hipMemcpy(out, g->packed, (size_t)n_keyphrases * g->n_docs * 8, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(out, g->packed.p, (size_t)n_keyphrases * g->n_docs * 8, hipMemcpyDeviceToHost));
         g->gather_ms = wall_ms_since(t1);
     });
 }

@@ -1,0 +1,215 @@
+// score_host.h -- the host side of score.h: the resident keyphrases, the k-gram tables and the score walk.
+#pragma once
+#include "handle.h"
+#include "score.h"
+
+// The walk writes one fp64 per (keyphrase suffix, document); that scratch is bounded -- a table over a million
+// one-line documents would need hundreds of GB -- and the documents are scored a stretch at a time.
+static u32 score_doc_chunk(u32 n_q, u32 n_docs, size_t scratch_bytes)
+{
+    const size_t per_doc = (size_t)n_q * 8;
+    const size_t fit = per_doc ? scratch_bytes / per_doc : n_docs;
+    return (u32)std::min<size_t>(n_docs, std::max<size_t>(fit, 1));
+}
+
+static void set_keyphrases(east_hip_index *h, const u32 *q_symbols, const i64 *q_offsets, int32_t n_kp)
+{
+    if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
+    if (!h->built) east_throw(EAST_HIP_ERR_NOT_BUILT, "no index has been built on this handle");
+    if (n_kp < 1 || !q_symbols || !q_offsets) east_throw(EAST_HIP_ERR_INVALID, "no keyphrases");
+    if (q_offsets[0] != 0) east_throw(EAST_HIP_ERR_INVALID, "q_offsets[0] must be 0");
+    for (int32_t k = 0; k < n_kp; k++)
+        if (q_offsets[k + 1] <= q_offsets[k])
+            east_throw(EAST_HIP_ERR_INVALID, "empty keyphrase (the reference raises ZeroDivisionError, easa.py:134)");
+    const i64 S = q_offsets[n_kp];
+    if (S >= (i64)0x7FFFFFF0 || (i64)n_kp * h->n_docs >= ((i64)1 << 40))
+        east_throw(EAST_HIP_ERR_INVALID, "keyphrase set too large");
+    use_device(h);
+    h->table_scored = false;
+    const u32 n_q = (u32)S;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const Knobs kn = knobs_snapshot();
+    const u32 chunk = score_doc_chunk(n_q, h->n_docs, kn.score_scratch_bytes);
+    const size_t bytes = 256 + al((size_t)n_q * 4) * 3 + al(((size_t)n_kp + 1) * 4) * 3 +
+                         al((size_t)n_q * chunk * 8) + al((size_t)n_kp * h->n_docs * 8) * 2;
+    h->q_buf.ensure(bytes, "the score scratch", h->stream);
+    char *p = h->q_buf.p + 256;                            // (the first bytes hold the probe counter of east_hip_score_probes)
+    h->q_raw = (u32 *)p;  p += al((size_t)n_q * 4);
+    h->q_code = (u32 *)p; p += al((size_t)n_q * 4);
+    h->q_end = (u32 *)p;  p += al((size_t)n_q * 4);
+    h->q_off = (u32 *)p;  p += al(((size_t)n_kp + 1) * 4);
+    h->group_off = (u32 *)p; p += al(((size_t)n_kp + 1) * 4);      // synonym-expanded scoring: variants per keyphrase
+    h->q_blk = (u32 *)p;  p += al(((size_t)n_kp + 1) * 4);
+    h->suffix = (double *)p; p += al((size_t)n_q * chunk * 8);
+    h->table = (double *)p; p += al((size_t)n_kp * h->n_docs * 8);
+    h->table_g = (double *)p;
+    std::vector<u32> end(n_q), off((size_t)n_kp + 1);
+    for (int32_t k = 0; k < n_kp; k++) {
+        off[k] = (u32)q_offsets[k];
+        for (i64 i = q_offsets[k]; i < q_offsets[k + 1]; i++) end[i] = (u32)q_offsets[k + 1];
+    }
+    off[n_kp] = n_q;
+    // the score walk's workgroups take whole keyphrases (score.h: score_walk_kernel, blk): consecutive keyphrases packed
+    // into stretches of at most BLOCK suffixes
+    std::vector<u32> blk;
+    blk.push_back(0);
+    bool fits = kn.score_fused;
+    for (int32_t k = 0, used = 0; k < n_kp && fits; k++) {
+        const i64 len = q_offsets[k + 1] - q_offsets[k];
+        if (len > BLOCK) { fits = false; break; }
+        if (used + len > BLOCK) { blk.push_back((u32)k); used = 0; }
+        used += (int32_t)len;
+    }
+    blk.push_back((u32)n_kp);
+    h->n_blk = fits ? (u32)blk.size() - 1 : 0;
+    if (fits) HIP_CHECK(hipMemcpyAsync(h->q_blk, blk.data(), blk.size() * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(hipMemcpyAsync(h->q_raw, q_symbols, (size_t)n_q * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(hipMemcpyAsync(h->q_end, end.data(), (size_t)n_q * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(hipMemcpyAsync(h->q_off, off.data(), off.size() * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    h->n_kp = (u32)n_kp;
+    h->n_q = n_q;
+    h->score_chunk = chunk;
+}
+
+// device memory for n_docs rows of bins + 1 entries plus the fill's chunk scratch; false if it cannot be had
+static bool kgram_reserve(east_hip_index *h, u64 bins, u32 n_docs)
+{
+    // (room for the pair layout: 8-byte entries of the last level + the table of the level above; the filled 4-byte
+    // layout with its chunk scratch is smaller)
+    const size_t chunks = (size_t)((bins + KGF_CHUNK - 1) / KGF_CHUNK);
+    const size_t bytes = (2 * (size_t)(bins + 1) + (size_t)(bins / 2 + 2) + (size_t)(bins / 4 + 8) + 2 * chunks) * n_docs * 4 + 256;
+    return h->kg.try_ensure(bytes, h->stream);
+}
+
+// k-gram bucket tables of the current index (score.h); k = 0 when the alphabet is too wide
+static void ensure_kgram(east_hip_index *h, Ctx &ctx)
+{
+    if (h->kg_built) return;
+    if (h->kg_marked && h->kg_pairs) {
+        // the pair layout: the last level stays as the build marked it (+ its end entries), the small table above it is filled
+        const u32 bins3 = h->kg_bins / h->kg_A;
+        LAUNCH(ctx, kgram_pairs_end_kernel, ceil_div_u32(h->n_docs, BLOCK), (const u32 *)h->doc_off, h->n_docs, h->kg_bins, h->kg.as<u32>());
+        LAUNCH(ctx, kgram_fill_kernel, h->n_docs, (const u32 *)h->doc_off, bins3, h->kg3);
+        // (levels 1 .. k - 2 as tables of their own: A + 1, A^2 + 1, ... entries per document)
+        h->kg_up_stride = 0;
+        u32 len = h->kg_A;
+        for (int l = 1; l < h->kg_k - 1; l++) { h->kg_up_stride += len + 1; len *= h->kg_A; }
+        if (h->kg_up_stride && h->kg_up)
+            LAUNCH(ctx, kgram_upper_kernel, h->n_docs, (const u32 *)h->kg3, bins3, h->kg_A, h->kg_k - 1, h->kg_up_stride, h->kg_up);
+        h->kg_built = true;
+        return;
+    }
+    if (h->kg_marked) {
+        // the build left the bucket starts in the table: suffix minimum per document, in chunks
+        const u32 bins = h->kg_bins, n_chunks = ceil_div_u32(bins, KGF_CHUNK);
+        u32 *cmin = h->kg.as<u32>() + (size_t)(bins + 1) * h->n_docs, *csuf = cmin + (size_t)n_chunks * h->n_docs;
+        LAUNCH(ctx, kgram_chunk_min_kernel, dim3(n_chunks, h->n_docs), h->kg.as<const u32>(), bins, n_chunks, cmin);
+        LAUNCH(ctx, kgram_chunk_suffix_kernel, h->n_docs, (const u32 *)cmin, (const u32 *)h->doc_off, n_chunks, csuf);
+        LAUNCH(ctx, kgram_chunk_fill_kernel, dim3(n_chunks, h->n_docs), (const u32 *)csuf, (const u32 *)h->doc_off, bins,
+               n_chunks, h->kg.as<u32>());
+        h->kg_built = true;
+        return;
+    }
+    h->kg_k = 0;
+    h->kg_pairs = false;
+    h->kg_built = true;
+    if (!h->use_s8 || h->n_docs > 65535) return;
+    const u32 A = h->sigma_t + 2;
+    int k = 0;
+    u64 bins = 1;
+    while (k < KGRAM_MAX_K && bins * A <= KGRAM_MAX_BINS && bins * A * 16 <= h->n / h->n_docs + 4096 &&
+           (bins * A + 1) * h->n_docs * 4 <= ((u64)1 << 30)) {
+        bins *= A;
+        k++;
+    }
+    if (k == 0) return;
+    const size_t bytes = (size_t)(bins + 1) * h->n_docs * 4;
+    if (!kgram_reserve(h, bins, h->n_docs)) return;              // no table: plain binary search
+    if ((u64)h->n / h->n_docs >= 256 * bins) {
+        // long documents: every table entry by binary search on the suffix array
+        LAUNCH(ctx, kgram_search_kernel, dim3(ceil_div_u32(bins + 1, BLOCK), h->n_docs), (const u32 *)h->sa,
+               (const uint8_t *)h->s8, (const u32 *)h->doc_off, k, A, (u32)bins, h->kg.as<u32>());
+    } else {
+        HIP_CHECK(hipMemsetAsync(h->kg.p, 0xFF, bytes, h->stream));
+        i64 longest = 0;
+        for (u32 d = 0; d < h->n_docs; d++) longest = std::max(longest, h->h_doc_off[d + 1] - h->h_doc_off[d]);
+        if (h->n_docs > 1)
+            LAUNCH_NAMED(ctx, "kgram_mark_kernel", kgram_mark_tiled_kernel,
+                         dim3(ceil_div_u32((u64)longest + 3, BLOCK * 4), h->n_docs), (const u32 *)h->lcp, (const u32 *)h->sa,
+                         (const uint8_t *)h->s8, (const u32 *)h->doc_off, h->n_docs, h->n, k, A, (u32)bins, h->kg.as<u32>());
+        else
+            LAUNCH(ctx, kgram_mark_kernel, dim3(ceil_div_u32((u64)longest, BLOCK), h->n_docs), (const u32 *)h->lcp,
+                   (const u32 *)h->sa, (const uint8_t *)h->s8, (const u32 *)h->doc_off, h->n_docs, h->n, k, A, (u32)bins,
+                   h->kg.as<u32>());
+        LAUNCH(ctx, kgram_fill_kernel, h->n_docs, (const u32 *)h->doc_off, (u32)bins, h->kg.as<u32>());
+    }
+    h->kg_k = k;
+    h->kg_A = A;
+    h->kg_bins = (u32)bins;
+}
+
+// queues the score kernels; result in h->table (K x D) / h->suffix (D x S)
+static void score_resident(east_hip_index *h, int normalized, unsigned long long *probe_count = nullptr,
+                           double *suffix_host = nullptr)
+{
+    if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
+    if (!h->built) east_throw(EAST_HIP_ERR_NOT_BUILT, "no index has been built on this handle");
+    if (!h->n_kp) east_throw(EAST_HIP_ERR_INVALID, "no keyphrases set");
+    use_device(h);
+    Ctx ctx = handle_ctx(h);
+    HIP_CHECK(hipEventRecord(h->ev0, h->stream));
+    ensure_kgram(h, ctx);
+    LAUNCH(ctx, query_map_kernel, ceil_div_u32(h->n_q, BLOCK), (const u32 *)h->q_raw, h->n_q,
+           (const u32 *)h->code_map, (const u32 *)h->hi_bits, (const u32 *)h->hi_rank,
+           h->sigma_hi ? h->sigma_t - h->sigma_hi + 1u : 0u, h->q_code);
+    KgTables kt;
+    kt.kg = h->kg.as<u32>(); kt.kg3 = h->kg3; kt.k = h->kg_k; kt.pairs = h->kg_k > 0 && h->kg_pairs; kt.A = h->kg_A; kt.bins = h->kg_bins;
+    if (kt.pairs && h->kg_up_stride && h->kg_up) {
+        kt.up = h->kg_up;
+        kt.up_stride = h->kg_up_stride;
+        static const bool up_lds_off = getenv("EAST_HIP_SCORE_UP_LDS") && atoi(getenv("EAST_HIP_SCORE_UP_LDS")) == 0;   // (A/B timing)
+        kt.up_lds = !up_lds_off && h->kg_up_stride <= KG_UP_LDS_WORDS;
+    }
+    if (kt.k > 0) kt.finish();
+    kt.endgame = ctx.knobs.score_endgame;
+    // whole keyphrases per workgroup, summed in the walk (no per-suffix results unless the caller wants them: then the
+    // documents go a stretch at a time, as far as the scratch reaches); otherwise per-suffix results + the reduction kernel
+    const bool fused = h->n_blk > 0;
+    u32 chunk = h->score_chunk;
+    if (fused && !suffix_host) {
+        // (no scratch to bound the stretch -- the grid does: a launch of at most Knobs::score_grid_blocks workgroups, far below
+        // HIP's limit of 2^32 threads per grid dimension; many short documents times thousands of keyphrases go a stretch
+        // of documents at a time, a multiple of 8 for the XCD-aware order)
+        const u64 fit = ctx.knobs.score_grid_blocks / h->n_blk;
+        chunk = (u32)std::min<u64>(h->n_docs, fit >= 8 ? fit & ~(u64)7 : std::max<u64>(fit, 1));
+    }
+    for (u32 first = 0; first < h->n_docs; first += chunk) {
+        const u32 count = std::min(chunk, h->n_docs - first);
+        const int xcd_order = count >= 64;                // see score_walk_kernel
+        const u32 per_doc = fused ? h->n_blk : ceil_div_u32(h->n_q, BLOCK);
+        const u64 walk_grid64 = (u64)(xcd_order ? 8u * ceil_div_u32(count, 8) : count) * per_doc;
+        if (walk_grid64 >= ((u64)1 << 24)) east_throw(EAST_HIP_ERR_INVALID, "keyphrase set too large for one score launch");
+        const u32 walk_grid = (u32)walk_grid64;
+        double *suffix = fused && !suffix_host ? (double *)nullptr : h->suffix;
+        const u32 *blk = fused ? (const u32 *)h->q_blk : (const u32 *)nullptr;
+        if (h->use_s8)
+            LAUNCH_NAMED(ctx, "score_walk_kernel", (score_walk_kernel<uint8_t>), walk_grid, (const uint8_t *)h->s8,
+                         (const u32 *)h->sa, (const u32 *)h->doc_off, (const u32 *)h->n_strings, h->n_docs,
+                         (const u32 *)h->q_code, (const u32 *)h->q_end, h->n_q, normalized, kt, xcd_order, first, count, suffix,
+                         probe_count, blk, h->n_blk, (const u32 *)h->q_off, h->table);
+        else
+            LAUNCH_NAMED(ctx, "score_walk_kernel", (score_walk_kernel<u32>), walk_grid, (const u32 *)h->s,
+                         (const u32 *)h->sa, (const u32 *)h->doc_off, (const u32 *)h->n_strings, h->n_docs,
+                         (const u32 *)h->q_code, (const u32 *)h->q_end, h->n_q, normalized, kt, xcd_order, first, count, suffix,
+                         probe_count, blk, h->n_blk, (const u32 *)h->q_off, h->table);
+        if (!fused)
+            LAUNCH(ctx, score_reduce_kernel, ceil_div_u32((u64)h->n_kp * count, BLOCK), (const double *)h->suffix,
+                   (const u32 *)h->q_off, h->n_kp, h->n_docs, h->n_q, first, count, h->table);
+        if (suffix_host)                                  // the per-suffix results of this stretch of documents (D x S, row-major)
+            HIP_CHECK(hipMemcpyAsync(suffix_host + (size_t)first * h->n_q, h->suffix, (size_t)count * h->n_q * 8,
+                                     hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_CHECK(hipEventRecord(h->ev1, h->stream));
+    h->table_scored = true;
+}

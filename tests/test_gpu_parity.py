@@ -855,7 +855,7 @@ def test_segmented_sort_of_unequal_documents(hip, oracle, suffix_sort_path):
 @pytest.mark.parametrize("document_number_in_keys", [False, True])
 def test_first_build_plans_the_window_from_its_own_text(hip, oracle, suffix_sort_path, document_number_in_keys):
     """The first build on a fresh handle takes the window width and the fused finish from a sample of its own text
-    (csrc/east_hip.hip: sample_prefix_kernel) -- no build has to go before: natural-language-like text over a large
+    (csrc/alphabet.h: sample_prefix_kernel) -- no build has to go before: natural-language-like text over a large
     alphabet (most suffixes tied behind the three symbols that fit a 32-bit key) sorts 64-bit first-level keys at once,
     a random word stream 32-bit keys with the last digit ordered in LDS; a second build on the handle (queued without
     waiting, no sample) does as the first.  The tables are the oracle's either way."""
@@ -1547,7 +1547,7 @@ def test_long_repeats_in_one_batched_build(hip, oracle, suffix_sort_path):
 def test_host_symbols_go_up_as_16_bit_words(hip, oracle, request):
     """east_hip_build from host symbols of the reference encoding (4 Mi symbols or more): from a handle's second call on --
     the first one leaves the pinning of the ring to a background thread -- the symbols are narrowed to 16 bits by host
-    threads, go up through the pinned ring and are widened on the device (east_hip.hip: upload_symbols_narrow); text
+    threads, go up through the pinned ring and are widened on the device (upload.h: upload_symbols_narrow); text
     symbols right below U+0A00 and terminators far above it included.  Tables and scores as with the plain copy and as
     the oracle's."""
     _only_paths(request, "window_sort", "dc3_only", "window_sort_seg")
@@ -1591,7 +1591,7 @@ def test_host_symbols_go_up_as_16_bit_words(hip, oracle, request):
 
 def test_host_symbols_go_up_as_bytes_when_the_text_fits_them(hip, oracle, request):
     """Text whose code points all lie below 0xFF -- the word streams of every BASELINE config -- goes up as BYTES (a
-    quarter of the ABI's four bytes per symbol; east_hip.hip: upload_symbols_narrow<uint8_t>, build_info[25] == 2): same
+    quarter of the ABI's four bytes per symbol; upload.h: upload_symbols_narrow<uint8_t>, build_info[25] == 2): same
     tables and scores as the plain copy and as the oracle's.  A text symbol a byte cannot hold, met half-way through the
     upload (far behind the 64 Ki symbols the call looks at first), starts it over with 16-bit words -- for that call, with
     the right tables, and for the handle's later calls at once."""
@@ -1770,7 +1770,7 @@ def test_device_text_preparation_large(hip, chunk):
 @pytest.mark.parametrize("slot", [64, 1000, 100000, 0])
 def test_device_text_preparation_through_the_pinned_ring(hip, monkeypatch, request, slot):
     """Separate texts (east_hip_build_texts_v) of a streamed preparation go up through a ring of pinned host memory, filled
-    by a few host threads and sent slot by slot (east_hip.hip: tp_fill_stream): forced on, with slots of 64 bytes to 4 MiB
+    by a few host threads and sent slot by slot (textfront.h: tp_fill_stream): forced on, with slots of 64 bytes to 4 MiB
     -- slots that end inside texts, at separators, inside chunks and at their ends, many times round the ring -- the
     prepared symbols equal the host chain's.  Fixtures, a fuzz, 40 documents of 300 KB, and the default path's choice."""
     import random

@@ -365,7 +365,7 @@ def test_score_table_is_the_dict_of_dicts_and_the_graph_from_the_array_is_the_gr
 
 
 def test_host_symbols_are_narrowed_to_16_bit_words_as_the_plain_loop_does():
-    """east_hip_build sends host symbols of the reference encoding over the link as 16-bit words (east_hip.hip:
+    """east_hip_build sends host symbols of the reference encoding over the link as 16-bit words (upload.h:
     upload_symbols_narrow): text below U+0A00 as it is, every terminator as 0xFFFF.  The host threads narrow with AVX2 and
     streaming stores where the CPU has them -- an alignment prologue, sixteen symbols a step, a tail --: every start
     alignment and length against numpy and against the library's plain loop (host only, no device)."""
@@ -397,7 +397,7 @@ def test_host_symbols_are_narrowed_to_16_bit_words_as_the_plain_loop_does():
 
 def test_host_symbols_are_narrowed_to_bytes_when_the_text_fits_them():
     """Text whose code points all lie below 0xFF (ASCII word text: every BASELINE input) goes over the link as BYTES,
-    0xFF = a terminator (east_hip.hip: upload_symbols_narrow<uint8_t>): the AVX2 form -- an alignment prologue, 32
+    0xFF = a terminator (upload.h: upload_symbols_narrow<uint8_t>): the AVX2 form -- an alignment prologue, 32
     symbols a step through two saturating packs and a lane permutation, a tail -- and the plain loop against numpy on
     every start alignment and length, and the verdict "a symbol did not fit" (0xFF .. 0x9FF is text a byte cannot hold:
     the upload then starts over with 16-bit words) wherever such a symbol sits."""
