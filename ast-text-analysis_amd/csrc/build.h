@@ -125,7 +125,10 @@ static void build_impl(east_hip_index *h, Ctx &ctx, const u32 *d_sym, u32 n, u32
     h->next = ar.alloc<u32>(n);
     h->doc_off = ar.alloc<u32>((size_t)n_docs + 1);
     h->n_strings = ar.alloc<u32>(n_docs);
-    h->code_map = ar.alloc<u32>(TEXT_SYMBOLS + FLAG_WORDS + PRESENT_WORDS + 1 + LCP_BUDGET_SLOTS);   // + the flag words (FLAG_*) + the presence bitmap and its status word + the budget of deep LCP comparisons
+    // + the flag words (FLAG_*) + the presence bitmap and its status word + the budget of deep LCP comparisons + the digit
+    // totals of the first-level sort (a row set for the pass counted ahead, two for the sort): everything one fill zeroes
+    constexpr size_t ZEROED_WORDS = FLAG_WORDS + PRESENT_WORDS + 1 + LCP_BUDGET_SLOTS, TOTAL_WORDS = (size_t)RS_TOTAL_SHARDS * RS_BINS;
+    h->code_map = ar.alloc<u32>(TEXT_SYMBOLS + ZEROED_WORDS + 3 * TOTAL_WORDS);
     h->hi_bits = tagged ? ar.alloc<u32>(HI_WORDS) : nullptr;
     h->hi_rank = tagged ? ar.alloc<u32>(HI_WORDS) : nullptr;
     Pyramid pyr;
@@ -159,7 +162,22 @@ static void build_impl(east_hip_index *h, Ctx &ctx, const u32 *d_sym, u32 n, u32
     u32 *flags = h->code_map + TEXT_SYMBOLS;              // flag words behind the code map
     u32 *capped = flags + FLAG_CAPPED, *status = flags + FLAG_STATUS;
     u32 *present = flags + FLAG_WORDS;                    // PRESENT_WORDS + 1 (status word): zeroed in the same fill
-    if (!ctx.dry) HIP_CHECK(hipMemsetAsync(flags, 0, (FLAG_WORDS + PRESENT_WORDS + 1 + LCP_BUDGET_SLOTS) * sizeof(u32), ctx.stream));
+    if (!ctx.dry) HIP_CHECK(hipMemsetAsync(flags, 0, (ZEROED_WORDS + 3 * TOTAL_WORDS) * sizeof(u32), ctx.stream));
+    ctx.zeroed_totals = ctx.dry ? nullptr : flags + ZEROED_WORDS + TOTAL_WORDS;
+    // Speculative build of one document whose first level the build before sorted on fixed-width text keys: the remap
+    // pass counts that sort's first histogram on the way (presence_remap_hist_kernel).  Its tables outlive the alphabet
+    // block below; the sort takes them if it turns out to run that very pass (radix_sort_pairs), else counts itself.
+    RsFirstHist first_hist;
+    ctx.first_hist = nullptr;
+    const Ctx::FirstPassPlan fp = ctx.spec && ctx.knobs.first_hist && n_docs == 1 && !tagged ? h->first_plan : Ctx::FirstPassPlan();
+    if (ctx.dry || fp.valid) {
+        first_hist.n = n;
+        first_hist.n_tiles = ceil_div_u32(n, RS_TILE);
+        first_hist.n_groups = ceil_div_u32(first_hist.n_tiles, RS_GROUP);
+        first_hist.hist = ar.alloc<u32>((size_t)RS_BINS * first_hist.n_tiles);
+        first_hist.group_sum = ar.alloc<u32>((size_t)RS_BINS * first_hist.n_groups);
+        first_hist.digit_total = flags + ZEROED_WORDS;
+    }
     // (deep LCP comparisons -- beyond LCP_SOFT_CAP symbols -- this build may make: n / 256, see common.h)
     ctx.lcp_budget.slots = ctx.dry ? nullptr : present + PRESENT_WORDS + 1;
     ctx.lcp_budget.per_slot = std::max<u32>(n / 256u / LCP_BUDGET_SLOTS, 4u);
@@ -172,7 +190,22 @@ static void build_impl(east_hip_index *h, Ctx &ctx, const u32 *d_sym, u32 n, u32
         u32 *term_ex = ar.alloc<u32>((size_t)n + 1);      // wide-alphabet path only
         const int vec = ((uintptr_t)d_sym & 15u) == 0;
         const bool fused = ctx.spec && vec && h->guess.p;     // (the bytes come out of the same pass, through the last build's map)
-        if (fused) LAUNCH(ctx, presence_remap_kernel, std::min<u32>(gn, 2048), d_sym, n, h->guess.as<const u32>(), present, h->s8);
+        if (fused && fp.valid && !ctx.dry) {
+            first_hist.s8 = h->s8;
+            first_hist.key_bytes = fp.key_bytes; first_hist.w = fp.w; first_hist.b = fp.b; first_hist.spare = fp.spare;
+            first_hist.term_first = fp.term_first; first_hist.shift = fp.shift; first_hist.mask = fp.mask;
+            if (fp.key_bytes == 8)
+                LAUNCH_NAMED(ctx, "presence_remap_hist_kernel", (presence_remap_hist_kernel<u64, TextWindowGen<u64>>), first_hist.n_groups,
+                             d_sym, n, h->guess.as<const u32>(), present, h->s8,
+                             TextWindowGen<u64>{h->s8, n, fp.w, fp.b, fp.spare, fp.term_first, DocKey()}, fp.shift, fp.mask,
+                             first_hist.n_tiles, first_hist.hist, first_hist.group_sum, first_hist.digit_total);
+            else
+                LAUNCH_NAMED(ctx, "presence_remap_hist_kernel", (presence_remap_hist_kernel<u32, TextWindowGen<u32>>), first_hist.n_groups,
+                             d_sym, n, h->guess.as<const u32>(), present, h->s8,
+                             TextWindowGen<u32>{h->s8, n, fp.w, fp.b, fp.spare, fp.term_first, DocKey()}, fp.shift, fp.mask,
+                             first_hist.n_tiles, first_hist.hist, first_hist.group_sum, first_hist.digit_total);
+            ctx.first_hist = &first_hist;
+        } else if (fused) LAUNCH(ctx, presence_remap_kernel, std::min<u32>(gn, 2048), d_sym, n, h->guess.as<const u32>(), present, h->s8);
         else LAUNCH(ctx, presence_kernel, std::min<u32>(gn, 2048), d_sym, n, vec, present);
         LAUNCH(ctx, validate_last_symbol_kernel, ceil_div_u32(n_docs, BLOCK), d_sym, (const u32 *)h->doc_off, n_docs,
                (u32)tagged, present + PRESENT_WORDS);
@@ -558,6 +591,7 @@ static void build_common(east_hip_index *h, const u32 *sym, bool sym_on_host, i6
         ctx.plan_fused = spec ? h->plan_fused : -1;
         ctx.plan_ht = spec ? h->plan_ht : -1;
         ctx.plan_persist = spec ? h->plan_persist : -1;
+        ctx.did_first = Ctx::FirstPassPlan();
         try {
             build_impl(h, ctx, sym, n, (u32)n_docs, doc_offsets, n_strings, h->hint_sigma, tagged);
         } catch (const SpecAbort &) {
@@ -611,6 +645,8 @@ static void build_common(east_hip_index *h, const u32 *sym, bool sym_on_host, i6
     if (h->stats.first_n > 0 && ((ctx.did_fused && h->stats.first_kept * 20 > h->stats.first_n) ||
                                  (!ctx.did_fused && h->stats.first_kept * 50 < h->stats.first_n)))
         h->plan_fused = -1;
+    // (the first radix pass as this build ran it, for the next remap pass to count ahead: only while the plan it came from stands)
+    h->first_plan = h->stats.window_sorted && h->plan_wide >= 0 && h->plan_fused >= 0 ? ctx.did_first : Ctx::FirstPassPlan();
     h->hint_no_rounds = h->stats.window_sorted && h->stats.refine_rounds == 0 && !h->stats.long_repeats;
     h->prof.collect();
     HIP_CHECK(hipEventElapsedTime(&h->last_build_ms, h->ev0, h->ev1));

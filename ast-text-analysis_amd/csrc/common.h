@@ -133,6 +133,7 @@ struct Stats {
     i64 ht_keys = 0;            // the first-level keys held variable-length code words (ht_code.h)
     i64 seg_sort = 0;           // the first-level sort was segmented by document (radix_sort.h: RsSeg)
     i64 persist_rounds = 0;     // rounds run inside ONE launch by the workgroups that keep their tiles (persist_rounds.h)
+    i64 first_hist_fused = 0;   // the first radix pass's histogram came out of the remap pass (presence_remap_hist_kernel)
 };
 
 // Optional per-kernel timing with HIP events on the handle's own stream (the
@@ -215,6 +216,7 @@ struct Knobs {
     int persist_max_wgs = env_int("EAST_HIP_PERSIST_WGS", 0);          // ... with at most this many workgroups (0: what the device holds)
     size_t rank_bucket_bytes = (size_t)192 << 20;                       // east_hip_debug_set_rank_bucket_bytes
     bool speculate = getenv("EAST_HIP_NO_SPECULATION") == nullptr;      // east_hip_debug_set_speculation
+    bool first_hist = getenv("EAST_HIP_NO_FIRST_HIST") == nullptr;      // ... (2 switches it off): the first radix histogram counted by the remap pass
     bool kg_pairs = getenv("EAST_HIP_NO_KG_PAIRS") == nullptr;          // east_hip_debug_set_score_path
     bool kg_pairs_forced = false;                                       // ... (4)
     bool score_fused = getenv("EAST_HIP_SCORE_UNFUSED") == nullptr;     // ... (1 / 3 / 4)
@@ -254,6 +256,15 @@ struct Ctx {
     bool spec_rounds = false;   // ... nor for the placement pass's counts (it goes on as if no tie group were large)
     u32 *spec_out = nullptr;    // [0] suffixes left in large groups, [1] placement gave up on a long repeat
     u32 *zeroed_word = nullptr; // one word the build has already zeroed: the first level-0 pass takes it for its fail flag
+    u32 *zeroed_totals = nullptr;   // 2 * RS_TOTAL_SHARDS * RS_BINS words likewise: the digit totals of the first unsegmented radix sort
+    // Speculative build: the first level's first radix pass as the build before ran it (FirstPassPlan), and -- where the
+    // remap pass counted that pass's histogram ahead -- the counts for the sort to take (radix_sort.h: RsFirstHist)
+    const struct RsFirstHist *first_hist = nullptr;
+    struct FirstPassPlan {
+        bool valid = false;                 // fixed-width keys of text only: no document number, not segmented, all suffixes
+        int key_bytes = 0, w = 0, b = 0, spare = 0, shift = 0;
+        u32 term_first = 0, mask = 0;
+    } did_first;                            // out: what the all-suffix window sort's first pass was
     u32 *kg_bad = nullptr;      // raised by the fused finish when the k-gram marks it writes are incomplete (a bucket handed to the rounds)
     // What the sample of the build's own text says (sample_prefix_kernel; a handle's first build and every build that
     // waits for the alphabet): of sample_n consecutive suffixes, sample_dup2[l] / sample_dup4[l] share their first

@@ -46,6 +46,53 @@ template <class K> static void debug_sort(int device, K *keys, u32 *vals, i64 n,
     HIP_CHECK(hipStreamSynchronize(sc.stream));
 }
 
+template <class K>
+static void debug_first_pass_hist(int device, const u32 *symbols, i64 n64, const u32 *code_map, int w, int b, int spare,
+                                  u32 term_first, int shift, u32 mask, uint8_t *s8_out, u32 *present_out, u32 *hist_out,
+                                  u32 *group_sum_out, u32 *digit_total_out)
+{
+    if (!symbols || !code_map || !s8_out || !present_out || !hist_out || !group_sum_out || !digit_total_out || n64 < 1 ||
+        n64 >= (i64)0x7FFFFFF0 || w < 1 || w > 12 || b < 1 || b > 8 || spare < 0 || spare >= b ||
+        w * b + spare > (int)sizeof(K) * 8 || shift < 0 || shift >= (int)sizeof(K) * 8 || mask > 255u || term_first > 255u)
+        east_throw(EAST_HIP_ERR_INVALID, "bad first-pass histogram arguments");
+    const u32 n = (u32)n64, n_tiles = ceil_div_u32(n, RS_TILE), n_groups = ceil_div_u32(n_tiles, RS_GROUP);
+    const size_t hist_words = (size_t)RS_BINS * n_tiles, sum_words = (size_t)RS_BINS * n_groups, total_words = (size_t)RS_TOTAL_SHARDS * RS_BINS;
+    DebugScope sc(device, (size_t)n * 4 + 2 * ((size_t)n + 64) + 2 * (hist_words + sum_words + total_words + PRESENT_WORDS + 1) * 4 +
+                              TEXT_SYMBOLS * 4 + (1u << 20));
+    Arena &ar = sc.arena;
+    u32 *d_sym = ar.alloc<u32>(n), *d_map = ar.alloc<u32>(TEXT_SYMBOLS);
+    HIP_CHECK(hipMemcpyAsync(d_sym, symbols, (size_t)n * 4, hipMemcpyHostToDevice, sc.stream));
+    HIP_CHECK(hipMemcpyAsync(d_map, code_map, TEXT_SYMBOLS * 4, hipMemcpyHostToDevice, sc.stream));
+    for (int v = 0; v < 2; v++) {
+        uint8_t *s8 = ar.alloc<uint8_t>((size_t)n + 64);
+        u32 *present = ar.alloc<u32>(PRESENT_WORDS + 1), *hist = ar.alloc<u32>(hist_words), *group_sum = ar.alloc<u32>(sum_words);
+        u32 *total = ar.alloc<u32>(total_words);
+        // (what lies behind the pad differs between the two: no counted key may depend on it)
+        HIP_CHECK(hipMemsetAsync(s8, v ? 0xA5 : 0x5A, (size_t)n + 64, sc.stream));
+        HIP_CHECK(hipMemsetAsync(present, 0, (PRESENT_WORDS + 1) * 4, sc.stream));
+        HIP_CHECK(hipMemsetAsync(hist, 0xEE, hist_words * 4, sc.stream));
+        HIP_CHECK(hipMemsetAsync(group_sum, 0xEE, sum_words * 4, sc.stream));
+        HIP_CHECK(hipMemsetAsync(total, 0, total_words * 4, sc.stream));
+        const TextWindowGen<K> gen{s8, n, w, b, spare, term_first, DocKey()};
+        if (v == 0) {
+            LAUNCH_NAMED(sc.ctx, "presence_remap_hist_kernel", (presence_remap_hist_kernel<K, TextWindowGen<K>>), n_groups,
+                         (const u32 *)d_sym, n, (const u32 *)d_map, present, s8, gen, shift, mask, n_tiles, hist, group_sum, total);
+        } else {
+            LAUNCH(sc.ctx, presence_kernel, std::min<u32>(ceil_div_u32(n, BLOCK), 2048), (const u32 *)d_sym, n, 1, present);
+            LAUNCH(sc.ctx, remap_bytes_kernel, ceil_div_u32((u64)n + 16, BLOCK * 16), (const u32 *)d_sym, (const u32 *)d_map, n, 1, s8);
+            hipLaunchKernelGGL((radix_hist_kernel<K, TextWindowGen<K>, false>), dim3(n_groups), dim3(RS_HIST_THREADS), 0, sc.stream, gen, n,
+                               shift, mask, n_tiles, hist, group_sum, total, RsSeg());
+            HIP_CHECK(hipGetLastError());
+        }
+        HIP_CHECK(hipMemcpyAsync(s8_out + (size_t)v * ((size_t)n + 16), s8, (size_t)n + 16, hipMemcpyDeviceToHost, sc.stream));
+        HIP_CHECK(hipMemcpyAsync(present_out + (size_t)v * PRESENT_WORDS, present, PRESENT_WORDS * 4, hipMemcpyDeviceToHost, sc.stream));
+        HIP_CHECK(hipMemcpyAsync(hist_out + v * hist_words, hist, hist_words * 4, hipMemcpyDeviceToHost, sc.stream));
+        HIP_CHECK(hipMemcpyAsync(group_sum_out + v * sum_words, group_sum, sum_words * 4, hipMemcpyDeviceToHost, sc.stream));
+        HIP_CHECK(hipMemcpyAsync(digit_total_out + v * total_words, total, total_words * 4, hipMemcpyDeviceToHost, sc.stream));
+    }
+    HIP_CHECK(hipStreamSynchronize(sc.stream));
+}
+
 extern "C" {
 
 int east_hip_debug_set_rank_bucket_bytes(int64_t bytes)
@@ -190,8 +237,21 @@ int east_hip_debug_set_score_path(int mode)
 
 int east_hip_debug_set_speculation(int enabled)
 {
-    knobs_update([&](Knobs &k) { k.speculate = enabled != 0; });
+    // 0: every build waits for the alphabet and the placement counts; 1: the default; 2: as 1, the first radix pass's
+    // histogram counted by a launch of its own (no presence_remap_hist_kernel)
+    knobs_update([&](Knobs &k) { k.speculate = enabled != 0; k.first_hist = enabled != 2 && getenv("EAST_HIP_NO_FIRST_HIST") == nullptr; });
     return EAST_HIP_OK;
+}
+
+int east_hip_debug_first_pass_hist(int device, const uint32_t *symbols, int64_t n, const uint32_t *code_map, int key_bytes,
+                                   int w, int b, int spare, uint32_t term_first, int shift, uint32_t mask, uint8_t *s8,
+                                   uint32_t *present, uint32_t *hist, uint32_t *group_sum, uint32_t *digit_total)
+{
+    return guarded([&] {
+        if (key_bytes == 8) debug_first_pass_hist<u64>(device, symbols, n, code_map, w, b, spare, term_first, shift, mask, s8, present, hist, group_sum, digit_total);
+        else if (key_bytes == 4) debug_first_pass_hist<u32>(device, symbols, n, code_map, w, b, spare, term_first, shift, mask, s8, present, hist, group_sum, digit_total);
+        else east_throw(EAST_HIP_ERR_INVALID, "key_bytes must be 4 or 8");
+    });
 }
 
 int east_hip_debug_radix_sort_u64(int device, uint64_t *keys, uint32_t *vals, int64_t n, int bits)

@@ -349,6 +349,7 @@ int east_hip_reset(east_hip_handle_t h)
         h->prof.enabled = false;
         h->prof.only.clear();
         h->plan_wide = h->plan_fused = h->plan_ht = h->plan_persist = -1;
+        h->first_plan = Ctx::FirstPassPlan();
         h->ht_valid = false;
         h->stats = Stats();
         // a recycled handle keeps its stream and a small arena, not gigabytes of side allocations
@@ -374,16 +375,16 @@ void *east_hip_stream(east_hip_handle_t h) { return h ? (void *)h->stream : null
 int east_hip_build_info(east_hip_handle_t h, int64_t *out, int32_t cap)
 {
     if (!h || !out) return EAST_HIP_ERR_INVALID;
-    const int64_t v[27] = {h->n, h->n_docs, h->m_total, h->sigma_t, h->bits0, h->stats.levels,
+    const int64_t v[28] = {h->n, h->n_docs, h->m_total, h->sigma_t, h->bits0, h->stats.levels,
                            (int64_t)h->arena.cap, (int64_t)h->arena.high, h->stats.radix_passes,
                            h->stats.radix_elems, h->stats.radix_elem_bytes, h->stats.radix_passes_u32,
                            h->stats.radix_elems_u32, h->stats.radix_passes_u64, h->stats.radix_elems_u64,
                            h->stats.levels_resolved, h->stats.merge_elems, h->stats.refine_rounds,
                            h->stats.window_sorted, h->stats.lds_sorted, h->stats.fused_finish, h->stats.first_kept,
                            h->stats.first_n, h->stats.ht_keys, h->stats.seg_sort, h->narrow_upload,
-                           h->stats.persist_rounds};
-    for (int i = 0; i < 27 && i < cap; i++) out[i] = v[i];
-    return 27;
+                           h->stats.persist_rounds, h->stats.first_hist_fused};
+    for (int i = 0; i < 28 && i < cap; i++) out[i] = v[i];
+    return 28;
 }
 
 int east_hip_profile_enable(east_hip_handle_t h, int on)

@@ -34,6 +34,7 @@ struct east_hip_index {
     int plan_wide = -1, plan_fused = -1;   // what the last build's window sort did (wide first window, fused finish): a speculative build does the same
     int plan_ht = -1;                      // ... (first-level keys of variable-length code words)
     int plan_persist = -1;                 // ... (the first domain went straight to the persistent rounds)
+    Ctx::FirstPassPlan first_plan;         // ... (the first radix pass of its first level: what the next remap pass counts ahead)
     // the order-preserving variable-length code of the last build that made one (ht_code.h): device tables (own
     // allocation: 256 x u32 enc, 4096 x u16 dec), valid for text with ht_sigma text symbols
     DevBuf ht_tab;

@@ -16,6 +16,7 @@
 // 3-pass sort as slow as the 4-pass one; see DESIGN.md.)
 #pragma once
 #include "common.h"
+#include "alphabet.h"
 #include "scan.h"
 
 #define RS_THREADS 1024                // threads per scatter workgroup (16 waves)
@@ -190,6 +191,200 @@ __global__ __launch_bounds__(RS_HIST_THREADS) void radix_hist_kernel(Src src, u3
     // (segmented: a row of totals per document)
     const u32 row = seg.n_docs ? seg.group_doc[g] * seg.shards + g % seg.shards : g % RS_TOTAL_SHARDS;
     if (run) atomicAdd(&digit_total[(size_t)row * RS_BINS + threadIdx.x], run);
+}
+
+// ---- speculative build: presence bitmap, byte stream AND the first pass's histogram in one kernel --------
+// presence_remap_kernel (alphabet.h) streams the symbols at the speed of memory, radix_hist_kernel<gen> one launch later
+// reads the bytes back and is bound by its LDS atomics: here one wave does both for a tile, a stretch at a time -- the
+// symbols of the stretch with 16-byte loads, all in flight at once; through the guessed code map in LDS to bytes, which
+// go to s8 and stay in the wave's own piece of LDS; the keys rolled out of those with Gen::keys_of_run and counted
+// exactly as Gen::hist_tile counts them, while the loads of the wave's next stretch are under way.  Unsegmented, no
+// document number in the keys (Gen = TextWindowGen<K> with docs.bits == 0); n_tiles tiles of RS_TILE positions from 0 on.
+//
+// The counts equal radix_hist_kernel<K, Gen, false>'s on the s8 written here, whatever the bytes are (the scatter
+// takes its destinations from them while reading s8 itself): the key of position q holds the bytes q .. q + w, w <= 12,
+// so the keys of a stretch need its bytes and the RS_FIRST_HALO = 16 behind it -- mapped from the symbols like the
+// stretch's own where they lie below n, zero from n on, which is what the pad written here holds.  The bytes from
+// n + 16 on, which load_run touches for the last run, lie behind every counted key (q < n: q + 12 < n + 16).
+#define RS_FIRST_HALO 16u
+// stretches a tile goes through a wave in.  One (16 loads in flight per lane, 102 VGPRs, 37 KiB of LDS: 4 waves a SIMD)
+// 108 us on the 64 MiB document, two (68 VGPRs, 29 KiB: 5 waves) 99 us, four (52 VGPRs, 25 KiB: 6 waves) 104 us.
+#ifndef RS_FIRST_PARTS
+#define RS_FIRST_PARTS 2
+#endif
+#define RS_GEN_RUN 8                    // positions a generator rolls out at once (window_sort.h: TW_RUN)
+struct RsFirstHist {                    // the counts of a first pass made ahead of the sort, and what they were counted with
+    u32 *hist = nullptr, *group_sum = nullptr, *digit_total = nullptr;
+    const uint8_t *s8 = nullptr;
+    u32 n = 0, n_tiles = 0, n_groups = 0;
+    int key_bytes = 0, w = 0, b = 0, spare = 0;
+    u32 term_first = 0;
+    int shift = 0;
+    u32 mask = 0;
+};
+// (the generators that a first pass can be counted ahead for say so themselves: window_sort.h)
+template <class Gen> static inline bool rs_first_hist_counted_for(const RsFirstHist &, const Gen &) { return false; }
+
+template <class K, class Gen>
+__global__ __launch_bounds__(RS_HIST_THREADS) void presence_remap_hist_kernel(const u32 *__restrict__ sym, u32 n,
+                                                                              const u32 *__restrict__ guess, u32 *__restrict__ present,
+                                                                              uint8_t *__restrict__ s8, Gen gen, int shift, u32 mask,
+                                                                              u32 n_tiles, u32 *__restrict__ hist,
+                                                                              u32 *__restrict__ group_sum, u32 *__restrict__ digit_total)
+{
+    constexpr int UW = RS_HIST_THREADS / WAVE;
+    constexpr int PARTS = RS_FIRST_PARTS, SUB = RS_TILE / PARTS;
+    constexpr int LOADS = SUB / (WAVE * 4);             // 16-byte loads of a lane per stretch: four symbols each
+    static_assert(SUB * PARTS == RS_TILE && SUB % (WAVE * RS_GEN_RUN) == 0, "stretches of whole runs for every lane");
+    static_assert(RS_HIST_THREADS == RS_BINS, "thread d owns digit d");
+    static_assert(RS_TILE % (WAVE * RS_GEN_RUN) == 0 && RS_FIRST_HALO % 4 == 0 && RS_FIRST_HALO / 4 <= WAVE, "whole runs, a halo of whole words");
+    __shared__ u32 bins[RS_GROUP][RS_HIST_COPIES][RS_BINS];
+    // the guessed code map, 16 bits a symbol: the code, and bit 8 once this workgroup has met the symbol -- ONE LDS read per
+    // symbol answers both "which byte" and "is its presence recorded" (presence_remap_kernel reads a bitmap and a byte map)
+    __shared__ __attribute__((aligned(16))) u32 tab[TEXT_SYMBOLS / 2];
+    __shared__ __attribute__((aligned(16))) u32 bytes[UW][(SUB + RS_FIRST_HALO) / 4];
+    typedef uint16_t __attribute__((may_alias)) tab16_t;
+    const tab16_t *tab16 = reinterpret_cast<const tab16_t *>(tab);
+#pragma unroll
+    for (int k = 0; k < RS_GROUP; k++)
+#pragma unroll
+        for (int c = 0; c < RS_HIST_COPIES; c++) bins[k][c][threadIdx.x] = 0;
+    {
+        // (the code map's words with 16-byte loads, all of a thread's requested before the first is used: presence_remap_kernel)
+        static_assert(TEXT_SYMBOLS % 4 == 0, "whole 16-byte groups");
+        constexpr u32 GROUPS = TEXT_SYMBOLS / 4, ROUNDS = (GROUPS + RS_HIST_THREADS - 1) / RS_HIST_THREADS;
+        uint4 q[ROUNDS];
+#pragma unroll
+        for (u32 r = 0; r < ROUNDS; r++) {
+            const u32 g = threadIdx.x + r * RS_HIST_THREADS;
+            q[r] = reinterpret_cast<const uint4 *>(guess)[g < GROUPS ? g : 0u];
+        }
+#pragma unroll
+        for (u32 r = 0; r < ROUNDS; r++) {
+            const u32 g = threadIdx.x + r * RS_HIST_THREADS;
+            if (g < GROUPS)
+                reinterpret_cast<uint2 *>(tab)[g] = uint2{(q[r].x & 0xFFu) | ((q[r].y & 0xFFu) << 16), (q[r].z & 0xFFu) | ((q[r].w & 0xFFu) << 16)};
+        }
+    }
+    __syncthreads();
+    // (a plain read: an entry only ever gains its bit, and a stale one costs a redundant atomic.  The four symbols of a
+    // load are looked up side by side and the marking is a branch per load, not per symbol: one symbol after the other, each
+    // waiting for its own LDS read, a wave spent more time here than counting)
+    auto mark = [&](u32 c) {
+        if (c < TEXT_SYMBOLS) atomicOr(&tab[c >> 1], 0x100u << (16u * (c & 1u)));
+    };
+    auto word = [&](const uint4 q) -> u32 {
+        const u32 vx = tab16[q.x < TEXT_SYMBOLS ? q.x : 0u], vy = tab16[q.y < TEXT_SYMBOLS ? q.y : 0u];
+        const u32 vz = tab16[q.z < TEXT_SYMBOLS ? q.z : 0u], vw = tab16[q.w < TEXT_SYMBOLS ? q.w : 0u];
+        const u32 bx = q.x < TEXT_SYMBOLS ? vx : 0x1FFu, by = q.y < TEXT_SYMBOLS ? vy : 0x1FFu;
+        const u32 bz = q.z < TEXT_SYMBOLS ? vz : 0x1FFu, bw = q.w < TEXT_SYMBOLS ? vw : 0x1FFu;
+        if (!(bx & by & bz & bw & 0x100u)) { mark(q.x); mark(q.y); mark(q.z); mark(q.w); }
+        return (bx & 0xFFu) | ((by & 0xFFu) << 8) | ((bz & 0xFFu) << 16) | (bw << 24);
+    };
+    auto code = [&](u32 c) -> u32 {
+        if (c >= TEXT_SYMBOLS) return 0xFFu;
+        const u32 v = tab16[c];
+        if (!(v & 0x100u)) mark(c);
+        return v & 0xFFu;
+    };
+    // the four bytes from position 4 * g on where the 16-byte load does not apply: symbol by symbol below n, zero behind
+    auto word_slow = [&](u32 g) -> u32 {
+        u32 v = 0;
+#pragma unroll
+        for (u32 k = 0; k < 4; k++) {
+            const u64 p = (u64)g * 4u + k;
+            if (p < n) v |= code(sym[p]) << (8u * k);
+        }
+        return v;
+    };
+    const u32 g = blockIdx.x, lane = lane_id(), n4 = n >> 2;
+    const u32 t0 = g * RS_GROUP, t1 = t0 + RS_GROUP < n_tiles ? t0 + RS_GROUP : n_tiles;
+    u32 *mine_bytes = bytes[wave_id()];
+    u32 *out = reinterpret_cast<u32 *>(s8);
+    uint4 q[LOADS];
+    // (a load of a group that does not lie wholly below n is not made: word_slow reads its symbols)
+    auto request = [&](u32 tile, u32 part) {
+        const u32 g0 = tile * (u32)(RS_TILE / 4) + part * (u32)(SUB / 4) + lane;
+#pragma unroll
+        for (int j = 0; j < LOADS; j++) {
+            const u32 gi = g0 + (u32)j * WAVE;
+            q[j] = gi < n4 ? reinterpret_cast<const uint4 *>(sym)[gi] : uint4{0u, 0u, 0u, 0u};
+        }
+    };
+    u32 tile = t0 + wave_id(), part = 0;
+    if (tile < t1) request(tile, 0);
+    while (tile < t1) {
+        const u32 g0 = tile * (u32)(RS_TILE / 4) + part * (u32)(SUB / 4) + lane;
+        const u32 base = tile * (u32)RS_TILE + part * (u32)SUB;
+        const u32 count = base < n ? (n - base < (u32)SUB ? n - base : (u32)SUB) : 0u;
+#pragma unroll
+        for (int j = 0; j < LOADS; j++) {
+            const u32 gi = g0 + (u32)j * WAVE;
+            u32 v;
+            if (gi < n4) { v = word(q[j]); out[gi] = v; }
+            else v = word_slow(gi);                      // (the last n % 4 symbols and the pad go to s8 below)
+            mine_bytes[(u32)j * WAVE + lane] = v;
+        }
+        if (lane < RS_FIRST_HALO / 4u) {
+            // the bytes behind the stretch: the next one's first, through the same map (their presence is recorded there)
+            const u32 gi = (base + (u32)SUB) / 4u + lane;
+            u32 v = 0;
+#pragma unroll
+            for (u32 k = 0; k < 4; k++) {
+                const u64 p = (u64)gi * 4u + k;
+                if (p < n) { const u32 c = sym[p]; v |= (c < TEXT_SYMBOLS ? (u32)tab16[c] & 0xFFu : 0xFFu) << (8u * k); }
+            }
+            mine_bytes[SUB / 4 + lane] = v;
+        }
+        const u32 next_part = part + 1u < (u32)PARTS ? part + 1u : 0u, next_tile = next_part ? tile : tile + UW;
+        if (next_tile < t1) request(next_tile, next_part);
+        __builtin_amdgcn_sched_barrier(0);              // (the next stretch's loads are under way while this one is counted)
+        // (the wave reads what its own lanes wrote: LDS operations of a wave complete in order)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        u32 *mine = bins[tile - t0][lane & (RS_HIST_COPIES - 1)];
+        for (u32 r0 = lane * RS_GEN_RUN; r0 < count; r0 += WAVE * RS_GEN_RUN) {      // as Gen::hist_tile, the bytes from LDS
+            u32 x[6];
+            K k[RS_GEN_RUN];
+            const uint2 a = *reinterpret_cast<const uint2 *>(&mine_bytes[r0 / 4]), c = *reinterpret_cast<const uint2 *>(&mine_bytes[r0 / 4 + 2]);
+            const uint2 e = *reinterpret_cast<const uint2 *>(&mine_bytes[r0 / 4 + 4]);
+            x[0] = a.x; x[1] = a.y; x[2] = c.x; x[3] = c.y; x[4] = e.x; x[5] = e.y;
+            gen.keys_of_run(x, k);
+#pragma unroll
+            for (int qq = 0; qq < RS_GEN_RUN; qq++)
+                if (r0 + qq < count) radix_hist_add<false>(mine, (u32)(k[qq] >> shift) & mask);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        tile = next_tile;
+        part = next_part;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < 20u) {            // the last n % 4 symbols and the 16 pad bytes
+        const u32 j = (n4 << 2) + threadIdx.x;
+        if (j < n) { const u32 c = sym[j]; s8[j] = (uint8_t)(c < TEXT_SYMBOLS ? (u32)tab16[c] & 0xFFu : 0xFFu); }
+        else if (j < n + 16u) s8[j] = 0;
+    }
+    // the epilogue of radix_hist_kernel
+    syncthreads_after_lds_atomics();
+    u32 run = 0;
+#pragma unroll
+    for (int k = 0; k < RS_GROUP; k++) {
+        if (t0 + k < t1) hist[(size_t)(t0 + k) * RS_BINS + threadIdx.x] = run;
+#pragma unroll
+        for (int c = 0; c < RS_HIST_COPIES; c++) run += bins[k][c][threadIdx.x];
+    }
+    group_sum[(size_t)g * RS_BINS + threadIdx.x] = run;
+    if (run) atomicAdd(&digit_total[(size_t)(g % RS_TOTAL_SHARDS) * RS_BINS + threadIdx.x], run);
+    if (threadIdx.x < PRESENT_WORDS) {                    // the symbols met, as a word of the presence bitmap
+        u32 bits = 0;
+#pragma unroll
+        for (u32 k = 0; k < 16; k++) {
+            const u32 v = tab[threadIdx.x * 16u + k];
+            bits |= (((v >> 8) & 1u) | ((v >> 23) & 2u)) << (2u * k);
+        }
+        if (bits) atomicOr(&present[threadIdx.x], bits);
+    }
 }
 
 // ---- spine: exclusive scan down the groups, per digit column, plus the digit bases --------------------
@@ -519,9 +714,12 @@ static inline void radix_account(Ctx &ctx, size_t key_bytes, u32 n, bool generat
 // that hold the sorted pairs.
 // check_from_bit: the histogram passes at or above that bit test every key for "the whole wavefront on one bin" (keys
 // that arrive sorted on their high bits: group numbers, document numbers); the passes below take the digits as spread out.
+// pre: the first pass's histogram was counted ahead (presence_remap_hist_kernel).  It is taken -- that pass's
+// radix_hist_kernel<gen> launch left out -- only if it was counted with exactly what this sort is about to use: the
+// generator's parameters, n, the tile geometry, the first digit; otherwise the sort runs as if there were none.
 template <class K, class Gen = NoGen>
 static int radix_sort_pairs(Ctx &ctx, SortBufs<K> &b, u32 n, int bits, int begin_bit = 0, Gen gen = Gen(), int check_from_bit = 0,
-                            RsSeg seg = RsSeg())
+                            RsSeg seg = RsSeg(), const RsFirstHist *pre = nullptr)
 {
     constexpr bool HAS_GEN = !std::is_same<Gen, NoGen>::value;
     if (n == 0 || bits <= begin_bit) return 0;
@@ -533,8 +731,18 @@ static int radix_sort_pairs(Ctx &ctx, SortBufs<K> &b, u32 n, int bits, int begin
     u32 *group_sum = ctx.arena->alloc<u32>((size_t)RS_BINS * n_groups);
     u32 *group_prefix = ctx.arena->alloc<u32>((size_t)RS_BINS * n_groups);
     u32 *totals = ctx.arena->alloc<u32>(2 * total_words);
-    if (!ctx.dry) HIP_CHECK(hipMemsetAsync(totals, 0, 2 * total_words * sizeof(u32), ctx.stream));
+    if (!ctx.dry && !seg.n_docs && ctx.zeroed_totals) {
+        totals = ctx.zeroed_totals;              // (zeroed with the build's flag words: one fill less)
+        ctx.zeroed_totals = nullptr;
+    } else if (!ctx.dry) HIP_CHECK(hipMemsetAsync(totals, 0, 2 * total_words * sizeof(u32), ctx.stream));
     const bool prof = ctx.prof && ctx.prof->enabled;
+    bool counted = false;
+    if constexpr (HAS_GEN) {
+        counted = pre && !ctx.dry && !seg.n_docs && pre->hist && pre->key_bytes == (int)sizeof(K) && pre->n == n &&
+                  pre->n_tiles == n_tiles && pre->n_groups == n_groups && pre->shift == begin_bit &&
+                  pre->mask == (1u << std::min(RS_DB, bits - begin_bit)) - 1u && rs_first_hist_counted_for(*pre, gen);
+    }
+    if (counted && ctx.stats) ctx.stats->first_hist_fused = 1;
     int cur = 0, pass = 0;
     bool first = HAS_GEN;                       // the generator pass reads no buffers and writes [0]
     for (int shift = begin_bit; shift < bits; shift += RS_DB, pass++) {
@@ -542,12 +750,16 @@ static int radix_sort_pairs(Ctx &ctx, SortBufs<K> &b, u32 n, int bits, int begin
         const PairSrc<K> src{b.keys[cur], b.vals[cur]};
         const int out = first ? 0 : cur ^ 1;
         u32 *tot = totals + (pass & 1) * total_words, *tot_next = totals + ((pass & 1) ^ 1) * total_words;
+        // (the pass counted ahead: its own tables, read by the spine and the scatter of this pass only)
+        const bool have = first && counted;
+        u32 *hist_p = have ? pre->hist : hist, *group_sum_p = have ? pre->group_sum : group_sum;
+        if (have) tot = pre->digit_total;
         // (static strings: the profiler keeps the pointers)
         const char *name_hist = sizeof(K) == 8 ? (first ? "radix_hist_kernel<u64,gen>" : "radix_hist_kernel<u64>")
                                                : (first ? "radix_hist_kernel<u32,gen>" : "radix_hist_kernel<u32>");
         const char *name_scatter = sizeof(K) == 8 ? (first ? "radix_scatter_kernel<u64,gen>" : "radix_scatter_kernel<u64>")
                                                   : (first ? "radix_scatter_kernel<u32,gen>" : "radix_scatter_kernel<u32>");
-        if (!ctx.dry) {
+        if (!ctx.dry && !have) {
             if (prof) ctx.prof->begin(name_hist, ctx.stream);
             const bool check = shift + RS_DB > check_from_bit;
             if constexpr (HAS_GEN) {
@@ -569,12 +781,12 @@ static int radix_sort_pairs(Ctx &ctx, SortBufs<K> &b, u32 n, int bits, int begin
         }
         if (seg.n_docs) {
             if (seg.n_big < seg.n_docs)
-                LAUNCH(ctx, radix_spine_docs_kernel, seg.n_docs, (const u32 *)group_sum, (const u32 *)tot, tot_next, group_prefix, seg);
+                LAUNCH(ctx, radix_spine_docs_kernel, seg.n_docs, (const u32 *)group_sum_p, (const u32 *)tot, tot_next, group_prefix, seg);
             if (seg.n_big)
-                LAUNCH(ctx, radix_spine_kernel, dim3(RS_BINS / RS_SPINE_COLS, seg.n_big), (const u32 *)group_sum, n_groups,
+                LAUNCH(ctx, radix_spine_kernel, dim3(RS_BINS / RS_SPINE_COLS, seg.n_big), (const u32 *)group_sum_p, n_groups,
                        (const u32 *)tot, tot_next, group_prefix, seg);
         } else {
-            LAUNCH(ctx, radix_spine_kernel, dim3(RS_BINS / RS_SPINE_COLS, 1u), (const u32 *)group_sum, n_groups, (const u32 *)tot,
+            LAUNCH(ctx, radix_spine_kernel, dim3(RS_BINS / RS_SPINE_COLS, 1u), (const u32 *)group_sum_p, n_groups, (const u32 *)tot,
                    tot_next, group_prefix, seg);
         }
         if (!ctx.dry) {
@@ -583,11 +795,11 @@ static int radix_sort_pairs(Ctx &ctx, SortBufs<K> &b, u32 n, int bits, int begin
             if constexpr (HAS_GEN) {
                 if (first)
                     hipLaunchKernelGGL((radix_scatter_kernel<K, Gen>), grid, dim3(RS_THREADS), 0, ctx.stream, gen, b.keys[out],
-                                       b.vals[out], n, shift, mask, (const u32 *)hist, (const u32 *)group_prefix, n_tiles, seg);
+                                       b.vals[out], n, shift, mask, (const u32 *)hist_p, (const u32 *)group_prefix, n_tiles, seg);
             }
             if (!first)
                 hipLaunchKernelGGL((radix_scatter_kernel<K, PairSrc<K>>), grid, dim3(RS_THREADS), 0, ctx.stream, src, b.keys[out],
-                                   b.vals[out], n, shift, mask, (const u32 *)hist, (const u32 *)group_prefix, n_tiles, seg);
+                                   b.vals[out], n, shift, mask, (const u32 *)hist_p, (const u32 *)group_prefix, n_tiles, seg);
             HIP_CHECK(hipGetLastError());
             if (prof) ctx.prof->end(ctx.stream);
         }

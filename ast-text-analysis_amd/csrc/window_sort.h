@@ -357,6 +357,14 @@ template <class K> struct TextWindowGen {
     }
 };
 
+static_assert(TW_RUN == RS_GEN_RUN, "presence_remap_hist_kernel rolls out the same runs");
+// the counts of presence_remap_hist_kernel stand for this generator's first pass: the same bytes, the same window
+template <class K> static inline bool rs_first_hist_counted_for(const RsFirstHist &p, const TextWindowGen<K> &g)
+{
+    return !g.docs.bits && !g.docs.seg.n_docs && p.s8 == g.s8 && p.n == g.n && p.key_bytes == (int)sizeof(K) && p.w == g.w &&
+           p.b == g.b && p.spare == g.spare && p.term_first == g.term_first;
+}
+
 // The same for keys of VARIABLE-LENGTH code words (ht_code.h): the key of position q is the first `sb` bits of the coded
 // suffix -- stream(q) = code(x[q]) on top of stream(q + 1) moved down by its length, nothing behind a terminator's code
 // word --, under the document number.  Code words have at least HT_MIN_LEN = 3 bits, so 16 symbols fill the HT_MAX_STREAM =
@@ -1883,6 +1891,53 @@ __global__ __launch_bounds__(BLOCK) void spec_counts_kernel(const u32 *__restric
     }
 }
 
+// Several stretches of device memory set to a value each in ONE launch (the k-gram marks' table, the keep bits and the
+// group-start bits in front of the first placement pass: a fill launch each cost a launch-sized gap on the build's one
+// stream).  Regions of whole words that start at multiples of 16 bytes; a workgroup belongs to one region and a thread
+// stores four 16-byte groups.
+#define CLEAR_MAX_REGIONS 4
+#define CLEAR_BLOCK_WORDS (BLOCK * 16u)
+struct ClearRegions {
+    u32 *p[CLEAR_MAX_REGIONS];
+    u32 words[CLEAR_MAX_REGIONS], value[CLEAR_MAX_REGIONS], first_block[CLEAR_MAX_REGIONS + 1];
+    int count = 0;
+};
+__global__ __launch_bounds__(BLOCK) void clear_regions_kernel(ClearRegions r)
+{
+    int k = 0;
+    while (k + 1 < r.count && blockIdx.x >= r.first_block[k + 1]) k++;
+    u32 *p = r.p[k];
+    const u32 words = r.words[k], v = r.value[k];
+    const u32 w0 = (blockIdx.x - r.first_block[k]) * CLEAR_BLOCK_WORDS;
+#pragma unroll
+    for (u32 j = 0; j < 4; j++) {
+        const u32 i = w0 + (j * BLOCK + threadIdx.x) * 4u;
+        if (i + 4u <= words) *reinterpret_cast<uint4 *>(p + i) = uint4{v, v, v, v};
+        else
+            for (u32 q = i; q < words; q++) p[q] = v;
+    }
+}
+// (a stretch the kernel cannot take -- not 16-byte aligned, no whole words, 16 GiB or more -- gets a fill of its own)
+static void clear_add(Ctx &ctx, ClearRegions &r, void *p, size_t bytes, int byte_value)
+{
+    if (ctx.dry || !bytes) return;
+    if (((uintptr_t)p & 15u) || (bytes & 3u) || (bytes >> 2) > 0xFFFFFFFFull - CLEAR_BLOCK_WORDS || r.count == CLEAR_MAX_REGIONS) {
+        HIP_CHECK(hipMemsetAsync(p, byte_value, bytes, ctx.stream));
+        return;
+    }
+    if (!r.count) r.first_block[0] = 0;
+    r.p[r.count] = (u32 *)p;
+    r.words[r.count] = (u32)(bytes >> 2);
+    r.value[r.count] = 0x01010101u * (u32)(byte_value & 0xFF);
+    r.first_block[r.count + 1] = r.first_block[r.count] + ceil_div_u32(bytes >> 2, CLEAR_BLOCK_WORDS);
+    r.count++;
+}
+static void clear_run(Ctx &ctx, const ClearRegions &r)
+{
+    if (ctx.dry || !r.count) return;
+    LAUNCH(ctx, clear_regions_kernel, r.first_block[r.count], r);
+}
+
 // The persistent rounds (persist_rounds.h): how many of its workgroups the device holds at once -- the launch never asks
 // for more -- and the lock that keeps two such launches of one process from sharing the chip half resident each.
 #define PERSIST_SMALL_INPUT ((u32)4 << 20)      // inputs whose names cost next to nothing to initialise (0.1 ms)
@@ -1996,7 +2051,15 @@ static bool dc3_level0_bytes(Ctx &ctx, const uint8_t *s8, u32 n0, u32 n02, int w
                      : radix_sort_pairs<K, TextWindowGen<K>>(ctx, sb, n02, total_bits, low_bits,
                                                              TextWindowGen<K>{s8, n02, w, bt, spare, term_first, docs},
                                                              // (suffixes in text order: only the document number is sorted)
-                                                             docs.bits ? total_bits - docs.bits : total_bits + RS_DB, docs.seg);
+                                                             docs.bits ? total_bits - docs.bits : total_bits + RS_DB, docs.seg,
+                                                             ctx.first_hist);
+    if (n0 == 0 && !ctx.dry) {
+        // what the next speculative build's remap pass may count ahead (build.h): the first pass of fixed-width text keys
+        Ctx::FirstPassPlan &fp = ctx.did_first;
+        fp.valid = !ht && !docs.bits && !docs.seg.n_docs && total_bits > low_bits;
+        fp.key_bytes = (int)sizeof(K); fp.w = w; fp.b = bt; fp.spare = spare; fp.term_first = term_first;
+        fp.shift = low_bits; fp.mask = (1u << std::min(RS_DB, total_bits - low_bits)) - 1u;
+    }
     KeyNeqWindowIn<K> starts = KeyNeqWindowIn<K>::make(sb.keys[r], ht ? 0 : w, bt, spare, term_first);
     if (ht) { starts.ht_sb = ht_sb; starts.ht_wmin = w; starts.ht_dec = ht->dec; }
     const u32 *sorted_vals = sb.vals[r];
@@ -2018,6 +2081,7 @@ static bool dc3_level0_bytes(Ctx &ctx, const uint8_t *s8, u32 n0, u32 n02, int w
     // ---- the whole sorted input as the first domain --------------------------------------
     // (a small input is better off with the direct ordering of much larger groups than with a round of ~50 launches)
     KgMark km;                                          // k-gram bucket starts ride along with the first placement pass
+    ClearRegions clears;                                // what that pass wants preset: one launch for all of it
     // (repetitive text -- the sample says, or the build before did -- is not ordered directly however small it is: its tie
     // groups agree for hundreds of symbols, and every member would compare itself with every other to the end; the
     // persistent rounds take it, persist_rounds.h)
@@ -2032,8 +2096,8 @@ static bool dc3_level0_bytes(Ctx &ctx, const uint8_t *s8, u32 n0, u32 n02, int w
         for (int i = 0; i < km.k; i++) km.bins *= km.A;
         km.pairs = km.kg3 && km.k >= 2;
         km.by_rank = docs.seg.n_docs != 0;
-        HIP_CHECK(hipMemsetAsync(km.kg, 0xFF, (size_t)(km.bins + 1) * km.n_docs * (km.pairs ? 8 : 4), ctx.stream));
-        if (km.pairs) HIP_CHECK(hipMemsetAsync(km.kg3, 0xFF, (size_t)(km.bins / km.A + 1) * km.n_docs * sizeof(u32), ctx.stream));
+        clear_add(ctx, clears, km.kg, (size_t)(km.bins + 1) * km.n_docs * (km.pairs ? 8 : 4), 0xFF);
+        if (km.pairs) clear_add(ctx, clears, km.kg3, (size_t)(km.bins / km.A + 1) * km.n_docs * sizeof(u32), 0xFF);
         *kg_mark = km;
     }
     u32 m = n02, m_next = n02, h_fail = 0;              // (sizing run: as if everything were tied)
@@ -2053,11 +2117,11 @@ static bool dc3_level0_bytes(Ctx &ctx, const uint8_t *s8, u32 n0, u32 n02, int w
         fa.km = small_input ? KgMark() : km;
         if (ht) { fa.ht_sb = ht_sb; fa.ht_wmin = w; fa.ht_dec = ht->dec; fa.xdep0 = xdep0; }
         if (sr.n_docs) { fa.km.by_rank = 1; fa.km.doc_off = sr.doc_off; fa.km.n_docs = sr.n_docs; }
-        if (!ctx.dry) {
-            HIP_CHECK(hipMemsetAsync(keep, 0, (((size_t)n02 >> 6) + 2) * sizeof(u64), ctx.stream));
-            HIP_CHECK(hipMemsetAsync(gstart_bits, 0, (((size_t)n02 >> 6) + 2) * sizeof(u64), ctx.stream));
-        }
+        // (keep lies in the keys the sort's last pass read: cleared behind it, with the rest)
+        clear_add(ctx, clears, keep, (((size_t)n02 >> 6) + 2) * sizeof(u64), 0);
+        clear_add(ctx, clears, gstart_bits, (((size_t)n02 >> 6) + 2) * sizeof(u64), 0);
     }
+    clear_run(ctx, clears);
     auto place = [&](int mode) {
         if (fused) {
             if (mode != 0) throw FusedAbort();

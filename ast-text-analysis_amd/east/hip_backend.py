@@ -71,6 +71,10 @@ SIGNATURES = {
     "east_hip_debug_set_persist": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "east_hip_debug_set_segmented_sort": (ctypes.c_int, [ctypes.c_int]),
     "east_hip_debug_set_speculation": (ctypes.c_int, [ctypes.c_int]),
+    "east_hip_debug_first_pass_hist": (ctypes.c_int, [ctypes.c_int, _c_u32p, ctypes.c_int64, _c_u32p, ctypes.c_int,
+                                                      ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int,
+                                                      ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint8), _c_u32p, _c_u32p,
+                                                      _c_u32p, _c_u32p]),
     "east_hip_debug_set_score_scratch": (ctypes.c_int, [ctypes.c_int64]),
     "east_hip_debug_set_score_path": (ctypes.c_int, [ctypes.c_int]),
     "east_hip_debug_set_score_grid": (ctypes.c_int, [ctypes.c_int64]),
@@ -126,7 +130,8 @@ BUILD_INFO_FIELDS = ("n_total", "n_docs", "n_strings", "sigma_text", "bits_level
                      "arena_high_water", "radix_passes", "radix_elements", "radix_element_bytes",
                      "radix_passes_u32", "radix_elements_u32", "radix_passes_u64", "radix_elements_u64",
                      "dc3_levels_resolved", "merge_elements", "refine_rounds", "window_sorted", "lds_sorted",
-                     "fused_finish", "first_kept", "first_n", "ht_keys", "seg_sort", "narrow_upload", "persist_rounds")
+                     "fused_finish", "first_kept", "first_n", "ht_keys", "seg_sort", "narrow_upload", "persist_rounds",
+                     "first_hist_fused")
 COSINE_INFO_FIELDS = ("built", "n_docs", "kept_tokens", "words", "terms", "classes", "postings", "hash_attempts", "build_us",
                       "score_us")
 

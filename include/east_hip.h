@@ -390,7 +390,9 @@ void *east_hip_stream(east_hip_handle_t h);
  * kept every document inside its own range of ranks (the segmented sort, csrc/radix_sort.h: RsSeg), [25] 1 when
  * east_hip_build's host symbols went up as 16-bit words through the pinned ring (half the bytes over the link; reference
  * encoding, 4 Mi symbols or more), 2 when they went up as bytes (text below 0xFF),
- * [26] refinement rounds run inside one persistent launch (csrc/persist_rounds.h; they count in [17] too).
+ * [26] refinement rounds run inside one persistent launch (csrc/persist_rounds.h; they count in [17] too),
+ * [27] 1 when the first radix pass's histogram was counted by the remap pass of a speculative build
+ * (csrc/radix_sort.h: presence_remap_hist_kernel) and the sort took it.
  */
 int east_hip_build_info(east_hip_handle_t h, int64_t *out, int32_t cap);
 
@@ -449,8 +451,18 @@ int east_hip_debug_set_persist(int force_large, int max_workgroups);   /* the pe
 int east_hip_debug_set_lds_rounds(int enabled);   /* 0 / 1 (default: the in-LDS rounds also classify the next domain; a domain that fits the chip is finished by one persistent launch) / 2 (in-LDS rounds + the stand-alone classification pass, launch by launch) / 3 (as 1 without the persistent launch) */
 /* Test knob: 0 = every build waits for the device's answers (alphabet size, tie groups) as a handle's
  * first build does; 1 (default) = later builds on a handle are queued without waiting, on the strength
- * of what the build before found, and checked by the one read-back at their end. */
+ * of what the build before found, and checked by the one read-back at their end; 2 = as 1, but
+ * the first radix pass's histogram is counted by a launch of its own, not by the remap pass. */
 int east_hip_debug_set_speculation(int enabled);
+/* Kernel-level test of the remap pass that counts the first radix histogram (csrc/radix_sort.h:
+ * presence_remap_hist_kernel): n host symbols go through code_map (2 560 words: code point -> byte) (a) in that kernel and
+ * (b) through remap_bytes_kernel + presence_kernel + radix_hist_kernel on window keys of key_bytes (4 / 8) x 8 bits --
+ * w symbols of b bits + spare bits, terminators as term_first, digit (key >> shift) & mask.  Every output holds (a)'s
+ * result followed by (b)'s: s8 2 x (n + 16) bytes, present 2 x 80 words, hist 2 x 256 x tiles (tiles = ceil(n / 4096)),
+ * group_sum 2 x 256 x ceil(tiles / 8), digit_total 2 x 2 048. */
+int east_hip_debug_first_pass_hist(int device, const uint32_t *symbols, int64_t n, const uint32_t *code_map, int key_bytes,
+                                   int w, int b, int spare, uint32_t term_first, int shift, uint32_t mask, uint8_t *s8,
+                                   uint32_t *present, uint32_t *hist, uint32_t *group_sum, uint32_t *digit_total);
 /* Test knob: bytes of per-suffix scratch a score call may use (default 1 GiB; 0 restores it); a table over
  * more documents than fit is scored a stretch of documents at a time.  Takes effect at the next
  * east_hip_set_keyphrases / east_hip_score_table. */
