@@ -108,6 +108,7 @@ void east_hip_destroy(east_hip_handle_t h)
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     cos_destroy(h);
     graph_destroy(h);
+    syn_destroy(h);
     if (h->arena.base) (void)hipFree(h->arena.base);
     for (DevBuf *b : h->bufs) b->release();
     for (auto e : h->copy_events) (void)hipEventDestroy(e);
@@ -358,6 +359,7 @@ int east_hip_reset(east_hip_handle_t h)
             if (b->cap > keep) b->release();
         cos_reset(h);
         graph_reset(h);
+        syn_reset(h);
     });
 }
 
@@ -454,3 +456,5 @@ double east_hip_last_score_ms(east_hip_handle_t h) { return h ? (double)h->last_
 // ---- the cosine relevance measure ------------------------------------------------------------------
 #include "cosine.h"
 #include "graph.h"
+// ---- synonym extraction from dependency triples ------------------------------------------------------
+#include "synonyms.h"

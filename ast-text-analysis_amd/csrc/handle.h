@@ -93,6 +93,8 @@ struct east_hip_index {
     bool table_scored = false;
     // the keyphrase graph (graph.h; own allocations, made by the first east_hip_graph_build_*)
     struct GraphState *graph = nullptr;
+    // the synonyms' feature rows and pair list (synonyms.h; own allocations, made by the first east_hip_synonyms_build)
+    struct SynState *syn = nullptr;
     // the handle's own device allocations besides the arena: east_hip_destroy frees them, east_hip_reset the large ones
     DevBuf *bufs[6] = {&guess, &ht_tab, &q_buf, &kg, &tp_tables, &prep_sym};
 };
@@ -100,6 +102,8 @@ static void cos_reset(east_hip_index *h);
 static void cos_destroy(east_hip_index *h);
 static void graph_reset(east_hip_index *h);
 static void graph_destroy(east_hip_index *h);
+static void syn_reset(east_hip_index *h);
+static void syn_destroy(east_hip_index *h);
 
 struct SpecAbort {};             // a speculative build cannot go on: build_common starts over with the read-backs in place
 

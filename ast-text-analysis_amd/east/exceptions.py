@@ -61,6 +61,18 @@ class NoSuchTermWeighting(NotFoundException):
     msg_fmt = "There is no term weighting with name `%(name)s` (use 'tf' or 'tf-idf')."
 
 
+class TomitaNotInstalledException(EastException):
+    """The reference's name (exceptions.py:57): here it says that no dependency triples were given -- the parser that
+    makes them from text is not part of this project."""
+    msg_fmt = ("Synonym extraction needs dependency triples: pass `triples=` (Tomita's XML output, or lines of "
+               "w1<TAB>relation<TAB>w2); the Tomita parser itself is not available here.")
+
+
+class TriplesFormatException(EastException):
+    """New: a dependency triple that cannot be read (east/synonyms)."""
+    msg_fmt = "Malformed dependency triple at line %(line)d of %(source)s: expected w1<TAB>relation<TAB>w2."
+
+
 class LemmataUnavailableException(EastException):
     """New: the reference declares the 'lemmata' vector space and raises when it is used (relevance.py:98-100)."""
     msg_fmt = "The 'lemmata' vector space has no implementation (nor has the reference's): use '-v words' or '-v stems'."

@@ -124,6 +124,15 @@ SIGNATURES = {
                                                  ctypes.c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _c_i64p]),
     "east_hip_graph_fetch": (ctypes.c_int, [ctypes.c_void_p] + [_c_i32p] * 5),
     "east_hip_last_graph_ms": (ctypes.c_double, [ctypes.c_void_p]),
+    "east_hip_synonyms_build": (ctypes.c_int, [ctypes.c_void_p, _c_i32p, _c_i32p, _c_i32p, ctypes.c_int64, _c_i32p,
+                                               ctypes.c_int32, ctypes.c_int32]),
+    "east_hip_synonyms_info": (ctypes.c_int, [ctypes.c_void_p, _c_i64p, ctypes.c_int32]),
+    "east_hip_synonyms_get_rows": (ctypes.c_int, [ctypes.c_void_p, _c_i64p, _c_i32p, _c_i32p, _c_dblp, _c_dblp]),
+    "east_hip_synonyms_similarity": (ctypes.c_int, [ctypes.c_void_p, _c_i32p, _c_i32p, ctypes.c_int64, _c_dblp]),
+    "east_hip_synonyms_pairs": (ctypes.c_int, [ctypes.c_void_p, _c_i32p, ctypes.c_int32, ctypes.c_double, _c_i64p]),
+    "east_hip_synonyms_fetch": (ctypes.c_int, [ctypes.c_void_p, _c_i32p, _c_i32p, _c_dblp]),
+    "east_hip_last_synonyms_ms": (ctypes.c_double, [ctypes.c_void_p]),
+    "east_hip_debug_set_synonyms_chunk": (ctypes.c_int, [ctypes.c_int]),
 }
 
 BUILD_INFO_FIELDS = ("n_total", "n_docs", "n_strings", "sigma_text", "bits_level0", "dc3_levels", "arena_bytes",
@@ -632,6 +641,82 @@ class HipCosineIndex(object):
     @property
     def last_graph_ms(self):
         return float(self._lib.east_hip_last_graph_ms(self._h))
+
+
+SYNONYMS_INFO_FIELDS = ("raw_triples", "distinct_triples", "words", "relations", "features", "longest_row")
+
+
+class HipSynonyms(object):
+    """The feature rows of a SynonymExtractor on the device (include/east_hip.h, "Synonym extraction"): built from interned
+    dependency triples, queried for rows, similarities and all pairs of candidates above a threshold.  It lives in the
+    handle of a HipIndex, as HipCosineIndex does: its own one unless `index` is given."""
+
+    def __init__(self, device=None, index=None):
+        self._owner = index is None
+        self.index = HipIndex(device) if index is None else index
+        self._lib = self.index._lib
+        self.device = self.index.device
+        self.n_words = 0
+
+    @property
+    def _h(self):
+        return self.index._h
+
+    def close(self):
+        if self._owner:
+            self.index.close()
+
+    def build(self, w1, relation, w2, inverse_relation, n_words):
+        """The raw triples as int32 id arrays; inverse_relation[r] = the id of r's inverse (synonyms.py:81)."""
+        w1, relation, w2, inverse_relation = (np.ascontiguousarray(x, dtype=np.int32) for x in (w1, relation, w2, inverse_relation))
+        if not (w1.size == relation.size == w2.size):
+            raise exceptions.HipBackendError(reason="the three id arrays of the triples differ in length")
+        _check(self._lib.east_hip_synonyms_build(self._h, _ptr(w1, _c_i32p), _ptr(relation, _c_i32p), _ptr(w2, _c_i32p), w1.size,
+                                                 _ptr(inverse_relation, _c_i32p), int(n_words), inverse_relation.size))
+        self.n_words = int(n_words)
+
+    def info(self):
+        buf = np.zeros(len(SYNONYMS_INFO_FIELDS), dtype=np.int64)
+        _check(self._lib.east_hip_synonyms_info(self._h, _ptr(buf, _c_i64p), buf.size))
+        return dict(zip(SYNONYMS_INFO_FIELDS, (int(x) for x in buf)))
+
+    def rows(self):
+        """(offsets int64[n_words + 1], relation int32[F], word int32[F], I float64[F], row_sum float64[n_words])."""
+        info = self.info()
+        F, W = info["features"], info["words"]
+        offsets = np.zeros(W + 1, dtype=np.int64)
+        relation, word = np.zeros(F, dtype=np.int32), np.zeros(F, dtype=np.int32)
+        value, row_sum = np.zeros(F, dtype=np.float64), np.zeros(W, dtype=np.float64)
+        _check(self._lib.east_hip_synonyms_get_rows(self._h, _ptr(offsets, _c_i64p), _ptr(relation, _c_i32p), _ptr(word, _c_i32p),
+                                                    _ptr(value, _c_dblp), _ptr(row_sum, _c_dblp)))
+        return offsets, relation, word, value, row_sum
+
+    def similarity(self, a, b):
+        """similarity(a[i], b[i]) of word ids -> float64."""
+        a, b = np.ascontiguousarray(a, dtype=np.int32), np.ascontiguousarray(b, dtype=np.int32)
+        if a.size != b.size:
+            raise exceptions.HipBackendError(reason="the two id arrays of the pairs differ in length")
+        out = np.zeros(a.size, dtype=np.float64)
+        _check(self._lib.east_hip_synonyms_similarity(self._h, _ptr(a, _c_i32p), _ptr(b, _c_i32p), a.size, _ptr(out, _c_dblp)))
+        return out
+
+    def pairs(self, candidates, threshold, fetch=True):
+        """Every pair (i < j in list order) of the candidate word ids with similarity > threshold ->
+        (a int32, b int32, similarity float64), ordered by i, then j; fetch=False: only their number."""
+        candidates = np.ascontiguousarray(candidates, dtype=np.int32)
+        n = ctypes.c_int64(0)
+        _check(self._lib.east_hip_synonyms_pairs(self._h, _ptr(candidates, _c_i32p), candidates.size, float(threshold),
+                                                 ctypes.byref(n)))
+        if not fetch:
+            return int(n.value)
+        a, b = np.zeros(n.value, dtype=np.int32), np.zeros(n.value, dtype=np.int32)
+        sim = np.zeros(n.value, dtype=np.float64)
+        _check(self._lib.east_hip_synonyms_fetch(self._h, _ptr(a, _c_i32p), _ptr(b, _c_i32p), _ptr(sim, _c_dblp)))
+        return a, b, sim
+
+    @property
+    def last_ms(self):
+        return float(self._lib.east_hip_last_synonyms_ms(self._h))
 
 
 class HipGroup(object):

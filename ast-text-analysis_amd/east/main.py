@@ -8,6 +8,9 @@ README.rst:27-63; the shipped reference main crashes with a NameError, SURVEY.md
     east -s cosine [-w tf|tf-idf] [-v stems|words] keyphrases table|graph ...
         the cosine measure (relevance.CosineRelevanceMeasure) on one device; `-v stems` (the default) needs nltk's
         Snowball stemmer, and without nltk's stopword list no stopwords are removed (said on stderr)
+    east -y -t <triples file> keyphrases table|graph ...
+        synonym extraction (synonyms.SynonymExtractor, reference main.py:104-133) from dependency triples made elsewhere:
+        Tomita's XML output, or lines of w1<TAB>relation<TAB>w2; one device; -y without -t is refused (no parser here)
 
 Several GPUs (one process per GPU, documents sharded over the ranks, one RCCL all-gather of the score blocks --
 east/parallel.py; the reference's loops relevance.py:41-53 / applications.py:43-52 are what is sharded):
@@ -32,7 +35,7 @@ def _read(path):
         return f.read()
 
 
-_OPTIONS = "s:a:w:v:l:f:c:r:p:g:dy"
+_OPTIONS = "s:a:w:v:l:f:c:r:p:g:t:dy"
 _VALUE_OPTIONS = frozenset(c for c, nxt in zip(_OPTIONS, _OPTIONS[1:] + " ") if nxt == ":")
 
 
@@ -70,6 +73,11 @@ def main(argv=None, measure_factory=None):
         if rank == 0:
             print("Relevance measure 'cosine' runs on one device: a launcher with WORLD_SIZE=%d is not supported." % world)
         return 1
+    with_synonyms = "-y" in opts and "-t" in opts            # (-y alone ends in _main with the line it always printed)
+    if world > 1 and with_synonyms:
+        if rank == 0:
+            print("Synonym extraction (-y) runs on one device: a launcher with WORLD_SIZE=%d is not supported." % world)
+        return 1
     if world == 1:
         try:
             n_ranks = int(opts.get("-g", os.environ.get("EAST_HIP_DEVICES", "1")))
@@ -79,6 +87,9 @@ def main(argv=None, measure_factory=None):
         if n_ranks > 1 and cosine:
             # (several devices would need an all-reduce of the document frequencies)
             print("Relevance measure 'cosine' runs on one device: -g %d is not supported." % n_ranks)
+            return 1
+        if n_ranks > 1 and with_synonyms:
+            print("Synonym extraction (-y) runs on one device: -g %d is not supported." % n_ranks)
             return 1
         if n_ranks > 1 and os.environ.get("EAST_HIP_MULTI", "threads") != "process":
             # the default: N devices in THIS process (one AST shard and one host thread of the library per device, one
@@ -155,14 +166,28 @@ def _main(opts, args, world, measure_factory):
     if measure_name.lower() != "ast" and not cosine:
         print("Relevance measure '%s' is not available (use 'ast' or 'cosine')." % measure_name)
         return 1
-    if "-y" in opts:
+    if "-y" in opts and "-t" not in opts:
         print("Synonym extraction (-y) needs the external Tomita parser and is not available.")
         return 1
+    if "-t" in opts and "-y" not in opts:
+        print("Option -t names the dependency triples of synonym extraction: use it with -y.")
+        return 1
+    synonimizer = None
+    if "-y" in opts:                                                                            # main.py:104-106
+        if distributed:
+            print("Synonym extraction (-y) runs on one device: the collective path is not supported.")
+            return 1
+        try:
+            from east import synonyms
+            synonimizer = synonyms.SynonymExtractor(text_collection_path, triples=os.path.abspath(opts["-t"]))
+        except (exceptions.EastException, EnvironmentError) as e:
+            print(e)
+            return 1
     if cosine:
         if distributed:
             print("Relevance measure 'cosine' runs on one device: the collective path is not supported.")
             return 1
-        return _run_cosine(subcommand, keyphrases, texts, opts)
+        return _run_cosine(subcommand, keyphrases, texts, opts, synonimizer)
 
     group_up = False
     try:
@@ -189,7 +214,7 @@ def _main(opts, args, world, measure_factory):
             similarity_measure = relevance.MultiDeviceASTRelevanceMeasure(opts["-a"], "-d" not in opts, int(opts["-g"]))
         else:
             similarity_measure = relevance.ASTRelevanceMeasure(opts["-a"], "-d" not in opts)      # main.py:95-98
-        return _run(subcommand, keyphrases, texts, similarity_measure, opts)
+        return _run(subcommand, keyphrases, texts, similarity_measure, opts, synonimizer)
     except exceptions.EastException as e:       # (no device, a failed build ...): a message, not a traceback
         print(e)
         return 1
@@ -199,7 +224,7 @@ def _main(opts, args, world, measure_factory):
             dist.destroy_process_group()
 
 
-def _run_cosine(subcommand, keyphrases, texts, opts):
+def _run_cosine(subcommand, keyphrases, texts, opts, synonimizer=None):
     """-s cosine with its -w / -v options (reference main.py:95-98, relevance.py:58-62); bad values, -v lemmata and a
     missing stemmer end here with one line, before anything touches the device."""
     try:
@@ -207,15 +232,15 @@ def _run_cosine(subcommand, keyphrases, texts, opts):
                                                    opts.get("-w", consts.TermWeighting.TF_IDF))
         if measure.stopwords_source == "none":
             sys.stderr.write("nltk's English stopword list is not available: no stopwords are removed.\n")
-        return _run(subcommand, keyphrases, texts, measure, opts)
+        return _run(subcommand, keyphrases, texts, measure, opts, synonimizer)
     except exceptions.EastException as e:
         print(e)
         return 1
 
 
-def _run(subcommand, keyphrases, texts, similarity_measure, opts):
+def _run(subcommand, keyphrases, texts, similarity_measure, opts, synonimizer=None):
     if subcommand == "table":
-        table = applications.keyphrases_table(keyphrases, texts, similarity_measure, None, opts["-l"])
+        table = applications.keyphrases_table(keyphrases, texts, similarity_measure, synonimizer, opts["-l"])
         table_format = opts.get("-f", "xml").lower()
         try:
             print(formatting.format_table(table, table_format))
@@ -229,7 +254,7 @@ def _run(subcommand, keyphrases, texts, similarity_measure, opts):
         opts.setdefault("-p", "1")      # support threshold for graph nodes
         # (the graph as arrays: the formatters write it from them, no dict per edge)
         graph = applications.keyphrases_graph_arrays(keyphrases, texts, float(opts["-c"]), float(opts["-r"]),
-                                                     float(opts["-p"]), similarity_measure, None, opts["-l"])
+                                                     float(opts["-p"]), similarity_measure, synonimizer, opts["-l"])
         graph_format = opts.get("-f", "edges").lower()
         try:
             print(formatting.format_graph(graph, graph_format))

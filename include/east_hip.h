@@ -317,6 +317,48 @@ int east_hip_graph_fetch(east_hip_handle_t h, int32_t *support, int32_t *kept, i
 double east_hip_last_graph_ms(east_hip_handle_t h);
 
 /*
+ * Synonym extraction (`east -y -t <triples>`): the arithmetic of the reference's SynonymExtractor
+ * (east/synonyms/synonyms.py:116-169) on the device, from dependency triples the caller has -- the parser that makes them
+ * (:52-88) is not part of this library.  (How: csrc/synonyms.h)
+ *
+ * The build call (replaces synonyms.py:74-86, :116-142) takes the n_triples RAW triples (w1[i], relation[i], w2[i]) as ids,
+ * 0 <= word id < n_words <= 2^26, 0 <= relation id < n_relations <= 2^12 (the fields of the 64-bit triple key; more is
+ * EAST_HIP_ERR_INVALID, as are ids out of range and 2^30 triples or more), and inverse_relation[r] = the id of r without a
+ * trailing "_of", or of r + "_of" (:81): an involution of the relation ids.  Every triple is entered with its inverse
+ * (w2, r', w1); f(t) = occurrences of t in that doubled list; F_r, F_w1r, F_rw2 = the sums of f^2 over the distinct triples
+ * with that relation / first two / last two members (:129-131 add f once per occurrence); q = (double)f * F_r / F_w1r /
+ * F_rw2 in exactly this order, I = max(log(q), 0).  A feature (r, w2) belongs to T(w1) iff q > 1.0 -- the reference's bit
+ * for bit; only the last place of log may differ.  The rows are kept in CSR form: row = word, columns = its features in
+ * ascending (relation id, word id) order.
+ * The info call gives {raw triples, distinct triples (inverses included), words, relations, kept features, longest row}
+ * and returns 0; the rows call gives (each pointer nullable) offsets[n_words + 1], per kept feature its relation id, word
+ * id and I, and per word the sum of its I (the divisor's half, :147-148, added in column order).
+ * The similarity call (:144-152) gives out[i] = similarity(a[i], b[i]) for n_pairs pairs of word ids: the sum of
+ * I(a, .) + I(b, .) over the common features in ascending column order, divided once by the two row sums, 0.0 where the
+ * divisor is 0.
+ * The pairs call (:154-169) takes the candidate word ids -- distinct, in the order the caller wants the pairs in -- and the
+ * threshold (>= 0; negative or NaN is EAST_HIP_ERR_INVALID, as is a duplicate candidate or more than 2^20 of them) and
+ * finds every pair of candidates (i < j in list order) with similarity > threshold; *n_pairs = how many.  The fetch call
+ * gives them (each pointer nullable): a[k] = candidates[i], b[k] = candidates[j] and the similarity, ordered by i, then j.
+ * No atomic decides a slot and no floating-point sum depends on timing: two runs give the same bytes.
+ * EAST_HIP_ERR_NOT_BUILT before a successful build (fetch: before a pairs call).  The buffers are the handle's own: a
+ * synonyms build leaves the EASA index, the cosine index and the graph alone and they leave it alone; the reset call
+ * releases them, destroying the handle too.
+ * Device time of the last build or pairs call in milliseconds (events on the handle's stream around it, read-backs
+ * included), -1 when there is none.
+ */
+int east_hip_synonyms_build(east_hip_handle_t h, const int32_t *w1, const int32_t *relation, const int32_t *w2,
+                            int64_t n_triples, const int32_t *inverse_relation, int32_t n_words, int32_t n_relations);
+int east_hip_synonyms_info(east_hip_handle_t h, int64_t *out, int32_t cap);
+int east_hip_synonyms_get_rows(east_hip_handle_t h, int64_t *offsets, int32_t *relation, int32_t *word, double *value,
+                               double *row_sum);
+int east_hip_synonyms_similarity(east_hip_handle_t h, const int32_t *a, const int32_t *b, int64_t n_pairs, double *out);
+int east_hip_synonyms_pairs(east_hip_handle_t h, const int32_t *candidates, int32_t n_candidates, double threshold,
+                            int64_t *n_pairs);
+int east_hip_synonyms_fetch(east_hip_handle_t h, int32_t *a, int32_t *b, double *similarity);
+double east_hip_last_synonyms_ms(east_hip_handle_t h);
+
+/*
  * Several devices in one process ("single-process/8-device fits the one-process CLI best").
  * Every document is an independent AST (east/relevance.py:41-46) and every (keyphrase, document) score is independent
  * (east/applications.py:43-52): a GROUP shards a collection at document granularity -- contiguous blocks of documents
@@ -485,6 +527,10 @@ int east_hip_debug_set_text_ring(int mode, int64_t slot_bytes);
  * all 61, the default), so that different words collide, the verification finds it and the build starts over with the
  * next seed (east_hip_cosine_info: hash attempts).  The index does not depend on it. */
 int east_hip_debug_set_term_hash_bits(int bits);
+/* Test knob: the number of entries of a source row the synonyms' pair kernel stages in LDS at a time (1 .. 128; 0 or less =
+ * the default, 128), so that rows of a few dozen entries go through the chunk-to-chunk path.  Process-wide, read when a
+ * pairs call starts.  The pairs do not depend on it. */
+int east_hip_debug_set_synonyms_chunk(int entries);
 /* Host only (needs no device): the order-preserving variable-length code csrc/ht_code.h makes for n symbols (in their
  * order) with the given weights -- code[i] = the len[i] bits of symbol i's code word, right-aligned.  EAST_HIP_ERR_DOMAIN
  * if no code with word lengths in [3, 12] exists for them (n < 8, n > 256). */
