@@ -228,6 +228,7 @@ struct Knobs {
     size_t tp_ring_slot = getenv("EAST_HIP_RING_SLOT") ? std::min<size_t>(TP_RING_SLOT, (size_t)std::max(64, atoi(getenv("EAST_HIP_RING_SLOT")))) : TP_RING_SLOT;
     int term_hash_bits = 0;                                             // east_hip_debug_set_term_hash_bits (0: all 61 bits)
     int syn_chunk = 128;                                                // east_hip_debug_set_synonyms_chunk (synonyms.h: SY_MAX_CHUNK)
+    int top_tile = 64;                                                  // east_hip_debug_set_top_tile (top.h: TOP_TILE)
     u32 plan_epoch = 1;                                                 // bumped by the knobs that change what a build allocates
 };
 static Knobs g_knobs;

@@ -109,6 +109,7 @@ void east_hip_destroy(east_hip_handle_t h)
     cos_destroy(h);
     graph_destroy(h);
     syn_destroy(h);
+    top_destroy(h);
     if (h->arena.base) (void)hipFree(h->arena.base);
     for (DevBuf *b : h->bufs) b->release();
     for (auto e : h->copy_events) (void)hipEventDestroy(e);
@@ -360,6 +361,7 @@ int east_hip_reset(east_hip_handle_t h)
         cos_reset(h);
         graph_reset(h);
         syn_reset(h);
+        top_reset(h);
     });
 }
 
@@ -458,3 +460,5 @@ double east_hip_last_score_ms(east_hip_handle_t h) { return h ? (double)h->last_
 #include "graph.h"
 // ---- synonym extraction from dependency triples ------------------------------------------------------
 #include "synonyms.h"
+// ---- ranked keyphrases ---------------------------------------------------------------------------------
+#include "top.h"

@@ -95,6 +95,8 @@ struct east_hip_index {
     struct GraphState *graph = nullptr;
     // the synonyms' feature rows and pair list (synonyms.h; own allocations, made by the first east_hip_synonyms_build)
     struct SynState *syn = nullptr;
+    // the ranked keyphrases' candidates, result and uploaded table (top.h; own allocations, made by the first east_hip_top_build_*)
+    struct TopState *top = nullptr;
     // the handle's own device allocations besides the arena: east_hip_destroy frees them, east_hip_reset the large ones
     DevBuf *bufs[6] = {&guess, &ht_tab, &q_buf, &kg, &tp_tables, &prep_sym};
 };
@@ -104,6 +106,8 @@ static void graph_reset(east_hip_index *h);
 static void graph_destroy(east_hip_index *h);
 static void syn_reset(east_hip_index *h);
 static void syn_destroy(east_hip_index *h);
+static void top_reset(east_hip_index *h);
+static void top_destroy(east_hip_index *h);
 
 struct SpecAbort {};             // a speculative build cannot go on: build_common starts over with the read-backs in place
 

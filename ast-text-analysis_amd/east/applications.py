@@ -1,5 +1,5 @@
 # -*- coding: utf-8 -*-
-"""keyphrases_table / keyphrases_graph (reference east/applications.py:11-149)."""
+"""keyphrases_table / keyphrases_graph (reference east/applications.py:11-149) and keyphrases_top."""
 
 import os
 from collections.abc import Mapping
@@ -299,3 +299,84 @@ def _graph_from_array(keyphrases, table, referral_confidence, relevance_threshol
             edges.append({"source": int(kept[i]), "target": int(kept[j]), "confidence": c})
     return {"nodes": nodes, "edges": edges, "referral_confidence": referral_confidence,
             "relevance_threshold": relevance_threshold, "support_threshold": support_threshold}
+
+
+# ---- ranked keyphrases ---------------------------------------------------------------------------------------------------
+TOP_MAX_N = 1024
+_TOP_AXES = ("text", "keyphrase")
+
+
+def _device_top_applies(measure, texts, synonimizer):
+    """Whether keyphrases_top selects on the device: the measure scores into a table that stays there (`relevance_top`;
+    None counts as absent: the measures over several devices or ranks), no synonimizer, distinct text titles, and
+    EAST_HIP_TOP is not `host` (the precedent: EAST_HIP_GRAPH)."""
+    titles = list(texts.keys())
+    return (getattr(measure, "relevance_top", None) is not None and not synonimizer
+            and len(set(titles)) == len(titles) and os.environ.get("EAST_HIP_TOP", "device") != "host")
+
+
+def _top_select(scores, axis, n, threshold):
+    """The contract of include/east_hip.h ("Ranked keyphrases") in numpy: per segment (a column for axis 0, a row for
+    axis 1) the eligible members (score >= threshold; a NaN never is) by score descending, member index ascending among
+    equal scores (-0.0 == +0.0), the first n of them.  -> per segment a list of (member, score)."""
+    scores = np.asarray(scores, dtype=np.float64)
+    segments = scores.T if axis == 0 else scores
+    found = []
+    for values in segments:
+        eligible = np.flatnonzero(values >= threshold)
+        order = eligible[np.lexsort((eligible, -values[eligible]))][:n]      # (-(-0.0) == -(0.0) in the comparison: a tie)
+        found.append(list(zip(order.tolist(), values[order].tolist())))
+    return found
+
+
+def _top_named(found, segment_names, member_names):
+    return {segment: [(member_names[m], score) for m, score in entries] for segment, entries in zip(segment_names, found)}
+
+
+def keyphrases_top(keyphrases, texts, n=10, by="text", relevance_threshold=None, similarity_measure=None, synonimizer=None,
+                   language=consts.Language.ENGLISH):
+    """The best-matching keyphrases of every text, or the best-matching texts of every keyphrase.
+
+    :param keyphrases: raw keyphrase strings, taken as keyphrases_table takes them (empty ones are skipped, duplicates
+                       collapse)
+    :param texts: {text name: text}
+    :param n: entries per text / keyphrase at most, 1 .. 1024
+    :param by: "text" -- {text name: [(keyphrase, score), ...]}; "keyphrase" -- {keyphrase: [(text name, score), ...]}
+    :param relevance_threshold: only scores >= it are listed (None: every score that is a number)
+    :returns: the dict, its entries best first: by score descending and, among equal scores, in the order of the keyphrase
+              list / of `texts`; plain Python values
+
+    The selection runs on the device, on the score table where the score call left it (csrc/top.h), when the measure has
+    `relevance_top`, no synonimizer is given, the text titles are distinct and EAST_HIP_TOP is not `host`; in every other
+    case on the host, from keyphrases_table's array.  The result is the same either way.
+    """
+    if by not in _TOP_AXES:
+        raise ValueError("keyphrases_top: by must be 'text' or 'keyphrase', not %r" % (by,))
+    if isinstance(n, bool) or int(n) != n or not 1 <= n <= TOP_MAX_N:
+        raise ValueError("keyphrases_top: n must be an integer from 1 to %d, not %r" % (TOP_MAX_N, n))
+    n = int(n)
+    threshold = -np.inf if relevance_threshold is None else float(relevance_threshold)
+    if threshold != threshold:
+        raise ValueError("keyphrases_top: the relevance threshold is not a number")
+    axis = _TOP_AXES.index(by)
+    measure = similarity_measure or relevance.ASTRelevanceMeasure()
+    titles = list(texts.keys())
+    wanted = [kp for kp in dict.fromkeys(keyphrases) if kp]              # applications.py:44-45
+    if not wanted:
+        return {title: [] for title in titles} if axis == 0 else {}
+
+    if _device_top_applies(measure, texts, synonimizer):
+        measure.set_text_collection(list(texts.values()), language)
+        found = measure.relevance_top([utils.prepare_text(kp) for kp in wanted], axis, n, threshold)
+        lists = [list(zip(index[:count], score[:count]))
+                 for count, index, score in zip(found.count.tolist(), found.index.tolist(), found.score.tolist())]
+    else:
+        table = keyphrases_table(wanted, texts, measure, synonimizer, language)
+        if isinstance(table, ScoreTable):
+            scores = np.asarray(table.scores, dtype=np.float64)
+        else:                                                            # (a plain dict: a repeated title holds its last column;
+            titles = [title for title in titles if title in table[wanted[0]]]       # a rank that does not print has no columns)
+            scores =np.array([[table[kp][title] for title in titles] for kp in wanted], dtype=np.float64).reshape(len(wanted), -1)
+        titles = titles[:scores.shape[1]]
+        lists = _top_select(scores, axis, n, threshold)
+    return _top_named(lists, titles, wanted) if axis == 0 else _top_named(lists, wanted, titles)

@@ -81,6 +81,36 @@ def table2csv(keyphrases_table):
     return "\n".join(rows) + "\n"
 
 
+def format_top(top, by, format):
+    """A ranking (applications.keyphrases_top: {segment: [(member, score), ...]}, by = "text" or "keyphrase")."""
+    renderers = {"xml": top2xml, "csv": top2csv}
+    if format not in renderers:
+        raise Exception("Unknown ranking format: '%s'. Please use one of: 'xml', 'csv'." % format)
+    if by not in ("text", "keyphrase"):
+        raise Exception("Unknown ranking direction: '%s'. Please use one of: 'text', 'keyphrase'." % by)
+    return renderers[format](top, by)
+
+
+def top2xml(top, by):
+    """<top by=..> / <text name=..> / <keyphrase value=.. rank=..>score</keyphrase> (the two roles swapped for
+    by="keyphrase"); segments sorted by name as table2xml sorts, entries in rank order."""
+    outer, inner = (("text", "name"), ("keyphrase", "value")) if by == "text" else (("keyphrase", "value"), ("text", "name"))
+    lines = ['<top by="%s">' % by]
+    for segment in sorted(top):
+        lines.append('  <%s %s="%s">' % (outer[0], outer[1], segment))
+        lines.extend('    <%s %s="%s" rank="%d">%s</%s>' % (inner[0], inner[1], member, rank, _SCORE % score, inner[0])
+                     for rank, (member, score) in enumerate(top[segment], 1))
+        lines.append("  </%s>" % outer[0])
+    lines.append("</top>")
+    return "\n".join(lines) + "\n"
+
+
+def top2csv(top, by):
+    """One line per entry: "segment","member",rank,score; segments sorted by name, entries in rank order."""
+    return "".join("%s,%s,%d,%s\n" % (_csv_quote(segment), _csv_quote(member), rank, _SCORE % score)
+                   for segment in sorted(top) for rank, (member, score) in enumerate(top[segment], 1))
+
+
 def format_graph(graph, format):
     renderers = {"gml": graph2gml, "edges": graph2edges}
     if format not in renderers:

@@ -133,6 +133,13 @@ SIGNATURES = {
     "east_hip_synonyms_fetch": (ctypes.c_int, [ctypes.c_void_p, _c_i32p, _c_i32p, _c_dblp]),
     "east_hip_last_synonyms_ms": (ctypes.c_double, [ctypes.c_void_p]),
     "east_hip_debug_set_synonyms_chunk": (ctypes.c_int, [ctypes.c_int]),
+    "east_hip_top_build_resident": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                   ctypes.c_double, _c_i64p]),
+    "east_hip_top_build_host": (ctypes.c_int, [ctypes.c_void_p, _c_dblp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                               ctypes.c_int32, ctypes.c_double, _c_i64p]),
+    "east_hip_top_fetch": (ctypes.c_int, [ctypes.c_void_p, _c_i32p, _c_i32p, _c_dblp]),
+    "east_hip_last_top_ms": (ctypes.c_double, [ctypes.c_void_p]),
+    "east_hip_debug_set_top_tile": (ctypes.c_int, [ctypes.c_int]),
 }
 
 BUILD_INFO_FIELDS = ("n_total", "n_docs", "n_strings", "sigma_text", "bits_level0", "dc3_levels", "arena_bytes",
@@ -145,6 +152,8 @@ COSINE_INFO_FIELDS = ("built", "n_docs", "kept_tokens", "words", "terms", "class
                       "score_us")
 
 GRAPH_SOURCE_AST, GRAPH_SOURCE_COSINE, GRAPH_SOURCE_UPLOADED = 0, 1, 2      # east_hip_graph_build_resident: which resident table
+TOP_BY_TEXT, TOP_BY_KEYPHRASE = 0, 1                                        # east_hip_top_build_*: what a segment is
+TOP_MAX_N = 1024
 
 _lib = None
 
@@ -313,6 +322,34 @@ def _graph_build(lib, h, source, table, rows, relevance_threshold, support_thres
                       *(np.empty(int(counts[1]), dtype=np.int32) for _ in range(3)))
     _check(lib.east_hip_graph_fetch(h, *(_ptr(getattr(out, name), _c_i32p) for name in GraphArrays.__slots__)))
     return out
+
+
+class TopArrays(object):
+    """A ranking as the device selected it (include/east_hip.h, "Ranked keyphrases"): `count[S]` (int32), and per segment
+    its best members first: `index[S, n]` (int32, -1 behind count[s]) and `score[S, n]` (float64, the table's own bytes,
+    0.0 behind count[s])."""
+
+    __slots__ = ("count", "index", "score")
+
+    def __init__(self, count, index, score):
+        self.count, self.index, self.score = count, index, score
+
+
+def _top_build(lib, h, source, table, axis, n, threshold):
+    """east_hip_top_build_resident (table None) / _host, then east_hip_top_fetch."""
+    out = np.zeros(2, dtype=np.int64)
+    if table is None:
+        _check(lib.east_hip_top_build_resident(h, int(source), int(axis), int(n), float(threshold), _ptr(out, _c_i64p)))
+    else:
+        table = np.ascontiguousarray(table, dtype=np.float64)
+        if table.ndim != 2:
+            raise exceptions.HipBackendError(reason="the score table of a ranking is a K x D array")
+        _check(lib.east_hip_top_build_host(h, _ptr(table, _c_dblp), table.shape[0], table.shape[1], int(axis), int(n),
+                                           float(threshold), _ptr(out, _c_i64p)))
+    S = int(out[0])
+    found = TopArrays(np.empty(S, dtype=np.int32), np.empty((S, int(n)), dtype=np.int32), np.empty((S, int(n)), dtype=np.float64))
+    _check(lib.east_hip_top_fetch(h, _ptr(found.count, _c_i32p), _ptr(found.index, _c_i32p), _ptr(found.score, _c_dblp)))
+    return found
 
 
 class HipIndex(object):
@@ -554,6 +591,24 @@ class HipIndex(object):
     def last_graph_ms(self):
         return float(self._lib.east_hip_last_graph_ms(self._h))
 
+    # -- ranked keyphrases -----------------------------------------------------
+    def top(self, axis, n, threshold=-np.inf):
+        """The n best members of every segment of the score table the last score call left on the device (axis
+        TOP_BY_TEXT: per text its keyphrases, TOP_BY_KEYPHRASE: per keyphrase its texts) -> TopArrays."""
+        return _top_build(self._lib, self._h, GRAPH_SOURCE_AST, None, axis, n, threshold)
+
+    def top_from_table(self, table, axis, n, threshold=-np.inf):
+        """The same from a K x D host array, which is uploaded first (tables from elsewhere, tests)."""
+        return _top_build(self._lib, self._h, None, table, axis, n, threshold)
+
+    def top_from_uploaded(self, axis, n, threshold=-np.inf):
+        """Another ranking of the table top_from_table left on the device: no upload."""
+        return _top_build(self._lib, self._h, GRAPH_SOURCE_UPLOADED, None, axis, n, threshold)
+
+    @property
+    def last_top_ms(self):
+        return float(self._lib.east_hip_last_top_ms(self._h))
+
 
 class HipCosineIndex(object):
     """The cosine measure's term index (include/east_hip.h, "The cosine relevance measure"): the postings (term, document,
@@ -641,6 +696,15 @@ class HipCosineIndex(object):
     @property
     def last_graph_ms(self):
         return float(self._lib.east_hip_last_graph_ms(self._h))
+
+    def top(self, axis, n, threshold=-np.inf):
+        """The n best members of every segment of the table the last score_table left on the device -> TopArrays
+        (HipIndex.top)."""
+        return _top_build(self._lib, self._h, GRAPH_SOURCE_COSINE, None, axis, n, threshold)
+
+    @property
+    def last_top_ms(self):
+        return float(self._lib.east_hip_last_top_ms(self._h))
 
 
 SYNONYMS_INFO_FIELDS = ("raw_triples", "distinct_triples", "words", "relations", "features", "longest_row")

@@ -5,7 +5,10 @@ README.rst:27-63; the shipped reference main crashes with a NameError, SURVEY.md
     east [-s ast] [-a easa|easa_hip|ast_linear|ast_naive] [-d] [-f xml|csv] \\
          keyphrases table <keyphrases file> <directory with .txt files | single file>
     east [-c confidence] [-r relevance] [-p support] [-f edges|gml] keyphrases graph <keyphrases file> <texts>
-    east -s cosine [-w tf|tf-idf] [-v stems|words] keyphrases table|graph ...
+    east [-n N] [-b text|keyphrase] [-r threshold] [-f xml|csv] keyphrases top <keyphrases file> <texts>
+        the N (default 10, at most 1024) best keyphrases of every text (-b text, the default) or the N best texts of every
+        keyphrase, best first, selected on the device (csrc/top.h); -r: only scores that reach it (default: no threshold)
+    east -s cosine [-w tf|tf-idf] [-v stems|words] keyphrases table|graph|top ...
         the cosine measure (relevance.CosineRelevanceMeasure) on one device; `-v stems` (the default) needs nltk's
         Snowball stemmer, and without nltk's stopword list no stopwords are removed (said on stderr)
     east -y -t <triples file> keyphrases table|graph ...
@@ -35,7 +38,7 @@ def _read(path):
         return f.read()
 
 
-_OPTIONS = "s:a:w:v:l:f:c:r:p:g:t:dy"
+_OPTIONS = "s:a:w:v:l:f:c:r:p:g:t:n:b:dy"
 _VALUE_OPTIONS = frozenset(c for c, nxt in zip(_OPTIONS, _OPTIONS[1:] + " ") if nxt == ":")
 
 
@@ -68,6 +71,13 @@ def main(argv=None, measure_factory=None):
     opt_list = opts                                         # (as given: repeated options, empty values)
     opts = dict(opts)
     world, rank = _world()
+    if args[:2] == ["keyphrases", "top"]:
+        # (-n, -b, -r: refused here, before a rank is started, a file is read or anything touches the device)
+        refusal = _top_options(opts)[3]
+        if refusal:
+            if rank == 0:
+                print(refusal)
+            return 1
     cosine = opts.get("-s", "").lower() == consts.RelevanceMeasure.COSINE
     if world > 1 and cosine:
         if rank == 0:
@@ -125,7 +135,7 @@ def _main(opts, args, world, measure_factory):
         print("Invalid syntax: EAST should be called as:\n\n"
               "    east [options] <command> <subcommand> args\n\n"
               "Commands available: keyphrases.\n"
-              "Subcommands available: table/graph.")
+              "Subcommands available: table/graph/top.")
         return 1
 
     command, subcommand = args[0], args[1]
@@ -238,6 +248,30 @@ def _run_cosine(subcommand, keyphrases, texts, opts, synonimizer=None):
         return 1
 
 
+def _top_options(opts):
+    """(n, by, threshold, None) of `keyphrases top`, or (None, None, None, the one line that says what is wrong)."""
+    try:
+        n = int(opts.get("-n", "10"))
+    except ValueError:
+        return None, None, None, "Invalid number of entries: '%s'. Please use an integer from 1 to %d." % (
+            opts["-n"], applications.TOP_MAX_N)
+    if not 1 <= n <= applications.TOP_MAX_N:
+        return None, None, None, "Invalid number of entries: '%s'. Please use an integer from 1 to %d." % (
+            opts["-n"], applications.TOP_MAX_N)
+    by = opts.get("-b", "text").lower()
+    if by not in ("text", "keyphrase"):
+        return None, None, None, "Invalid ranking direction: '%s'. Please use one of: 'text', 'keyphrase'." % opts["-b"]
+    threshold = None
+    if "-r" in opts:
+        try:
+            threshold = float(opts["-r"])
+        except ValueError:
+            threshold = float("nan")
+        if threshold != threshold:
+            return None, None, None, "Invalid relevance threshold: '%s'." % opts["-r"]
+    return n, by, threshold, None
+
+
 def _run(subcommand, keyphrases, texts, similarity_measure, opts, synonimizer=None):
     if subcommand == "table":
         table = applications.keyphrases_table(keyphrases, texts, similarity_measure, synonimizer, opts["-l"])
@@ -262,7 +296,16 @@ def _run(subcommand, keyphrases, texts, similarity_measure, opts, synonimizer=No
             print(e)
             return 1
         return 0
-    print("Invalid subcommand: '%s'. Please use one of: 'table', 'graph'." % subcommand)
+    elif subcommand == "top":
+        n, by, threshold, _ = _top_options(opts)
+        top = applications.keyphrases_top(keyphrases, texts, n, by, threshold, similarity_measure, synonimizer, opts["-l"])
+        try:
+            print(formatting.format_top(top, by, opts.get("-f", "xml").lower()))
+        except Exception as e:
+            print(e)
+            return 1
+        return 0
+    print("Invalid subcommand: '%s'. Please use one of: 'table', 'graph', 'top'." % subcommand)
     return 1
 
 

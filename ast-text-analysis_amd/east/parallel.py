@@ -102,6 +102,7 @@ class DistributedASTRelevanceMeasure(relevance.ASTRelevanceMeasure):
         self._factory = measure_factory or (lambda: relevance.ASTRelevanceMeasure(ast_algorithm, normalized, self.gpu))
 
     relevance_graph = None       # (every rank holds a block of the table: keyphrases_graph keeps its host path)
+    relevance_top = None         # (... and keyphrases_top too)
 
     def _on_gpu(self):
         import torch.distributed as dist

@@ -220,6 +220,18 @@ class ASTRelevanceMeasure(RelevanceMeasure):
         self.index.score_resident(self.normalized)
         return self.index.graph(rows, relevance_threshold, support_threshold, referral_confidence)
 
+    def relevance_top(self, prepared_keyphrases, axis, n, threshold=-np.inf):
+        """The n best keyphrases of every text (axis hip_backend.TOP_BY_TEXT) or the n best texts of every keyphrase
+        (TOP_BY_KEYPHRASE): the keyphrases are scored as relevance_graph scores them, the K x D table stays on the device
+        and the selection runs on it there.  -> hip_backend.TopArrays."""
+        queries = [kp.replace(" ", "") for kp in prepared_keyphrases]
+        if not all(queries):
+            raise ZeroDivisionError("float division by zero")
+        qs, qo = hip_backend.pack_queries(queries)
+        self.index.set_keyphrases(qs, qo)
+        self.index.score_resident(self.normalized)
+        return self.index.top(axis, n, threshold)
+
 
 class MultiDeviceASTRelevanceMeasure(ASTRelevanceMeasure):
     """ASTRelevanceMeasure over several GPUs of this process (`east -g N`): the documents are sharded over the devices --
@@ -237,6 +249,7 @@ class MultiDeviceASTRelevanceMeasure(ASTRelevanceMeasure):
         self._shards = []
 
     relevance_graph = None       # (the table is spread over the devices: keyphrases_graph keeps its host path)
+    relevance_top = None         # (... and so does keyphrases_top)
 
     def _after_build(self, n_docs):
         self._shards = []
@@ -383,6 +396,11 @@ class CosineRelevanceMeasure(RelevanceMeasure):
         as relevance_table prepares them, the table stays on the device."""
         self._score(prepared_keyphrases, False)
         return self.index.graph(rows, relevance_threshold, support_threshold, referral_confidence)
+
+    def relevance_top(self, prepared_keyphrases, axis, n, threshold=-np.inf):
+        """The n best members of every text or keyphrase (ASTRelevanceMeasure.relevance_top); the table stays on the device."""
+        self._score(prepared_keyphrases, False)
+        return self.index.top(axis, n, threshold)
 
     def _score(self, prepared_keyphrases, fetch):
         per_query = [self._query_terms(q) for q in prepared_keyphrases]

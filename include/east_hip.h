@@ -359,6 +359,39 @@ int east_hip_synonyms_fetch(east_hip_handle_t h, int32_t *a, int32_t *b, double 
 double east_hip_last_synonyms_ms(east_hip_handle_t h);
 
 /*
+ * Ranked keyphrases (`east keyphrases top`): the N best rows of every column of a K x D score table that is already on the
+ * device, or the N best columns of every row.  (How: csrc/top.h)
+ *
+ * The table is K x D doubles, row-major (t[k * D + d]).  axis EAST_HIP_TOP_BY_TEXT: a SEGMENT is a column d and its MEMBERS
+ * are the K rows; axis EAST_HIP_TOP_BY_KEYPHRASE: a segment is a row k and its members are the D columns.  S = the number
+ * of segments, L = the members of each.  For every segment the result is the first min(n, eligible) members of this total
+ * order: (1) a member is eligible when score >= threshold -- a NaN score never is, -0.0 >= 0.0 is, the threshold -inf means
+ * every number, a NaN threshold is EAST_HIP_ERR_INVALID; (2) eligible members are ordered by score descending and, among
+ * equal scores (-0.0 and +0.0 are equal), by member index ascending.  In Python, for one segment with scores v:
+ * sorted((i for i in range(L) if v[i] >= threshold), key=lambda i: (-v[i], i))[:n].  1 <= n <= 1024 (anything else is
+ * EAST_HIP_ERR_INVALID, as is an unknown axis); n > L is allowed, the lists are then shorter.
+ * The build call on the RESIDENT table takes `source` as east_hip_graph_build_resident does, under the same conditions and
+ * with the same EAST_HIP_ERR_NOT_BUILT cases: EAST_HIP_GRAPH_SOURCE_AST, EAST_HIP_GRAPH_SOURCE_COSINE, and
+ * EAST_HIP_GRAPH_SOURCE_UPLOADED = the copy the last east_hip_top_build_host left on the device (NOT the graph's table).
+ * The build call on a HOST table uploads K x D doubles first.  out[0] = S, out[1] = the sum of the counts.  A result the
+ * device cannot hold is EAST_HIP_ERR_OOM with the sizes in the message.
+ * The fetch call gives the last ranking (each pointer nullable): count[S]; index[S * n], member indices best first, -1 in
+ * the places behind count[s]; score[S * n], the table's own bytes (a selected -0.0 comes back as -0.0), 0.0 behind count[s].
+ * Two builds of the same input give the same bytes (a member's place is its rank; no atomic exists).  The ranking's buffers
+ * are the handle's own -- not the EASA arena, the cosine buffers or the graph's: a graph and a ranking of one handle live
+ * side by side --; the reset call releases them, destroying the handle too.
+ * Device time of the last ranking in milliseconds (events on the handle's stream around the two kernels and the read-back
+ * of the counts), -1 when there is none.
+ */
+#define EAST_HIP_TOP_BY_TEXT 0
+#define EAST_HIP_TOP_BY_KEYPHRASE 1
+int east_hip_top_build_resident(east_hip_handle_t h, int32_t source, int32_t axis, int32_t n, double threshold, int64_t *out);
+int east_hip_top_build_host(east_hip_handle_t h, const double *table, int32_t n_keyphrases, int32_t n_docs, int32_t axis,
+                            int32_t n, double threshold, int64_t *out);
+int east_hip_top_fetch(east_hip_handle_t h, int32_t *count, int32_t *index, double *score);
+double east_hip_last_top_ms(east_hip_handle_t h);
+
+/*
  * Several devices in one process ("single-process/8-device fits the one-process CLI best").
  * Every document is an independent AST (east/relevance.py:41-46) and every (keyphrase, document) score is independent
  * (east/applications.py:43-52): a GROUP shards a collection at document granularity -- contiguous blocks of documents
@@ -531,6 +564,10 @@ int east_hip_debug_set_term_hash_bits(int bits);
  * the default, 128), so that rows of a few dozen entries go through the chunk-to-chunk path.  Process-wide, read when a
  * pairs call starts.  The pairs do not depend on it. */
 int east_hip_debug_set_synonyms_chunk(int entries);
+/* Test knob: the members of a segment the ranking (east_hip_top_build_*) ranks as one tile (1 .. 64, more is taken as 64; 0
+ * or less = the default, 64), so that a segment of a few hundred members spans many tiles and the merge does the work.
+ * Process-wide, read when a build call starts.  The ranking does not depend on it. */
+int east_hip_debug_set_top_tile(int members);
 /* Host only (needs no device): the order-preserving variable-length code csrc/ht_code.h makes for n symbols (in their
  * order) with the given weights -- code[i] = the len[i] bits of symbol i's code word, right-aligned.  EAST_HIP_ERR_DOMAIN
  * if no code with word lengths in [3, 12] exists for them (n < 8, n > 256). */
