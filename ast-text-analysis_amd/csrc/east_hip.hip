@@ -110,6 +110,7 @@ void east_hip_destroy(east_hip_handle_t h)
     graph_destroy(h);
     syn_destroy(h);
     top_destroy(h);
+    sim_destroy(h);
     if (h->arena.base) (void)hipFree(h->arena.base);
     for (DevBuf *b : h->bufs) b->release();
     for (auto e : h->copy_events) (void)hipEventDestroy(e);
@@ -362,6 +363,7 @@ int east_hip_reset(east_hip_handle_t h)
         graph_reset(h);
         syn_reset(h);
         top_reset(h);
+        sim_reset(h);
     });
 }
 
@@ -460,5 +462,7 @@ double east_hip_last_score_ms(east_hip_handle_t h) { return h ? (double)h->last_
 #include "graph.h"
 // ---- synonym extraction from dependency triples ------------------------------------------------------
 #include "synonyms.h"
+// ---- similar texts and keyphrases (in front of top.h, which ranks the matrix) ------------------------------
+#include "similarity.h"
 // ---- ranked keyphrases ---------------------------------------------------------------------------------
 #include "top.h"

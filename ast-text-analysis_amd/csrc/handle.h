@@ -97,6 +97,8 @@ struct east_hip_index {
     struct SynState *syn = nullptr;
     // the ranked keyphrases' candidates, result and uploaded table (top.h; own allocations, made by the first east_hip_top_build_*)
     struct TopState *top = nullptr;
+    // the similarity's uploaded table, q and M x M matrix (similarity.h; own allocations, made by the first east_hip_similarity_build_*)
+    struct SimState *sim = nullptr;
     // the handle's own device allocations besides the arena: east_hip_destroy frees them, east_hip_reset the large ones
     DevBuf *bufs[6] = {&guess, &ht_tab, &q_buf, &kg, &tp_tables, &prep_sym};
 };
@@ -108,6 +110,8 @@ static void syn_reset(east_hip_index *h);
 static void syn_destroy(east_hip_index *h);
 static void top_reset(east_hip_index *h);
 static void top_destroy(east_hip_index *h);
+static void sim_reset(east_hip_index *h);
+static void sim_destroy(east_hip_index *h);
 
 struct SpecAbort {};             // a speculative build cannot go on: build_common starts over with the read-backs in place
 

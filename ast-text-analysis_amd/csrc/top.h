@@ -27,8 +27,8 @@
 // back are the table's own bytes, read again by the merge kernel (the key has lost the sign of a zero).  The tile length
 // is a test knob (east_hip_debug_set_top_tile); the result does not depend on it.
 //
-// Included at the end of east_hip.hip, behind graph.h and synonyms.h: the host half needs the handle and both resident
-// tables.
+// Included at the end of east_hip.hip, behind graph.h, synonyms.h and similarity.h: the host half needs the handle, both
+// resident tables and the similarity matrix (a fourth table source: EAST_HIP_GRAPH_SOURCE_SIMILARITY).
 #pragma once
 #include "common.h"
 
@@ -302,6 +302,10 @@ int east_hip_top_build_resident(east_hip_handle_t h, int32_t source, int32_t axi
             if (!h->top || !h->top->table_K)
                 east_throw(EAST_HIP_ERR_NOT_BUILT, "ranked keyphrases: no host table has been uploaded to this handle");
             top_build(h, (const double *)h->top->table.p, h->top->table_K, h->top->table_D, axis, n, threshold, out);
+        } else if (source == EAST_HIP_GRAPH_SOURCE_SIMILARITY) {
+            if (!h->sim || !h->sim->valid)
+                east_throw(EAST_HIP_ERR_NOT_BUILT, "ranked keyphrases: no similarity matrix has been built on this handle");
+            top_build(h, h->sim->matrix, h->sim->M, h->sim->M, axis, n, threshold, out);
         } else {
             east_throw(EAST_HIP_ERR_INVALID, "ranked keyphrases: unknown table source");
         }

@@ -1,5 +1,5 @@
 # -*- coding: utf-8 -*-
-"""keyphrases_table / keyphrases_graph (reference east/applications.py:11-149) and keyphrases_top."""
+"""keyphrases_table / keyphrases_graph (reference east/applications.py:11-149), keyphrases_top and keyphrases_similar."""
 
 import os
 from collections.abc import Mapping
@@ -380,3 +380,83 @@ def keyphrases_top(keyphrases, texts, n=10, by="text", relevance_threshold=None,
         titles = titles[:scores.shape[1]]
         lists = _top_select(scores, axis, n, threshold)
     return _top_named(lists, titles, wanted) if axis == 0 else _top_named(lists, wanted, titles)
+
+
+# ---- similar texts and keyphrases ----------------------------------------------------------------------------------------
+def _device_similar_applies(measure, texts, synonimizer):
+    """Whether keyphrases_similar runs on the device: the conditions of keyphrases_top (`relevance_similar` in the place of
+    `relevance_top`), and EAST_HIP_SIMILAR is not `host`."""
+    titles = list(texts.keys())
+    return (getattr(measure, "relevance_similar", None) is not None and not synonimizer
+            and len(set(titles)) == len(titles) and os.environ.get("EAST_HIP_SIMILAR", "device") != "host")
+
+
+def _similarity_matrix(scores, axis):
+    """The contract of include/east_hip.h ("Similar texts and keyphrases") in numpy: the profiles are the columns (axis 0)
+    or the rows (axis 1) of the K x D array; S[a][b] = G_ab / (sqrt(q_a) * sqrt(q_b)), +0.0 where a q is zero, NaN on the
+    diagonal.  -> the M x M array."""
+    profiles = np.asarray(scores, dtype=np.float64)
+    profiles = np.ascontiguousarray(profiles.T if axis == 0 else profiles)
+    q = np.einsum("ml,ml->m", profiles, profiles)
+    root = np.sqrt(q)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        matrix = (profiles @ profiles.T) / (root[:, None] * root[None, :])
+    matrix[(q == 0.0)[:, None] | (q == 0.0)[None, :]] = 0.0
+    np.fill_diagonal(matrix, np.nan)
+    return matrix
+
+
+def keyphrases_similar(keyphrases, texts, n=10, by="text", similarity_threshold=None, similarity_measure=None, synonimizer=None,
+                       language=consts.Language.ENGLISH):
+    """The texts most like every text, or the keyphrases most like every keyphrase.  A text is its column of the
+    keyphrase x text score table (its keyphrase profile), a keyphrase its row (its text profile); alike means the cosine
+    of two profiles (+0.0 where a profile is all zeros).
+
+    :param keyphrases: raw keyphrase strings, taken as keyphrases_table takes them (empty ones are skipped, duplicates
+                       collapse)
+    :param texts: {text name: text}
+    :param n: entries per text / keyphrase at most, 1 .. 1024
+    :param by: "text" -- {text name: [(other text name, similarity), ...]}; "keyphrase" -- {keyphrase: [(other keyphrase,
+               similarity), ...]}
+    :param similarity_threshold: only similarities >= it are listed (None: every similarity that is a number)
+    :returns: the dict, its entries best first: by similarity descending and, among equal similarities, in the order of
+              `texts` / of the keyphrase list; a member never lists itself; plain Python values
+
+    The matrix and its ranking are made on the device, from the score table where the score call left it
+    (csrc/similarity.h, csrc/top.h), when the measure has `relevance_similar`, no synonimizer is given, the text titles are
+    distinct and EAST_HIP_SIMILAR is not `host`; in every other case on the host, from keyphrases_table's array.  The two
+    paths sum in different orders: their similarities agree to (2 L + 16) * 2^-53 (L = the length of a profile) and they
+    name the same members in the same order wherever neighbouring similarities lie further apart than twice that -- they
+    are NOT promised to be the same bytes.
+    """
+    if by not in _TOP_AXES:
+        raise ValueError("keyphrases_similar: by must be 'text' or 'keyphrase', not %r" % (by,))
+    if isinstance(n, bool) or int(n) != n or not 1 <= n <= TOP_MAX_N:
+        raise ValueError("keyphrases_similar: n must be an integer from 1 to %d, not %r" % (TOP_MAX_N, n))
+    n = int(n)
+    threshold = -np.inf if similarity_threshold is None else float(similarity_threshold)
+    if threshold != threshold:
+        raise ValueError("keyphrases_similar: the similarity threshold is not a number")
+    axis = _TOP_AXES.index(by)
+    measure = similarity_measure or relevance.ASTRelevanceMeasure()
+    titles = list(texts.keys())
+    wanted = [kp for kp in dict.fromkeys(keyphrases) if kp]              # applications.py:44-45
+    if not wanted:
+        return {title: [] for title in titles} if axis == 0 else {}
+
+    if _device_similar_applies(measure, texts, synonimizer):
+        measure.set_text_collection(list(texts.values()), language)
+        found = measure.relevance_similar([utils.prepare_text(kp) for kp in wanted], axis, n, threshold)
+        lists = [list(zip(index[:count], score[:count]))
+                 for count, index, score in zip(found.count.tolist(), found.index.tolist(), found.score.tolist())]
+    else:
+        table = keyphrases_table(wanted, texts, measure, synonimizer, language)
+        if isinstance(table, ScoreTable):
+            scores = np.asarray(table.scores, dtype=np.float64)
+        else:                                                            # (as keyphrases_top reads a plain dict)
+            titles = [title for title in titles if title in table[wanted[0]]]
+            scores = np.array([[table[kp][title] for title in titles] for kp in wanted], dtype=np.float64).reshape(len(wanted), -1)
+        titles = titles[:scores.shape[1]]
+        lists = _top_select(_similarity_matrix(scores, axis), 1, n, threshold)
+    names = titles if axis == 0 else wanted
+    return _top_named(lists, names, names)

@@ -111,6 +111,37 @@ def top2csv(top, by):
                    for segment in sorted(top) for rank, (member, score) in enumerate(top[segment], 1))
 
 
+def format_similar(result, by, format):
+    """Similar members (applications.keyphrases_similar: {member: [(other member, similarity), ...]}, by = "text" or
+    "keyphrase")."""
+    renderers = {"xml": similar2xml, "csv": similar2csv}
+    if format not in renderers:
+        raise Exception("Unknown similarity format: '%s'. Please use one of: 'xml', 'csv'." % format)
+    if by not in ("text", "keyphrase"):
+        raise Exception("Unknown similarity direction: '%s'. Please use one of: 'text', 'keyphrase'." % by)
+    return renderers[format](result, by)
+
+
+def similar2xml(result, by):
+    """<similar by=..> / <text name=..> / <text name=.. rank=..>similarity</text> (<keyphrase value=..> on both levels for
+    by="keyphrase"); members sorted by name as top2xml sorts, entries in rank order."""
+    element, attribute = ("text", "name") if by == "text" else ("keyphrase", "value")
+    lines = ['<similar by="%s">' % by]
+    for member in sorted(result):
+        lines.append('  <%s %s="%s">' % (element, attribute, member))
+        lines.extend('    <%s %s="%s" rank="%d">%s</%s>' % (element, attribute, other, rank, _SCORE % similarity, element)
+                     for rank, (other, similarity) in enumerate(result[member], 1))
+        lines.append("  </%s>" % element)
+    lines.append("</similar>")
+    return "\n".join(lines) + "\n"
+
+
+def similar2csv(result, by):
+    """One line per entry: "member","other",rank,similarity; members sorted by name, entries in rank order."""
+    return "".join("%s,%s,%d,%s\n" % (_csv_quote(member), _csv_quote(other), rank, _SCORE % similarity)
+                   for member in sorted(result) for rank, (other, similarity) in enumerate(result[member], 1))
+
+
 def format_graph(graph, format):
     renderers = {"gml": graph2gml, "edges": graph2edges}
     if format not in renderers:

@@ -140,6 +140,11 @@ SIGNATURES = {
     "east_hip_top_fetch": (ctypes.c_int, [ctypes.c_void_p, _c_i32p, _c_i32p, _c_dblp]),
     "east_hip_last_top_ms": (ctypes.c_double, [ctypes.c_void_p]),
     "east_hip_debug_set_top_tile": (ctypes.c_int, [ctypes.c_int]),
+    "east_hip_similarity_build_resident": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, _c_i64p]),
+    "east_hip_similarity_build_host": (ctypes.c_int, [ctypes.c_void_p, _c_dblp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                      _c_i64p]),
+    "east_hip_similarity_fetch": (ctypes.c_int, [ctypes.c_void_p, _c_dblp, _c_dblp]),
+    "east_hip_last_similarity_ms": (ctypes.c_double, [ctypes.c_void_p]),
 }
 
 BUILD_INFO_FIELDS = ("n_total", "n_docs", "n_strings", "sigma_text", "bits_level0", "dc3_levels", "arena_bytes",
@@ -152,6 +157,7 @@ COSINE_INFO_FIELDS = ("built", "n_docs", "kept_tokens", "words", "terms", "class
                       "score_us")
 
 GRAPH_SOURCE_AST, GRAPH_SOURCE_COSINE, GRAPH_SOURCE_UPLOADED = 0, 1, 2      # east_hip_graph_build_resident: which resident table
+GRAPH_SOURCE_SIMILARITY = 3                 # east_hip_top_build_resident only: the matrix the last similarity build left
 TOP_BY_TEXT, TOP_BY_KEYPHRASE = 0, 1                                        # east_hip_top_build_*: what a segment is
 TOP_MAX_N = 1024
 
@@ -350,6 +356,27 @@ def _top_build(lib, h, source, table, axis, n, threshold):
     found = TopArrays(np.empty(S, dtype=np.int32), np.empty((S, int(n)), dtype=np.int32), np.empty((S, int(n)), dtype=np.float64))
     _check(lib.east_hip_top_fetch(h, _ptr(found.count, _c_i32p), _ptr(found.index, _c_i32p), _ptr(found.score, _c_dblp)))
     return found
+
+
+def _similarity_build(lib, h, source, table, axis):
+    """east_hip_similarity_build_resident (table None) / _host -> (M, L)."""
+    out = np.zeros(2, dtype=np.int64)
+    if table is None:
+        _check(lib.east_hip_similarity_build_resident(h, int(source), int(axis), _ptr(out, _c_i64p)))
+    else:
+        table = np.ascontiguousarray(table, dtype=np.float64)
+        if table.ndim != 2:
+            raise exceptions.HipBackendError(reason="the score table of a similarity matrix is a K x D array")
+        _check(lib.east_hip_similarity_build_host(h, _ptr(table, _c_dblp), table.shape[0], table.shape[1], int(axis),
+                                                  _ptr(out, _c_i64p)))
+    return int(out[0]), int(out[1])
+
+
+def _similarity_fetch(lib, h, M):
+    """east_hip_similarity_fetch -> (matrix[M, M], norm2[M])."""
+    matrix, norm2 = np.empty((M, M), dtype=np.float64), np.empty(M, dtype=np.float64)
+    _check(lib.east_hip_similarity_fetch(h, _ptr(matrix, _c_dblp), _ptr(norm2, _c_dblp)))
+    return matrix, norm2
 
 
 class HipIndex(object):
@@ -609,6 +636,41 @@ class HipIndex(object):
     def last_top_ms(self):
         return float(self._lib.east_hip_last_top_ms(self._h))
 
+    # -- similar texts and keyphrases --------------------------------------------
+    def similarity(self, axis):
+        """The cosine of every two profiles of the score table the last score call left on the device (axis TOP_BY_TEXT:
+        the texts' columns, TOP_BY_KEYPHRASE: the keyphrases' rows); the M x M matrix stays on the device -> (M, L)."""
+        self._sim_M, L = _similarity_build(self._lib, self._h, GRAPH_SOURCE_AST, None, axis)
+        return self._sim_M, L
+
+    def similarity_from_table(self, table, axis):
+        """The same from a K x D host array, which is uploaded first (tables from elsewhere, tests)."""
+        self._sim_M, L = _similarity_build(self._lib, self._h, None, table, axis)
+        return self._sim_M, L
+
+    def similarity_from_uploaded(self, axis):
+        """Another matrix (the other axis) of the table similarity_from_table left on the device: no upload."""
+        self._sim_M, L = _similarity_build(self._lib, self._h, GRAPH_SOURCE_UPLOADED, None, axis)
+        return self._sim_M, L
+
+    def similarity_matrix(self):
+        """The last similarity matrix of this handle and the squared norms of its profiles -> (matrix[M, M], norm2[M])."""
+        return _similarity_fetch(self._lib, self._h, getattr(self, "_sim_M", 0))
+
+    def similar(self, axis, n, threshold=-np.inf):
+        """similarity(axis), then the n most similar other members of every member (the ranking of the matrix by row: the
+        NaN on its diagonal is never eligible) -> TopArrays.  It is the handle's one ranking: it replaces top()'s."""
+        self.similarity(axis)
+        return self.rank_similarity(n, threshold)
+
+    def rank_similarity(self, n, threshold=-np.inf):
+        """Another ranking of the last similarity matrix (other n, other threshold): no new matrix."""
+        return _top_build(self._lib, self._h, GRAPH_SOURCE_SIMILARITY, None, TOP_BY_KEYPHRASE, n, threshold)
+
+    @property
+    def last_similarity_ms(self):
+        return float(self._lib.east_hip_last_similarity_ms(self._h))
+
 
 class HipCosineIndex(object):
     """The cosine measure's term index (include/east_hip.h, "The cosine relevance measure"): the postings (term, document,
@@ -705,6 +767,24 @@ class HipCosineIndex(object):
     @property
     def last_top_ms(self):
         return float(self._lib.east_hip_last_top_ms(self._h))
+
+    def similarity(self, axis):
+        """The similarity matrix of the table the last score_table left on the device -> (M, L) (HipIndex.similarity)."""
+        M, L = _similarity_build(self._lib, self._h, GRAPH_SOURCE_COSINE, None, axis)
+        self.index._sim_M = M
+        return M, L
+
+    def similarity_matrix(self):
+        return self.index.similarity_matrix()
+
+    def similar(self, axis, n, threshold=-np.inf):
+        """similarity(axis), then the n most similar other members of every member -> TopArrays (HipIndex.similar)."""
+        self.similarity(axis)
+        return self.index.rank_similarity(n, threshold)
+
+    @property
+    def last_similarity_ms(self):
+        return self.index.last_similarity_ms
 
 
 SYNONYMS_INFO_FIELDS = ("raw_triples", "distinct_triples", "words", "relations", "features", "longest_row")

@@ -8,7 +8,11 @@ README.rst:27-63; the shipped reference main crashes with a NameError, SURVEY.md
     east [-n N] [-b text|keyphrase] [-r threshold] [-f xml|csv] keyphrases top <keyphrases file> <texts>
         the N (default 10, at most 1024) best keyphrases of every text (-b text, the default) or the N best texts of every
         keyphrase, best first, selected on the device (csrc/top.h); -r: only scores that reach it (default: no threshold)
-    east -s cosine [-w tf|tf-idf] [-v stems|words] keyphrases table|graph|top ...
+    east [-n N] [-b text|keyphrase] [-r threshold] [-f xml|csv] keyphrases similar <keyphrases file> <texts>
+        the N texts most like every text (-b text: the cosine of their keyphrase profiles, the columns of the score table) or
+        the N keyphrases most like every keyphrase (-b keyphrase: of their text profiles, the rows), best first, matrix and
+        ranking on the device (csrc/similarity.h); -r: only similarities that reach it (default: no threshold)
+    east -s cosine [-w tf|tf-idf] [-v stems|words] keyphrases table|graph|top|similar ...
         the cosine measure (relevance.CosineRelevanceMeasure) on one device; `-v stems` (the default) needs nltk's
         Snowball stemmer, and without nltk's stopword list no stopwords are removed (said on stderr)
     east -y -t <triples file> keyphrases table|graph ...
@@ -71,7 +75,7 @@ def main(argv=None, measure_factory=None):
     opt_list = opts                                         # (as given: repeated options, empty values)
     opts = dict(opts)
     world, rank = _world()
-    if args[:2] == ["keyphrases", "top"]:
+    if args[:2] in (["keyphrases", "top"], ["keyphrases", "similar"]):
         # (-n, -b, -r: refused here, before a rank is started, a file is read or anything touches the device)
         refusal = _top_options(opts)[3]
         if refusal:
@@ -135,7 +139,7 @@ def _main(opts, args, world, measure_factory):
         print("Invalid syntax: EAST should be called as:\n\n"
               "    east [options] <command> <subcommand> args\n\n"
               "Commands available: keyphrases.\n"
-              "Subcommands available: table/graph/top.")
+              "Subcommands available: table/graph/top/similar.")
         return 1
 
     command, subcommand = args[0], args[1]
@@ -249,7 +253,7 @@ def _run_cosine(subcommand, keyphrases, texts, opts, synonimizer=None):
 
 
 def _top_options(opts):
-    """(n, by, threshold, None) of `keyphrases top`, or (None, None, None, the one line that says what is wrong)."""
+    """(n, by, threshold, None) of `keyphrases top` and `keyphrases similar`, or (None, None, None, the one line that says what is wrong)."""
     try:
         n = int(opts.get("-n", "10"))
     except ValueError:
@@ -305,7 +309,16 @@ def _run(subcommand, keyphrases, texts, similarity_measure, opts, synonimizer=No
             print(e)
             return 1
         return 0
-    print("Invalid subcommand: '%s'. Please use one of: 'table', 'graph', 'top'." % subcommand)
+    elif subcommand == "similar":
+        n, by, threshold, _ = _top_options(opts)
+        similar = applications.keyphrases_similar(keyphrases, texts, n, by, threshold, similarity_measure, synonimizer, opts["-l"])
+        try:
+            print(formatting.format_similar(similar, by, opts.get("-f", "xml").lower()))
+        except Exception as e:
+            print(e)
+            return 1
+        return 0
+    print("Invalid subcommand: '%s'. Please use one of: 'table', 'graph', 'top', 'similar'." % subcommand)
     return 1
 
 

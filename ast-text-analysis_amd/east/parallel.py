@@ -103,6 +103,7 @@ class DistributedASTRelevanceMeasure(relevance.ASTRelevanceMeasure):
 
     relevance_graph = None       # (every rank holds a block of the table: keyphrases_graph keeps its host path)
     relevance_top = None         # (... and keyphrases_top too)
+    relevance_similar = None     # (... and keyphrases_similar)
 
     def _on_gpu(self):
         import torch.distributed as dist

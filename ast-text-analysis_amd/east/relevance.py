@@ -232,6 +232,19 @@ class ASTRelevanceMeasure(RelevanceMeasure):
         self.index.score_resident(self.normalized)
         return self.index.top(axis, n, threshold)
 
+    def relevance_similar(self, prepared_keyphrases, axis, n, threshold=-np.inf):
+        """The n most similar other texts of every text (axis hip_backend.TOP_BY_TEXT: the cosine of two columns of the
+        score table) or the n most similar other keyphrases of every keyphrase (TOP_BY_KEYPHRASE: of two rows).  The
+        keyphrases are scored exactly as relevance_top scores them; the table, the M x M similarity matrix and its ranking
+        stay on the device (csrc/similarity.h).  -> hip_backend.TopArrays."""
+        queries = [kp.replace(" ", "") for kp in prepared_keyphrases]
+        if not all(queries):
+            raise ZeroDivisionError("float division by zero")
+        qs, qo = hip_backend.pack_queries(queries)
+        self.index.set_keyphrases(qs, qo)
+        self.index.score_resident(self.normalized)
+        return self.index.similar(axis, n, threshold)
+
 
 class MultiDeviceASTRelevanceMeasure(ASTRelevanceMeasure):
     """ASTRelevanceMeasure over several GPUs of this process (`east -g N`): the documents are sharded over the devices --
@@ -250,6 +263,7 @@ class MultiDeviceASTRelevanceMeasure(ASTRelevanceMeasure):
 
     relevance_graph = None       # (the table is spread over the devices: keyphrases_graph keeps its host path)
     relevance_top = None         # (... and so does keyphrases_top)
+    relevance_similar = None     # (... and keyphrases_similar)
 
     def _after_build(self, n_docs):
         self._shards = []
@@ -401,6 +415,11 @@ class CosineRelevanceMeasure(RelevanceMeasure):
         """The n best members of every text or keyphrase (ASTRelevanceMeasure.relevance_top); the table stays on the device."""
         self._score(prepared_keyphrases, False)
         return self.index.top(axis, n, threshold)
+
+    def relevance_similar(self, prepared_keyphrases, axis, n, threshold=-np.inf):
+        """The n most similar other members of every text or keyphrase (ASTRelevanceMeasure.relevance_similar)."""
+        self._score(prepared_keyphrases, False)
+        return self.index.similar(axis, n, threshold)
 
     def _score(self, prepared_keyphrases, fetch):
         per_query = [self._query_terms(q) for q in prepared_keyphrases]

@@ -392,6 +392,49 @@ int east_hip_top_fetch(east_hip_handle_t h, int32_t *count, int32_t *index, doub
 double east_hip_last_top_ms(east_hip_handle_t h);
 
 /*
+ * Similar texts and keyphrases (`east keyphrases similar`): the cosine of every two columns of a K x D score table that is
+ * already on the device, or of every two rows, and -- through the ranking above -- the n most similar others of each.
+ * (How: csrc/similarity.h)
+ *
+ * The table is K x D doubles, row-major.  axis EAST_HIP_TOP_BY_TEXT: the M = D MEMBERS are the texts, the PROFILE of text d
+ * is its column, p_d[l] = t[l * D + d], L = K entries; axis EAST_HIP_TOP_BY_KEYPHRASE: M = K, the profile of keyphrase k is
+ * its row, p_k[l] = t[k * D + l], L = D.
+ * q_a = the sum over l of p_a[l]^2, G_ab = the sum over l of p_a[l] * p_b[l].  The similarity matrix is M x M doubles,
+ * row-major: S[a][a] = NaN; S[a][b] = +0.0 when q_a == 0 or q_b == 0; otherwise S[a][b] = G_ab / (sqrt(q_a) * sqrt(q_b)),
+ * four IEEE double operations in that order (not sqrt(q_a * q_b), which overflows where this does not).  Nothing is
+ * clamped: two equal profiles may come out one or two ulp off 1.  Non-finite table entries propagate as the arithmetic
+ * propagates them; a NaN similarity is never ranked.
+ * Guaranteed: S[a][b] and S[b][a] are the same bytes; two builds of the same input give the same bytes (no atomic is used,
+ * no sum's order depends on timing).  The order of the sums is otherwise the implementation's choice.
+ * Accuracy, for finite tables: |S - S_exact| <= (2 L + 16) * 2^-53.  (With u = 2^-53: summation in any order, with or
+ * without fma, gives |G_ab error| <= gamma_(L+2) * sum |p_a p_b| <= gamma_(L+2) * sqrt(q_a q_b); the same relative bound
+ * holds on q and half of it survives each square root; one u each for the two roots, the product and the quotient.)
+ *
+ * The build call on the RESIDENT table takes `source` as east_hip_top_build_resident does, with the same
+ * EAST_HIP_ERR_NOT_BUILT cases: EAST_HIP_GRAPH_SOURCE_AST, EAST_HIP_GRAPH_SOURCE_COSINE, and EAST_HIP_GRAPH_SOURCE_UPLOADED =
+ * the copy the last east_hip_similarity_build_host left on the device (the similarity's own copy: NOT the graph's and NOT
+ * the ranking's).  An unknown axis or source is EAST_HIP_ERR_INVALID.  The build call on a HOST table uploads K x D doubles
+ * first.  out[0] = M, out[1] = L.  A matrix the device cannot hold is EAST_HIP_ERR_OOM with M and the bytes in the message.
+ * The fetch call gives the last matrix (each pointer nullable): matrix[M * M] and norm2[M] = q.  EAST_HIP_ERR_NOT_BUILT
+ * before a build.
+ * Ranking the matrix: east_hip_top_build_resident accepts the source EAST_HIP_GRAPH_SOURCE_SIMILARITY = the M x M matrix
+ * the last similarity build of this handle left, ranked like any table (callers use EAST_HIP_TOP_BY_KEYPHRASE: a segment is
+ * a row; the NaN on the diagonal is never eligible, so no member lists itself); EAST_HIP_ERR_NOT_BUILT before a similarity
+ * build.  The result is the handle's ONE ranking: it replaces the previous one, as any later ranking replaces it.
+ * The similarity's buffers (the uploaded copy, q, the matrix) are the handle's own -- not the EASA arena, the cosine
+ * buffers, the graph's or the ranking's; a later score call does not invalidate a finished matrix; the reset call releases
+ * them, destroying the handle too.
+ * Device time of the last similarity build in milliseconds (events on the handle's stream around the two kernels), -1 when
+ * there is none.
+ */
+#define EAST_HIP_GRAPH_SOURCE_SIMILARITY 3
+int east_hip_similarity_build_resident(east_hip_handle_t h, int32_t source, int32_t axis, int64_t *out);
+int east_hip_similarity_build_host(east_hip_handle_t h, const double *table, int32_t n_keyphrases, int32_t n_docs, int32_t axis,
+                                   int64_t *out);
+int east_hip_similarity_fetch(east_hip_handle_t h, double *matrix, double *norm2);
+double east_hip_last_similarity_ms(east_hip_handle_t h);
+
+/*
  * Several devices in one process ("single-process/8-device fits the one-process CLI best").
  * Every document is an independent AST (east/relevance.py:41-46) and every (keyphrase, document) score is independent
  * (east/applications.py:43-52): a GROUP shards a collection at document granularity -- contiguous blocks of documents
