@@ -292,3 +292,136 @@ def test_binding_against_the_header():
     assert lib.east_hip_debug_set_synonyms_chunk(0) == 0
     assert lib.east_hip_last_synonyms_ms(None) == -1.0
     assert lib.east_hip_synonyms_info(None, None, 0) < 0
+
+
+# ---- the model on id arrays (tests/test_gpu_synonyms_scale.py's yardstick) ------------------------------------------------
+def _close(got, want, rel=1e-15):
+    return abs(float(got) - float(want)) <= rel * abs(float(want))
+
+
+def _array_model_against_the_decimal_model(triples, candidates=None):
+    from east.synonyms import synonyms
+    model = synonyms_exact.Model(triples)
+    words, relations, w1, rel, w2, inverse = synonyms.intern_triples(triples)
+    assert words == model.words and relations == model.relations
+    am = synonyms_exact.array_model(w1, rel, w2, inverse, len(words))
+    assert am.info() == {"raw_triples": len(triples), "distinct_triples": len(model.f), "words": len(words), "relations": len(relations),
+                         "features": sum(len(r) for r in model.rows.values()), "longest_row": max(len(r) for r in model.rows.values())}
+    # every distinct triple: f and q bit-equal, in the key's order
+    names = [(words[a], relations[r], words[b]) for a, r, b in zip(am.w1.tolist(), am.rel.tolist(), am.w2.tolist())]
+    assert names == sorted(model.f, key=lambda t: (words.index(t[0]), relations.index(t[1]), words.index(t[2])))
+    assert am.f.tolist() == [model.f[t] for t in names]
+    assert am.q.tolist() == [model.q[t] for t in names]
+    # the same kept features in the same order, I and the row sums
+    offsets = am.offsets()
+    sums = am.sums()
+    for i, w in enumerate(words):
+        b, e = int(offsets[i]), int(offsets[i + 1])
+        assert [(relations[r], words[x]) for r, x in zip(am.relation[b:e].tolist(), am.word[b:e].tolist())] == [k for k, _ in model.rows[w]]
+        assert all(_close(v, d) for v, (_, d) in zip(am.I[b:e], model.rows[w]))
+        assert _close(sums[i], model.row_sum[w])
+    # every candidate pair
+    cand = words if candidates is None else candidates
+    ids = [words.index(w) for w in cand]
+    a, b, sim, shared, n_a, n_b = synonyms_exact.pairs_model(am, ids)
+    want = model.pairs(cand, 0.0)
+    assert [(words[x], words[y]) for x, y in zip(a.tolist(), b.tolist())] == [(x, y) for x, y, _ in want]
+    assert all(_close(s, t[2]) for s, t in zip(sim.tolist(), want))
+    assert shared.tolist() == [len(model.shared(x, y)) for x, y, _ in want]
+    assert n_a.tolist() == [len(model.rows[x]) for x, _, _ in want] and n_b.tolist() == [len(model.rows[y]) for _, y, _ in want]
+    pa = [ids[i] for i in range(len(ids)) for _ in ids[i + 1:]]
+    pb = [y for i in range(len(ids)) for y in ids[i + 1:]]
+    looked_up = synonyms_exact.similarity_model(am, pa, pb)[0]
+    got = {(x, y): s for x, y, s in zip(a.tolist(), b.tolist(), sim.tolist())}
+    assert all(_close(s, got.get((x, y), 0.0)) for s, x, y in zip(looked_up.tolist(), pa, pb))     # (another order of the wide sum)
+    return am
+
+
+@pytest.mark.parametrize("case", GOLDEN, ids=[c["name"] for c in GOLDEN])
+def test_array_model_against_the_decimal_model(case):
+    _array_model_against_the_decimal_model(case_triples(case), case["candidates"])
+
+
+def test_array_model_against_the_decimal_model_on_zipf_triples():
+    am = _array_model_against_the_decimal_model(synonyms_exact.zipf_triples(seed=77, n_words=300, n_relations=6, n_triples=3000))
+    assert am.info()["features"] > 1000
+
+
+def _crossed(model, multiple):
+    """The multiples of `multiple`, in distinct-triple order, that a group (w1, r) lies across."""
+    at = np.arange(multiple, model.key.size, multiple)
+    return at[model.gid[at - 1] == model.gid[at]]
+
+
+def test_the_scale_case_holds_what_it_is_for():
+    (w1, rel, w2, inverse, W), m = synonyms_exact.scale_case()
+    assert W == 40000 and inverse.size == 64 and np.flatnonzero(inverse == np.arange(64)).tolist() == list(synonyms_exact.SCALE_SELF_INVERSE)
+    assert 480000 < w1.size < 500000
+    D = m.key.size
+    assert D > 524288                                                   # the marginals kernel's loop takes a second turn
+    group_sizes = np.bincount(m.gid)
+    assert (group_sizes > 64).any() and (group_sizes > 256).any()
+    assert _crossed(m, 64).size and _crossed(m, 256).size and _crossed(m, 524288).tolist() == [524288]
+    assert int(m.f.max()) ** 2 > 2 ** 32 and int(m.F_r.max()) > 2 ** 32 and int(m.F_w1r.max()) > 2 ** 32
+    assert int(m.f.max()) ** 2 < 2 ** 53                                # (what stays untested: integers a double cannot hold)
+    for r in synonyms_exact.SCALE_SELF_INVERSE:                         # self-inverse relations in use, kept features among them
+        assert (m.relation == r).sum() > 1000
+    ones = m.q == 1.0
+    assert ones.sum() == 2 * sum(na * nb for _, na, nb in synonyms_exact.SCALE_BLOCKS) and not m.keep[ones].any()
+    assert sorted(set(m.rel[ones].tolist())) == [56, 57, 58, 59]
+    assert np.unique(m.rel).size == 64                                  # every LDS relation counter of the 64
+    assert m.w1.max() == W - 1 or m.w1.max() >= 1 << 15                 # ids in the sort's highest bit
+
+
+def test_the_top_case_holds_what_it_is_for():
+    for n_words in (1 << 26, (1 << 25) + 3):
+        w1, rel, w2, inverse, W = synonyms_exact.top_case(n_words)
+        assert W == n_words and inverse.size == 4096 and 200 <= w1.size <= 400
+        m = synonyms_exact.array_model(w1, rel, w2, inverse, W)
+        top, half = n_words - 1, 1 << 25
+        assert {0, 1, 2, half - 1, half, top - 1, top} <= set(m.row.tolist()) and {0, half - 1, half, top - 1, top} <= set(m.word.tolist())
+        assert set(m.relation.tolist()) == {0, 1, 2047, 2048, 4094, 4095}
+        assert ((m.row == top) & (m.relation == 4095) & (m.word >= top - 1)).any()      # every field at its top in one key
+        assert m.info()["features"] > 50 and (~m.keep).sum() > 10
+        # what a relation mask one bit short would do is visible: 2048 and 0, 4095 and 2047 have different marginals
+        assert m.F_r[2048] != m.F_r[0] and m.F_r[4095] != m.F_r[2047] and m.F_r[4094] != m.F_r[2046]
+    assert (1 << 25) + 2 < (1 << 26) and ((1 << 25) + 2).bit_length() == ((1 << 26) - 1).bit_length()    # the same sort width
+
+
+@pytest.mark.parametrize("W", synonyms_exact.WORD_COUNTS)
+def test_the_word_count_cases_hold_what_they_are_for(W):
+    w1, rel, w2, inverse, n_words = synonyms_exact.word_count_case(W)
+    assert n_words == W and w1.size == 200
+    assert (w1 == W - 1).any() and (w2 == W - 1).any()
+    m = synonyms_exact.array_model(w1, rel, w2, inverse, W)
+    if W == 1:
+        assert not w1.any() and not w2.any() and m.info()["features"] == 0         # (0, r, 0): q == 1 / f
+    if W >= 255:
+        assert (m.row == W - 1).any() and (m.word == W - 1).any()                   # the highest id in a kept feature, both ways
+        assert m.info()["features"] > 50
+
+
+@pytest.mark.parametrize("D", synonyms_exact.DISTINCT_COUNTS)
+def test_the_distinct_count_cases_hold_what_they_are_for(D):
+    w1, rel, w2, inverse, W = synonyms_exact.distinct_count_case(D)
+    m = synonyms_exact.array_model(w1, rel, w2, inverse, W)
+    assert m.key.size == D and w1.size == D // 2 + D % 2
+    assert np.unique(synonyms_exact.pack_keys(w1, rel, w2)).size == w1.size        # all raw triples distinct
+    assert m.f.max() == (2 if D % 2 else 1)
+    assert m.info()["features"] > D // 4
+
+
+def test_the_pair_case_holds_what_it_is_for():
+    (w1, rel, w2, inverse, W), m = synonyms_exact.pair_case()
+    assert (W, inverse.size, w1.size) == (9000, 24, 90000)
+    hub = int(m.row_words[np.argmax(m.row_len)])
+    assert m.row_len.max() > 16 * 128                                   # more than 16 chunks of the default length
+    for C in synonyms_exact.PAIR_CANDIDATES:
+        cand = synonyms_exact.pair_candidates(m, C)
+        assert cand.size == C == np.unique(cand).size and hub in cand.tolist()
+        assert (np.diff(cand) < 0).any() and (np.diff(cand) > 0).any()             # in no id order
+        a, b, sim, shared, n_a, n_b = synonyms_exact.pairs_model(m, cand)
+        assert np.abs(sim - synonyms_exact.PAIR_THRESHOLD).min() > synonyms_exact.PAIR_MARGIN
+        assert (sim > synonyms_exact.PAIR_THRESHOLD).sum() > 1000 and a.size > 30000 and shared.max() > 40
+    assert 1300 * -(-1300 // 256) + 1 > 4096                            # two scan tiles of pair counts
+    assert -(-4097 // 256) == 17
