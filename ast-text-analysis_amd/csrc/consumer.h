@@ -1,0 +1,182 @@
+// consumer.h -- the host frame of the handle's consumers: the cosine term index, the keyphrase graph, the synonyms, the
+// ranking and the similarity.  A consumer is a struct of device buffers and results that the handle owns beside its arena,
+// made by the consumer's first call.  Nothing in here knows one consumer from another ("The consumer frame").
+#pragma once
+#include "handle.h"
+#include "scan.h"
+
+// ---- a score table on the device ------------------------------------------------------------------------------------------
+struct TableRef {               // K x D doubles on the handle's device, ordered behind everything queued on its stream
+    const double *p = nullptr;  // (nullptr: no table)
+    u32 K = 0, D = 0;
+};
+
+// ---- state, lifetime, timing ----------------------------------------------------------------------------------------------
+struct Consumer {
+    bool valid = false;                     // the last build's result can be fetched
+    float ms = -1.f;                        // device time of the last call that succeeded; -1 from the start of a call until it has
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;    // (made by the first ConsumerTimer)
+    std::vector<DevBuf *> bufs;             // every device allocation of the consumer (its constructor lists them)
+    size_t keep_bytes = 0;                  // east_hip_reset releases the buffers larger than this
+
+    Consumer() = default;
+    Consumer(const Consumer &) = delete;    // (bufs points into the object)
+    virtual void clear() = 0;               // the consumer's own fields, back to "nothing built"
+    virtual TableRef offers() const { return TableRef(); }      // the score table other consumers may read where it lies
+    void reset()
+    {
+        valid = false;
+        ms = -1.f;
+        clear();
+        for (DevBuf *b : bufs)
+            if (b->cap > keep_bytes) b->release();
+    }
+    virtual ~Consumer()
+    {
+        for (DevBuf *b : bufs) b->release();
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+    }
+};
+
+// T::SLOT names T's place in the handle.  consumer_peek: nullptr before the consumer's first call; consumer_state makes it.
+template <class T> static T *consumer_peek(const east_hip_index *h) { return static_cast<T *>(h->consumers[T::SLOT]); }
+template <class T> static T &consumer_state(east_hip_index *h)
+{
+    if (!h->consumers[T::SLOT]) h->consumers[T::SLOT] = new T();
+    return *consumer_peek<T>(h);
+}
+template <class T> static double consumer_ms(const east_hip_index *h) { return h && h->consumers[T::SLOT] ? (double)h->consumers[T::SLOT]->ms : -1.0; }
+
+// Brackets a call's launches on the handle's stream: ev0 now; finish() records ev1, waits for the stream and stores the time.
+struct ConsumerTimer {
+    east_hip_index *h;
+    Consumer &c;
+    ConsumerTimer(east_hip_index *h_, Consumer &c_) : h(h_), c(c_)
+    {
+        if (!c.ev1) {
+            if (!c.ev0) HIP_CHECK(hipEventCreate(&c.ev0));
+            HIP_CHECK(hipEventCreate(&c.ev1));
+        }
+        HIP_CHECK(hipEventRecord(c.ev0, h->stream));
+    }
+    void finish()
+    {
+        HIP_CHECK(hipEventRecord(c.ev1, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+        HIP_CHECK(hipEventElapsedTime(&c.ms, c.ev0, c.ev1));
+    }
+};
+
+// ---- a host table's copy --------------------------------------------------------------------------------------------------
+// Every consumer that takes a host table keeps a copy of its OWN (include/east_hip.h promises that they are separate).
+struct UploadedTable {
+    DevBuf buf;
+    u32 K = 0, D = 0;                       // K x D while the copy is whole, 0 x 0 while there is none or it is being replaced
+    TableRef ref() const
+    {
+        TableRef t;
+        if (K) { t.p = (const double *)buf.p; t.K = K; t.D = D; }
+        return t;
+    }
+    void withdraw() { K = D = 0; }
+    TableRef upload(east_hip_index *h, const double *table, u32 n_keyphrases, u32 n_docs, const char *what)
+    {
+        withdraw();
+        const size_t bytes = (size_t)n_keyphrases * (size_t)n_docs * 8;
+        buf.ensure(bytes, what, h->stream);
+        HIP_CHECK(hipMemcpyAsync(buf.p, table, bytes, hipMemcpyHostToDevice, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+        K = n_keyphrases;
+        D = n_docs;
+        return ref();
+    }
+};
+
+// ---- which table a *_build_resident call reads ----------------------------------------------------------------------------
+// who: the consumer's name in front of its messages; own: the caller's uploaded copy (nullptr before its first call);
+// similarity_ok: the similarity matrix is a source too (the ranking alone).
+static TableRef resolve_table(const east_hip_index *h, int32_t source, const UploadedTable *own, const char *who, bool similarity_ok = false)
+{
+    auto offered = [&](int slot) { return h->consumers[slot] ? h->consumers[slot]->offers() : TableRef(); };
+    TableRef t;
+    const char *missing = nullptr;
+    if (source == EAST_HIP_GRAPH_SOURCE_AST) {
+        if (h->built && h->table_scored) { t.p = h->table; t.K = h->n_kp; t.D = h->n_docs; }
+        missing = ": no score table is resident (score the keyphrases first)";
+    } else if (source == EAST_HIP_GRAPH_SOURCE_COSINE) {
+        t = offered(east_hip_index::SLOT_COS);
+        missing = ": no cosine score table is resident (score the keyphrases first)";
+    } else if (source == EAST_HIP_GRAPH_SOURCE_UPLOADED) {
+        if (own) t = own->ref();
+        missing = ": no host table has been uploaded to this handle";
+    } else if (source == EAST_HIP_GRAPH_SOURCE_SIMILARITY && similarity_ok) {
+        t = offered(east_hip_index::SLOT_SIM);
+        missing = ": no similarity matrix has been built on this handle";
+    } else {
+        east_throw(EAST_HIP_ERR_INVALID, std::string(who) + ": unknown table source");
+    }
+    if (!t.p) east_throw(EAST_HIP_ERR_NOT_BUILT, std::string(who) + missing);
+    return t;
+}
+
+// ---- count, scan, fill ----------------------------------------------------------------------------------------------------
+// A list of unknown length written without an atomic: a first pass counts per (row, target block), the exclusive scan of the
+// counts in that order gives every block's offset inside its row (modulo 2^32: differences inside a row are exact), the
+// kernel below the 64-bit number of entries in front of every row, and a second pass writes every entry to its slot.
+
+// row_base[s] = edges of the sources in front of s, in 64 bits; row_base[M] = all edges.  One workgroup: M values.
+__global__ __launch_bounds__(BLOCK) void graph_row_base_kernel(const u32 *__restrict__ cnt_ex, u32 M, u32 TB, u64 *__restrict__ row_base)
+{
+    __shared__ u32 lds4[WAVES_PER_BLOCK];
+    u64 carry = 0;
+    for (u32 b = 0; b < M; b += BLOCK) {
+        const u32 s = b + threadIdx.x;
+        const u32 x = s < M ? cnt_ex[(size_t)(s + 1u) * TB] - cnt_ex[(size_t)s * TB] : 0u;      // (at most M - 1 each: 256 of them fit 32 bits)
+        u32 total = 0;
+        const u32 ex = block_exclusive_sum(x, lds4, total);
+        if (s < M) row_base[s] = carry + ex;
+        carry += total;
+    }
+    if (threadIdx.x == 0) row_base[M] = carry;
+}
+
+struct EmitCounts {
+    u32 rows, TB, n;            // n = rows * TB counts + the sentinel the scan leaves the total in
+    size_t bytes;               // what the counts, the row bases and the scan's scratch take of the caller's arena
+};
+
+// too_many: the message of EAST_HIP_ERR_INVALID when the counts do not fit one scan (a printf format: %u = rows)
+static EmitCounts emit_counts(u32 rows, u32 TB, const char *too_many)
+{
+    const u64 n = (u64)rows * TB + 1;
+    if (n >= (u64)0xFFFFFFF0u) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), too_many, rows);
+        east_throw(EAST_HIP_ERR_INVALID, msg);
+    }
+    return EmitCounts{rows, TB, (u32)n, n * 4 + ((size_t)rows + 1) * 8 + ((size_t)ceil_div_u32(n, SCAN_TILE) + 1) * 8 + 16 * 256};
+}
+
+// ctx.arena: the caller's, with e.bytes to spare.  count(cnt) launches the counting pass; zero_all: it leaves counts unwritten,
+// which are to read 0.  size(total) makes room for a total > 0; fill(cnt, row_base) launches the filling pass.  One
+// synchronisation: the read-back of the total, which is returned.
+template <class Count, class Size, class Fill>
+static u64 emit_count_scan_fill(Ctx &ctx, const EmitCounts &e, bool zero_all, Count count, Size size, Fill fill)
+{
+    u32 *cnt = ctx.arena->alloc<u32>(e.n);
+    u64 *row_base = ctx.arena->alloc<u64>((size_t)e.rows + 1);
+    if (zero_all) HIP_CHECK(hipMemsetAsync(cnt, 0, (size_t)e.n * 4, ctx.stream));
+    else HIP_CHECK(hipMemsetAsync(cnt + (e.n - 1u), 0, 4, ctx.stream));
+    count(cnt);
+    device_scan<ArrIn, false>(ctx, ArrIn{cnt}, e.n, cnt);
+    LAUNCH(ctx, graph_row_base_kernel, 1, (const u32 *)cnt, e.rows, e.TB, row_base);
+    u64 total = 0;
+    HIP_CHECK(hipMemcpyAsync(&total, row_base + e.rows, 8, hipMemcpyDeviceToHost, ctx.stream));
+    HIP_CHECK(hipStreamSynchronize(ctx.stream));
+    if (total) {
+        size(total);
+        fill(cnt, (const u64 *)row_base);
+    }
+    return total;
+}

@@ -549,7 +549,8 @@ struct CosUnits {
     bool w_valid[2] = {false, false};
 };
 
-struct CosState {
+struct CosState : Consumer {
+    static constexpr int SLOT = east_hip_index::SLOT_COS;
     bool built = false, use_classes = false;
     u32 n_docs = 0, n_kept = 0, n_runs = 0, V = 0, attempts = 0;
     u64 B = 0, mask = 0;                                  // hash base and mask of the attempt that passed the verification
@@ -563,17 +564,35 @@ struct CosState {
     u32 *run_term = nullptr, *term_off = nullptr, *term_len = nullptr, *tcp = nullptr, *n_d = nullptr;
     CosUnits terms, cls;
     float build_ms = -1.f, score_ms = -1.f;
-    double *table = nullptr;                              // the last score call's K x D table, where it lies in `score` (graph.h reads it there)
+    double *table = nullptr;                              // the last score call's K x D table, where it lies in `score` (offers(): the graph, the ranking and the similarity read it there)
     u32 table_K = 0;
     bool table_valid = false;
-    DevBuf *bufs[8] = {&text, &work, &index, &term_text, &classes, &score, &terms.weights, &cls.weights};
+    CosState()
+    {
+        bufs = {&text, &work, &index, &term_text, &classes, &score, &terms.weights, &cls.weights};
+        keep_bytes = (size_t)64 << 20;                      // (a recycled handle keeps small buffers only, as east_hip_reset does)
+    }
+    void clear() override
+    {
+        built = use_classes = false;
+        table_valid = false;
+        terms.w_valid[0] = terms.w_valid[1] = cls.w_valid[0] = cls.w_valid[1] = false;
+        build_ms = score_ms = -1.f;
+    }
+    TableRef offers() const override
+    {
+        TableRef t;
+        if (built && table_valid) { t.p = table; t.K = table_K; t.D = n_docs; }
+        return t;
+    }
 };
 
 static CosState &cos_built(east_hip_index *h)
 {
     if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
-    if (!h->cos || !h->cos->built) east_throw(EAST_HIP_ERR_NOT_BUILT, "no cosine index has been built on this handle");
-    return *h->cos;
+    CosState *c = consumer_peek<CosState>(h);
+    if (!c || !c->built) east_throw(EAST_HIP_ERR_NOT_BUILT, "no cosine index has been built on this handle");
+    return *c;
 }
 
 // The postings in document order: a stable sort by document keeps the ascending unit order inside every document
@@ -621,8 +640,7 @@ static void cos_build(east_hip_index *h, const uint8_t *bytes, i64 n_bytes64, co
     for (int32_t w = 0; w < n_stop; w++)
         if (stop_offsets[w + 1] < stop_offsets[w]) east_throw(EAST_HIP_ERR_INVALID, "stopword offsets must not decrease");
     use_device(h);
-    if (!h->cos) h->cos = new CosState();
-    CosState &c = *h->cos;
+    CosState &c = consumer_state<CosState>(h);
     c.built = c.use_classes = false;
     c.table_valid = false;
     c.terms.w_valid[0] = c.terms.w_valid[1] = c.cls.w_valid[0] = c.cls.w_valid[1] = false;
@@ -994,26 +1012,6 @@ static void cos_score(east_hip_index *h, const int32_t *q_ids, const i64 *q_offs
     HIP_CHECK(hipEventElapsedTime(&c.score_ms, h->ev0, h->ev1));
 }
 
-static void cos_reset(east_hip_index *h)
-{
-    CosState *c = h->cos;
-    if (!c) return;
-    c->built = c->use_classes = false;
-    c->table_valid = false;
-    c->terms.w_valid[0] = c->terms.w_valid[1] = c->cls.w_valid[0] = c->cls.w_valid[1] = false;
-    c->build_ms = c->score_ms = -1.f;
-    for (DevBuf *b : c->bufs)                               // (a recycled handle keeps small buffers only, as east_hip_reset does)
-        if (b->cap > ((size_t)64 << 20)) b->release();
-}
-
-static void cos_destroy(east_hip_index *h)
-{
-    if (!h->cos) return;
-    for (DevBuf *b : h->cos->bufs) b->release();
-    delete h->cos;
-    h->cos = nullptr;
-}
-
 extern "C" {
 
 int east_hip_cosine_build_texts(east_hip_handle_t h, const uint8_t *bytes, int64_t n_bytes, const int64_t *text_offsets,
@@ -1047,7 +1045,7 @@ int east_hip_cosine_build_texts_v(east_hip_handle_t h, const uint8_t *const *tex
 int east_hip_cosine_info(east_hip_handle_t h, int64_t *out, int32_t cap)
 {
     if (!h || !out || cap < 0) return EAST_HIP_ERR_INVALID;
-    const CosState *c = h->cos;
+    const CosState *c = consumer_peek<CosState>(h);
     const bool b = c && c->built;
     const int64_t v[10] = {b ? 1 : 0,
                            b ? (int64_t)c->n_docs : 0,

@@ -21,6 +21,7 @@
 #include "common.h"         // errors, Arena, DevBuf, Knobs, Ctx, the launch macros
 #include "alphabet.h"       // the kernels in front of the suffix sort
 #include "handle.h"         // struct east_hip_index
+#include "consumer.h"       // what the handle's consumers share: state and lifetime, table sources, uploads, count-scan-fill
 #include "upload.h"         // the pinned ring, host symbols narrowed on their way up
 #include "build.h"          // build_impl, the arena planner, build_common
 #include "textfront.h"      // raw texts: streamed or one-piece preparation, then the build
@@ -106,11 +107,7 @@ void east_hip_destroy(east_hip_handle_t h)
     (void)hipGetDevice(&cur);
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    cos_destroy(h);
-    graph_destroy(h);
-    syn_destroy(h);
-    top_destroy(h);
-    sim_destroy(h);
+    for (Consumer *c : h->consumers) delete c;
     if (h->arena.base) (void)hipFree(h->arena.base);
     for (DevBuf *b : h->bufs) b->release();
     for (auto e : h->copy_events) (void)hipEventDestroy(e);
@@ -359,11 +356,8 @@ int east_hip_reset(east_hip_handle_t h)
         const size_t keep = (size_t)64 << 20;
         for (DevBuf *b : h->bufs)
             if (b->cap > keep) b->release();
-        cos_reset(h);
-        graph_reset(h);
-        syn_reset(h);
-        top_reset(h);
-        sim_reset(h);
+        for (Consumer *c : h->consumers)
+            if (c) c->reset();
     });
 }
 
@@ -457,12 +451,9 @@ double east_hip_last_score_ms(east_hip_handle_t h) { return h ? (double)h->last_
 // ---- several devices in one process ------------------------------------------------------------------
 #include "multi.h"
 #include "format.h"
-// ---- the cosine relevance measure ------------------------------------------------------------------
-#include "cosine.h"
-#include "graph.h"
-// ---- synonym extraction from dependency triples ------------------------------------------------------
-#include "synonyms.h"
-// ---- similar texts and keyphrases (in front of top.h, which ranks the matrix) ------------------------------
-#include "similarity.h"
-// ---- ranked keyphrases ---------------------------------------------------------------------------------
-#include "top.h"
+// ---- the consumers (consumer.h), each with its kernels, its state and its entry points -------------------
+#include "cosine.h"         // the cosine relevance measure
+#include "graph.h"          // the keyphrase graph
+#include "synonyms.h"       // synonym extraction from dependency triples
+#include "similarity.h"     // similar texts and keyphrases
+#include "top.h"            // ranked keyphrases

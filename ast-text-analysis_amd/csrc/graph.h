@@ -23,10 +23,9 @@
 // at once where the first one counted no edge for any of the tile's 64 sources, so a sparse graph pays for it where its
 // edges are, and a dense one is bound by writing its edges either way.
 //
-// Included at the end of east_hip.hip, behind cosine.h: the host half needs the handle and both resident tables.
+// The host half is a consumer of the handle (consumer.h): it reads whichever table resolve_table names.
 #pragma once
-#include "common.h"
-#include "scan.h"
+#include "consumer.h"
 
 #define GR_TILE 64u                        // sources and targets of a workgroup's tile
 #define GR_SRC_PER_WAVE (GR_TILE / WAVES_PER_BLOCK)
@@ -183,47 +182,24 @@ __global__ __launch_bounds__(BLOCK) void graph_pairs_kernel(const u64 *__restric
     if (!FILL && mine) cnt[(size_t)(s0 + lane) * TB + tb] = my_cnt;
 }
 
-// row_base[s] = edges of the sources in front of s, in 64 bits; row_base[M] = all edges.  One workgroup: M values.
-__global__ __launch_bounds__(BLOCK) void graph_row_base_kernel(const u32 *__restrict__ cnt_ex, u32 M, u32 TB, u64 *__restrict__ row_base)
-{
-    __shared__ u32 lds4[WAVES_PER_BLOCK];
-    u64 carry = 0;
-    for (u32 b = 0; b < M; b += BLOCK) {
-        const u32 s = b + threadIdx.x;
-        const u32 x = s < M ? cnt_ex[(size_t)(s + 1u) * TB] - cnt_ex[(size_t)s * TB] : 0u;      // (at most M - 1 each: 256 of them fit 32 bits)
-        u32 total = 0;
-        const u32 ex = block_exclusive_sum(x, lds4, total);
-        if (s < M) row_base[s] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) row_base[M] = carry;
-}
-
 // ============================================================================================================ host ==
 // The graph's device buffers belong to the handle and to nothing else: not the EASA arena, not the cosine buffers.
-struct GraphState {
-    bool valid = false;
+struct GraphState : Consumer {
+    static constexpr int SLOT = east_hip_index::SLOT_GRAPH;
     u32 n = 0, M = 0;                       // node positions, kept nodes
     i64 E = 0;                              // edges
-    DevBuf table;                           // a host table's copy (east_hip_graph_build_host), table_K x table_D while it is whole
-    u32 table_K = 0, table_D = 0;
+    UploadedTable table;                    // a host table's copy (east_hip_graph_build_host)
     DevBuf nodes, pairs, edges;
     u32 *support = nullptr, *kept = nullptr;
     int32_t *e_src = nullptr, *e_dst = nullptr, *e_shared = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    float ms = -1.f;
-    DevBuf *bufs[4] = {&table, &nodes, &pairs, &edges};
-};
-
-static GraphState &graph_state(east_hip_index *h)
-{
-    if (!h->graph) {
-        h->graph = new GraphState();
-        HIP_CHECK(hipEventCreate(&h->graph->ev0));
-        HIP_CHECK(hipEventCreate(&h->graph->ev1));
+    GraphState() { bufs = {&table.buf, &nodes, &pairs, &edges}; }
+    void clear() override
+    {
+        n = M = 0;
+        E = 0;
+        table.withdraw();
     }
-    return *h->graph;
-}
+};
 
 template <bool FILL>
 static void graph_launch_pairs(Ctx &ctx, u32 grid, const u64 *cbits, const u32 *csup, const u32 *kept, u32 M, u32 W, u32 TB, double rc,
@@ -239,23 +215,22 @@ static void graph_launch_pairs(Ctx &ctx, u32 grid, const u64 *cbits, const u32 *
 #undef GR_PAIRS
 }
 
-// d_table: K x D doubles on the handle's device, ordered behind everything queued on the handle's stream
-static void graph_build(east_hip_index *h, const double *d_table, u32 K, u32 D, const int32_t *rows, i64 n_pos, double relevance_threshold,
-                        double support_threshold, double referral_confidence, i64 *out)
+static void graph_build(east_hip_index *h, TableRef t, const int32_t *rows, i64 n_pos, double relevance_threshold, double support_threshold,
+                        double referral_confidence, i64 *out)
 {
     if (n_pos < 0 || n_pos >= (i64)0x7FFFFFF0 || (n_pos > 0 && !rows)) east_throw(EAST_HIP_ERR_INVALID, "bad node positions");
     for (i64 p = 0; p < n_pos; p++)
-        if (rows[p] < 0 || (u32)rows[p] >= K) east_throw(EAST_HIP_ERR_INVALID, "a node position names a row outside the score table");
-    GraphState &g = graph_state(h);
+        if (rows[p] < 0 || (u32)rows[p] >= t.K) east_throw(EAST_HIP_ERR_INVALID, "a node position names a row outside the score table");
+    GraphState &g = consumer_state<GraphState>(h);
     g.valid = false;
     g.ms = -1.f;
-    const u32 n = (u32)n_pos, W = ceil_div_u32(D, 64);
+    const u32 n = (u32)n_pos, D = t.D, W = ceil_div_u32(D, 64);
     g.n = n;
     g.M = 0;
     g.E = 0;
     Stats stats;
     Ctx ctx = handle_ctx(h, nullptr, &stats);
-    HIP_CHECK(hipEventRecord(g.ev0, h->stream));
+    ConsumerTimer timer(h, g);
     if (n) {
         const size_t n1 = (size_t)n + 1;
         g.nodes.ensure(n1 * 20 + (size_t)n * W * 8 + ((size_t)ceil_div_u32(n1, SCAN_TILE) + 1) * 8 + 16 * 256, "the keyphrase graph's node positions");
@@ -266,7 +241,7 @@ static void graph_build(east_hip_index *h, const double *d_table, u32 K, u32 D, 
         u32 *d_rows = a.alloc<u32>(n1), *keep = a.alloc<u32>(n1), *keep_ex = a.alloc<u32>(n1);
         u64 *bits = a.alloc<u64>((size_t)n * W);
         HIP_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
-        LAUNCH(ctx, graph_bits_kernel, ceil_div_u32(n, WAVES_PER_BLOCK), d_table, D, (const u32 *)d_rows, n, W, relevance_threshold, bits,
+        LAUNCH(ctx, graph_bits_kernel, ceil_div_u32(n, WAVES_PER_BLOCK), t.p, D, (const u32 *)d_rows, n, W, relevance_threshold, bits,
                g.support);
         LAUNCH(ctx, graph_keep_kernel, ceil_div_u32(n1, BLOCK), (const u32 *)g.support, n, support_threshold, keep);
         device_scan<ArrIn, false>(ctx, ArrIn{keep}, n + 1u, keep_ex);
@@ -275,68 +250,36 @@ static void graph_build(east_hip_index *h, const double *d_table, u32 K, u32 D, 
         HIP_CHECK(hipStreamSynchronize(h->stream));
         g.M = M;
         if (M) {
-            const u32 TB = ceil_div_u32(M, GR_TILE);
-            const u64 n_cnt = (u64)M * TB + 1;
-            if (n_cnt >= (u64)0xFFFFFFF0u) {
-                char msg[160];
-                snprintf(msg, sizeof(msg), "keyphrase graph: %u nodes are more than one device builds a graph of", M);
-                east_throw(EAST_HIP_ERR_INVALID, msg);
-            }
-            g.pairs.ensure((size_t)M * W * 8 + (size_t)M * 12 + n_cnt * 4 + ((size_t)ceil_div_u32(n_cnt, SCAN_TILE) + 1) * 8 + 16 * 256,
-                           "the keyphrase graph's nodes");
+            const u32 TB = ceil_div_u32(M, GR_TILE), grid = TB * TB;
+            const EmitCounts e = emit_counts(M, TB, "keyphrase graph: %u nodes are more than one device builds a graph of");
+            g.pairs.ensure((size_t)M * W * 8 + (size_t)M * 4 + e.bytes, "the keyphrase graph's nodes");
             Arena b = g.pairs.arena();
             ctx.arena = &b;
-            u64 *cbits = b.alloc<u64>((size_t)M * W), *row_base = b.alloc<u64>((size_t)M + 1);
-            u32 *csup = b.alloc<u32>(M), *cnt = b.alloc<u32>(n_cnt);
+            u64 *cbits = b.alloc<u64>((size_t)M * W);
+            u32 *csup = b.alloc<u32>(M);
             LAUNCH(ctx, graph_compact_kernel, ceil_div_u32(n, WAVES_PER_BLOCK), (const u32 *)keep_ex, (const u32 *)g.support,
                    (const u64 *)bits, n, W, g.kept, csup, cbits);
-            HIP_CHECK(hipMemsetAsync(cnt + (n_cnt - 1), 0, 4, h->stream));
-            const u32 grid = TB * TB;
-            graph_launch_pairs<false>(ctx, grid, cbits, csup, g.kept, M, W, TB, referral_confidence, cnt, nullptr, nullptr, nullptr, nullptr);
-            device_scan<ArrIn, false>(ctx, ArrIn{cnt}, (u32)n_cnt, cnt);
-            LAUNCH(ctx, graph_row_base_kernel, 1, (const u32 *)cnt, M, TB, row_base);
-            u64 E = 0;
-            HIP_CHECK(hipMemcpyAsync(&E, row_base + M, 8, hipMemcpyDeviceToHost, h->stream));
-            HIP_CHECK(hipStreamSynchronize(h->stream));
-            if (E) {
-                const size_t eb = (((size_t)E * 4) + 255) & ~(size_t)255;
-                g.edges.ensure(eb * 3, "the keyphrase graph's edges");
-                g.e_src = (int32_t *)g.edges.p;
-                g.e_dst = (int32_t *)(g.edges.p + eb);
-                g.e_shared = (int32_t *)(g.edges.p + 2 * eb);
-                graph_launch_pairs<true>(ctx, grid, cbits, csup, g.kept, M, W, TB, referral_confidence, cnt, row_base, g.e_src, g.e_dst,
-                                         g.e_shared);
-            }
-            g.E = (i64)E;
+            g.E = (i64)emit_count_scan_fill(
+                ctx, e, false,
+                [&](u32 *cnt) {
+                    graph_launch_pairs<false>(ctx, grid, cbits, csup, g.kept, M, W, TB, referral_confidence, cnt, nullptr, nullptr, nullptr, nullptr);
+                },
+                [&](u64 E) {
+                    const size_t eb = (((size_t)E * 4) + 255) & ~(size_t)255;
+                    g.edges.ensure(eb * 3, "the keyphrase graph's edges");
+                    g.e_src = (int32_t *)g.edges.p;
+                    g.e_dst = (int32_t *)(g.edges.p + eb);
+                    g.e_shared = (int32_t *)(g.edges.p + 2 * eb);
+                },
+                [&](u32 *cnt, const u64 *row_base) {
+                    graph_launch_pairs<true>(ctx, grid, cbits, csup, g.kept, M, W, TB, referral_confidence, cnt, row_base, g.e_src, g.e_dst,
+                                             g.e_shared);
+                });
         }
     }
-    HIP_CHECK(hipEventRecord(g.ev1, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    HIP_CHECK(hipEventElapsedTime(&g.ms, g.ev0, g.ev1));
+    timer.finish();
     g.valid = true;
     if (out) { out[0] = g.M; out[1] = g.E; }
-}
-
-static void graph_reset(east_hip_index *h)
-{
-    GraphState *g = h->graph;
-    if (!g) return;
-    g->valid = false;
-    g->n = g->M = 0;
-    g->E = 0;
-    g->ms = -1.f;
-    g->table_K = g->table_D = 0;
-    for (DevBuf *b : g->bufs) b->release();
-}
-
-static void graph_destroy(east_hip_index *h)
-{
-    if (!h->graph) return;
-    graph_reset(h);
-    if (h->graph->ev0) (void)hipEventDestroy(h->graph->ev0);
-    if (h->graph->ev1) (void)hipEventDestroy(h->graph->ev1);
-    delete h->graph;
-    h->graph = nullptr;
 }
 
 extern "C" {
@@ -347,23 +290,9 @@ int east_hip_graph_build_resident(east_hip_handle_t h, int32_t source, const int
     return guarded([&] {
         if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
         use_device(h);
-        if (source == EAST_HIP_GRAPH_SOURCE_AST) {
-            if (!h->built || !h->table_scored)
-                east_throw(EAST_HIP_ERR_NOT_BUILT, "keyphrase graph: no score table is resident (score the keyphrases first)");
-            graph_build(h, h->table, h->n_kp, h->n_docs, rows, n_positions, relevance_threshold, support_threshold, referral_confidence, out);
-        } else if (source == EAST_HIP_GRAPH_SOURCE_COSINE) {
-            if (!h->cos || !h->cos->built || !h->cos->table_valid)
-                east_throw(EAST_HIP_ERR_NOT_BUILT, "keyphrase graph: no cosine score table is resident (score the keyphrases first)");
-            graph_build(h, h->cos->table, h->cos->table_K, h->cos->n_docs, rows, n_positions, relevance_threshold, support_threshold,
-                        referral_confidence, out);
-        } else if (source == EAST_HIP_GRAPH_SOURCE_UPLOADED) {
-            if (!h->graph || !h->graph->table_K)
-                east_throw(EAST_HIP_ERR_NOT_BUILT, "keyphrase graph: no host table has been uploaded to this handle");
-            graph_build(h, (const double *)h->graph->table.p, h->graph->table_K, h->graph->table_D, rows, n_positions,
-                        relevance_threshold, support_threshold, referral_confidence, out);
-        } else {
-            east_throw(EAST_HIP_ERR_INVALID, "keyphrase graph: unknown table source");
-        }
+        const GraphState *g = consumer_peek<GraphState>(h);
+        graph_build(h, resolve_table(h, source, g ? &g->table : nullptr, "keyphrase graph"), rows, n_positions, relevance_threshold, support_threshold,
+                    referral_confidence, out);
     });
 }
 
@@ -375,17 +304,10 @@ int east_hip_graph_build_host(east_hip_handle_t h, const double *table, int32_t 
         if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
         if (!table || n_keyphrases < 1 || n_docs < 1) east_throw(EAST_HIP_ERR_INVALID, "keyphrase graph: null or empty score table");
         use_device(h);
-        GraphState &g = graph_state(h);
-        g.valid = false;
-        g.table_K = g.table_D = 0;
-        const size_t bytes = (size_t)n_keyphrases * (size_t)n_docs * 8;
-        g.table.ensure(bytes, "the keyphrase graph's score table");
-        HIP_CHECK(hipMemcpyAsync(g.table.p, table, bytes, hipMemcpyHostToDevice, h->stream));
-        HIP_CHECK(hipStreamSynchronize(h->stream));
-        g.table_K = (u32)n_keyphrases;
-        g.table_D = (u32)n_docs;
-        graph_build(h, (const double *)g.table.p, (u32)n_keyphrases, (u32)n_docs, rows, n_positions, relevance_threshold, support_threshold,
-                    referral_confidence, out);
+        GraphState &g = consumer_state<GraphState>(h);
+        g.valid = false;                                      // (the rows are checked after the upload: the new table is the uploaded one)
+        graph_build(h, g.table.upload(h, table, (u32)n_keyphrases, (u32)n_docs, "the keyphrase graph's score table"), rows, n_positions,
+                    relevance_threshold, support_threshold, referral_confidence, out);
     });
 }
 
@@ -394,9 +316,10 @@ int east_hip_graph_fetch(east_hip_handle_t h, int32_t *support, int32_t *kept, i
 {
     return guarded([&] {
         if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
-        if (!h->graph || !h->graph->valid) east_throw(EAST_HIP_ERR_NOT_BUILT, "no keyphrase graph has been built on this handle");
+        GraphState *gp = consumer_peek<GraphState>(h);
+        if (!gp || !gp->valid) east_throw(EAST_HIP_ERR_NOT_BUILT, "no keyphrase graph has been built on this handle");
         use_device(h);
-        GraphState &g = *h->graph;
+        GraphState &g = *gp;
         const size_t eb = (size_t)g.E * 4;
         if (support && g.n) HIP_CHECK(hipMemcpyAsync(support, g.support, (size_t)g.n * 4, hipMemcpyDeviceToHost, h->stream));
         if (kept && g.M) HIP_CHECK(hipMemcpyAsync(kept, g.kept, (size_t)g.M * 4, hipMemcpyDeviceToHost, h->stream));
@@ -407,6 +330,6 @@ int east_hip_graph_fetch(east_hip_handle_t h, int32_t *support, int32_t *kept, i
     });
 }
 
-double east_hip_last_graph_ms(east_hip_handle_t h) { return h && h->graph ? (double)h->graph->ms : -1.0; }
+double east_hip_last_graph_ms(east_hip_handle_t h) { return consumer_ms<GraphState>(h); }
 
 }  // extern "C"

@@ -5,6 +5,8 @@
 #include <atomic>
 #include <thread>
 
+struct Consumer;            // consumer.h
+
 struct east_hip_index {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -86,32 +88,17 @@ struct east_hip_index {
     i64 prep_n = 0;
     std::vector<i64> prep_doc_off;
     std::vector<int32_t> prep_n_strings;
-    // the cosine measure's term index (cosine.h; own allocations, made by the first east_hip_cosine_build_texts)
-    struct CosState *cos = nullptr;
     // the AST score table of the resident keyphrases (h->table) holds the scores of the index as it stands: set by the score
-    // walk, withdrawn by every build and every new set of keyphrases (the keyphrase graph reads it where it lies, graph.h)
+    // walk, withdrawn by every build and every new set of keyphrases (consumer.h: resolve_table hands it out where it lies)
     bool table_scored = false;
-    // the keyphrase graph (graph.h; own allocations, made by the first east_hip_graph_build_*)
-    struct GraphState *graph = nullptr;
-    // the synonyms' feature rows and pair list (synonyms.h; own allocations, made by the first east_hip_synonyms_build)
-    struct SynState *syn = nullptr;
-    // the ranked keyphrases' candidates, result and uploaded table (top.h; own allocations, made by the first east_hip_top_build_*)
-    struct TopState *top = nullptr;
-    // the similarity's uploaded table, q and M x M matrix (similarity.h; own allocations, made by the first east_hip_similarity_build_*)
-    struct SimState *sim = nullptr;
+    // the consumers (consumer.h): the cosine measure's term index (cosine.h), the keyphrase graph (graph.h), the synonyms'
+    // feature rows and pair list (synonyms.h), the ranking (top.h) and the similarity matrix (similarity.h).  Each owns its
+    // device allocations and is made by its first call; east_hip_reset and east_hip_destroy go over the array
+    enum { SLOT_COS, SLOT_GRAPH, SLOT_SYN, SLOT_TOP, SLOT_SIM, N_CONSUMERS };
+    Consumer *consumers[N_CONSUMERS] = {};
     // the handle's own device allocations besides the arena: east_hip_destroy frees them, east_hip_reset the large ones
     DevBuf *bufs[6] = {&guess, &ht_tab, &q_buf, &kg, &tp_tables, &prep_sym};
 };
-static void cos_reset(east_hip_index *h);
-static void cos_destroy(east_hip_index *h);
-static void graph_reset(east_hip_index *h);
-static void graph_destroy(east_hip_index *h);
-static void syn_reset(east_hip_index *h);
-static void syn_destroy(east_hip_index *h);
-static void top_reset(east_hip_index *h);
-static void top_destroy(east_hip_index *h);
-static void sim_reset(east_hip_index *h);
-static void sim_destroy(east_hip_index *h);
 
 struct SpecAbort {};             // a speculative build cannot go on: build_common starts over with the read-backs in place
 

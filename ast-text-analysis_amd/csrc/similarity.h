@@ -33,9 +33,9 @@
 //
 // Determinism: no atomic, no split of L across workgroups or wavefronts; the order of every sum is fixed by the code.
 //
-// Included from east_hip.hip in front of top.h, which ranks the matrix.
+// The host half is a consumer of the handle (consumer.h); its matrix is what it offers() the ranking (top.h) as a table.
 #pragma once
-#include "common.h"
+#include "consumer.h"
 
 #define SIM_TILE 64u
 #define SIM_CHUNK 32u                      // entries of a profile staged at a time (by keyphrase)
@@ -203,39 +203,39 @@ __global__ __launch_bounds__(BLOCK) void sim_gram_kernel(const double *__restric
 // ============================================================================================================ host ==
 // The similarity's device buffers belong to the handle and to nothing else: not the EASA arena, the cosine buffers, the
 // graph's or the ranking's.
-struct SimState {
-    bool valid = false;
+struct SimState : Consumer {
+    static constexpr int SLOT = east_hip_index::SLOT_SIM;
     u32 M = 0, L = 0;
-    DevBuf table;                           // a host table's copy (east_hip_similarity_build_host), table_K x table_D while it is whole
-    u32 table_K = 0, table_D = 0;
+    UploadedTable table;                    // a host table's copy (east_hip_similarity_build_host)
     DevBuf out;                             // q[M], matrix[M x M]
     double *q = nullptr, *matrix = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    float ms = -1.f;
-    DevBuf *bufs[2] = {&table, &out};
-};
-
-static SimState &sim_state(east_hip_index *h)
-{
-    if (!h->sim) {
-        h->sim = new SimState();
-        HIP_CHECK(hipEventCreate(&h->sim->ev0));
-        HIP_CHECK(hipEventCreate(&h->sim->ev1));
+    SimState() { bufs = {&table.buf, &out}; }
+    void clear() override
+    {
+        M = L = 0;
+        table.withdraw();
+        q = matrix = nullptr;
     }
-    return *h->sim;
-}
+    TableRef offers() const override        // (the ranking reads the matrix where it lies)
+    {
+        TableRef t;
+        if (valid) { t.p = matrix; t.K = t.D = M; }
+        return t;
+    }
+};
 
 static void sim_check(int32_t axis)
 {
     if (axis != EAST_HIP_TOP_BY_TEXT && axis != EAST_HIP_TOP_BY_KEYPHRASE) east_throw(EAST_HIP_ERR_INVALID, "similarity: unknown axis");
 }
 
-// d_table: K x D doubles on the handle's device, ordered behind everything queued on the handle's stream
-static void sim_build(east_hip_index *h, const double *d_table, u32 K, u32 D, int32_t axis, i64 *out)
+static void sim_build(east_hip_index *h, TableRef t, int32_t axis, i64 *out)
 {
     sim_check(axis);
+    const double *d_table = t.p;
+    const u32 K = t.K, D = t.D;
     if (K < 1 || D < 1 || K >= 0x7FFFFFF0u || D >= 0x7FFFFFF0u) east_throw(EAST_HIP_ERR_INVALID, "similarity: empty score table");
-    SimState &g = sim_state(h);
+    SimState &g = consumer_state<SimState>(h);
     g.valid = false;
     g.ms = -1.f;
     const bool by_text = axis == EAST_HIP_TOP_BY_TEXT;
@@ -256,7 +256,7 @@ static void sim_build(east_hip_index *h, const double *d_table, u32 K, u32 D, in
     g.M = M;
     g.L = L;
     const u32 NT = ceil_div_u32(M, SIM_TILE);
-    HIP_CHECK(hipEventRecord(g.ev0, h->stream));
+    ConsumerTimer timer(h, g);
     if (by_text) {
         LAUNCH(ctx, sim_norm_col_kernel, ceil_div_u32(D, SIM_NORM_COLS), d_table, K, D, g.q);
         LAUNCH_NAMED(ctx, "sim_gram_text_kernel", sim_gram_kernel<true>, dim3(NT, NT), d_table, K, D, (const double *)g.q, g.matrix);
@@ -264,33 +264,9 @@ static void sim_build(east_hip_index *h, const double *d_table, u32 K, u32 D, in
         LAUNCH(ctx, sim_norm_row_kernel, ceil_div_u32(K, WAVES_PER_BLOCK), d_table, K, D, g.q);
         LAUNCH_NAMED(ctx, "sim_gram_keyphrase_kernel", sim_gram_kernel<false>, dim3(NT, NT), d_table, K, D, (const double *)g.q, g.matrix);
     }
-    HIP_CHECK(hipEventRecord(g.ev1, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    HIP_CHECK(hipEventElapsedTime(&g.ms, g.ev0, g.ev1));
+    timer.finish();
     g.valid = true;
     if (out) { out[0] = (i64)M; out[1] = (i64)L; }
-}
-
-static void sim_reset(east_hip_index *h)
-{
-    SimState *g = h->sim;
-    if (!g) return;
-    g->valid = false;
-    g->M = g->L = 0;
-    g->ms = -1.f;
-    g->table_K = g->table_D = 0;
-    g->q = g->matrix = nullptr;
-    for (DevBuf *b : g->bufs) b->release();
-}
-
-static void sim_destroy(east_hip_index *h)
-{
-    if (!h->sim) return;
-    sim_reset(h);
-    if (h->sim->ev0) (void)hipEventDestroy(h->sim->ev0);
-    if (h->sim->ev1) (void)hipEventDestroy(h->sim->ev1);
-    delete h->sim;
-    h->sim = nullptr;
 }
 
 extern "C" {
@@ -300,21 +276,8 @@ int east_hip_similarity_build_resident(east_hip_handle_t h, int32_t source, int3
     return guarded([&] {
         if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
         use_device(h);
-        if (source == EAST_HIP_GRAPH_SOURCE_AST) {
-            if (!h->built || !h->table_scored)
-                east_throw(EAST_HIP_ERR_NOT_BUILT, "similarity: no score table is resident (score the keyphrases first)");
-            sim_build(h, h->table, h->n_kp, h->n_docs, axis, out);
-        } else if (source == EAST_HIP_GRAPH_SOURCE_COSINE) {
-            if (!h->cos || !h->cos->built || !h->cos->table_valid)
-                east_throw(EAST_HIP_ERR_NOT_BUILT, "similarity: no cosine score table is resident (score the keyphrases first)");
-            sim_build(h, h->cos->table, h->cos->table_K, h->cos->n_docs, axis, out);
-        } else if (source == EAST_HIP_GRAPH_SOURCE_UPLOADED) {
-            if (!h->sim || !h->sim->table_K)
-                east_throw(EAST_HIP_ERR_NOT_BUILT, "similarity: no host table has been uploaded to this handle");
-            sim_build(h, (const double *)h->sim->table.p, h->sim->table_K, h->sim->table_D, axis, out);
-        } else {
-            east_throw(EAST_HIP_ERR_INVALID, "similarity: unknown table source");
-        }
+        const SimState *g = consumer_peek<SimState>(h);
+        sim_build(h, resolve_table(h, source, g ? &g->table : nullptr, "similarity"), axis, out);
     });
 }
 
@@ -325,16 +288,9 @@ int east_hip_similarity_build_host(east_hip_handle_t h, const double *table, int
         if (!table || n_keyphrases < 1 || n_docs < 1) east_throw(EAST_HIP_ERR_INVALID, "similarity: null or empty score table");
         sim_check(axis);                                      // (before the upload: a refused call leaves the uploaded table alone)
         use_device(h);
-        SimState &g = sim_state(h);
+        SimState &g = consumer_state<SimState>(h);
         g.valid = false;
-        g.table_K = g.table_D = 0;
-        const size_t bytes = (size_t)n_keyphrases * (size_t)n_docs * 8;
-        g.table.ensure(bytes, "the similarity's score table", h->stream);
-        HIP_CHECK(hipMemcpyAsync(g.table.p, table, bytes, hipMemcpyHostToDevice, h->stream));
-        HIP_CHECK(hipStreamSynchronize(h->stream));
-        g.table_K = (u32)n_keyphrases;
-        g.table_D = (u32)n_docs;
-        sim_build(h, (const double *)g.table.p, (u32)n_keyphrases, (u32)n_docs, axis, out);
+        sim_build(h, g.table.upload(h, table, (u32)n_keyphrases, (u32)n_docs, "the similarity's score table"), axis, out);
     });
 }
 
@@ -342,15 +298,16 @@ int east_hip_similarity_fetch(east_hip_handle_t h, double *matrix, double *norm2
 {
     return guarded([&] {
         if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
-        if (!h->sim || !h->sim->valid) east_throw(EAST_HIP_ERR_NOT_BUILT, "no similarity matrix has been built on this handle");
+        SimState *gp = consumer_peek<SimState>(h);
+        if (!gp || !gp->valid) east_throw(EAST_HIP_ERR_NOT_BUILT, "no similarity matrix has been built on this handle");
         use_device(h);
-        SimState &g = *h->sim;
+        SimState &g = *gp;
         if (matrix) HIP_CHECK(hipMemcpyAsync(matrix, g.matrix, (size_t)g.M * g.M * 8, hipMemcpyDeviceToHost, h->stream));
         if (norm2) HIP_CHECK(hipMemcpyAsync(norm2, g.q, (size_t)g.M * 8, hipMemcpyDeviceToHost, h->stream));
         HIP_CHECK(hipStreamSynchronize(h->stream));
     });
 }
 
-double east_hip_last_similarity_ms(east_hip_handle_t h) { return h && h->sim ? (double)h->sim->ms : -1.0; }
+double east_hip_last_similarity_ms(east_hip_handle_t h) { return consumer_ms<SimState>(h); }
 
 }  // extern "C"

@@ -26,11 +26,10 @@
 // The one shortcut is exact: two rows without a common feature have numerator 0, similarity 0.0, which exceeds no
 // threshold >= 0 (negative thresholds are refused), so such a pair costs no division.
 //
-// Included at the end of east_hip.hip, behind graph.h (whose row-base kernel it shares).
+// The host half is a consumer of the handle (consumer.h); its pair list comes out of the frame's count-scan-fill driver.
 #pragma once
-#include "common.h"
+#include "consumer.h"
 #include "radix_sort.h"
-#include "scan.h"
 #include <math.h>
 
 #define SY_WORD_BITS 26
@@ -352,8 +351,9 @@ __global__ __launch_bounds__(BLOCK) void syn_pairs_kernel(const u32 *__restrict_
 
 // ============================================================================================================ host ==
 // The synonyms' device buffers belong to the handle and to nothing else: not the EASA arena, the cosine buffers or the graph.
-struct SynState {
-    bool valid = false, pairs_valid = false;
+struct SynState : Consumer {             // valid: the feature rows; ms: the last build or pair pass
+    static constexpr int SLOT = east_hip_index::SLOT_SYN;
+    bool pairs_valid = false;
     i64 n_raw = 0, n_distinct = 0, n_features = 0, longest_row = 0, n_pairs = 0;
     u32 W = 0, R = 0;
     DevBuf work, csr, pairs, out;           // build scratch; the CSR rows; candidates + counts; the pair list
@@ -362,26 +362,21 @@ struct SynState {
     double *val = nullptr, *row_sum = nullptr;
     int32_t *o_a = nullptr, *o_b = nullptr;
     double *o_sim = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    float ms = -1.f;
-    DevBuf *bufs[4] = {&work, &csr, &pairs, &out};
-};
-
-static SynState &syn_state(east_hip_index *h)
-{
-    if (!h->syn) {
-        h->syn = new SynState();
-        HIP_CHECK(hipEventCreate(&h->syn->ev0));
-        HIP_CHECK(hipEventCreate(&h->syn->ev1));
+    SynState() { bufs = {&work, &csr, &pairs, &out}; }
+    void clear() override
+    {
+        pairs_valid = false;
+        n_raw = n_distinct = n_features = longest_row = n_pairs = 0;
+        W = R = 0;
     }
-    return *h->syn;
-}
+};
 
 static SynState &syn_built(east_hip_index *h)
 {
     if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
-    if (!h->syn || !h->syn->valid) east_throw(EAST_HIP_ERR_NOT_BUILT, "no synonym features have been built on this handle");
-    return *h->syn;
+    SynState *g = consumer_peek<SynState>(h);
+    if (!g || !g->valid) east_throw(EAST_HIP_ERR_NOT_BUILT, "no synonym features have been built on this handle");
+    return *g;
 }
 
 static void syn_build(east_hip_index *h, const int32_t *w1, const int32_t *rel, const int32_t *w2, i64 n_triples, const int32_t *inv,
@@ -399,7 +394,7 @@ static void syn_build(east_hip_index *h, const int32_t *w1, const int32_t *rel, 
         if (w1[i] < 0 || w1[i] >= n_words || w2[i] < 0 || w2[i] >= n_words || rel[i] < 0 || rel[i] >= n_relations)
             east_throw(EAST_HIP_ERR_INVALID, "synonyms: a triple names a word or a relation outside the given counts");
     use_device(h);
-    SynState &g = syn_state(h);
+    SynState &g = consumer_state<SynState>(h);
     g.valid = g.pairs_valid = false;
     g.ms = -1.f;
     const u32 N = (u32)n_triples, M = 2u * N, W = (u32)n_words, R = (u32)n_relations;
@@ -408,7 +403,7 @@ static void syn_build(east_hip_index *h, const int32_t *w1, const int32_t *rel, 
     g.work.ensure((size_t)M * 84 + (size_t)N * 12 + (size_t)R * 12 + (size_t)M / 2 + ((size_t)4 << 20), "the synonyms' triples", h->stream);
     Arena a = g.work.arena();
     ctx.arena = &a;
-    HIP_CHECK(hipEventRecord(g.ev0, h->stream));
+    ConsumerTimer timer(h, g);
     int32_t *d_w1 = a.alloc<int32_t>(N), *d_rel = a.alloc<int32_t>(N), *d_w2 = a.alloc<int32_t>(N), *d_inv = a.alloc<int32_t>(R);
     HIP_CHECK(hipMemcpyAsync(d_w1, w1, (size_t)N * 4, hipMemcpyHostToDevice, h->stream));
     HIP_CHECK(hipMemcpyAsync(d_rel, rel, (size_t)N * 4, hipMemcpyHostToDevice, h->stream));
@@ -459,9 +454,7 @@ static void syn_build(east_hip_index *h, const int32_t *w1, const int32_t *rel, 
     LAUNCH(ctx, syn_row_sum_kernel, ceil_div_u32(W, BLOCK), (const u32 *)g.row_off, (const double *)g.val, W, g.row_sum);
     std::vector<u32> off((size_t)W + 1);
     HIP_CHECK(hipMemcpyAsync(off.data(), g.row_off, ((size_t)W + 1) * 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(hipEventRecord(g.ev1, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    HIP_CHECK(hipEventElapsedTime(&g.ms, g.ev0, g.ev1));
+    timer.finish();
     u32 longest = 0;
     for (u32 w = 0; w < W; w++) longest = std::max(longest, off[w + 1] - off[w]);
     g.n_raw = N;
@@ -505,62 +498,32 @@ static void syn_pairs(east_hip_index *h, const int32_t *candidates, i64 n_candid
     Stats stats;
     Ctx ctx = handle_ctx(h, nullptr, &stats);
     const u32 L = (u32)std::min<int>(std::max(ctx.knobs.syn_chunk, 1), (int)SY_MAX_CHUNK);
-    HIP_CHECK(hipEventRecord(g.ev0, h->stream));
+    ConsumerTimer timer(h, g);
     if (C >= 2u) {
-        const u32 TB = ceil_div_u32(C, SY_TGT), SB = ceil_div_u32(C, SY_SRC);
-        const u64 n_cnt = (u64)C * TB + 1;
-        if (n_cnt >= (u64)0xFFFFFFF0u) east_throw(EAST_HIP_ERR_INVALID, "synonyms: more candidates than one pair pass counts");
-        g.pairs.ensure((size_t)C * 4 + n_cnt * 4 + ((size_t)C + 1) * 8 + ((size_t)ceil_div_u32(n_cnt, SCAN_TILE) + 1) * 8 + 16 * 256,
-                       "the synonyms' pair counts", h->stream);
+        const u32 TB = ceil_div_u32(C, SY_TGT), grid = ceil_div_u32(C, SY_SRC) * TB;
+        const EmitCounts e = emit_counts(C, TB, "synonyms: more candidates than one pair pass counts");
+        g.pairs.ensure((size_t)C * 4 + e.bytes, "the synonyms' pair counts", h->stream);
         Arena b = g.pairs.arena();
         ctx.arena = &b;
-        u32 *cand = b.alloc<u32>(C), *cnt = b.alloc<u32>(n_cnt);
-        u64 *row_base = b.alloc<u64>((size_t)C + 1);
+        u32 *cand = b.alloc<u32>(C);
         HIP_CHECK(hipMemcpyAsync(cand, candidates, (size_t)C * 4, hipMemcpyHostToDevice, h->stream));
-        HIP_CHECK(hipMemsetAsync(cnt, 0, n_cnt * 4, h->stream));
-        const u32 grid = SB * TB;
-        syn_launch_pairs<false>(ctx, grid, g, cand, C, L, TB, threshold, cnt, nullptr, nullptr, nullptr, nullptr);
-        device_scan<ArrIn, false>(ctx, ArrIn{cnt}, (u32)n_cnt, cnt);
-        LAUNCH(ctx, graph_row_base_kernel, 1, (const u32 *)cnt, C, TB, row_base);
-        u64 E = 0;
-        HIP_CHECK(hipMemcpyAsync(&E, row_base + C, 8, hipMemcpyDeviceToHost, h->stream));
-        HIP_CHECK(hipStreamSynchronize(h->stream));
-        if (E) {
-            const size_t ib = (((size_t)E * 4) + 255) & ~(size_t)255, db = (((size_t)E * 8) + 255) & ~(size_t)255;
-            g.out.ensure(2 * ib + db, "the synonym pairs", h->stream);
-            g.o_a = (int32_t *)g.out.p;
-            g.o_b = (int32_t *)(g.out.p + ib);
-            g.o_sim = (double *)(g.out.p + 2 * ib);
-            syn_launch_pairs<true>(ctx, grid, g, cand, C, L, TB, threshold, cnt, row_base, g.o_a, g.o_b, g.o_sim);
-        }
-        g.n_pairs = (i64)E;
+        g.n_pairs = (i64)emit_count_scan_fill(
+            ctx, e, true,                                     // (the tiles that leave early write no count)
+            [&](u32 *cnt) { syn_launch_pairs<false>(ctx, grid, g, cand, C, L, TB, threshold, cnt, nullptr, nullptr, nullptr, nullptr); },
+            [&](u64 E) {
+                const size_t ib = (((size_t)E * 4) + 255) & ~(size_t)255, db = (((size_t)E * 8) + 255) & ~(size_t)255;
+                g.out.ensure(2 * ib + db, "the synonym pairs", h->stream);
+                g.o_a = (int32_t *)g.out.p;
+                g.o_b = (int32_t *)(g.out.p + ib);
+                g.o_sim = (double *)(g.out.p + 2 * ib);
+            },
+            [&](u32 *cnt, const u64 *row_base) {
+                syn_launch_pairs<true>(ctx, grid, g, cand, C, L, TB, threshold, cnt, row_base, g.o_a, g.o_b, g.o_sim);
+            });
     }
-    HIP_CHECK(hipEventRecord(g.ev1, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    HIP_CHECK(hipEventElapsedTime(&g.ms, g.ev0, g.ev1));
+    timer.finish();
     g.pairs_valid = true;
     if (n_pairs) *n_pairs = g.n_pairs;
-}
-
-static void syn_reset(east_hip_index *h)
-{
-    SynState *g = h->syn;
-    if (!g) return;
-    g->valid = g->pairs_valid = false;
-    g->n_raw = g->n_distinct = g->n_features = g->longest_row = g->n_pairs = 0;
-    g->W = g->R = 0;
-    g->ms = -1.f;
-    for (DevBuf *b : g->bufs) b->release();
-}
-
-static void syn_destroy(east_hip_index *h)
-{
-    if (!h->syn) return;
-    syn_reset(h);
-    if (h->syn->ev0) (void)hipEventDestroy(h->syn->ev0);
-    if (h->syn->ev1) (void)hipEventDestroy(h->syn->ev1);
-    delete h->syn;
-    h->syn = nullptr;
 }
 
 extern "C" {
@@ -648,7 +611,7 @@ int east_hip_synonyms_fetch(east_hip_handle_t h, int32_t *a, int32_t *b, double 
     });
 }
 
-double east_hip_last_synonyms_ms(east_hip_handle_t h) { return h && h->syn ? (double)h->syn->ms : -1.0; }
+double east_hip_last_synonyms_ms(east_hip_handle_t h) { return consumer_ms<SynState>(h); }
 
 int east_hip_debug_set_synonyms_chunk(int entries)
 {

@@ -27,10 +27,10 @@
 // back are the table's own bytes, read again by the merge kernel (the key has lost the sign of a zero).  The tile length
 // is a test knob (east_hip_debug_set_top_tile); the result does not depend on it.
 //
-// Included at the end of east_hip.hip, behind graph.h, synonyms.h and similarity.h: the host half needs the handle, both
-// resident tables and the similarity matrix (a fourth table source: EAST_HIP_GRAPH_SOURCE_SIMILARITY).
+// The host half is a consumer of the handle (consumer.h); it alone also ranks the similarity matrix, a fourth table source
+// (EAST_HIP_GRAPH_SOURCE_SIMILARITY).
 #pragma once
-#include "common.h"
+#include "consumer.h"
 
 #define TOP_TILE 64u                       // members of a tile at most: one a lane
 #define TOP_LDS_STRIDE 65u                 // 8-byte words from one column's keys to the next (see above)
@@ -179,29 +179,22 @@ __global__ __launch_bounds__(BLOCK) void top_merge_kernel(const u64 *__restrict_
 
 // ============================================================================================================ host ==
 // The ranking's device buffers belong to the handle and to nothing else: not the EASA arena, the cosine buffers or the graph's.
-struct TopState {
-    bool valid = false;
+struct TopState : Consumer {
+    static constexpr int SLOT = east_hip_index::SLOT_TOP;
     u32 S = 0, n = 0;                       // segments, places per segment
     i64 total = 0;                          // the sum of the counts
-    DevBuf table;                           // a host table's copy (east_hip_top_build_host), table_K x table_D while it is whole
-    u32 table_K = 0, table_D = 0;
+    UploadedTable table;                    // a host table's copy (east_hip_top_build_host)
     DevBuf cand, result;
     int32_t *count = nullptr, *index = nullptr;
     double *score = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    float ms = -1.f;
-    DevBuf *bufs[3] = {&table, &cand, &result};
-};
-
-static TopState &top_state(east_hip_index *h)
-{
-    if (!h->top) {
-        h->top = new TopState();
-        HIP_CHECK(hipEventCreate(&h->top->ev0));
-        HIP_CHECK(hipEventCreate(&h->top->ev1));
+    TopState() { bufs = {&table.buf, &cand, &result}; }
+    void clear() override
+    {
+        S = n = 0;
+        total = 0;
+        table.withdraw();
     }
-    return *h->top;
-}
+};
 
 static void top_check(int32_t axis, int32_t n_best, double threshold)
 {
@@ -210,12 +203,13 @@ static void top_check(int32_t axis, int32_t n_best, double threshold)
     if (threshold != threshold) east_throw(EAST_HIP_ERR_INVALID, "ranked keyphrases: the threshold is not a number");
 }
 
-// d_table: K x D doubles on the handle's device, ordered behind everything queued on the handle's stream
-static void top_build(east_hip_index *h, const double *d_table, u32 K, u32 D, int32_t axis, int32_t n_best, double threshold, i64 *out)
+static void top_build(east_hip_index *h, TableRef t, int32_t axis, int32_t n_best, double threshold, i64 *out)
 {
     top_check(axis, n_best, threshold);
+    const double *d_table = t.p;
+    const u32 K = t.K, D = t.D;
     if (K < 1 || D < 1 || K >= 0x7FFFFFF0u || D >= 0x7FFFFFF0u) east_throw(EAST_HIP_ERR_INVALID, "ranked keyphrases: empty score table");
-    TopState &g = top_state(h);
+    TopState &g = consumer_state<TopState>(h);
     g.valid = false;
     g.ms = -1.f;
     g.total = 0;
@@ -245,7 +239,7 @@ static void top_build(east_hip_index *h, const double *d_table, u32 K, u32 D, in
     g.S = S;
     g.n = n;
     std::vector<int32_t> counts(S);
-    HIP_CHECK(hipEventRecord(g.ev0, h->stream));
+    ConsumerTimer timer(h, g);
     if (by_text)
         LAUNCH(ctx, top_select_text_kernel, (u32)grid, d_table, K, D, T, NT, cap, threshold, ckey, cidx, ccnt);
     else
@@ -253,34 +247,10 @@ static void top_build(east_hip_index *h, const double *d_table, u32 K, u32 D, in
     LAUNCH(ctx, top_merge_kernel, S, (const u64 *)ckey, (const u32 *)cidx, (const u32 *)ccnt, NT, cap, n, d_table,
            by_text ? (size_t)1 : (size_t)D, by_text ? (size_t)D : (size_t)1, g.count, g.index, g.score);
     HIP_CHECK(hipMemcpyAsync(counts.data(), g.count, (size_t)S * 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(hipEventRecord(g.ev1, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    HIP_CHECK(hipEventElapsedTime(&g.ms, g.ev0, g.ev1));
+    timer.finish();
     for (int32_t c : counts) g.total += c;
     g.valid = true;
     if (out) { out[0] = (i64)S; out[1] = g.total; }
-}
-
-static void top_reset(east_hip_index *h)
-{
-    TopState *g = h->top;
-    if (!g) return;
-    g->valid = false;
-    g->S = g->n = 0;
-    g->total = 0;
-    g->ms = -1.f;
-    g->table_K = g->table_D = 0;
-    for (DevBuf *b : g->bufs) b->release();
-}
-
-static void top_destroy(east_hip_index *h)
-{
-    if (!h->top) return;
-    top_reset(h);
-    if (h->top->ev0) (void)hipEventDestroy(h->top->ev0);
-    if (h->top->ev1) (void)hipEventDestroy(h->top->ev1);
-    delete h->top;
-    h->top = nullptr;
 }
 
 extern "C" {
@@ -290,25 +260,8 @@ int east_hip_top_build_resident(east_hip_handle_t h, int32_t source, int32_t axi
     return guarded([&] {
         if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
         use_device(h);
-        if (source == EAST_HIP_GRAPH_SOURCE_AST) {
-            if (!h->built || !h->table_scored)
-                east_throw(EAST_HIP_ERR_NOT_BUILT, "ranked keyphrases: no score table is resident (score the keyphrases first)");
-            top_build(h, h->table, h->n_kp, h->n_docs, axis, n, threshold, out);
-        } else if (source == EAST_HIP_GRAPH_SOURCE_COSINE) {
-            if (!h->cos || !h->cos->built || !h->cos->table_valid)
-                east_throw(EAST_HIP_ERR_NOT_BUILT, "ranked keyphrases: no cosine score table is resident (score the keyphrases first)");
-            top_build(h, h->cos->table, h->cos->table_K, h->cos->n_docs, axis, n, threshold, out);
-        } else if (source == EAST_HIP_GRAPH_SOURCE_UPLOADED) {
-            if (!h->top || !h->top->table_K)
-                east_throw(EAST_HIP_ERR_NOT_BUILT, "ranked keyphrases: no host table has been uploaded to this handle");
-            top_build(h, (const double *)h->top->table.p, h->top->table_K, h->top->table_D, axis, n, threshold, out);
-        } else if (source == EAST_HIP_GRAPH_SOURCE_SIMILARITY) {
-            if (!h->sim || !h->sim->valid)
-                east_throw(EAST_HIP_ERR_NOT_BUILT, "ranked keyphrases: no similarity matrix has been built on this handle");
-            top_build(h, h->sim->matrix, h->sim->M, h->sim->M, axis, n, threshold, out);
-        } else {
-            east_throw(EAST_HIP_ERR_INVALID, "ranked keyphrases: unknown table source");
-        }
+        const TopState *g = consumer_peek<TopState>(h);
+        top_build(h, resolve_table(h, source, g ? &g->table : nullptr, "ranked keyphrases", true), axis, n, threshold, out);
     });
 }
 
@@ -320,16 +273,9 @@ int east_hip_top_build_host(east_hip_handle_t h, const double *table, int32_t n_
         if (!table || n_keyphrases < 1 || n_docs < 1) east_throw(EAST_HIP_ERR_INVALID, "ranked keyphrases: null or empty score table");
         top_check(axis, n, threshold);                        // (before the upload: a refused call leaves the uploaded table alone)
         use_device(h);
-        TopState &g = top_state(h);
+        TopState &g = consumer_state<TopState>(h);
         g.valid = false;
-        g.table_K = g.table_D = 0;
-        const size_t bytes = (size_t)n_keyphrases * (size_t)n_docs * 8;
-        g.table.ensure(bytes, "the ranking's score table", h->stream);
-        HIP_CHECK(hipMemcpyAsync(g.table.p, table, bytes, hipMemcpyHostToDevice, h->stream));
-        HIP_CHECK(hipStreamSynchronize(h->stream));
-        g.table_K = (u32)n_keyphrases;
-        g.table_D = (u32)n_docs;
-        top_build(h, (const double *)g.table.p, (u32)n_keyphrases, (u32)n_docs, axis, n, threshold, out);
+        top_build(h, g.table.upload(h, table, (u32)n_keyphrases, (u32)n_docs, "the ranking's score table"), axis, n, threshold, out);
     });
 }
 
@@ -337,9 +283,10 @@ int east_hip_top_fetch(east_hip_handle_t h, int32_t *count, int32_t *index, doub
 {
     return guarded([&] {
         if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
-        if (!h->top || !h->top->valid) east_throw(EAST_HIP_ERR_NOT_BUILT, "no keyphrase ranking has been built on this handle");
+        TopState *gp = consumer_peek<TopState>(h);
+        if (!gp || !gp->valid) east_throw(EAST_HIP_ERR_NOT_BUILT, "no keyphrase ranking has been built on this handle");
         use_device(h);
-        TopState &g = *h->top;
+        TopState &g = *gp;
         const size_t places = (size_t)g.S * g.n;
         if (count) HIP_CHECK(hipMemcpyAsync(count, g.count, (size_t)g.S * 4, hipMemcpyDeviceToHost, h->stream));
         if (index) HIP_CHECK(hipMemcpyAsync(index, g.index, places * 4, hipMemcpyDeviceToHost, h->stream));
@@ -348,7 +295,7 @@ int east_hip_top_fetch(east_hip_handle_t h, int32_t *count, int32_t *index, doub
     });
 }
 
-double east_hip_last_top_ms(east_hip_handle_t h) { return h && h->top ? (double)h->top->ms : -1.0; }
+double east_hip_last_top_ms(east_hip_handle_t h) { return consumer_ms<TopState>(h); }
 
 int east_hip_debug_set_top_tile(int members)
 {

@@ -176,13 +176,14 @@ class KeyphraseGraph(object):
         return result if result is NotImplemented else not result
 
 
-def _device_graph_applies(measure, texts, synonimizer):
-    """Whether keyphrases_graph builds the graph on the device: the measure scores into a table that stays there
-    (`relevance_graph`; None counts as absent: the measures over several devices or ranks), no synonimizer, distinct
-    text titles, and EAST_HIP_GRAPH is not `host` (the precedent: EAST_HIP_TEXT_PREP=host)."""
+def _device_applies(measure, texts, synonimizer, method, env):
+    """Whether an application runs its main loop on the device: the measure scores into a table that stays there (it has
+    `method`: relevance_graph, relevance_top or relevance_similar; None counts as absent: the measures over several
+    devices or ranks), no synonimizer, distinct text titles, and the environment variable `env` (EAST_HIP_GRAPH,
+    EAST_HIP_TOP, EAST_HIP_SIMILAR) is not `host` (the precedent: EAST_HIP_TEXT_PREP=host)."""
     titles = list(texts.keys())
-    return (getattr(measure, "relevance_graph", None) is not None and not synonimizer
-            and len(set(titles)) == len(titles) and os.environ.get("EAST_HIP_GRAPH", "device") != "host")
+    return (getattr(measure, method, None) is not None and not synonimizer
+            and len(set(titles)) == len(titles) and os.environ.get(env, "device") != "host")
 
 
 def _graph_on_device(keyphrases, texts, referral_confidence, relevance_threshold, support_threshold, measure, language):
@@ -209,7 +210,7 @@ def keyphrases_graph_arrays(keyphrases, texts, referral_confidence=0.6, relevanc
     formatters take it as it is).  Built on the device where keyphrases_graph builds it there; elsewhere the host path's
     dict, wrapped, so that a caller gets one type."""
     measure = similarity_measure or relevance.ASTRelevanceMeasure()
-    if _device_graph_applies(measure, texts, synonimizer):
+    if _device_applies(measure, texts, synonimizer, "relevance_graph", "EAST_HIP_GRAPH"):
         graph = _graph_on_device(keyphrases, texts, referral_confidence, relevance_threshold, support_threshold, measure,
                                  language)
         if graph is not None:
@@ -237,7 +238,7 @@ def keyphrases_graph(keyphrases, texts, referral_confidence=0.6, relevance_thres
     in every other case on the host, below.  The graph is the same either way.
     """
     measure = similarity_measure or relevance.ASTRelevanceMeasure()
-    if _device_graph_applies(measure, texts, synonimizer):
+    if _device_applies(measure, texts, synonimizer, "relevance_graph", "EAST_HIP_GRAPH"):
         graph = _graph_on_device(keyphrases, texts, referral_confidence, relevance_threshold, support_threshold, measure,
                                  language)
         if graph is not None:
@@ -306,13 +307,34 @@ TOP_MAX_N = 1024
 _TOP_AXES = ("text", "keyphrase")
 
 
-def _device_top_applies(measure, texts, synonimizer):
-    """Whether keyphrases_top selects on the device: the measure scores into a table that stays there (`relevance_top`;
-    None counts as absent: the measures over several devices or ranks), no synonimizer, distinct text titles, and
-    EAST_HIP_TOP is not `host` (the precedent: EAST_HIP_GRAPH)."""
-    titles = list(texts.keys())
-    return (getattr(measure, "relevance_top", None) is not None and not synonimizer
-            and len(set(titles)) == len(titles) and os.environ.get("EAST_HIP_TOP", "device") != "host")
+def _ranking_arguments(who, by, n, threshold, what):
+    """The (by, n, threshold) of keyphrases_top and keyphrases_similar, checked: `who` is the caller's name in the messages,
+    `what` its name for the threshold.  -> (axis, n, threshold)"""
+    if by not in _TOP_AXES:
+        raise ValueError("%s: by must be 'text' or 'keyphrase', not %r" % (who, by))
+    if isinstance(n, bool) or int(n) != n or not 1 <= n <= TOP_MAX_N:
+        raise ValueError("%s: n must be an integer from 1 to %d, not %r" % (who, TOP_MAX_N, n))
+    threshold = -np.inf if threshold is None else float(threshold)
+    if threshold != threshold:
+        raise ValueError("%s: the %s threshold is not a number" % (who, what))
+    return _TOP_AXES.index(by), int(n), threshold
+
+
+def _score_array(table, wanted, titles):
+    """What keyphrases_table returned, a ScoreTable or a plain dict, as (the K x D array of the `wanted` keyphrases, the
+    titles of its columns).  A plain dict: a repeated title holds its last column; a rank that does not print has none."""
+    if isinstance(table, ScoreTable):
+        scores = np.asarray(table.scores, dtype=np.float64)
+    else:
+        titles = [title for title in titles if title in table[wanted[0]]]
+        scores = np.array([[table[kp][title] for title in titles] for kp in wanted], dtype=np.float64).reshape(len(wanted), -1)
+    return scores, titles[:scores.shape[1]]
+
+
+def _top_lists(found):
+    """hip_backend.TopArrays -> per segment a list of (member, score), as _top_select gives it."""
+    return [list(zip(index[:count], score[:count]))
+            for count, index, score in zip(found.count.tolist(), found.index.tolist(), found.score.tolist())]
 
 
 def _top_select(scores, axis, n, threshold):
@@ -350,47 +372,23 @@ def keyphrases_top(keyphrases, texts, n=10, by="text", relevance_threshold=None,
     `relevance_top`, no synonimizer is given, the text titles are distinct and EAST_HIP_TOP is not `host`; in every other
     case on the host, from keyphrases_table's array.  The result is the same either way.
     """
-    if by not in _TOP_AXES:
-        raise ValueError("keyphrases_top: by must be 'text' or 'keyphrase', not %r" % (by,))
-    if isinstance(n, bool) or int(n) != n or not 1 <= n <= TOP_MAX_N:
-        raise ValueError("keyphrases_top: n must be an integer from 1 to %d, not %r" % (TOP_MAX_N, n))
-    n = int(n)
-    threshold = -np.inf if relevance_threshold is None else float(relevance_threshold)
-    if threshold != threshold:
-        raise ValueError("keyphrases_top: the relevance threshold is not a number")
-    axis = _TOP_AXES.index(by)
+    axis, n, threshold = _ranking_arguments("keyphrases_top", by, n, relevance_threshold, "relevance")
     measure = similarity_measure or relevance.ASTRelevanceMeasure()
     titles = list(texts.keys())
     wanted = [kp for kp in dict.fromkeys(keyphrases) if kp]              # applications.py:44-45
     if not wanted:
         return {title: [] for title in titles} if axis == 0 else {}
 
-    if _device_top_applies(measure, texts, synonimizer):
+    if _device_applies(measure, texts, synonimizer, "relevance_top", "EAST_HIP_TOP"):
         measure.set_text_collection(list(texts.values()), language)
-        found = measure.relevance_top([utils.prepare_text(kp) for kp in wanted], axis, n, threshold)
-        lists = [list(zip(index[:count], score[:count]))
-                 for count, index, score in zip(found.count.tolist(), found.index.tolist(), found.score.tolist())]
+        lists = _top_lists(measure.relevance_top([utils.prepare_text(kp) for kp in wanted], axis, n, threshold))
     else:
-        table = keyphrases_table(wanted, texts, measure, synonimizer, language)
-        if isinstance(table, ScoreTable):
-            scores = np.asarray(table.scores, dtype=np.float64)
-        else:                                                            # (a plain dict: a repeated title holds its last column;
-            titles = [title for title in titles if title in table[wanted[0]]]       # a rank that does not print has no columns)
-            scores =np.array([[table[kp][title] for title in titles] for kp in wanted], dtype=np.float64).reshape(len(wanted), -1)
-        titles = titles[:scores.shape[1]]
+        scores, titles = _score_array(keyphrases_table(wanted, texts, measure, synonimizer, language), wanted, titles)
         lists = _top_select(scores, axis, n, threshold)
     return _top_named(lists, titles, wanted) if axis == 0 else _top_named(lists, wanted, titles)
 
 
 # ---- similar texts and keyphrases ----------------------------------------------------------------------------------------
-def _device_similar_applies(measure, texts, synonimizer):
-    """Whether keyphrases_similar runs on the device: the conditions of keyphrases_top (`relevance_similar` in the place of
-    `relevance_top`), and EAST_HIP_SIMILAR is not `host`."""
-    titles = list(texts.keys())
-    return (getattr(measure, "relevance_similar", None) is not None and not synonimizer
-            and len(set(titles)) == len(titles) and os.environ.get("EAST_HIP_SIMILAR", "device") != "host")
-
-
 def _similarity_matrix(scores, axis):
     """The contract of include/east_hip.h ("Similar texts and keyphrases") in numpy: the profiles are the columns (axis 0)
     or the rows (axis 1) of the K x D array; S[a][b] = G_ab / (sqrt(q_a) * sqrt(q_b)), +0.0 where a q is zero, NaN on the
@@ -429,34 +427,18 @@ def keyphrases_similar(keyphrases, texts, n=10, by="text", similarity_threshold=
     name the same members in the same order wherever neighbouring similarities lie further apart than twice that -- they
     are NOT promised to be the same bytes.
     """
-    if by not in _TOP_AXES:
-        raise ValueError("keyphrases_similar: by must be 'text' or 'keyphrase', not %r" % (by,))
-    if isinstance(n, bool) or int(n) != n or not 1 <= n <= TOP_MAX_N:
-        raise ValueError("keyphrases_similar: n must be an integer from 1 to %d, not %r" % (TOP_MAX_N, n))
-    n = int(n)
-    threshold = -np.inf if similarity_threshold is None else float(similarity_threshold)
-    if threshold != threshold:
-        raise ValueError("keyphrases_similar: the similarity threshold is not a number")
-    axis = _TOP_AXES.index(by)
+    axis, n, threshold = _ranking_arguments("keyphrases_similar", by, n, similarity_threshold, "similarity")
     measure = similarity_measure or relevance.ASTRelevanceMeasure()
     titles = list(texts.keys())
     wanted = [kp for kp in dict.fromkeys(keyphrases) if kp]              # applications.py:44-45
     if not wanted:
         return {title: [] for title in titles} if axis == 0 else {}
 
-    if _device_similar_applies(measure, texts, synonimizer):
+    if _device_applies(measure, texts, synonimizer, "relevance_similar", "EAST_HIP_SIMILAR"):
         measure.set_text_collection(list(texts.values()), language)
-        found = measure.relevance_similar([utils.prepare_text(kp) for kp in wanted], axis, n, threshold)
-        lists = [list(zip(index[:count], score[:count]))
-                 for count, index, score in zip(found.count.tolist(), found.index.tolist(), found.score.tolist())]
+        lists = _top_lists(measure.relevance_similar([utils.prepare_text(kp) for kp in wanted], axis, n, threshold))
     else:
-        table = keyphrases_table(wanted, texts, measure, synonimizer, language)
-        if isinstance(table, ScoreTable):
-            scores = np.asarray(table.scores, dtype=np.float64)
-        else:                                                            # (as keyphrases_top reads a plain dict)
-            titles = [title for title in titles if title in table[wanted[0]]]
-            scores = np.array([[table[kp][title] for title in titles] for kp in wanted], dtype=np.float64).reshape(len(wanted), -1)
-        titles = titles[:scores.shape[1]]
+        scores, titles = _score_array(keyphrases_table(wanted, texts, measure, synonimizer, language), wanted, titles)
         lists = _top_select(_similarity_matrix(scores, axis), 1, n, threshold)
     names = titles if axis == 0 else wanted
     return _top_named(lists, names, names)

@@ -310,20 +310,25 @@ class GraphArrays(object):
         self.edge_source, self.edge_target, self.edge_shared = edge_source, edge_target, edge_shared
 
 
+def _table_build(resident, host, h, source, table, noun, *args):
+    """One *_build_resident / *_build_host pair: resident(h, source, *args) when table is None, else host(h, table, K, D,
+    *args) of the K x D host array `table`; noun names the consumer where the array is refused."""
+    if table is None:
+        _check(resident(h, int(source), *args))
+        return
+    table = np.ascontiguousarray(table, dtype=np.float64)
+    if table.ndim != 2:
+        raise exceptions.HipBackendError(reason="the score table of %s is a K x D array" % noun)
+    _check(host(h, _ptr(table, _c_dblp), table.shape[0], table.shape[1], *args))
+
+
 def _graph_build(lib, h, source, table, rows, relevance_threshold, support_threshold, referral_confidence):
     """east_hip_graph_build_resident (table None) / _host, then east_hip_graph_fetch."""
     rows = np.ascontiguousarray(rows, dtype=np.int32)
     counts = np.zeros(2, dtype=np.int64)
-    thresholds = (float(relevance_threshold), float(support_threshold), float(referral_confidence))
-    if table is None:
-        _check(lib.east_hip_graph_build_resident(h, int(source), _ptr(rows, _c_i32p), rows.size, *thresholds,
-                                                 _ptr(counts, _c_i64p)))
-    else:
-        table = np.ascontiguousarray(table, dtype=np.float64)
-        if table.ndim != 2:
-            raise exceptions.HipBackendError(reason="the score table of a keyphrase graph is a K x D array")
-        _check(lib.east_hip_graph_build_host(h, _ptr(table, _c_dblp), table.shape[0], table.shape[1], _ptr(rows, _c_i32p),
-                                             rows.size, *thresholds, _ptr(counts, _c_i64p)))
+    _table_build(lib.east_hip_graph_build_resident, lib.east_hip_graph_build_host, h, source, table, "a keyphrase graph",
+                 _ptr(rows, _c_i32p), rows.size, float(relevance_threshold), float(support_threshold),
+                 float(referral_confidence), _ptr(counts, _c_i64p))
     out = GraphArrays(np.empty(rows.size, dtype=np.int32), np.empty(int(counts[0]), dtype=np.int32),
                       *(np.empty(int(counts[1]), dtype=np.int32) for _ in range(3)))
     _check(lib.east_hip_graph_fetch(h, *(_ptr(getattr(out, name), _c_i32p) for name in GraphArrays.__slots__)))
@@ -344,14 +349,8 @@ class TopArrays(object):
 def _top_build(lib, h, source, table, axis, n, threshold):
     """east_hip_top_build_resident (table None) / _host, then east_hip_top_fetch."""
     out = np.zeros(2, dtype=np.int64)
-    if table is None:
-        _check(lib.east_hip_top_build_resident(h, int(source), int(axis), int(n), float(threshold), _ptr(out, _c_i64p)))
-    else:
-        table = np.ascontiguousarray(table, dtype=np.float64)
-        if table.ndim != 2:
-            raise exceptions.HipBackendError(reason="the score table of a ranking is a K x D array")
-        _check(lib.east_hip_top_build_host(h, _ptr(table, _c_dblp), table.shape[0], table.shape[1], int(axis), int(n),
-                                           float(threshold), _ptr(out, _c_i64p)))
+    _table_build(lib.east_hip_top_build_resident, lib.east_hip_top_build_host, h, source, table, "a ranking", int(axis),
+                 int(n), float(threshold), _ptr(out, _c_i64p))
     S = int(out[0])
     found = TopArrays(np.empty(S, dtype=np.int32), np.empty((S, int(n)), dtype=np.int32), np.empty((S, int(n)), dtype=np.float64))
     _check(lib.east_hip_top_fetch(h, _ptr(found.count, _c_i32p), _ptr(found.index, _c_i32p), _ptr(found.score, _c_dblp)))
@@ -361,14 +360,8 @@ def _top_build(lib, h, source, table, axis, n, threshold):
 def _similarity_build(lib, h, source, table, axis):
     """east_hip_similarity_build_resident (table None) / _host -> (M, L)."""
     out = np.zeros(2, dtype=np.int64)
-    if table is None:
-        _check(lib.east_hip_similarity_build_resident(h, int(source), int(axis), _ptr(out, _c_i64p)))
-    else:
-        table = np.ascontiguousarray(table, dtype=np.float64)
-        if table.ndim != 2:
-            raise exceptions.HipBackendError(reason="the score table of a similarity matrix is a K x D array")
-        _check(lib.east_hip_similarity_build_host(h, _ptr(table, _c_dblp), table.shape[0], table.shape[1], int(axis),
-                                                  _ptr(out, _c_i64p)))
+    _table_build(lib.east_hip_similarity_build_resident, lib.east_hip_similarity_build_host, h, source, table,
+                 "a similarity matrix", int(axis), _ptr(out, _c_i64p))
     return int(out[0]), int(out[1])
 
 
@@ -379,8 +372,71 @@ def _similarity_fetch(lib, h, M):
     return matrix, norm2
 
 
-class HipIndex(object):
+class _ResidentTableConsumers(object):
+    """The graph, the ranking and the similarity of the score table that lies on the device of a handle (self._lib,
+    self._h): the table `_table_source` names -- the AST table of a HipIndex, the cosine table of a HipCosineIndex."""
+
+    _table_source = None
+
+    @property
+    def _sim_holder(self):
+        """The HipIndex that remembers the size of the handle's last similarity matrix."""
+        return self
+
+    # -- keyphrase graph -------------------------------------------------------
+    def graph(self, rows, relevance_threshold, support_threshold, referral_confidence):
+        """The keyphrase graph of the score table the last score call left on the device (rows[p] = the table row of node
+        position p) -> GraphArrays."""
+        return _graph_build(self._lib, self._h, self._table_source, None, rows, relevance_threshold, support_threshold,
+                            referral_confidence)
+
+    @property
+    def last_graph_ms(self):
+        return float(self._lib.east_hip_last_graph_ms(self._h))
+
+    # -- ranked keyphrases -----------------------------------------------------
+    def top(self, axis, n, threshold=-np.inf):
+        """The n best members of every segment of the score table the last score call left on the device (axis
+        TOP_BY_TEXT: per text its keyphrases, TOP_BY_KEYPHRASE: per keyphrase its texts) -> TopArrays."""
+        return _top_build(self._lib, self._h, self._table_source, None, axis, n, threshold)
+
+    @property
+    def last_top_ms(self):
+        return float(self._lib.east_hip_last_top_ms(self._h))
+
+    # -- similar texts and keyphrases --------------------------------------------
+    def _similarity(self, source, table, axis):
+        self._sim_holder._sim_M, L = _similarity_build(self._lib, self._h, source, table, axis)
+        return self._sim_holder._sim_M, L
+
+    def similarity(self, axis):
+        """The cosine of every two profiles of the score table the last score call left on the device (axis TOP_BY_TEXT:
+        the texts' columns, TOP_BY_KEYPHRASE: the keyphrases' rows); the M x M matrix stays on the device -> (M, L)."""
+        return self._similarity(self._table_source, None, axis)
+
+    def similarity_matrix(self):
+        """The last similarity matrix of this handle and the squared norms of its profiles -> (matrix[M, M], norm2[M])."""
+        return _similarity_fetch(self._lib, self._h, getattr(self._sim_holder, "_sim_M", 0))
+
+    def similar(self, axis, n, threshold=-np.inf):
+        """similarity(axis), then the n most similar other members of every member (the ranking of the matrix by row: the
+        NaN on its diagonal is never eligible) -> TopArrays.  It is the handle's one ranking: it replaces top()'s."""
+        self.similarity(axis)
+        return self.rank_similarity(n, threshold)
+
+    def rank_similarity(self, n, threshold=-np.inf):
+        """Another ranking of the last similarity matrix (other n, other threshold): no new matrix."""
+        return _top_build(self._lib, self._h, GRAPH_SOURCE_SIMILARITY, None, TOP_BY_KEYPHRASE, n, threshold)
+
+    @property
+    def last_similarity_ms(self):
+        return float(self._lib.east_hip_last_similarity_ms(self._h))
+
+
+class HipIndex(_ResidentTableConsumers):
     """One device-resident batch of annotated suffix arrays (an AST shard)."""
+
+    _table_source = GRAPH_SOURCE_AST
 
     def __init__(self, device=None, reserve_symbols=0):
         self._lib = load()
@@ -597,13 +653,7 @@ class HipIndex(object):
     def last_score_ms(self):
         return float(self._lib.east_hip_last_score_ms(self._h))
 
-    # -- keyphrase graph -------------------------------------------------------
-    def graph(self, rows, relevance_threshold, support_threshold, referral_confidence):
-        """The keyphrase graph of the score table the last score call left on the device (rows[p] = the table row of node
-        position p) -> GraphArrays."""
-        return _graph_build(self._lib, self._h, GRAPH_SOURCE_AST, None, rows, relevance_threshold, support_threshold,
-                            referral_confidence)
-
+    # -- tables from elsewhere: each consumer keeps an uploaded copy of its own ------
     def graph_from_table(self, table, rows, relevance_threshold, support_threshold, referral_confidence):
         """The same from a K x D host array, which is uploaded first (tables from elsewhere, tests)."""
         return _graph_build(self._lib, self._h, None, table, rows, relevance_threshold, support_threshold,
@@ -614,16 +664,6 @@ class HipIndex(object):
         return _graph_build(self._lib, self._h, GRAPH_SOURCE_UPLOADED, None, rows, relevance_threshold, support_threshold,
                             referral_confidence)
 
-    @property
-    def last_graph_ms(self):
-        return float(self._lib.east_hip_last_graph_ms(self._h))
-
-    # -- ranked keyphrases -----------------------------------------------------
-    def top(self, axis, n, threshold=-np.inf):
-        """The n best members of every segment of the score table the last score call left on the device (axis
-        TOP_BY_TEXT: per text its keyphrases, TOP_BY_KEYPHRASE: per keyphrase its texts) -> TopArrays."""
-        return _top_build(self._lib, self._h, GRAPH_SOURCE_AST, None, axis, n, threshold)
-
     def top_from_table(self, table, axis, n, threshold=-np.inf):
         """The same from a K x D host array, which is uploaded first (tables from elsewhere, tests)."""
         return _top_build(self._lib, self._h, None, table, axis, n, threshold)
@@ -632,51 +672,22 @@ class HipIndex(object):
         """Another ranking of the table top_from_table left on the device: no upload."""
         return _top_build(self._lib, self._h, GRAPH_SOURCE_UPLOADED, None, axis, n, threshold)
 
-    @property
-    def last_top_ms(self):
-        return float(self._lib.east_hip_last_top_ms(self._h))
-
-    # -- similar texts and keyphrases --------------------------------------------
-    def similarity(self, axis):
-        """The cosine of every two profiles of the score table the last score call left on the device (axis TOP_BY_TEXT:
-        the texts' columns, TOP_BY_KEYPHRASE: the keyphrases' rows); the M x M matrix stays on the device -> (M, L)."""
-        self._sim_M, L = _similarity_build(self._lib, self._h, GRAPH_SOURCE_AST, None, axis)
-        return self._sim_M, L
-
     def similarity_from_table(self, table, axis):
         """The same from a K x D host array, which is uploaded first (tables from elsewhere, tests)."""
-        self._sim_M, L = _similarity_build(self._lib, self._h, None, table, axis)
-        return self._sim_M, L
+        return self._similarity(None, table, axis)
 
     def similarity_from_uploaded(self, axis):
         """Another matrix (the other axis) of the table similarity_from_table left on the device: no upload."""
-        self._sim_M, L = _similarity_build(self._lib, self._h, GRAPH_SOURCE_UPLOADED, None, axis)
-        return self._sim_M, L
-
-    def similarity_matrix(self):
-        """The last similarity matrix of this handle and the squared norms of its profiles -> (matrix[M, M], norm2[M])."""
-        return _similarity_fetch(self._lib, self._h, getattr(self, "_sim_M", 0))
-
-    def similar(self, axis, n, threshold=-np.inf):
-        """similarity(axis), then the n most similar other members of every member (the ranking of the matrix by row: the
-        NaN on its diagonal is never eligible) -> TopArrays.  It is the handle's one ranking: it replaces top()'s."""
-        self.similarity(axis)
-        return self.rank_similarity(n, threshold)
-
-    def rank_similarity(self, n, threshold=-np.inf):
-        """Another ranking of the last similarity matrix (other n, other threshold): no new matrix."""
-        return _top_build(self._lib, self._h, GRAPH_SOURCE_SIMILARITY, None, TOP_BY_KEYPHRASE, n, threshold)
-
-    @property
-    def last_similarity_ms(self):
-        return float(self._lib.east_hip_last_similarity_ms(self._h))
+        return self._similarity(GRAPH_SOURCE_UPLOADED, None, axis)
 
 
-class HipCosineIndex(object):
+class HipCosineIndex(_ResidentTableConsumers):
     """The cosine measure's term index (include/east_hip.h, "The cosine relevance measure"): the postings (term, document,
     count) of a whole collection, built on the device from raw texts.  It lives in the handle of a HipIndex: its own one
     (device choice and handle pool as HipIndex) unless `index` is given -- then it shares that handle, whose EASA index it
     leaves alone, and closing is the owner's business."""
+
+    _table_source = GRAPH_SOURCE_COSINE          # graph(), top(), similarity(): of the table the last score_table left
 
     def __init__(self, device=None, index=None):
         self._owner = index is None
@@ -689,6 +700,10 @@ class HipCosineIndex(object):
     @property
     def _h(self):
         return self.index._h
+
+    @property
+    def _sim_holder(self):
+        return self.index
 
     def close(self):
         if self._owner:
@@ -749,42 +764,6 @@ class HipCosineIndex(object):
         _check(self._lib.east_hip_cosine_score_table(self._h, _ptr(q_ids, _c_i32p), _ptr(q_offsets, _c_i64p), q_ids.size, K,
                                                      1 if tfidf else 0, _ptr(out, _c_dblp) if fetch else None))
         return out
-
-    def graph(self, rows, relevance_threshold, support_threshold, referral_confidence):
-        """The keyphrase graph of the table the last score_table left on the device -> GraphArrays (HipIndex.graph)."""
-        return _graph_build(self._lib, self._h, GRAPH_SOURCE_COSINE, None, rows, relevance_threshold, support_threshold,
-                            referral_confidence)
-
-    @property
-    def last_graph_ms(self):
-        return float(self._lib.east_hip_last_graph_ms(self._h))
-
-    def top(self, axis, n, threshold=-np.inf):
-        """The n best members of every segment of the table the last score_table left on the device -> TopArrays
-        (HipIndex.top)."""
-        return _top_build(self._lib, self._h, GRAPH_SOURCE_COSINE, None, axis, n, threshold)
-
-    @property
-    def last_top_ms(self):
-        return float(self._lib.east_hip_last_top_ms(self._h))
-
-    def similarity(self, axis):
-        """The similarity matrix of the table the last score_table left on the device -> (M, L) (HipIndex.similarity)."""
-        M, L = _similarity_build(self._lib, self._h, GRAPH_SOURCE_COSINE, None, axis)
-        self.index._sim_M = M
-        return M, L
-
-    def similarity_matrix(self):
-        return self.index.similarity_matrix()
-
-    def similar(self, axis, n, threshold=-np.inf):
-        """similarity(axis), then the n most similar other members of every member -> TopArrays (HipIndex.similar)."""
-        self.similarity(axis)
-        return self.index.rank_similarity(n, threshold)
-
-    @property
-    def last_similarity_ms(self):
-        return self.index.last_similarity_ms
 
 
 SYNONYMS_INFO_FIELDS = ("raw_triples", "distinct_triples", "words", "relations", "features", "longest_row")

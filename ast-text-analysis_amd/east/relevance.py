@@ -207,29 +207,28 @@ class ASTRelevanceMeasure(RelevanceMeasure):
         qs, qo = hip_backend.pack_queries(queries)
         return self.index.score_table(qs, qo, self.normalized)
 
-    # HOT LOOP C (applications.py:59-149) on the device, from the table the score call leaves there
-    def relevance_graph(self, prepared_keyphrases, rows, referral_confidence, relevance_threshold, support_threshold):
-        """The keyphrase graph of K prepared keyphrases: they are scored as relevance_table scores them, the K x D table
-        stays on the device and the graph is built from it there.  rows[p] = the keyphrase (0 .. K - 1) of node position
-        p.  -> hip_backend.GraphArrays."""
+    def _score_resident(self, prepared_keyphrases):
+        """Scores K prepared keyphrases as relevance_table does and leaves the K x D table on the device."""
         queries = [kp.replace(" ", "") for kp in prepared_keyphrases]
         if not all(queries):
             raise ZeroDivisionError("float division by zero")
         qs, qo = hip_backend.pack_queries(queries)
         self.index.set_keyphrases(qs, qo)
         self.index.score_resident(self.normalized)
+
+    # HOT LOOP C (applications.py:59-149) on the device, from the table the score call leaves there
+    def relevance_graph(self, prepared_keyphrases, rows, referral_confidence, relevance_threshold, support_threshold):
+        """The keyphrase graph of K prepared keyphrases: they are scored as relevance_table scores them, the K x D table
+        stays on the device and the graph is built from it there.  rows[p] = the keyphrase (0 .. K - 1) of node position
+        p.  -> hip_backend.GraphArrays."""
+        self._score_resident(prepared_keyphrases)
         return self.index.graph(rows, relevance_threshold, support_threshold, referral_confidence)
 
     def relevance_top(self, prepared_keyphrases, axis, n, threshold=-np.inf):
         """The n best keyphrases of every text (axis hip_backend.TOP_BY_TEXT) or the n best texts of every keyphrase
         (TOP_BY_KEYPHRASE): the keyphrases are scored as relevance_graph scores them, the K x D table stays on the device
         and the selection runs on it there.  -> hip_backend.TopArrays."""
-        queries = [kp.replace(" ", "") for kp in prepared_keyphrases]
-        if not all(queries):
-            raise ZeroDivisionError("float division by zero")
-        qs, qo = hip_backend.pack_queries(queries)
-        self.index.set_keyphrases(qs, qo)
-        self.index.score_resident(self.normalized)
+        self._score_resident(prepared_keyphrases)
         return self.index.top(axis, n, threshold)
 
     def relevance_similar(self, prepared_keyphrases, axis, n, threshold=-np.inf):
@@ -237,12 +236,7 @@ class ASTRelevanceMeasure(RelevanceMeasure):
         score table) or the n most similar other keyphrases of every keyphrase (TOP_BY_KEYPHRASE: of two rows).  The
         keyphrases are scored exactly as relevance_top scores them; the table, the M x M similarity matrix and its ranking
         stay on the device (csrc/similarity.h).  -> hip_backend.TopArrays."""
-        queries = [kp.replace(" ", "") for kp in prepared_keyphrases]
-        if not all(queries):
-            raise ZeroDivisionError("float division by zero")
-        qs, qo = hip_backend.pack_queries(queries)
-        self.index.set_keyphrases(qs, qo)
-        self.index.score_resident(self.normalized)
+        self._score_resident(prepared_keyphrases)
         return self.index.similar(axis, n, threshold)
 
 
