@@ -444,7 +444,11 @@ class HipIndex(_ResidentTableConsumers):
         self.device = default_device() if device is None else int(device)
         pooled = _handle_pool.get(self.device)
         if pooled and not reserve_symbols:
-            self._h = pooled.pop()               # a recycled handle (reset: behaves like a new one)
+            # a recycled handle.  east_hip_reset gives it the state of a new one but for the build hints (alphabet size,
+            # "the window sort took it"): its first build speculates on the previous owner's text as a second build on one
+            # handle would.  Results are the same; the plan may differ -- without the planning sample a small repetitive
+            # input is not recognised as such (tests/test_gpu_score_exhaustive.py: _Knobs).
+            self._h = pooled.pop()
         else:
             _check(self._lib.east_hip_create(self.device, int(reserve_symbols), ctypes.byref(self._h)))
         self.n_docs = 0
