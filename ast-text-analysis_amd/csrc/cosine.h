@@ -616,23 +616,10 @@ static void cos_doc_order(Ctx &ctx, CosUnits &U, u32 D)
 
 static size_t cos_align(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
-static void cos_build(east_hip_index *h, const uint8_t *bytes, i64 n_bytes64, const i64 *text_offsets, int32_t n_docs,
-                      const uint8_t *cp_class, const u32 *cp_upper, const u32 *word_hi, const u32 *digit_hi,
-                      const u32 *hi_upper_from, const u32 *hi_upper_to, int32_t n_hi_upper, const uint8_t *const *texts,
-                      const u32 *stop_cps, const i64 *stop_offsets, int32_t n_stop)
+static void cos_build(east_hip_index *h, HostTexts in, const UnicodeTablesHost &tables, const u32 *stop_cps, const i64 *stop_offsets, int32_t n_stop)
 {
     if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
-    if ((!bytes && !texts) || !text_offsets || !cp_class || !cp_upper || !word_hi || !digit_hi || n_docs < 1 || n_hi_upper < 0 ||
-        (n_hi_upper > 0 && (!hi_upper_from || !hi_upper_to)))
-        east_throw(EAST_HIP_ERR_INVALID, "null argument or no documents");
-    if (n_bytes64 < n_docs || n_bytes64 >= (i64)0x7FFFFFF0) east_throw(EAST_HIP_ERR_INVALID, "total bytes out of range");
-    if (text_offsets[0] != 0 || text_offsets[n_docs] != n_bytes64)
-        east_throw(EAST_HIP_ERR_INVALID, "text_offsets must start at 0 and end at the total");
-    for (int32_t d = 0; d < n_docs; d++) {
-        if (text_offsets[d + 1] <= text_offsets[d]) east_throw(EAST_HIP_ERR_INVALID, "text_offsets must increase");
-        if (texts ? (text_offsets[d + 1] - text_offsets[d] > 1 && !texts[d]) : bytes[text_offsets[d + 1] - 1] != 0xFFu)
-            east_throw(EAST_HIP_ERR_INVALID, texts ? "null text" : "every text must be followed by one 0xFF separator byte");
-    }
+    host_texts_check(in, tables);
     if (n_stop < 0 || (n_stop > 0 && !stop_offsets)) east_throw(EAST_HIP_ERR_INVALID, "bad stopword arguments");
     const i64 n_stop_cps = n_stop ? stop_offsets[n_stop] : 0;
     if (n_stop && (stop_offsets[0] != 0 || n_stop_cps >= (i64)0x7FFFFFF0 || (n_stop_cps > 0 && !stop_cps)))
@@ -644,7 +631,7 @@ static void cos_build(east_hip_index *h, const uint8_t *bytes, i64 n_bytes64, co
     c.built = c.use_classes = false;
     c.table_valid = false;
     c.terms.w_valid[0] = c.terms.w_valid[1] = c.cls.w_valid[0] = c.cls.w_valid[1] = false;
-    const u32 N = (u32)n_bytes64, D = (u32)n_docs;
+    const u32 N = (u32)in.n_bytes, D = (u32)in.D;
     Stats stats;
 
     // ---- bytes -> code points -> tokens (at most one token per two code points, plus one)
@@ -655,49 +642,13 @@ static void cos_build(east_hip_index *h, const uint8_t *bytes, i64 n_bytes64, co
     HIP_CHECK(hipEventRecord(h->ev0, h->stream));
     uint8_t *d_bytes = a1.alloc<uint8_t>((size_t)N + 32);
     u32 *d_text_off = a1.alloc<u32>((size_t)D + 1);
-    if (texts) {                                          // (east_hip_cosine_build_texts_v: the texts one by one, unjoined)
-        HIP_CHECK(hipMemsetAsync(d_bytes, 0xFF, N, h->stream));
-        for (u32 d = 0; d < D; d++) {
-            const size_t len = (size_t)(text_offsets[d + 1] - text_offsets[d] - 1);
-            if (len) HIP_CHECK(hipMemcpyAsync(d_bytes + text_offsets[d], texts[d], len, hipMemcpyHostToDevice, h->stream));
-        }
-    } else {
-        HIP_CHECK(hipMemcpyAsync(d_bytes, bytes, N, hipMemcpyHostToDevice, h->stream));
-    }
-    HIP_CHECK(hipMemsetAsync(d_bytes + N, 0, 32, h->stream));
-    std::vector<u32> off32((size_t)D + 1);
-    for (u32 d = 0; d <= D; d++) off32[d] = (u32)text_offsets[d];
-    HIP_CHECK(hipMemcpyAsync(d_text_off, off32.data(), off32.size() * 4, hipMemcpyHostToDevice, h->stream));
-    const TpDevTables tb = tp_upload_tables(h, cp_class, cp_upper, word_hi, digit_hi, hi_upper_from, hi_upper_to, n_hi_upper);
-
-    const u32 n_bblk = ceil_div_u32(N, TP_RANK_BLOCK);
-    u32 *byte_prefix = a1.alloc<u32>((size_t)n_bblk + 1);
-    LAUNCH(ctx, (tp_block_counts_kernel<TpStartIn>), ceil_div_u32((u64)n_bblk + 1, 8), TpStartIn{d_bytes, N}, N, n_bblk, byte_prefix);
-    device_scan<ArrIn, false>(ctx, ArrIn{byte_prefix}, n_bblk + 1, byte_prefix);
-    u32 n_cp = 0;
-    HIP_CHECK(hipMemcpyAsync(&n_cp, byte_prefix + n_bblk, 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    u32 *cpu = a1.alloc<u32>((size_t)n_cp + 1);
-    uint8_t *cw = a1.alloc<uint8_t>((size_t)n_cp + 32);
-    u32 *doc_cp_off = a1.alloc<u32>((size_t)D + 1);
-    LAUNCH(ctx, tp_decode_kernel, ceil_div_u32(N, BLOCK), (const uint8_t *)d_bytes, N, (const u32 *)byte_prefix, tb.t, cpu, cw);
-    LAUNCH(ctx, tp_doc_cp_offsets_kernel, ceil_div_u32((u64)D + 1, WAVES_PER_BLOCK), (const uint8_t *)d_bytes, N,
-           (const u32 *)byte_prefix, (const u32 *)d_text_off, D, doc_cp_off);
-
-    const u32 n_tblk = ceil_div_u32(n_cp, TP_RANK_BLOCK);
-    u32 *tok_prefix = a1.alloc<u32>((size_t)n_tblk + 1);
-    LAUNCH(ctx, (tp_block_counts_kernel<TpTokStartIn>), ceil_div_u32((u64)n_tblk + 1, 8), TpTokStartIn{cw, n_cp}, n_cp, n_tblk,
-           tok_prefix);
-    device_scan<ArrIn, false>(ctx, ArrIn{tok_prefix}, n_tblk + 1, tok_prefix);
-    u32 n_tok = 0;
-    HIP_CHECK(hipMemcpyAsync(&n_tok, tok_prefix + n_tblk, 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    u32 *tstart = a1.alloc<u32>((size_t)n_tok + 1), *tend = a1.alloc<u32>((size_t)n_tok + 1), *tok_nd = a1.alloc<u32>((size_t)n_tok + 1);
+    upload_texts_whole(h, in, d_bytes, d_text_off);
+    const TpDevTables tb = tp_upload_tables(h, tables);
+    // (the cosine kernels read the code points: always decoded)
+    const TpTokens tk = tp_tokenize(ctx, D, N, d_bytes, d_text_off, tb, false);
+    const u32 n_cp = tk.n_cp, n_tok = tk.n_tok;
+    const u32 *cpu = tk.cpu, *doc_cp_off = tk.doc_cp_off, *tstart = tk.tstart, *tend = tk.tend;
     u32 *keep = a1.alloc<u32>((size_t)n_tok + 1), *keep_ex = a1.alloc<u32>((size_t)n_tok + 1);
-    HIP_CHECK(hipMemsetAsync(tok_nd, 0, ((size_t)n_tok + 1) * 4, h->stream));
-    if (n_tok)
-        LAUNCH(ctx, tp_token_bounds_kernel, ceil_div_u32(n_cp, BLOCK * TP_VEC), (const uint8_t *)cw, (const u32 *)tok_prefix, n_cp,
-               tstart, tend, tok_nd);
     LAUNCH(ctx, cos_keep_kernel, ceil_div_u32((u64)n_tok + 1, BLOCK), (const u32 *)tstart, (const u32 *)tend, n_tok, keep);
     device_scan<ArrIn, false>(ctx, ArrIn{keep}, n_tok + 1, keep_ex);
     u32 n_kept = 0;
@@ -1020,8 +971,7 @@ int east_hip_cosine_build_texts(east_hip_handle_t h, const uint8_t *bytes, int64
                                 int32_t n_hi_upper, const uint32_t *stop_cps, const int64_t *stop_offsets, int32_t n_stop)
 {
     return guarded([&] {
-        cos_build(h, bytes, n_bytes, text_offsets, n_docs, cp_class, cp_upper, word_hi, digit_hi, hi_upper_from, hi_upper_to,
-                  n_hi_upper, nullptr, stop_cps, stop_offsets, n_stop);
+        cos_build(h, host_texts_joined(bytes, n_bytes, text_offsets, n_docs), UnicodeTablesHost{cp_class, cp_upper, word_hi, digit_hi, hi_upper_from, hi_upper_to, n_hi_upper}, stop_cps, stop_offsets, n_stop);
     });
 }
 
@@ -1031,14 +981,7 @@ int east_hip_cosine_build_texts_v(east_hip_handle_t h, const uint8_t *const *tex
                                   int32_t n_hi_upper, const uint32_t *stop_cps, const int64_t *stop_offsets, int32_t n_stop)
 {
     return guarded([&] {
-        if (!texts || !lengths || n_docs < 1) east_throw(EAST_HIP_ERR_INVALID, "null argument or no documents");
-        std::vector<i64> off((size_t)n_docs + 1, 0);
-        for (int32_t d = 0; d < n_docs; d++) {
-            if (lengths[d] < 0) east_throw(EAST_HIP_ERR_INVALID, "negative text length");
-            off[d + 1] = off[d] + lengths[d] + 1;                                   // + the separator
-        }
-        cos_build(h, nullptr, off[n_docs], off.data(), n_docs, cp_class, cp_upper, word_hi, digit_hi, hi_upper_from, hi_upper_to,
-                  n_hi_upper, texts, stop_cps, stop_offsets, n_stop);
+        cos_build(h, host_texts_separate(texts, lengths, n_docs), UnicodeTablesHost{cp_class, cp_upper, word_hi, digit_hi, hi_upper_from, hi_upper_to, n_hi_upper}, stop_cps, stop_offsets, n_stop);
     });
 }
 

@@ -155,8 +155,7 @@ int east_hip_build_texts(east_hip_handle_t h, const uint8_t *bytes, int64_t n_by
                          int32_t n_hi_upper)
 {
     return guarded([&] {
-        build_from_texts(h, bytes, n_bytes, text_offsets, n_docs, cp_class, cp_upper, word_hi, digit_hi, hi_upper_from,
-                         hi_upper_to, n_hi_upper);
+        build_from_texts(h, host_texts_joined(bytes, n_bytes, text_offsets, n_docs), UnicodeTablesHost{cp_class, cp_upper, word_hi, digit_hi, hi_upper_from, hi_upper_to, n_hi_upper});
     });
 }
 
@@ -166,14 +165,7 @@ int east_hip_build_texts_v(east_hip_handle_t h, const uint8_t *const *texts, con
                            int32_t n_hi_upper)
 {
     return guarded([&] {
-        if (!texts || !lengths || n_docs < 1) east_throw(EAST_HIP_ERR_INVALID, "null argument or no documents");
-        std::vector<i64> off((size_t)n_docs + 1, 0);
-        for (int32_t d = 0; d < n_docs; d++) {
-            if (lengths[d] < 0) east_throw(EAST_HIP_ERR_INVALID, "negative text length");
-            off[d + 1] = off[d] + lengths[d] + 1;                                   // + the separator
-        }
-        build_from_texts(h, nullptr, off[n_docs], off.data(), n_docs, cp_class, cp_upper, word_hi, digit_hi, hi_upper_from,
-                         hi_upper_to, n_hi_upper, texts);
+        build_from_texts(h, host_texts_separate(texts, lengths, n_docs), UnicodeTablesHost{cp_class, cp_upper, word_hi, digit_hi, hi_upper_from, hi_upper_to, n_hi_upper});
     });
 }
 

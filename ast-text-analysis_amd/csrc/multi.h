@@ -372,9 +372,8 @@ int east_hip_group_build_texts_v(east_hip_group_t g, const uint8_t *const *texts
     return guarded([&] {
         group_check(g, false);
         use_device_ordinal(g->devices[0]);
-        if (!texts || !lengths || n_docs < 1) east_throw(EAST_HIP_ERR_INVALID, "null argument or no documents");
-        for (int32_t d = 0; d < n_docs; d++)
-            if (lengths[d] < 0) east_throw(EAST_HIP_ERR_INVALID, "negative text length");
+        (void)host_texts_separate(texts, lengths, n_docs);      // (the checks; every shard takes its part of the two arrays)
+        const UnicodeTablesHost tables{cp_class, cp_upper, word_hi, digit_hi, hi_upper_from, hi_upper_to, n_hi_upper};
         g->built = false;
         shard_by_size(lengths, n_docs, (int32_t)g->shard.size(), g->first_doc);
         g->n_docs = n_docs;
@@ -384,10 +383,7 @@ int east_hip_group_build_texts_v(east_hip_group_t g, const uint8_t *const *texts
             east_hip_index *h = g->shard[s];
             h->built = false;
             if (e == b) return;
-            std::vector<i64> off((size_t)(e - b) + 1, 0);
-            for (int32_t d = b; d < e; d++) off[d - b + 1] = off[d - b] + lengths[d] + 1;      // + the separator
-            build_from_texts(h, nullptr, off[e - b], off.data(), e - b, cp_class, cp_upper, word_hi, digit_hi, hi_upper_from,
-                             hi_upper_to, n_hi_upper, texts + b);
+            build_from_texts(h, host_texts_separate(texts + b, lengths + b, e - b), tables);
         });
         g->build_ms = wall_ms_since(t0);
         g->built = true;

@@ -6,6 +6,65 @@
 
 #define TP_WORD_HI_WORDS ((0x110000u - TP_TEXT_LIMIT + 31u) / 32u)
 
+// ---- the input: D raw texts, joined or apart --------------------------------------------------------------------------
+// Joined: `bytes` holds the texts, each followed by one 0xFF byte.  Apart: text d = texts[d], never joined on the host;
+// text_offsets then says where the texts would lie if they were joined with their separators.
+struct HostTexts {
+    const uint8_t *bytes = nullptr;
+    const uint8_t *const *texts = nullptr;
+    const i64 *text_offsets = nullptr;      // D + 1
+    int32_t D = 0;
+    i64 n_bytes = 0;                        // of the joined stream, separators included
+    std::vector<i64> own_offsets;           // what text_offsets points to when the input came as lengths
+    std::vector<u32> off32;                 // the offsets as the device takes them (host_texts_check)
+    HostTexts() = default;
+    HostTexts(HostTexts &&) = default;      // (no copies: text_offsets may point into own_offsets)
+};
+
+static HostTexts host_texts_joined(const uint8_t *bytes, i64 n_bytes, const i64 *text_offsets, int32_t n_docs)
+{
+    HostTexts in;
+    in.bytes = bytes; in.text_offsets = text_offsets; in.D = n_docs; in.n_bytes = n_bytes;
+    return in;
+}
+
+static HostTexts host_texts_separate(const uint8_t *const *texts, const i64 *lengths, int32_t n_docs)
+{
+    if (!texts || !lengths || n_docs < 1) east_throw(EAST_HIP_ERR_INVALID, "null argument or no documents");
+    HostTexts in;
+    in.own_offsets.assign((size_t)n_docs + 1, 0);
+    for (int32_t d = 0; d < n_docs; d++) {
+        if (lengths[d] < 0) east_throw(EAST_HIP_ERR_INVALID, "negative text length");
+        in.own_offsets[d + 1] = in.own_offsets[d] + lengths[d] + 1;                 // + the separator
+    }
+    in.texts = texts; in.text_offsets = in.own_offsets.data(); in.D = n_docs; in.n_bytes = in.own_offsets[n_docs];
+    return in;
+}
+
+// The caller's Unicode tables (hip_backend.py: unicode_tables()).
+struct UnicodeTablesHost {
+    const uint8_t *cp_class;
+    const u32 *cp_upper, *word_hi, *digit_hi, *hi_upper_from, *hi_upper_to;
+    int32_t n_hi_upper;
+    bool ok() const { return cp_class && cp_upper && word_hi && digit_hi && n_hi_upper >= 0 && (n_hi_upper == 0 || (hi_upper_from && hi_upper_to)); }
+};
+
+// The one check of a text input (after it the sizes fit 32 bits: off32).  Missing tables and missing texts are one error.
+static void host_texts_check(HostTexts &in, const UnicodeTablesHost &tables)
+{
+    if ((!in.bytes && !in.texts) || !in.text_offsets || !tables.ok() || in.D < 1) east_throw(EAST_HIP_ERR_INVALID, "null argument or no documents");
+    if (in.n_bytes < in.D || in.n_bytes >= (i64)0x7FFFFFF0) east_throw(EAST_HIP_ERR_INVALID, "total bytes out of range");
+    const i64 *off = in.text_offsets;
+    if (off[0] != 0 || off[in.D] != in.n_bytes) east_throw(EAST_HIP_ERR_INVALID, "text_offsets must start at 0 and end at the total");
+    in.off32.assign((size_t)in.D + 1, 0);
+    for (int32_t d = 0; d < in.D; d++) {
+        if (off[d + 1] <= off[d]) east_throw(EAST_HIP_ERR_INVALID, "text_offsets must increase");
+        if (in.texts ? (off[d + 1] - off[d] > 1 && !in.texts[d]) : in.bytes[off[d + 1] - 1] != 0xFFu)
+            east_throw(EAST_HIP_ERR_INVALID, in.texts ? "null text" : "every text must be followed by one 0xFF separator byte");
+        in.off32[d + 1] = (u32)off[d + 1];
+    }
+}
+
 // ---- the streamed preparation (textprep.h, "the streamed preparation") --------------------------------------------
 // -1: streamed for inputs of TP_STREAM_MIN bytes or more, in about TP_STREAM_CHUNKS chunks; 0: never; > 0: always, in chunks
 // of about that many bytes (east_hip_debug_set_text_stream: the tests push the fixtures through chunks of a few dozen bytes)
@@ -20,24 +79,25 @@ struct TpChunk {
 };
 
 // byte p of the concatenated stream (document d holds it)
-static inline u32 tp_byte_at(const uint8_t *bytes, const uint8_t *const *texts, const i64 *text_offsets, u32 d, u32 p)
+static inline u32 tp_byte_at(const HostTexts &in, u32 d, u32 p)
 {
-    if (p + 1 == (u32)text_offsets[d + 1]) return 0xFFu;              // the separator
-    return texts ? texts[d][p - (u32)text_offsets[d]] : bytes[p];
+    if (p + 1 == in.off32[d + 1]) return 0xFFu;                       // the separator
+    return in.texts ? in.texts[d][p - in.off32[d]] : in.bytes[p];
 }
 
 // Cuts of the stream where neither a token nor a UTF-8 unit can span them: behind a separator, or behind an ASCII byte
 // that is no word character (looked for in the 4 KiB in front of where the chunk would end; a document without one there
 // -- one endless token, binary junk -- stays whole).
-static std::vector<TpChunk> tp_plan_chunks(const uint8_t *bytes, const uint8_t *const *texts, const i64 *text_offsets, u32 D,
-                                           u32 n_bytes, u32 chunk_bytes, const uint8_t *cls256)
+static std::vector<TpChunk> tp_plan_chunks(const HostTexts &in, u32 chunk_bytes, const uint8_t *cls256)
 {
+    const u32 *text_offsets = in.off32.data();
+    const u32 n_bytes = (u32)in.n_bytes;
+    // (the first chunk is a quarter of the others: the preparation -- the slower side -- starts that much earlier)
+    const u32 first_div = getenv("EAST_HIP_TP_FIRST_DIV") ? (u32)std::max(1, atoi(getenv("EAST_HIP_TP_FIRST_DIV"))) : 4u;   // (experiments)
     std::vector<TpChunk> chunks;
     u32 pos = 0, d = 0;                                  // d: the document that holds byte pos
     while (pos < n_bytes) {
         u32 cut = n_bytes;
-        // (the first chunk is a quarter of the others: the preparation -- the slower side -- starts that much earlier)
-        const u32 first_div = getenv("EAST_HIP_TP_FIRST_DIV") ? (u32)std::max(1, atoi(getenv("EAST_HIP_TP_FIRST_DIV"))) : 4u;   // (experiments)
         const u32 want = pos == 0 && chunk_bytes >= 4096u ? chunk_bytes / first_div : chunk_bytes;
         if ((u64)pos + want < n_bytes) {
             const u32 target = pos + want;
@@ -47,7 +107,7 @@ static std::vector<TpChunk> tp_plan_chunks(const uint8_t *bytes, const uint8_t *
             const u32 lowest = std::max(pos + 1, target > 4096u ? target - 4096u : 0u);
             for (u32 q = target; q-- > lowest;) {
                 if (q < (u32)text_offsets[dt]) { cut = (u32)text_offsets[dt]; break; }     // (the document starts in the window: cut in front of it)
-                const u32 c = tp_byte_at(bytes, texts, text_offsets, dt, q);
+                const u32 c = tp_byte_at(in, dt, q);
                 if (c == 0xFFu || (c < 0x80u && !(cls256[c] & TP_CLASS_WORD))) { cut = q + 1; break; }
             }
         }
@@ -79,15 +139,16 @@ static thread_local std::chrono::steady_clock::time_point g_tp_call_start;     /
 #define TP_RING_MAX_TEXT ((u64)8 << 20)
 #define TP_RING_FIRST_TEXTS 128u              // a handle's first call pins the ring in line only for this many texts or more
 
-// bytes [a, b) of the concatenated stream (texts d with their 0xFF separators, text_offsets as in build_from_texts) -> dst
-static void tp_fill_stream(char *dst, u64 a, u64 b, const uint8_t *const *texts, const i64 *text_offsets, u32 D)
+// bytes [a, b) of the concatenated stream (the texts of `in`, which lie apart, with their 0xFF separators) -> dst
+static void tp_fill_stream(char *dst, u64 a, u64 b, const HostTexts &in)
 {
-    u32 d = (u32)(std::upper_bound(text_offsets, text_offsets + D + 1, (i64)a) - text_offsets) - 1u;
+    const i64 *text_offsets = in.text_offsets;
+    u32 d = (u32)(std::upper_bound(text_offsets, text_offsets + in.D + 1, (i64)a) - text_offsets) - 1u;
     while (a < b) {
         const u64 t0 = (u64)text_offsets[d], sep = (u64)text_offsets[d + 1] - 1u;      // text d = [t0, sep), then its separator
         if (a < sep) {
             const u64 e = std::min(b, sep);
-            memcpy(dst, texts[d] + (a - t0), (size_t)(e - a));
+            memcpy(dst, in.texts[d] + (a - t0), (size_t)(e - a));
             dst += e - a;
             a = e;
         }
@@ -96,16 +157,155 @@ static void tp_fill_stream(char *dst, u64 a, u64 b, const uint8_t *const *texts,
     }
 }
 
+// The caller's Unicode tables (290 KB) stay on the device between calls (own allocation): they are uploaded again only
+// when their content changes -- a 64-bit hash over all of them, taken while the text is on its way.  With them go the two
+// 256-entry tables of the byte-wise fast path (class and upper-cased code point of a byte that is a code point of its own).
+struct TpDevTables {
+    TpTables t;
+    const uint8_t *cls256;     // the 256-entry tables of the byte-wise fast path
+    const u32 *up256;
+};
+static TpDevTables tp_upload_tables(east_hip_index *h, const UnicodeTablesHost &u)
+{
+    const auto [cp_class, cp_upper, word_hi, digit_hi, hi_upper_from, hi_upper_to, n_hi_upper] = u;
+    const size_t tb_class = 0, tb_upper = tb_class + TP_TEXT_LIMIT, tb_word = tb_upper + (size_t)TP_TEXT_LIMIT * 4,
+                 tb_digit = tb_word + (size_t)TP_WORD_HI_WORDS * 4, tb_from = tb_digit + (size_t)TP_WORD_HI_WORDS * 4,
+                 tb_to = tb_from + ((size_t)n_hi_upper + 1) * 4, tb_cls256 = tb_to + ((size_t)n_hi_upper + 1) * 4,
+                 tb_up256 = tb_cls256 + 256, tb_total = tb_up256 + 1024;
+    {
+        u64 hash = 0x9E3779B97F4A7C15ull ^ (u64)n_hi_upper;
+        auto mix = [&](const void *p, size_t bytes) {
+            const u64 *q = (const u64 *)p;
+            for (size_t i = 0; i < bytes / 8; i++) hash = (hash ^ q[i]) * 0x100000001B3ull + (hash >> 29);
+        };
+        mix(cp_class, TP_TEXT_LIMIT); mix(cp_upper, (size_t)TP_TEXT_LIMIT * 4); mix(word_hi, (size_t)TP_WORD_HI_WORDS * 4);
+        mix(digit_hi, (size_t)TP_WORD_HI_WORDS * 4);
+        for (int32_t q = 0; q < n_hi_upper; q++) hash = (hash ^ (((u64)hi_upper_from[q] << 32) | hi_upper_to[q])) * 0x100000001B3ull + (hash >> 29);
+        if (h->tp_tables.cap < tb_total || h->tp_tables_hash != hash) {
+            h->tp_tables.ensure(tb_total, "the Unicode tables", h->stream);
+            h->tp_host_tables.resize(256 + 1024);
+            uint8_t *cls256 = h->tp_host_tables.data();
+            u32 *up256 = reinterpret_cast<u32 *>(h->tp_host_tables.data() + 256);
+            for (u32 x = 0; x < 256; x++) {              // (as tp_decode_kernel: upper first, then the class of the result)
+                u32 cp = x < 0x80u ? cp_upper[x] : TP_REPLACEMENT;
+                if (cp >= TP_TEXT_LIMIT) {
+                    for (int32_t q = 0; q < n_hi_upper; q++)
+                        if (hi_upper_from[q] == cp) { cp = hi_upper_to[q]; break; }
+                }
+                u32 cls;
+                if (cp < TP_TEXT_LIMIT) cls = cp_class[cp];
+                else { const u32 k = cp - TP_TEXT_LIMIT; cls = ((word_hi[k >> 5] >> (k & 31u)) & 1u) | (((digit_hi[k >> 5] >> (k & 31u)) & 1u) << 1); }
+                cls256[x] = (uint8_t)cls;
+                up256[x] = cp;
+            }
+            char *t = h->tp_tables.p;
+            HIP_CHECK(hipMemcpyAsync(t + tb_class, cp_class, TP_TEXT_LIMIT, hipMemcpyHostToDevice, h->stream));
+            HIP_CHECK(hipMemcpyAsync(t + tb_upper, cp_upper, (size_t)TP_TEXT_LIMIT * 4, hipMemcpyHostToDevice, h->stream));
+            HIP_CHECK(hipMemcpyAsync(t + tb_word, word_hi, (size_t)TP_WORD_HI_WORDS * 4, hipMemcpyHostToDevice, h->stream));
+            HIP_CHECK(hipMemcpyAsync(t + tb_digit, digit_hi, (size_t)TP_WORD_HI_WORDS * 4, hipMemcpyHostToDevice, h->stream));
+            if (n_hi_upper) {
+                HIP_CHECK(hipMemcpyAsync(t + tb_from, hi_upper_from, (size_t)n_hi_upper * 4, hipMemcpyHostToDevice, h->stream));
+                HIP_CHECK(hipMemcpyAsync(t + tb_to, hi_upper_to, (size_t)n_hi_upper * 4, hipMemcpyHostToDevice, h->stream));
+            }
+            HIP_CHECK(hipMemcpyAsync(t + tb_cls256, cls256, 256, hipMemcpyHostToDevice, h->stream));
+            HIP_CHECK(hipMemcpyAsync(t + tb_up256, up256, 1024, hipMemcpyHostToDevice, h->stream));
+            h->tp_tables_hash = hash;                   // (the read-back below waits for the stream: the host buffers are the caller's / the handle's)
+        }
+    }
+    const uint8_t *d_class = (const uint8_t *)(h->tp_tables.p + tb_class), *d_cls256 = (const uint8_t *)(h->tp_tables.p + tb_cls256);
+    const u32 *d_upper = (const u32 *)(h->tp_tables.p + tb_upper), *d_word_hi = (const u32 *)(h->tp_tables.p + tb_word),
+              *d_digit_hi = (const u32 *)(h->tp_tables.p + tb_digit), *d_hi_from = (const u32 *)(h->tp_tables.p + tb_from),
+              *d_hi_to = (const u32 *)(h->tp_tables.p + tb_to), *d_up256 = (const u32 *)(h->tp_tables.p + tb_up256);
+    return TpDevTables{TpTables{d_class, d_upper, d_word_hi, d_digit_hi, d_hi_from, d_hi_to, (u32)n_hi_upper}, d_cls256, d_up256};
+}
+
+// ---- the streamed preparation, one chunk ------------------------------------------------------------------------------
+// device state shared by the chunks
+struct TpStreamState {
+    TpCarry *carry;                 // [2]: what chunk c reads of its first document, chunk c + 1 writes
+    u32 *d_high, *doc_sym_off_all, *m_all, *prep_sym;
+};
+
+// per-chunk scratch (sized for the largest chunk, used by one chunk after the other)
+struct TpChunkScratch {
+    u32 *d_text_off, *byte_prefix, *tok_prefix, *cpu, *doc_cp_off, *tstart, *tend, *tok_nd, *keep, *klen, *keep_ex, *klen_ex, *first_tok, *n_loc,
+        *off_loc, *kept_tot, *chars_tot;
+    uint8_t *cw;
+    uint4 *tok_rec;
+    void alloc(Arena &ar, u32 nb_max, u32 dl_max, u32 ub_tok)
+    {
+        d_text_off = ar.alloc<u32>((size_t)dl_max + 1);
+        byte_prefix = ar.alloc<u32>((size_t)nb_max / TP_RANK_BLOCK + 2), tok_prefix = ar.alloc<u32>((size_t)nb_max / TP_RANK_BLOCK + 2);
+        cpu = ar.alloc<u32>(nb_max);
+        cw = ar.alloc<uint8_t>((size_t)nb_max + 32);
+        doc_cp_off = ar.alloc<u32>((size_t)dl_max + 1);
+        tstart = ar.alloc<u32>(ub_tok), tend = ar.alloc<u32>(ub_tok);
+        // (tok_nd, keep and klen side by side: one fill per chunk)
+        tok_nd = ar.alloc<u32>(3 * ((size_t)ub_tok + 1)), keep = tok_nd + ((size_t)ub_tok + 1), klen = keep + ((size_t)ub_tok + 1);
+        keep_ex = ar.alloc<u32>((size_t)ub_tok + 1), klen_ex = ar.alloc<u32>((size_t)ub_tok + 1);
+        tok_rec = ar.alloc<uint4>(ub_tok);
+        first_tok = ar.alloc<u32>((size_t)dl_max + 1), n_loc = ar.alloc<u32>((size_t)dl_max + 1);
+        off_loc = ar.alloc<u32>((size_t)dl_max + 1), kept_tot = ar.alloc<u32>(dl_max), chars_tot = ar.alloc<u32>(dl_max);
+    }
+};
+
+// Chunk c, whose bytes are on the device and hold n_cp code points: bytes -> code points -> tokens -> the symbols of its
+// documents, behind what the chunks before it emitted.
+static void tp_prepare_chunk(Ctx &ctx, const TpChunkScratch &s, const TpChunk &ch, u32 c, u32 n_cp, const uint8_t *d_bytes,
+                             const TpDevTables &tb, const TpStreamState &st)
+{
+    const u32 nb = ch.b1 - ch.b0, Dl = ch.n_docs;
+    const uint8_t *b = d_bytes + ch.b0;
+    HIP_CHECK(hipMemcpyAsync(s.d_text_off, ch.text_off.data(), ((size_t)Dl + 1) * 4, hipMemcpyHostToDevice, ctx.stream));
+    // bytes -> code points (a chunk in which every byte is a code point of its own needs no index)
+    const bool bytewise = n_cp == nb;
+    const u32 *ranks = bytewise ? nullptr : s.byte_prefix;
+    if (bytewise) {
+        LAUNCH(ctx, tp_classify_bytes_kernel, ceil_div_u32(nb, BLOCK * 16), b, nb, tb.cls256, s.cw);
+    } else {
+        const u32 n_bblk = ceil_div_u32(nb, TP_RANK_BLOCK);
+        LAUNCH(ctx, (tp_block_counts_kernel<TpStartIn>), ceil_div_u32((u64)n_bblk + 1, 8), TpStartIn{b, nb}, nb, n_bblk, s.byte_prefix);
+        device_scan<ArrIn, false>(ctx, ArrIn{s.byte_prefix}, n_bblk + 1, s.byte_prefix);
+        LAUNCH(ctx, tp_decode_kernel, ceil_div_u32(nb, BLOCK), b, nb, ranks, tb.t, s.cpu, s.cw);
+    }
+    LAUNCH(ctx, tp_doc_cp_offsets_kernel, ceil_div_u32(Dl + 1, WAVES_PER_BLOCK), b, nb, ranks, s.d_text_off, Dl, s.doc_cp_off);
+    // code points -> tokens (their number stays on the device: the last entry of the blocks' prefix sums)
+    const u32 n_tblk = ceil_div_u32(n_cp, TP_RANK_BLOCK);
+    LAUNCH(ctx, (tp_block_counts_kernel<TpTokStartIn>), ceil_div_u32((u64)n_tblk + 1, 8), TpTokStartIn{s.cw, n_cp}, n_cp, n_tblk, s.tok_prefix);
+    device_scan<ArrIn, false>(ctx, ArrIn{s.tok_prefix}, n_tblk + 1, s.tok_prefix);
+    const u32 *n_tok_dev = s.tok_prefix + n_tblk;
+    const u32 ub = n_cp / 2 + 2;
+    // (everything over the tokens is bounded by their number on the device -- a third to a quarter of the upper bound ub:
+    // the zeroing, and ONE scan for kept tokens and kept symbols together, scan.h: device_scan_pair_bounded)
+    LAUNCH(ctx, tp_zero_tokens_kernel, ceil_div_u32((u64)ub + 1, BLOCK * 4), s.tok_nd, s.keep, s.klen, ub, n_tok_dev);
+    LAUNCH(ctx, tp_token_bounds_kernel, ceil_div_u32(n_cp, BLOCK * TP_VEC), s.cw, s.tok_prefix, n_cp, s.tstart, s.tend, s.tok_nd);
+    LAUNCH(ctx, tp_token_keep_kernel, ceil_div_u32(ub, BLOCK), s.tstart, s.tend, s.tok_nd, ub, s.keep, s.klen, n_tok_dev);
+    device_scan_pair_bounded(ctx, s.keep, s.klen, ub + 1, n_tok_dev, 1u, s.keep_ex, s.klen_ex);
+    // tokens -> the documents' strings and symbols, with what earlier chunks emitted of the first document
+    const TpCarry *cin = st.carry + (c & 1u);
+    TpCarry *cout = st.carry + ((c + 1u) & 1u);
+    LAUNCH(ctx, tp_stream_docs_kernel, ceil_div_u32(Dl + 1, WAVES_PER_BLOCK), s.doc_cp_off, s.cw, n_cp, s.tok_prefix, s.keep_ex, s.klen_ex, Dl, ch.cont_in, ch.cont_out,
+           cin, s.first_tok, s.n_loc, s.kept_tot, s.chars_tot);
+    device_scan<ArrIn, false>(ctx, ArrIn{s.n_loc}, Dl + 1, s.off_loc);
+    LAUNCH(ctx, tp_stream_token_out_kernel, ceil_div_u32(ub, BLOCK), s.tstart, s.tend, s.keep_ex, s.klen_ex, s.doc_cp_off, s.first_tok, s.off_loc,
+           s.kept_tot, Dl, ch.cont_in, ch.cont_out, cin, n_tok_dev, s.tok_rec);
+    LAUNCH(ctx, tp_emit_kernel, ceil_div_u32(n_cp, BLOCK), bytewise ? nullptr : s.cpu, b, tb.up256, s.cw, s.tok_prefix, s.tok_rec, n_cp, st.prep_sym,
+           st.d_high);
+    LAUNCH(ctx, tp_stream_close_docs_kernel, ceil_div_u32(Dl, BLOCK), s.off_loc, s.n_loc, s.kept_tot, s.chars_tot, Dl, ch.doc_first, ch.cont_in, ch.cont_out, cin, cout,
+           st.doc_sym_off_all, st.m_all, st.prep_sym);
+}
+
 // Prepares the collection chunk by chunk; the symbols end up in h->prep_sym, the per-document offsets and string counts in
 // h_off / h_m.  Returns false when the monolithic preparation has to take over: kept text at or above U+0A00 (the tagged
 // encoding rewrites terminators the chunks no longer remember).  d_bytes: n_bytes + 32 bytes of the arena, nothing uploaded yet.
-static bool prepare_texts_streamed(east_hip_index *h, Ctx &ctx, const uint8_t *bytes, const uint8_t *const *texts,
-                                   const i64 *text_offsets, u32 D, u32 n_bytes, u32 chunk_bytes, uint8_t *d_bytes,
-                                   const TpTables &tables, const uint8_t *d_cls256, const u32 *d_up256,
-                                   std::vector<u32> &h_off, std::vector<u32> &h_m)
+static bool prepare_texts_streamed(east_hip_index *h, Ctx &ctx, const HostTexts &in, u32 chunk_bytes, uint8_t *d_bytes,
+                                   const TpDevTables &tb, std::vector<u32> &h_off, std::vector<u32> &h_m)
 {
     Arena &ar = *ctx.arena;
-    const std::vector<TpChunk> chunks = tp_plan_chunks(bytes, texts, text_offsets, D, n_bytes, chunk_bytes, h->tp_host_tables.data());
+    const uint8_t *bytes = in.bytes, *const *texts = in.texts;
+    const i64 *text_offsets = in.text_offsets;
+    const u32 D = (u32)in.D, n_bytes = (u32)in.n_bytes;
+    const std::vector<TpChunk> chunks = tp_plan_chunks(in, chunk_bytes, h->tp_host_tables.data());
     const u32 C = (u32)chunks.size();
     u32 nb_max = 0, dl_max = 0;
     for (const TpChunk &c : chunks) { nb_max = std::max(nb_max, c.b1 - c.b0); dl_max = std::max(dl_max, c.n_docs); }
@@ -119,17 +319,12 @@ static bool prepare_texts_streamed(east_hip_index *h, Ctx &ctx, const uint8_t *b
     // an empty document two
     const size_t sym_cap = (size_t)n_bytes + (size_t)n_bytes / 9 + 2 * (size_t)D + 64;
     h->prep_sym.ensure(sym_cap * 4, "the prepared symbols", h->stream);
-    u32 *prep_sym = h->prep_sym.as<u32>();
     // ---- device state shared by the chunks ----
-    TpCarry *carry = ar.alloc<TpCarry>(2);
-    u32 *d_high = ar.alloc<u32>(1);
-    u32 *doc_sym_off_all = ar.alloc<u32>((size_t)D + 1), *m_all = ar.alloc<u32>(D);
-    HIP_CHECK(hipMemsetAsync(carry, 0, 2 * sizeof(TpCarry), h->stream));
-    HIP_CHECK(hipMemsetAsync(d_high, 0, 4, h->stream));
-    // per-chunk scratch (sized for the largest chunk, used by one chunk after the other)
-    const u32 ub_tok = nb_max / 2 + 2;                   // a token needs a character and something behind it
-    u32 *d_text_off = ar.alloc<u32>((size_t)dl_max + 1);
-    u32 *byte_prefix = ar.alloc<u32>((size_t)nb_max / TP_RANK_BLOCK + 2), *tok_prefix = ar.alloc<u32>((size_t)nb_max / TP_RANK_BLOCK + 2);
+    const TpStreamState st{ar.alloc<TpCarry>(2), ar.alloc<u32>(1), ar.alloc<u32>((size_t)D + 1), ar.alloc<u32>(D), h->prep_sym.as<u32>()};
+    HIP_CHECK(hipMemsetAsync(st.carry, 0, 2 * sizeof(TpCarry), h->stream));
+    HIP_CHECK(hipMemsetAsync(st.d_high, 0, 4, h->stream));
+    TpChunkScratch scratch;
+    scratch.alloc(ar, nb_max, dl_max, nb_max / 2 + 2);   // (tokens: one needs a character and something behind it)
     // (the counts of the chunks: on the copy stream, each into a stretch of its own -- the host reads chunk c's while
     // chunk c + 1's may already be written)
     std::vector<u32> cnt_off(C + 1, 0);
@@ -137,16 +332,6 @@ static bool prepare_texts_streamed(east_hip_index *h, Ctx &ctx, const uint8_t *b
     u32 *cp_sums_aux = ar.alloc<u32>(cnt_off[C]);
     std::vector<std::vector<u32>> h_counts(C);
     for (u32 c = 0; c < C; c++) h_counts[c].resize(cnt_off[c + 1] - cnt_off[c]);
-    u32 *cpu = ar.alloc<u32>(nb_max);
-    uint8_t *cw = ar.alloc<uint8_t>((size_t)nb_max + 32);
-    u32 *doc_cp_off = ar.alloc<u32>((size_t)dl_max + 1);
-    u32 *tstart = ar.alloc<u32>(ub_tok), *tend = ar.alloc<u32>(ub_tok);
-    // (tok_nd, keep and klen side by side: one fill per chunk)
-    u32 *tok_nd = ar.alloc<u32>(3 * ((size_t)ub_tok + 1)), *keep = tok_nd + ((size_t)ub_tok + 1), *klen = keep + ((size_t)ub_tok + 1);
-    u32 *keep_ex = ar.alloc<u32>((size_t)ub_tok + 1), *klen_ex = ar.alloc<u32>((size_t)ub_tok + 1);
-    uint4 *tok_rec = ar.alloc<uint4>(ub_tok);
-    u32 *first_tok = ar.alloc<u32>((size_t)dl_max + 1), *n_loc = ar.alloc<u32>((size_t)dl_max + 1);
-    u32 *off_loc = ar.alloc<u32>((size_t)dl_max + 1), *kept_tot = ar.alloc<u32>(dl_max), *chars_tot = ar.alloc<u32>(dl_max);
 
     // ---- the uploads: a thread of their own (a copy out of pageable memory returns when it is staged) ----
     // (ONE uploader: two threads with a copy stream each, the chunks' halves side by side, were measured and are slower --
@@ -204,7 +389,7 @@ static bool prepare_texts_streamed(east_hip_index *h, Ctx &ctx, const uint8_t *b
                 }
                 const u64 a = (u64)sl * ring_slot, len = std::min<u64>(ring_slot, (u64)n_bytes - a);
                 const u64 lo = a + len * (u64)j / (u64)n_fill, hi = a + len * (u64)(j + 1) / (u64)n_fill;
-                if (hi > lo) tp_fill_stream(ring + (size_t)(sl % TP_RING_SLOTS) * ring_slot + (lo - a), lo, hi, texts, text_offsets, D);
+                if (hi > lo) tp_fill_stream(ring + (size_t)(sl % TP_RING_SLOTS) * ring_slot + (lo - a), lo, hi, in);
                 if (slot_parts[sl].fetch_add(1, std::memory_order_release) + 1 == n_fill && sl == 0) t_first_fill.store(since());
             }
         });
@@ -287,8 +472,6 @@ static bool prepare_texts_streamed(east_hip_index *h, Ctx &ctx, const uint8_t *b
 
     for (u32 c = 0; c < C; c++) {
         const TpChunk &ch = chunks[c];
-        const u32 nb = ch.b1 - ch.b0, Dl = ch.n_docs;
-        const uint8_t *b = d_bytes + ch.b0;
         // the chunk's bytes: recorded by the uploader, waited for by the compute stream
         while (uploaded.load(std::memory_order_acquire) <= (int)c) {
             if (upload_failed.load(std::memory_order_acquire)) east_throw(EAST_HIP_ERR_HIP, "upload of the raw text failed");
@@ -297,53 +480,11 @@ static bool prepare_texts_streamed(east_hip_index *h, Ctx &ctx, const uint8_t *b
         HIP_CHECK(hipStreamWaitEvent(h->stream, events[c], 0));
         HIP_CHECK(hipEventSynchronize(events[c]));         // (the host reads the chunk's counts)
         t_cnt[c] = since();
-        HIP_CHECK(hipMemcpyAsync(d_text_off, ch.text_off.data(), ((size_t)Dl + 1) * 4, hipMemcpyHostToDevice, h->stream));
-        // bytes -> code points (the count first: a chunk in which every byte is a code point of its own needs no index).
-        // The count only needs the chunk's bytes: the uploader queues it on the copy stream right behind them (and records
-        // the event behind it), so that the host has the answer -- and queues the chunk's kernels -- while the chunk
-        // before is still being prepared.
-        const u32 nb_cp = ceil_div_u32((u64)nb + 1, SCAN_TILE);
+        // the chunk's code point count: the uploader queued it on the copy stream right behind the bytes (and recorded the event
+        // behind it), so that the host has the answer -- and queues the chunk's kernels -- while the chunk before is still prepared
         u32 n_cp = 0;
-        for (u32 i = 0; i < nb_cp; i++) n_cp += h_counts[c][i];
-        const bool bytewise = n_cp == nb;
-        if (bytewise) {
-            LAUNCH(ctx, tp_classify_bytes_kernel, ceil_div_u32(nb, BLOCK * 16), b, nb, d_cls256, cw);
-        } else {
-            const u32 n_bblk = ceil_div_u32(nb, TP_RANK_BLOCK);
-            LAUNCH(ctx, (tp_block_counts_kernel<TpStartIn>), ceil_div_u32((u64)n_bblk + 1, 8), TpStartIn{b, nb}, nb, n_bblk, byte_prefix);
-            device_scan<ArrIn, false>(ctx, ArrIn{byte_prefix}, n_bblk + 1, byte_prefix);
-            LAUNCH(ctx, tp_decode_kernel, ceil_div_u32(nb, BLOCK), b, nb, (const u32 *)byte_prefix, tables, cpu, cw);
-        }
-        LAUNCH(ctx, tp_doc_cp_offsets_kernel, ceil_div_u32(Dl + 1, WAVES_PER_BLOCK), b, nb, bytewise ? (const u32 *)nullptr : (const u32 *)byte_prefix,
-               (const u32 *)d_text_off, Dl, doc_cp_off);
-        // code points -> tokens (their number stays on the device: the last entry of the blocks' prefix sums)
-        const u32 n_tblk = ceil_div_u32(n_cp, TP_RANK_BLOCK);
-        LAUNCH(ctx, (tp_block_counts_kernel<TpTokStartIn>), ceil_div_u32((u64)n_tblk + 1, 8), TpTokStartIn{cw, n_cp}, n_cp, n_tblk, tok_prefix);
-        device_scan<ArrIn, false>(ctx, ArrIn{tok_prefix}, n_tblk + 1, tok_prefix);
-        const u32 *n_tok_dev = tok_prefix + n_tblk;
-        const u32 ub = n_cp / 2 + 2;
-        // (everything over the tokens is bounded by their number on the device -- a third to a quarter of the upper bound ub:
-        // the zeroing, and ONE scan for kept tokens and kept symbols together, scan.h: device_scan_pair_bounded)
-        LAUNCH(ctx, tp_zero_tokens_kernel, ceil_div_u32((u64)ub + 1, BLOCK * 4), tok_nd, keep, klen, ub, n_tok_dev);
-        LAUNCH(ctx, tp_token_bounds_kernel, ceil_div_u32(n_cp, BLOCK * TP_VEC), (const uint8_t *)cw, (const u32 *)tok_prefix, n_cp, tstart,
-               tend, tok_nd);
-        LAUNCH(ctx, tp_token_keep_kernel, ceil_div_u32(ub, BLOCK), (const u32 *)tstart, (const u32 *)tend, (const u32 *)tok_nd, ub, keep,
-               klen, n_tok_dev);
-        device_scan_pair_bounded(ctx, keep, klen, ub + 1, n_tok_dev, 1u, keep_ex, klen_ex);
-        // tokens -> the documents' strings and symbols, with what earlier chunks emitted of the first document
-        const TpCarry *cin = carry + (c & 1u);
-        TpCarry *cout = carry + ((c + 1u) & 1u);
-        LAUNCH(ctx, tp_stream_docs_kernel, ceil_div_u32(Dl + 1, WAVES_PER_BLOCK), (const u32 *)doc_cp_off, (const uint8_t *)cw, n_cp, (const u32 *)tok_prefix, (const u32 *)keep_ex,
-               (const u32 *)klen_ex, Dl, (u32)ch.cont_in, (u32)ch.cont_out, cin, first_tok, n_loc, kept_tot, chars_tot);
-        device_scan<ArrIn, false>(ctx, ArrIn{n_loc}, Dl + 1, off_loc);
-        LAUNCH(ctx, tp_stream_token_out_kernel, ceil_div_u32(ub, BLOCK), (const u32 *)tstart, (const u32 *)tend, (const u32 *)keep_ex,
-               (const u32 *)klen_ex, (const u32 *)doc_cp_off, (const u32 *)first_tok, (const u32 *)off_loc, (const u32 *)kept_tot, Dl,
-               (u32)ch.cont_in, (u32)ch.cont_out, cin, n_tok_dev, tok_rec);
-        LAUNCH(ctx, tp_emit_kernel, ceil_div_u32(n_cp, BLOCK), bytewise ? (const u32 *)nullptr : (const u32 *)cpu, b, d_up256,
-               (const uint8_t *)cw, (const u32 *)tok_prefix, (const uint4 *)tok_rec, n_cp, prep_sym, d_high);
-        LAUNCH(ctx, tp_stream_close_docs_kernel, ceil_div_u32(Dl, BLOCK), (const u32 *)off_loc, (const u32 *)n_loc, (const u32 *)kept_tot,
-               (const u32 *)chars_tot, Dl, ch.doc_first, (u32)ch.cont_in, (u32)ch.cont_out, cin, cout, doc_sym_off_all, m_all,
-               prep_sym);
+        for (u32 x : h_counts[c]) n_cp += x;
+        tp_prepare_chunk(ctx, scratch, ch, c, n_cp, d_bytes, tb, st);
         t_queued[c] = since();
     }
     uploader.join();
@@ -354,10 +495,10 @@ static bool prepare_texts_streamed(east_hip_index *h, Ctx &ctx, const uint8_t *b
     u32 high = 0;
     TpCarry last;
     HIP_CHECK(hipEventRecord(h->ev1, h->stream));
-    HIP_CHECK(hipMemcpyAsync(h_off.data(), doc_sym_off_all, (size_t)D * 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(hipMemcpyAsync(h_m.data(), m_all, (size_t)D * 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(hipMemcpyAsync(&last, carry + (C & 1u), sizeof(last), hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(hipMemcpyAsync(&high, d_high, 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(hipMemcpyAsync(h_off.data(), st.doc_sym_off_all, (size_t)D * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(hipMemcpyAsync(h_m.data(), st.m_all, (size_t)D * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(hipMemcpyAsync(&last, st.carry + (C & 1u), sizeof(last), hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(hipMemcpyAsync(&high, st.d_high, 4, hipMemcpyDeviceToHost, h->stream));
     HIP_CHECK(hipStreamSynchronize(h->stream));
     if (g_trace) {
         fprintf(stderr, "[east_hip] streamed preparation, %u chunks (ms since its start: staged / counted / queued):", C);
@@ -371,127 +512,89 @@ static bool prepare_texts_streamed(east_hip_index *h, Ctx &ctx, const uint8_t *b
     return high == 0;
 }
 
-// The caller's Unicode tables (290 KB) stay on the device between calls (own allocation): they are uploaded again only
-// when their content changes -- a 64-bit hash over all of them, taken while the text is on its way.  With them go the two
-// 256-entry tables of the byte-wise fast path (class and upper-cased code point of a byte that is a code point of its own).
-struct TpDevTables {
-    TpTables t;
-    const uint8_t *cls256;     // the 256-entry tables of the byte-wise fast path
-    const u32 *up256;
-};
-static TpDevTables tp_upload_tables(east_hip_index *h, const uint8_t *cp_class, const u32 *cp_upper, const u32 *word_hi,
-                                    const u32 *digit_hi, const u32 *hi_upper_from, const u32 *hi_upper_to, int32_t n_hi_upper)
+// ---- the inputs that are prepared in one piece: the upload and the tokenizer ------------------------------------------
+// The whole stream to d_bytes (n_bytes + 32: the byte-class pass loads whole 16-byte groups) and the offsets to d_text_off,
+// on h->stream; a null destination is left out.
+static void upload_texts_whole(east_hip_index *h, const HostTexts &in, uint8_t *d_bytes, u32 *d_text_off)
 {
-    const size_t tb_class = 0, tb_upper = tb_class + TP_TEXT_LIMIT, tb_word = tb_upper + (size_t)TP_TEXT_LIMIT * 4,
-                 tb_digit = tb_word + (size_t)TP_WORD_HI_WORDS * 4, tb_from = tb_digit + (size_t)TP_WORD_HI_WORDS * 4,
-                 tb_to = tb_from + ((size_t)n_hi_upper + 1) * 4, tb_cls256 = tb_to + ((size_t)n_hi_upper + 1) * 4,
-                 tb_up256 = tb_cls256 + 256, tb_total = tb_up256 + 1024;
-    {
-        u64 hash = 0x9E3779B97F4A7C15ull ^ (u64)n_hi_upper;
-        auto mix = [&](const void *p, size_t bytes) {
-            const u64 *q = (const u64 *)p;
-            for (size_t i = 0; i < bytes / 8; i++) hash = (hash ^ q[i]) * 0x100000001B3ull + (hash >> 29);
-        };
-        mix(cp_class, TP_TEXT_LIMIT); mix(cp_upper, (size_t)TP_TEXT_LIMIT * 4); mix(word_hi, (size_t)TP_WORD_HI_WORDS * 4);
-        mix(digit_hi, (size_t)TP_WORD_HI_WORDS * 4);
-        for (int32_t q = 0; q < n_hi_upper; q++) hash = (hash ^ (((u64)hi_upper_from[q] << 32) | hi_upper_to[q])) * 0x100000001B3ull + (hash >> 29);
-        if (h->tp_tables.cap < tb_total || h->tp_tables_hash != hash) {
-            h->tp_tables.ensure(tb_total, "the Unicode tables", h->stream);
-            h->tp_host_tables.resize(256 + 1024);
-            uint8_t *cls256 = h->tp_host_tables.data();
-            u32 *up256 = reinterpret_cast<u32 *>(h->tp_host_tables.data() + 256);
-            for (u32 x = 0; x < 256; x++) {              // (as tp_decode_kernel: upper first, then the class of the result)
-                u32 cp = x < 0x80u ? cp_upper[x] : TP_REPLACEMENT;
-                if (cp >= TP_TEXT_LIMIT) {
-                    for (int32_t q = 0; q < n_hi_upper; q++)
-                        if (hi_upper_from[q] == cp) { cp = hi_upper_to[q]; break; }
-                }
-                u32 cls;
-                if (cp < TP_TEXT_LIMIT) cls = cp_class[cp];
-                else { const u32 k = cp - TP_TEXT_LIMIT; cls = ((word_hi[k >> 5] >> (k & 31u)) & 1u) | (((digit_hi[k >> 5] >> (k & 31u)) & 1u) << 1); }
-                cls256[x] = (uint8_t)cls;
-                up256[x] = cp;
-            }
-            char *t = h->tp_tables.p;
-            HIP_CHECK(hipMemcpyAsync(t + tb_class, cp_class, TP_TEXT_LIMIT, hipMemcpyHostToDevice, h->stream));
-            HIP_CHECK(hipMemcpyAsync(t + tb_upper, cp_upper, (size_t)TP_TEXT_LIMIT * 4, hipMemcpyHostToDevice, h->stream));
-            HIP_CHECK(hipMemcpyAsync(t + tb_word, word_hi, (size_t)TP_WORD_HI_WORDS * 4, hipMemcpyHostToDevice, h->stream));
-            HIP_CHECK(hipMemcpyAsync(t + tb_digit, digit_hi, (size_t)TP_WORD_HI_WORDS * 4, hipMemcpyHostToDevice, h->stream));
-            if (n_hi_upper) {
-                HIP_CHECK(hipMemcpyAsync(t + tb_from, hi_upper_from, (size_t)n_hi_upper * 4, hipMemcpyHostToDevice, h->stream));
-                HIP_CHECK(hipMemcpyAsync(t + tb_to, hi_upper_to, (size_t)n_hi_upper * 4, hipMemcpyHostToDevice, h->stream));
-            }
-            HIP_CHECK(hipMemcpyAsync(t + tb_cls256, cls256, 256, hipMemcpyHostToDevice, h->stream));
-            HIP_CHECK(hipMemcpyAsync(t + tb_up256, up256, 1024, hipMemcpyHostToDevice, h->stream));
-            h->tp_tables_hash = hash;                   // (the read-back below waits for the stream: the host buffers are the caller's / the handle's)
+    const u32 D = (u32)in.D, n_bytes = (u32)in.n_bytes;
+    if (d_bytes && in.texts) {                            // (the texts one by one, unjoined)
+        HIP_CHECK(hipMemsetAsync(d_bytes, 0xFF, n_bytes, h->stream));              // the separators
+        for (u32 d = 0; d < D; d++) {
+            const size_t len = (size_t)(in.off32[d + 1] - in.off32[d] - 1);
+            if (len) HIP_CHECK(hipMemcpyAsync(d_bytes + in.off32[d], in.texts[d], len, hipMemcpyHostToDevice, h->stream));
         }
+    } else if (d_bytes) {
+        HIP_CHECK(hipMemcpyAsync(d_bytes, in.bytes, n_bytes, hipMemcpyHostToDevice, h->stream));
     }
-    const uint8_t *d_class = (const uint8_t *)(h->tp_tables.p + tb_class), *d_cls256 = (const uint8_t *)(h->tp_tables.p + tb_cls256);
-    const u32 *d_upper = (const u32 *)(h->tp_tables.p + tb_upper), *d_word_hi = (const u32 *)(h->tp_tables.p + tb_word),
-              *d_digit_hi = (const u32 *)(h->tp_tables.p + tb_digit), *d_hi_from = (const u32 *)(h->tp_tables.p + tb_from),
-              *d_hi_to = (const u32 *)(h->tp_tables.p + tb_to), *d_up256 = (const u32 *)(h->tp_tables.p + tb_up256);
-    return TpDevTables{TpTables{d_class, d_upper, d_word_hi, d_digit_hi, d_hi_from, d_hi_to, (u32)n_hi_upper}, d_cls256, d_up256};
+    if (d_bytes) HIP_CHECK(hipMemsetAsync(d_bytes + n_bytes, 0, 32, h->stream));
+    if (d_text_off) HIP_CHECK(hipMemcpyAsync(d_text_off, in.off32.data(), in.off32.size() * 4, hipMemcpyHostToDevice, h->stream));
+}
+
+// bytes -> code points -> tokens of a stream that lies on the device in one piece, out of ctx.arena
+struct TpTokens {
+    u32 n_cp = 0, n_tok = 0;
+    bool bytewise = false;          // every byte a code point of its own: no cpu, the classes come from the byte table
+    u32 *cpu = nullptr, *doc_cp_off; // the code points, upper-cased; per document its first one
+    uint8_t *cw;                    // the code points' classes
+    u32 *byte_prefix, *tok_prefix;  // textprep.h, "ranks without a per-element index"
+    u32 *tstart, *tend, *tok_nd;    // n_tok + 1 each: a token's code points [tstart, tend), whether one of them is no digit
+};
+// bytewise_ok: the caller reads no code points of text in which every byte is one (it maps the kept bytes when it emits
+// them); otherwise cpu is always decoded, with one entry to spare.  Two read-backs: n_cp and n_tok.
+static TpTokens tp_tokenize(Ctx &ctx, u32 D, u32 n_bytes, const uint8_t *d_bytes, const u32 *d_text_off, const TpDevTables &tb,
+                            bool bytewise_ok)
+{
+    Arena &ar = *ctx.arena;
+    TpTokens t;
+    // (unit starts in front of every block of 256 bytes, the last entry: their total.  First only this count: text in which
+    // every byte is a code point of its own -- ASCII, Latin-1 junk -- needs no index at all, and it has to come back anyway)
+    const u32 n_bblk = ceil_div_u32(n_bytes, TP_RANK_BLOCK);
+    t.byte_prefix = ar.alloc<u32>((size_t)n_bblk + 1);
+    LAUNCH(ctx, (tp_block_counts_kernel<TpStartIn>), ceil_div_u32((u64)n_bblk + 1, 8), TpStartIn{d_bytes, n_bytes}, n_bytes, n_bblk, t.byte_prefix);
+    device_scan<ArrIn, false>(ctx, ArrIn{t.byte_prefix}, n_bblk + 1, t.byte_prefix);
+    HIP_CHECK(hipMemcpyAsync(&t.n_cp, t.byte_prefix + n_bblk, 4, hipMemcpyDeviceToHost, ctx.stream));
+    HIP_CHECK(hipStreamSynchronize(ctx.stream));          // also covers the caller's uploads
+    const u32 n_cp = t.n_cp;
+    t.bytewise = bytewise_ok && n_cp == n_bytes;
+    if (!t.bytewise) t.cpu = ar.alloc<u32>((size_t)n_cp + (bytewise_ok ? 0u : 1u));
+    t.cw = ar.alloc<uint8_t>((size_t)n_cp + 32);
+    t.doc_cp_off = ar.alloc<u32>((size_t)D + 1);
+    const u32 *ranks = t.bytewise ? nullptr : t.byte_prefix;
+    if (t.bytewise) LAUNCH(ctx, tp_classify_bytes_kernel, ceil_div_u32(n_bytes, BLOCK * 16), d_bytes, n_bytes, tb.cls256, t.cw);
+    else LAUNCH(ctx, tp_decode_kernel, ceil_div_u32(n_bytes, BLOCK), d_bytes, n_bytes, ranks, tb.t, t.cpu, t.cw);
+    LAUNCH(ctx, tp_doc_cp_offsets_kernel, ceil_div_u32((u64)D + 1, WAVES_PER_BLOCK), d_bytes, n_bytes, ranks, d_text_off, D, t.doc_cp_off);
+    // code points -> tokens (token starts in front of every block of 256 code points; the last entry: their number)
+    const u32 n_tblk = ceil_div_u32(n_cp, TP_RANK_BLOCK);
+    t.tok_prefix = ar.alloc<u32>((size_t)n_tblk + 1);
+    LAUNCH(ctx, (tp_block_counts_kernel<TpTokStartIn>), ceil_div_u32((u64)n_tblk + 1, 8), TpTokStartIn{t.cw, n_cp}, n_cp, n_tblk, t.tok_prefix);
+    device_scan<ArrIn, false>(ctx, ArrIn{t.tok_prefix}, n_tblk + 1, t.tok_prefix);
+    HIP_CHECK(hipMemcpyAsync(&t.n_tok, t.tok_prefix + n_tblk, 4, hipMemcpyDeviceToHost, ctx.stream));
+    HIP_CHECK(hipStreamSynchronize(ctx.stream));
+    const size_t n1 = (size_t)t.n_tok + 1;
+    t.tstart = ar.alloc<u32>(n1), t.tend = ar.alloc<u32>(n1), t.tok_nd = ar.alloc<u32>(n1);
+    HIP_CHECK(hipMemsetAsync(t.tok_nd, 0, n1 * 4, ctx.stream));
+    if (t.n_tok) LAUNCH(ctx, tp_token_bounds_kernel, ceil_div_u32(n_cp, BLOCK * TP_VEC), t.cw, t.tok_prefix, n_cp, t.tstart, t.tend, t.tok_nd);
+    return t;
 }
 
 // The preparation in one piece (small inputs, and kept text at or above U+0A00): d_bytes holds the whole stream.  The symbols
 // end up in h->prep_sym, the per-document offsets and string counts in h_off / h_m; returns whether the symbols are in the
 // tagged encoding.
 static bool prepare_texts_whole(east_hip_index *h, Ctx &ctx, u32 D, u32 n_bytes, const uint8_t *d_bytes, const u32 *d_text_off,
-                                u32 *d_high, const TpTables &tables, const uint8_t *d_cls256, const u32 *d_up256,
-                                std::vector<u32> &h_off, std::vector<u32> &h_m)
+                                u32 *d_high, const TpDevTables &tb, std::vector<u32> &h_off, std::vector<u32> &h_m)
 {
     Arena &ar = *ctx.arena;
-    // bytes -> code points
-    // (first only the count: text in which every byte is a code point of its own -- ASCII, Latin-1 junk -- needs no
-    // index at all, and the count has to come back to the host anyway)
-    // (unit starts in front of every block of 256 bytes -- textprep.h, "ranks without a per-element index" --; the last
-    // entry is their total)
-    const u32 n_bblk = ceil_div_u32(n_bytes, TP_RANK_BLOCK);
-    u32 *byte_prefix = ar.alloc<u32>((size_t)n_bblk + 1);
-    LAUNCH(ctx, (tp_block_counts_kernel<TpStartIn>), ceil_div_u32((u64)n_bblk + 1, 8), TpStartIn{d_bytes, n_bytes}, n_bytes, n_bblk,
-           byte_prefix);
-    device_scan<ArrIn, false>(ctx, ArrIn{byte_prefix}, n_bblk + 1, byte_prefix);
-    u32 n_cp = 0;
-    HIP_CHECK(hipMemcpyAsync(&n_cp, byte_prefix + n_bblk, 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));          // also covers off32
-    // (every byte a code point of its own: no code point array -- classes from a byte table, the kept bytes are mapped when
-    // they are emitted)
-    const bool bytewise = n_cp == n_bytes;
-    u32 *cpu = bytewise ? nullptr : ar.alloc<u32>(n_cp);
-    uint8_t *cw = ar.alloc<uint8_t>((size_t)n_cp + 32);
-    u32 *doc_cp_off = ar.alloc<u32>((size_t)D + 1);
-    if (bytewise) {
-        LAUNCH(ctx, tp_classify_bytes_kernel, ceil_div_u32(n_bytes, BLOCK * 16), (const uint8_t *)d_bytes, n_bytes,
-               (const uint8_t *)d_cls256, cw);
-    } else {
-        LAUNCH(ctx, tp_decode_kernel, ceil_div_u32(n_bytes, BLOCK), (const uint8_t *)d_bytes, n_bytes, (const u32 *)byte_prefix,
-               tables, cpu, cw);
-    }
-    LAUNCH(ctx, tp_doc_cp_offsets_kernel, ceil_div_u32(D + 1, WAVES_PER_BLOCK), (const uint8_t *)d_bytes, n_bytes,
-           bytewise ? (const u32 *)nullptr : (const u32 *)byte_prefix, (const u32 *)d_text_off, D, doc_cp_off);
-
-    // code points -> tokens (token starts in front of every block of 256 code points; the last entry: their number)
-    const u32 n_tblk = ceil_div_u32(n_cp, TP_RANK_BLOCK);
-    u32 *tok_prefix = ar.alloc<u32>((size_t)n_tblk + 1);
-    LAUNCH(ctx, (tp_block_counts_kernel<TpTokStartIn>), ceil_div_u32((u64)n_tblk + 1, 8), TpTokStartIn{cw, n_cp}, n_cp, n_tblk, tok_prefix);
-    device_scan<ArrIn, false>(ctx, ArrIn{tok_prefix}, n_tblk + 1, tok_prefix);
-    u32 n_tok = 0;
+    const TpTokens t = tp_tokenize(ctx, D, n_bytes, d_bytes, d_text_off, tb, true);
+    const u32 n_cp = t.n_cp, n_tok = t.n_tok;
+    const u32 *cpu = t.cpu, *doc_cp_off = t.doc_cp_off, *tok_prefix = t.tok_prefix, *tstart = t.tstart, *tend = t.tend, *tok_nd = t.tok_nd;
+    const uint8_t *cw = t.cw;
     u32 high = 0;
-    HIP_CHECK(hipMemcpyAsync(&n_tok, tok_prefix + n_tblk, 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    u32 *tstart = ar.alloc<u32>((size_t)n_tok + 1), *tend = ar.alloc<u32>((size_t)n_tok + 1);
     u32 *keep = ar.alloc<u32>((size_t)n_tok + 1), *klen = ar.alloc<u32>((size_t)n_tok + 1);
     u32 *keep_ex = ar.alloc<u32>((size_t)n_tok + 1), *klen_ex = ar.alloc<u32>((size_t)n_tok + 1);
-    u32 *tok_nd = ar.alloc<u32>((size_t)n_tok + 1);      // token holds a character that is not a digit
-    HIP_CHECK(hipMemsetAsync(tok_nd, 0, ((size_t)n_tok + 1) * 4, h->stream));
     HIP_CHECK(hipMemsetAsync(keep + n_tok, 0, 4, h->stream));
     HIP_CHECK(hipMemsetAsync(klen + n_tok, 0, 4, h->stream));
-    if (n_tok) {
-        LAUNCH(ctx, tp_token_bounds_kernel, ceil_div_u32(n_cp, BLOCK * TP_VEC), (const uint8_t *)cw, (const u32 *)tok_prefix, n_cp,
-               tstart, tend, tok_nd);
-        LAUNCH(ctx, tp_token_keep_kernel, ceil_div_u32(n_tok, BLOCK), (const u32 *)tstart, (const u32 *)tend,
-               (const u32 *)tok_nd, n_tok, keep, klen);
-    }
+    if (n_tok) LAUNCH(ctx, tp_token_keep_kernel, ceil_div_u32(n_tok, BLOCK), tstart, tend, tok_nd, n_tok, keep, klen);
     device_scan<ArrIn, false>(ctx, ArrIn{keep}, n_tok + 1, keep_ex);
     device_scan<ArrIn, false>(ctx, ArrIn{klen}, n_tok + 1, klen_ex);
 
@@ -499,8 +602,7 @@ static bool prepare_texts_whole(east_hip_index *h, Ctx &ctx, u32 D, u32 n_bytes,
     u32 *first_tok = ar.alloc<u32>((size_t)D + 1), *m_d = ar.alloc<u32>(D), *n_d = ar.alloc<u32>((size_t)D + 1);
     u32 *doc_sym_off = ar.alloc<u32>((size_t)D + 1);
     HIP_CHECK(hipMemsetAsync(n_d + D, 0, 4, h->stream));
-    LAUNCH(ctx, tp_doc_counts_kernel, ceil_div_u32(D + 1, WAVES_PER_BLOCK), (const u32 *)doc_cp_off, (const uint8_t *)cw, n_cp, (const u32 *)tok_prefix,
-           (const u32 *)keep_ex, (const u32 *)klen_ex, D, first_tok, m_d, n_d);
+    LAUNCH(ctx, tp_doc_counts_kernel, ceil_div_u32(D + 1, WAVES_PER_BLOCK), doc_cp_off, cw, n_cp, tok_prefix, keep_ex, klen_ex, D, first_tok, m_d, n_d);
     device_scan<ArrIn, false>(ctx, ArrIn{n_d}, D + 1, doc_sym_off);
     h_off.resize((size_t)D + 1);
     h_m.resize(D);
@@ -513,14 +615,11 @@ static bool prepare_texts_whole(east_hip_index *h, Ctx &ctx, u32 D, u32 n_bytes,
     if (n_tok) {
         u32 *tok_out = keep, *tok_term = klen;           // (keep / klen are dead once their scans exist)
         uint4 *tok_rec = ar.alloc<uint4>(n_tok);
-        LAUNCH(ctx, tp_token_out_kernel, ceil_div_u32(n_tok, BLOCK), (const u32 *)tstart, (const u32 *)keep_ex,
-               (const u32 *)klen_ex, (const u32 *)doc_cp_off, (const u32 *)first_tok, (const u32 *)doc_sym_off, D, n_tok,
-               (const u32 *)tend, tok_out, tok_term, tok_rec);
-        LAUNCH(ctx, tp_emit_kernel, ceil_div_u32(n_cp, BLOCK), (const u32 *)cpu, (const uint8_t *)d_bytes,
-               (const u32 *)d_up256, (const uint8_t *)cw, (const u32 *)tok_prefix, (const uint4 *)tok_rec, n_cp, prep_sym, d_high);
+        LAUNCH(ctx, tp_token_out_kernel, ceil_div_u32(n_tok, BLOCK), tstart, keep_ex, klen_ex, doc_cp_off, first_tok, doc_sym_off, D, n_tok, tend, tok_out,
+               tok_term, tok_rec);
+        LAUNCH(ctx, tp_emit_kernel, ceil_div_u32(n_cp, BLOCK), cpu, d_bytes, tb.up256, cw, tok_prefix, tok_rec, n_cp, prep_sym, d_high);
     }
-    LAUNCH(ctx, tp_empty_docs_kernel, ceil_div_u32(D, BLOCK), (const u32 *)first_tok, (const u32 *)keep_ex,
-           (const u32 *)doc_sym_off, D, prep_sym);
+    LAUNCH(ctx, tp_empty_docs_kernel, ceil_div_u32(D, BLOCK), first_tok, keep_ex, doc_sym_off, D, prep_sym);
     HIP_CHECK(hipEventRecord(h->ev1, h->stream));
     HIP_CHECK(hipMemcpyAsync(&high, d_high, 4, hipMemcpyDeviceToHost, h->stream));
     HIP_CHECK(hipStreamSynchronize(h->stream));
@@ -528,11 +627,8 @@ static bool prepare_texts_whole(east_hip_index *h, Ctx &ctx, u32 D, u32 n_bytes,
     const bool tagged = high != 0;
     if (tagged) {
         // kept word characters at or above U+0A00: the symbols go on in the tagged encoding
-        if (n_tok)
-            LAUNCH(ctx, tp_tag_terminators_kernel, ceil_div_u32(n_tok, BLOCK), (const u32 *)tstart, (const u32 *)tend,
-                   (const u32 *)keep, (const u32 *)klen, n_tok, prep_sym);
-        LAUNCH(ctx, tp_tag_empty_docs_kernel, ceil_div_u32(D, BLOCK), (const u32 *)first_tok, (const u32 *)keep_ex,
-               (const u32 *)doc_sym_off, D, prep_sym);
+        if (n_tok) LAUNCH(ctx, tp_tag_terminators_kernel, ceil_div_u32(n_tok, BLOCK), tstart, tend, keep, klen, n_tok, prep_sym);
+        LAUNCH(ctx, tp_tag_empty_docs_kernel, ceil_div_u32(D, BLOCK), first_tok, keep_ex, doc_sym_off, D, prep_sym);
     }
     return tagged;
 }
@@ -548,33 +644,17 @@ static void prep_publish(east_hip_index *h, const std::vector<u32> &offsets, con
     for (size_t d = 0; d < counts.size(); d++) h->prep_n_strings[d] = (int32_t)counts[d];
 }
 
-// bytes: the texts concatenated, each followed by one 0xFF byte (host pointer).
-// (texts != nullptr: the texts lie apart in host memory -- text d = texts[d], text_offsets as if they were
-// concatenated with their separators; they are uploaded one by one and never joined on the host)
-static void build_from_texts(east_hip_index *h, const uint8_t *bytes, i64 n_bytes64, const i64 *text_offsets,
-                             int32_t n_docs, const uint8_t *cp_class, const u32 *cp_upper, const u32 *word_hi,
-                             const u32 *digit_hi, const u32 *hi_upper_from, const u32 *hi_upper_to, int32_t n_hi_upper,
-                             const uint8_t *const *texts = nullptr)
+// Prepares the texts of `in` on the device -- streamed, or in one piece -- and builds the index from the symbols.
+static void build_from_texts(east_hip_index *h, HostTexts in, const UnicodeTablesHost &tables)
 {
     g_tp_call_start = std::chrono::steady_clock::now();
-    // ---- validate ----
     if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
-    if ((!bytes && !texts) || !text_offsets || !cp_class || !cp_upper || !word_hi || !digit_hi || n_docs < 1 || n_hi_upper < 0 ||
-        (n_hi_upper > 0 && (!hi_upper_from || !hi_upper_to)))
-        east_throw(EAST_HIP_ERR_INVALID, "null argument or no documents");
-    if (n_bytes64 < n_docs || n_bytes64 >= (i64)0x7FFFFFF0) east_throw(EAST_HIP_ERR_INVALID, "total bytes out of range");
-    if (text_offsets[0] != 0 || text_offsets[n_docs] != n_bytes64)
-        east_throw(EAST_HIP_ERR_INVALID, "text_offsets must start at 0 and end at the total");
-    for (int32_t d = 0; d < n_docs; d++) {
-        if (text_offsets[d + 1] <= text_offsets[d]) east_throw(EAST_HIP_ERR_INVALID, "text_offsets must increase");
-        if (texts ? (text_offsets[d + 1] - text_offsets[d] > 1 && !texts[d]) : bytes[text_offsets[d + 1] - 1] != 0xFFu)
-            east_throw(EAST_HIP_ERR_INVALID, texts ? "null text" : "every text must be followed by one 0xFF separator byte");
-    }
+    host_texts_check(in, tables);
     // ---- size the arena, upload the tables (and, in one piece, the text) ----
     use_device(h);
     h->built = false;
     h->table_scored = false;
-    const u32 n_bytes = (u32)n_bytes64, D = (u32)n_docs;
+    const u32 n_bytes = (u32)in.n_bytes, D = (u32)in.D;
     const size_t arena_before = h->arena.cap;
     size_t arena_need = (size_t)n_bytes * 46 + (size_t)D * 96 + (8u << 20);
     if (arena_before < arena_need) {
@@ -599,26 +679,11 @@ static void build_from_texts(east_hip_index *h, const uint8_t *bytes, i64 n_byte
     uint8_t *d_bytes = ar.alloc<uint8_t>((size_t)n_bytes + 32);    // (padding: the byte-class pass loads whole 16-byte groups)
     u32 *d_text_off = ar.alloc<u32>((size_t)D + 1);
     u32 *d_high = ar.alloc<u32>(1);
-    std::vector<u32> off32((size_t)D + 1);
-    for (u32 d = 0; d <= D; d++) off32[d] = (u32)text_offsets[d];
     // (large inputs: the text goes up chunk by chunk and is prepared as it arrives, see prepare_texts_streamed)
     const u32 stream_chunk = ctx.knobs.tp_stream > 0 ? (u32)std::min<i64>(ctx.knobs.tp_stream, 0x40000000)
                              : ctx.knobs.tp_stream < 0 && n_bytes >= TP_STREAM_MIN ? std::max<u32>(n_bytes / TP_STREAM_CHUNKS + 1, 1u << 20) : 0u;
-    auto upload_all = [&]() {
-        if (texts) {
-            HIP_CHECK(hipMemsetAsync(d_bytes, 0xFF, n_bytes, h->stream));              // the separators
-            for (u32 d = 0; d < D; d++) {
-                const size_t len = (size_t)(text_offsets[d + 1] - text_offsets[d] - 1);
-                if (len) HIP_CHECK(hipMemcpyAsync(d_bytes + text_offsets[d], texts[d], len, hipMemcpyHostToDevice, h->stream));
-            }
-        } else {
-            HIP_CHECK(hipMemcpyAsync(d_bytes, bytes, n_bytes, hipMemcpyHostToDevice, h->stream));
-        }
-        HIP_CHECK(hipMemsetAsync(d_bytes + n_bytes, 0, 32, h->stream));
-    };
-    if (!stream_chunk) upload_all();
-    HIP_CHECK(hipMemcpyAsync(d_text_off, off32.data(), off32.size() * 4, hipMemcpyHostToDevice, h->stream));
-    const TpDevTables tb = tp_upload_tables(h, cp_class, cp_upper, word_hi, digit_hi, hi_upper_from, hi_upper_to, n_hi_upper);
+    upload_texts_whole(h, in, stream_chunk ? nullptr : d_bytes, d_text_off);
+    const TpDevTables tb = tp_upload_tables(h, tables);
     HIP_CHECK(hipMemsetAsync(d_high, 0, 4, h->stream));
 
     // ---- the preparation: streamed, or in one piece ----
@@ -626,16 +691,15 @@ static void build_from_texts(east_hip_index *h, const uint8_t *bytes, i64 n_byte
     bool streamed = false, tagged = false;
     if (stream_chunk) {
         const size_t mark = ar.mark();
-        streamed = prepare_texts_streamed(h, ctx, bytes, texts, text_offsets, D, n_bytes, stream_chunk, d_bytes, tb.t, tb.cls256,
-                                          tb.up256, h_off, h_m);
+        streamed = prepare_texts_streamed(h, ctx, in, stream_chunk, d_bytes, tb, h_off, h_m);
         ar.release(mark);
         if (streamed) HIP_CHECK(hipEventElapsedTime(&h->last_prep_ms, h->ev0, h->ev1));
-        else upload_all();                              // (kept text at or above U+0A00: the preparation in one piece, tagged encoding)
+        else upload_texts_whole(h, in, d_bytes, nullptr);   // (kept text at or above U+0A00: the preparation in one piece, tagged encoding)
     }
-    if (!streamed) tagged = prepare_texts_whole(h, ctx, D, n_bytes, d_bytes, d_text_off, d_high, tb.t, tb.cls256, tb.up256, h_off, h_m);
+    if (!streamed) tagged = prepare_texts_whole(h, ctx, D, n_bytes, d_bytes, d_text_off, d_high, tb, h_off, h_m);
 
     // ---- publish and build ----
     prep_publish(h, h_off, h_m, h_off[D], tagged);
-    build_common(h, h->prep_sym.as<u32>(), false, h->prep_n, h->prep_doc_off.data(), h->prep_n_strings.data(), n_docs, tagged);
+    build_common(h, h->prep_sym.as<u32>(), false, h->prep_n, h->prep_doc_off.data(), h->prep_n_strings.data(), in.D, tagged);
     if (streamed) ring_pin_later(h);
 }

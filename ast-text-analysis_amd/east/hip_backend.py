@@ -290,6 +290,11 @@ def _join_free(raw):
         (len(raw) <= JOIN_FREE_RING_MAX_TEXTS and total >= JOIN_FREE_RING_BYTES and total >= JOIN_FREE_RING_MIN_MEAN * len(raw))
 
 
+def _separate(raw):
+    """The texts where they lie, for the _v entry points: (pointer array, lengths int64).  The pointers borrow from `raw`."""
+    return (ctypes.c_char_p * len(raw))(*raw), np.array([len(t) for t in raw], dtype=np.int64)
+
+
 def _joined(raw):
     """Every text followed by one 0xFF, in a single copy, and the D + 1 offsets."""
     blob = b"\xff".join(raw + [b""])
@@ -524,8 +529,7 @@ class HipIndex(_ResidentTableConsumers):
         if _join_free(raw):
             # a few large texts: uploaded one by one straight out of their bytes objects (joining 64 MiB costs
             # more host time than the device needs for the whole build)
-            ptrs = (ctypes.c_char_p * len(raw))(*raw)
-            lengths = np.array([len(t) for t in raw], dtype=np.int64)
+            ptrs, lengths = _separate(raw)
             _check(self._lib.east_hip_build_texts_v(self._h, ptrs, _ptr(lengths, _c_i64p), len(raw), *tables))
         else:
             blob, offsets = _joined(raw)
@@ -719,8 +723,7 @@ class HipCosineIndex(_ResidentTableConsumers):
         sw_cps, sw_off = pack_words(list(stopwords))
         args = _table_args() + (_ptr(sw_cps, _c_u32p), _ptr(sw_off, _c_i64p), sw_off.size - 1)
         if _join_free(raw):
-            ptrs = (ctypes.c_char_p * len(raw))(*raw)
-            lengths = np.array([len(t) for t in raw], dtype=np.int64)
+            ptrs, lengths = _separate(raw)
             _check(self._lib.east_hip_cosine_build_texts_v(self._h, ptrs, _ptr(lengths, _c_i64p), len(raw), *args))
         else:
             blob, offsets = _joined(raw)
@@ -906,13 +909,9 @@ class HipGroup(object):
         self._after_build(n_strings.size)
 
     def build_texts(self, texts):
-        raw = [t if isinstance(t, bytes) else t.encode("utf-8", errors="surrogatepass") for t in texts]
-        cls, upper, word_hi, digit_hi, hi_from, hi_to = unicode_tables()
-        ptrs = (ctypes.c_char_p * len(raw))(*raw)
-        lengths = np.array([len(t) for t in raw], dtype=np.int64)
-        _check(self._lib.east_hip_group_build_texts_v(
-            self._g, ptrs, _ptr(lengths, _c_i64p), len(raw), _ptr(cls, ctypes.POINTER(ctypes.c_uint8)), _ptr(upper, _c_u32p),
-            _ptr(word_hi, _c_u32p), _ptr(digit_hi, _c_u32p), _ptr(hi_from, _c_u32p), _ptr(hi_to, _c_u32p), hi_from.size))
+        raw = _raw_texts(texts)
+        ptrs, lengths = _separate(raw)
+        _check(self._lib.east_hip_group_build_texts_v(self._g, ptrs, _ptr(lengths, _c_i64p), len(raw), *_table_args()))
         self._from_texts = True
         self._after_build(len(raw))
 

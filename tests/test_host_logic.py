@@ -511,3 +511,49 @@ def test_bench_plain_run_options_and_dump_sampling(monkeypatch):
     assert np.array_equal(a, b) and a.ndim == 1 and 900 < a.size <= 1000 and np.all(np.diff(a) > 0)
     small = np.arange(12.0).reshape(3, 4)
     assert np.array_equal(bench._sample(small, 1000, 7), small)
+
+
+def test_the_three_build_texts_hand_the_library_the_same_pointers_and_lengths(monkeypatch):
+    """HipIndex, HipCosineIndex and HipGroup take separate texts to the _v entry points through one helper
+    (hip_backend._separate): for the same `raw` the library sees the same addresses -- those of the bytes objects, nothing
+    copied or joined -- the same lengths, the same count and the same seven table arguments."""
+    from east import hip_backend
+    raw = [b"", b"alpha", b"beta gamma delta", "été 中文".encode("utf-8"), b"\xc3 \xe2\x82 \xff"]
+    ptrs, lengths = hip_backend._separate(raw)
+    assert len(ptrs) == len(raw) and lengths.dtype == np.int64 and lengths.tolist() == [len(t) for t in raw]
+    addresses = ctypes.cast(ptrs, ctypes.POINTER(ctypes.c_void_p))
+    for d, t in enumerate(raw):
+        assert ctypes.string_at(addresses[d], len(t)) == t
+        assert addresses[d] == ctypes.cast(ctypes.c_char_p(t), ctypes.c_void_p).value       # the object's own buffer
+    assert len(hip_backend._separate([])[0]) == 0 and hip_backend._separate([])[1].size == 0
+
+    calls = {}
+
+    class Recorder(object):
+        def __getattr__(self, name):
+            def call(handle, *args):
+                if name.endswith("build_texts_v"):
+                    p, n, count = args[0], args[1], args[2]
+                    a = ctypes.cast(p, ctypes.POINTER(ctypes.c_void_p))
+                    tables = [ctypes.cast(x, ctypes.c_void_p).value for x in args[3:9]] + [int(args[9])]
+                    calls[name] = ([a[d] for d in range(count)], [n[d] for d in range(count)], count, tables)
+                return 0
+            return call
+
+    monkeypatch.setattr(hip_backend, "_join_free", lambda raw: True)
+    index = hip_backend.HipIndex.__new__(hip_backend.HipIndex)
+    index._lib, index._h, index._borrowed = Recorder(), ctypes.c_void_p(1), True
+    index.build_texts(raw)
+    cosine = hip_backend.HipCosineIndex.__new__(hip_backend.HipCosineIndex)
+    cosine._lib, cosine.index, cosine._owner = index._lib, index, False
+    cosine.build_texts(raw, stopwords=["ALPHA"])
+    group = hip_backend.HipGroup.__new__(hip_backend.HipGroup)
+    group._lib, group._g, group._after_build = index._lib, None, lambda n_docs: None
+    group.build_texts(raw)
+    assert sorted(calls) == ["east_hip_build_texts_v", "east_hip_cosine_build_texts_v", "east_hip_group_build_texts_v"]
+    want = ([addresses[d] for d in range(len(raw))], [len(t) for t in raw], len(raw))
+    for name, got in calls.items():
+        assert got[:3] == want, name
+        assert got[3] == calls["east_hip_build_texts_v"][3] and all(got[3][:4]) and got[3][6] > 0, name
+    # (str input is encoded once, by the same rule, on all three)
+    assert hip_backend._raw_texts(["\ud800x", b"y"]) == ["\ud800x".encode("utf-8", errors="surrogatepass"), b"y"]
