@@ -11,7 +11,8 @@ static bool kgram_reserve(east_hip_index *h, u64 bins, u32 n_docs);      // (sco
 
 // min pyramid over the LCP table and the annotation table: the streaming pass decides all but the widest
 // intervals and writes pyramid level 1 on the way, the upper levels follow, then the listed wide ones
-static void annotate(east_hip_index *h, Ctx &ctx)
+// (listed_total != nullptr, a test's: a zeroed device word that takes the number of ranks ann_wide_kernel decided)
+static void annotate(east_hip_index *h, Ctx &ctx, u32 *listed_total = nullptr)
 {
     const Pyramid &pyr = h->pyr;
     const u32 n = pyr.len[0];
@@ -30,8 +31,8 @@ static void annotate(east_hip_index *h, Ctx &ctx)
         LAUNCH(ctx, pyramid_level_kernel, ceil_div_u32(pyr_padded(pyr.len[l]), BLOCK), pyr.ptr[l - 1], pyr.len[l],
                pyr_padded(pyr.len[l]), (u32 *)pyr.ptr[l]);
     if (l < pyr.levels) LAUNCH(ctx, pyramid_top_kernel, 1, pyr, l);
-    LAUNCH(ctx, ann_wide_kernel, ceil_div_u32(n_tiles, BLOCK / ANN_WIDE_SLOTS), pyr, n, n_tiles, (const u32 *)wide_list,
-           (const u32 *)wide_count, h->ann);
+    LAUNCH(ctx, ann_wide_kernel, ceil_div_u32(n_tiles, ANN_WIDE_RUN) * ANN_WIDE_SLICES, pyr, n, n_tiles, (const u32 *)wide_list,
+           (const u32 *)wide_count, h->ann, listed_total);
     ar.release(mark);
 }
 

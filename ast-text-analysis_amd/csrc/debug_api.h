@@ -93,6 +93,56 @@ static void debug_first_pass_hist(int device, const u32 *symbols, i64 n64, const
     HIP_CHECK(hipStreamSynchronize(sc.stream));
 }
 
+// The annotation pass (build.h: annotate -- ann_stream_kernel, the upper pyramid, ann_wide_kernel) on a caller's table
+static void debug_annotate(int device, const u32 *lcp, i64 n64, const i64 *doc_off, int32_t n_docs, const int32_t *n_strings,
+                           u32 *ann_out, u32 *geometry_out, u32 *listed_out)
+{
+    if (!lcp || !doc_off || !n_strings || !ann_out || !geometry_out || !listed_out || n64 < 1 || n64 >= (i64)0x7FFFFFF0 ||
+        n_docs < 1 || doc_off[0] != 0 || doc_off[n_docs] != n64)
+        east_throw(EAST_HIP_ERR_INVALID, "bad annotation arguments");
+    for (int32_t d = 0; d < n_docs; d++)
+        if (doc_off[d + 1] <= doc_off[d]) east_throw(EAST_HIP_ERR_INVALID, "document offsets must increase");
+    const u32 n = (u32)n64;
+    std::vector<u32> off32((size_t)n_docs + 1), m32(n_docs);
+    for (int32_t d = 0; d <= n_docs; d++) off32[d] = (u32)doc_off[d];
+    for (int32_t d = 0; d < n_docs; d++) m32[d] = (u32)n_strings[d];
+    // table, annotation, the pyramid's upper levels (a sixteenth each), the tiles' lists and counts, the document tables
+    DebugScope sc(device, ((size_t)pyr_padded(n) * 2 + (size_t)n / 8 + (size_t)ceil_div_u32(n, ANN_TILE) * (ANN_TILE + 1) + 2 * (size_t)n_docs) * 4 +
+                              (1u << 20));
+    Arena &ar = sc.arena;
+    east_hip_index h;                   // (what annotate() reads of a handle, and no more)
+    h.lcp = ar.alloc<u32>(pyr_padded(n));
+    h.ann = ar.alloc<u32>(n);
+    h.doc_off = ar.alloc<u32>((size_t)n_docs + 1);
+    h.n_strings = ar.alloc<u32>(n_docs);
+    h.build_docs = (u32)n_docs;
+    u32 *listed = ar.alloc<u32>(1);
+    Pyramid &pyr = h.pyr;
+    pyr.levels = 1;
+    pyr.ptr[0] = h.lcp;
+    pyr.len[0] = n;
+    while (pyr.len[pyr.levels - 1] > PYR_FAN) {
+        const u32 len = ceil_div_u32(pyr.len[pyr.levels - 1], PYR_FAN);
+        pyr.ptr[pyr.levels] = ar.alloc<u32>(pyr_padded(len));
+        pyr.len[pyr.levels] = len;
+        pyr.levels++;
+    }
+    // (the table's padding and the annotation start out as something no result is: the pass writes both)
+    HIP_CHECK(hipMemsetAsync(h.lcp, 0x5A, (size_t)pyr_padded(n) * 4, sc.stream));
+    HIP_CHECK(hipMemsetAsync(h.ann, 0xEE, (size_t)n * 4, sc.stream));
+    HIP_CHECK(hipMemsetAsync(listed, 0, 4, sc.stream));
+    HIP_CHECK(hipMemcpyAsync(h.lcp, lcp, (size_t)n * 4, hipMemcpyHostToDevice, sc.stream));
+    HIP_CHECK(hipMemcpyAsync(h.doc_off, off32.data(), off32.size() * 4, hipMemcpyHostToDevice, sc.stream));
+    HIP_CHECK(hipMemcpyAsync(h.n_strings, m32.data(), m32.size() * 4, hipMemcpyHostToDevice, sc.stream));
+    annotate(&h, sc.ctx, listed);
+    HIP_CHECK(hipMemcpyAsync(ann_out, h.ann, (size_t)n * 4, hipMemcpyDeviceToHost, sc.stream));
+    HIP_CHECK(hipMemcpyAsync(listed_out, listed, 4, hipMemcpyDeviceToHost, sc.stream));
+    HIP_CHECK(hipStreamSynchronize(sc.stream));
+    geometry_out[0] = ANN_TILE;
+    geometry_out[1] = ANN_HALO;
+    geometry_out[2] = ANN_NEAR;
+}
+
 extern "C" {
 
 int east_hip_debug_set_rank_bucket_bytes(int64_t bytes)
@@ -252,6 +302,12 @@ int east_hip_debug_first_pass_hist(int device, const uint32_t *symbols, int64_t 
         else if (key_bytes == 4) debug_first_pass_hist<u32>(device, symbols, n, code_map, w, b, spare, term_first, shift, mask, s8, present, hist, group_sum, digit_total);
         else east_throw(EAST_HIP_ERR_INVALID, "key_bytes must be 4 or 8");
     });
+}
+
+int east_hip_debug_annotate(int device, const uint32_t *lcp, int64_t n, const int64_t *doc_off, int32_t n_docs,
+                            const int32_t *n_strings, uint32_t *ann_out, uint32_t *geometry_out, uint32_t *listed_out)
+{
+    return guarded([&] { debug_annotate(device, lcp, n, doc_off, n_docs, n_strings, ann_out, geometry_out, listed_out); });
 }
 
 int east_hip_debug_radix_sort_u64(int device, uint64_t *keys, uint32_t *vals, int64_t n, int bits)

@@ -568,35 +568,89 @@ __device__ __forceinline__ u32 pyr_leftmost_argmin(const Pyramid &P, u32 a, u32 
 
 // anntab (easa.py:306-331) in two launches.
 //
-// ann_stream_kernel: a workgroup stages 1024 consecutive LCP values plus ANN_HALO to either side in LDS.
-//   phase 1  every thread decides its 4 ranks from the 8 neighbours to either side (five 16-byte LDS
-//            reads); most ranks end here and the thread writes one 16-byte store;
-//   phase 2  the rest -- first l-indices of intervals wider than that, a few per cent -- go to an LDS
-//            work list and are looked at by eight lanes each over the staged values, at most ANN_LOCAL ranks
-//            to either side (one rank per thread: the tile's few dozen ranks queue up in one wavefront; a wave
-//            per rank with 64 neighbours per ballot was measured: twice as slow, the ranks then queue up
-//            behind one another);
-//   what is wider still (the top levels of the tree, about one rank in a hundred) is appended to a
-//   global list for ann_wide_kernel.
+// ann_stream_kernel: a workgroup stages ANN_TILE consecutive LCP values plus ANN_HALO to either side in LDS -- the
+//   window -- and with them the minimum of every aligned 16-rank group of the window, and the prefix and suffix minima
+//   of that row of group minima.
+//   phase 1  every thread decides 4 consecutive ranks at a time from the 8 neighbours to either side (five 16-byte
+//            LDS reads); most ranks end here and the thread writes one 16-byte store;
+//   phase 2  the rest -- first l-indices of intervals wider than that and later l-indices whose equal neighbour lies
+//            further away, a few per cent -- go to an LDS work list and are searched for by eight lanes each over the
+//            WHOLE window, in two levels: the rest of the rank's own group, then the row of group minima to the
+//            first group that holds an answer, then that group (a dozen LDS reads whatever the distance; the linear
+//            walk this replaced paid for its reach rank by rank, and a reach of 64 left 26 times more ranks to
+//            ann_wide_kernel than lie outside the window).  A rank whose answer lies outside the window learns that
+//            from the prefix / suffix minimum of its group and is listed without a search.
+//   Only the ranks whose PSE -- or, for a first l-index, whose NSV -- lies outside the window are appended to the
+//   tile's list for ann_wide_kernel (the top levels of the tree: 6 ranks in 10 000 of the 64 MiB word stream).
 //   The kernel also writes level 1 of the min pyramid (it has the values in LDS): the LCP table is read
 //   once for both.
 // ann_wide_kernel: the listed ranks, one per thread, through the pyramid (O(log16 n) groups each).
 // Document starts carry lcp == 0, which bounds every search inside the document; ranks outside
 // [0, n) read as 0.
+// A table that is not an LCP table (a speculative build after a wrong alphabet guess) is safe: every search is bounded
+// by the window, and no index is made from a table value.
 #ifndef ANN_NEAR
 #define ANN_NEAR 8
 #endif
-#define ANN_IPT 4                       // consecutive ranks per thread: 16-byte loads and stores
+// Ranks per thread, 4 or 8: one or two 16-byte loads per thread in flight (besides the halo's) and a tile of 1 024 or
+// 2 048 ranks.  Quad j of a thread holds the ranks tile_base + j * 4 * BLOCK + 4 * thread .. + 3: every load and
+// every store of a wavefront covers 1 KiB without gaps.
+#ifndef ANN_IPT
+#define ANN_IPT 8
+#endif
+#define ANN_QUADS (ANN_IPT / 4)
 #define ANN_TILE (BLOCK * ANN_IPT)
-// (round 4, with eight lanes per rank in phase 2 -- halo / walk 32 / 24, 64 / 64, 96 / 96, 128 / 128: configs[2] ann_stream +
-// ann_wide 0.77 + 0.63, 0.84 + 0.13, 0.93 + 0.13, 1.03 + 0.13 ms -- its depth-3 intervals are 51 ranks wide --; configs[1]
-// 0.16 + 0.08, 0.17 + 0.08, 0.18 + 0.07, 0.20 + 0.04; the Zipf stand-in 0.32 + 0.14, 0.37 + 0.05, ...)
+// The halo is the reach of phase 2 past the tile's ends.  Of the 64 MiB word stream's 61 142 967 ranks, 72 288 have
+// their answer outside a window of 1 024 + 2 x 64, 35 898 outside 1 024 + 2 x 128 and 35 863 outside 2 048 + 2 x 128
+// (tools/ann_reach_census.py): the depth-4 nodes of a 26-letter text are 127 +- 11 ranks wide.  A halo of 128 costs a
+// tile of 1 024 a quarter more reads than the table has, a tile of 2 048 an eighth.  (With the linear walk of rounds
+// 4-6, halo / walk 32 / 24, 64 / 64, 96 / 96, 128 / 128 gave ann_stream + ann_wide 0.77 + 0.63, 0.84 + 0.13,
+// 0.93 + 0.13, 1.03 + 0.13 ms on configs[2] and 0.16 + 0.08, 0.17 + 0.08, 0.18 + 0.07, 0.20 + 0.04 on configs[1]: the
+// walk's length was the price, not the halo's bytes.  The two-level search: DESIGN.md 5.8.)
 #ifndef ANN_HALO
-#define ANN_HALO 64
+#define ANN_HALO 128
 #endif
-#ifndef ANN_LOCAL
-#define ANN_LOCAL 64                    // phase 2 looks at most this far; what is wider goes to ann_wide_kernel
-#endif
+#define ANN_WINDOW (ANN_TILE + 2 * ANN_HALO)
+#define ANN_GROUPS (ANN_WINDOW / PYR_FAN)
+#define ANN_GROUPS_PER_LANE ((ANN_GROUPS + 63) / 64)
+static_assert(ANN_IPT == 4 || ANN_IPT == 8, "a thread holds one or two quads");
+static_assert(ANN_HALO % PYR_FAN == 0 && ANN_HALO >= ANN_NEAR + 4 && 2 * ANN_HALO / 4 <= BLOCK, "the halo: whole groups, one quad per thread");
+static_assert(ANN_TILE <= 65536, "the work list holds 16-bit tile offsets");
+
+// bits [sh, sh + 8) of a ballot: the answers of the eight lanes that share a rank
+__device__ __forceinline__ u32 ann_ballot8(bool pred, u32 sh) { return (u32)(__ballot(pred) >> sh) & 0xFFu; }
+
+// One side of phase 2, for the eight lanes (sub = 0 .. 7) of the rank at window index `at` with value v: the nearest
+// window index left of `at` holding a value <= v (LEFT), or right of it holding a value < v; NONE_U32 if the window
+// has none (or the rank does not `want` the search).  own: the rank's own group as a 16-bit mask of that predicate;
+// gedge[g]: the minimum of all groups before (LEFT) / behind group g.  Whole wavefronts call this together.
+template <bool LEFT>
+__device__ __forceinline__ u32 ann_window_search(const u32 *tile, const u32 *gmin, const u32 *gedge, bool want, u32 at,
+                                                 u32 v, u32 own, u32 sub, u32 sh)
+{
+    const u32 g = at >> PYR_SHIFT, o = at & (PYR_FAN - 1u);
+    u32 m = LEFT ? own & ((1u << o) - 1u) : own & ~((2u << o) - 1u);
+    u32 grp = g;
+    // nothing in the rest of the own group, and the groups further on do hold an answer: down the row of group minima,
+    // eight groups a step, to the first that does
+    bool walk = want && !m && (LEFT ? gedge[g] <= v : gedge[g] < v);
+    for (u32 t = 0; t < (ANN_GROUPS + 7) / 8 && __ballot(walk) != 0; t++) {
+        const u32 c = LEFT ? g - 1u - sub - 8u * t : g + 1u + sub + 8u * t;          // (LEFT: past group 0 this wraps to a number >= ANN_GROUPS)
+        const u32 x = gmin[c < ANN_GROUPS ? c : 0u];
+        const u32 h = ann_ballot8(walk && c < ANN_GROUPS && (LEFT ? x <= v : x < v), sh);
+        if (walk && h) {
+            const u32 s = (u32)__ffs((int)h) - 1u;
+            grp = LEFT ? g - 1u - 8u * t - s : g + 1u + 8u * t + s;
+            walk = false;
+        }
+    }
+    const bool fetch = want && grp != g;
+    const u32 y0 = tile[(grp << PYR_SHIFT) + sub], y1 = tile[(grp << PYR_SHIFT) + 8u + sub];
+    const u32 far = ann_ballot8(fetch && (LEFT ? y0 <= v : y0 < v), sh) | ann_ballot8(fetch && (LEFT ? y1 <= v : y1 < v), sh) << 8;
+    if (fetch) m = far;
+    if (!want || !m) return NONE_U32;
+    return (grp << PYR_SHIFT) + (LEFT ? 31u - (u32)__clz((int)m) : (u32)__ffs((int)m) - 1u);
+}
 
 __global__ __launch_bounds__(BLOCK) void ann_stream_kernel(const u32 *__restrict__ lcp, const u32 *__restrict__ doc_off,
                                                            const u32 *__restrict__ n_strings, u32 n_docs, u32 n,
@@ -605,74 +659,124 @@ __global__ __launch_bounds__(BLOCK) void ann_stream_kernel(const u32 *__restrict
                                                            u32 *__restrict__ wide_count,      // per tile: its own stretch / count
                                                            u32 *__restrict__ lcp_pad)         // != nullptr: the table's padding is still to be written
 {
-    __shared__ __attribute__((aligned(16))) u32 tile[ANN_TILE + 2 * ANN_HALO];
-    __shared__ u32 work[ANN_TILE];
+    __shared__ __attribute__((aligned(16))) u32 tile[ANN_WINDOW];
+    // minimum of every 16-rank group of the window (over the staged values: ranks outside [0, n) count as 0), and per
+    // group the minimum of all groups before it / behind it
+    __shared__ u32 gmin[ANN_GROUPS], gbefore[ANN_GROUPS], gbehind[ANN_GROUPS];
+    __shared__ uint16_t work[ANN_TILE];
     __shared__ u32 work_count, far_count;
     if (threadIdx.x == 0) { work_count = 0; far_count = 0; }
+    const u32 n_padded = pyr_padded_dev(n);
     // (the entries between n and the next multiple of 16 -- the pyramid searches of ann_wide_kernel read whole groups;
     // nothing in this kernel depends on them: ranks outside [0, n) are masked below)
-    if (lcp_pad && blockIdx.x == gridDim.x - 1 && threadIdx.x < PYR_FAN && n + threadIdx.x < ((n + PYR_FAN - 1u) & ~(PYR_FAN - 1u)))
+    if (lcp_pad && blockIdx.x == gridDim.x - 1 && threadIdx.x < PYR_FAN && n + threadIdx.x < n_padded)
         lcp_pad[n + threadIdx.x] = NONE_U32;
     const u32 tile_base = blockIdx.x * ANN_TILE;
-    const u32 k0 = tile_base + threadIdx.x * ANN_IPT;
     {
-        // own four values (the table is padded to a multiple of 16 entries, so whole groups can be loaded up
-        // to there); ranks outside [0, n) read as 0, which stops every scan
-        uint4 x = {0u, 0u, 0u, 0u};
-        if (k0 < ((n + PYR_FAN - 1u) & ~(PYR_FAN - 1u))) x = *reinterpret_cast<const uint4 *>(lcp + k0);
-        if (k0 + 0 >= n) x.x = 0u;
-        if (k0 + 1 >= n) x.y = 0u;
-        if (k0 + 2 >= n) x.z = 0u;
-        if (k0 + 3 >= n) x.w = 0u;
-        // (the halo is requested before the stretch is staged: one round trip for both)
+        // own quads (the table is padded to a multiple of 16 entries, so whole groups can be loaded up to there) and the
+        // halo, all requested before anything is staged: one round trip; ranks outside [0, n) read as 0, which stops
+        // every scan
+        uint4 x[ANN_QUADS];
+#pragma unroll
+        for (int j = 0; j < ANN_QUADS; j++) {
+            const u32 k0 = tile_base + (u32)j * 4u * BLOCK + threadIdx.x * 4u;
+            x[j] = uint4{0u, 0u, 0u, 0u};
+            if (k0 < n_padded) x[j] = *reinterpret_cast<const uint4 *>(lcp + k0);
+        }
         const bool has_halo = threadIdx.x < 2 * ANN_HALO / 4;       // ANN_HALO ranks to the left (first threads) and to the right (the next ones)
         const bool left = threadIdx.x < ANN_HALO / 4;
         const u32 q = left ? threadIdx.x : threadIdx.x - ANN_HALO / 4;
         const i64 g = left ? (i64)tile_base - ANN_HALO + 4 * q : (i64)tile_base + ANN_TILE + 4 * q;
         uint4 h = {0u, 0u, 0u, 0u};
-        if (has_halo && g >= 0 && g < (i64)((n + PYR_FAN - 1u) & ~(PYR_FAN - 1u))) h = *reinterpret_cast<const uint4 *>(lcp + g);
-        *reinterpret_cast<uint4 *>(&tile[ANN_HALO + threadIdx.x * ANN_IPT]) = x;
+        if (has_halo && g >= 0 && g < (i64)n_padded) h = *reinterpret_cast<const uint4 *>(lcp + g);
+#pragma unroll
+        for (int j = 0; j < ANN_QUADS; j++) {
+            const u32 local0 = (u32)j * 4u * BLOCK + threadIdx.x * 4u, k0 = tile_base + local0;
+            if (k0 + 0 >= n) x[j].x = 0u;
+            if (k0 + 1 >= n) x[j].y = 0u;
+            if (k0 + 2 >= n) x[j].z = 0u;
+            if (k0 + 3 >= n) x[j].w = 0u;
+            *reinterpret_cast<uint4 *>(&tile[ANN_HALO + local0]) = x[j];
+            // (a group is four threads' quads)
+            u32 m = min(min(x[j].x, x[j].y), min(x[j].z, x[j].w));
+            m = min(m, (u32)__shfl_xor((int)m, 1));
+            m = min(m, (u32)__shfl_xor((int)m, 2));
+            if ((threadIdx.x & 3u) == 0) gmin[(ANN_HALO + local0) >> PYR_SHIFT] = m;
+        }
+        if (g + 0 >= (i64)n) h.x = 0u;
+        if (g + 1 >= (i64)n) h.y = 0u;
+        if (g + 2 >= (i64)n) h.z = 0u;
+        if (g + 3 >= (i64)n) h.w = 0u;
+        const u32 at = left ? 4 * q : ANN_HALO + ANN_TILE + 4 * q;
+        u32 m = min(min(h.x, h.y), min(h.z, h.w));
+        m = min(m, (u32)__shfl_xor((int)m, 1));
+        m = min(m, (u32)__shfl_xor((int)m, 2));
         if (has_halo) {
-            if (g + 0 >= (i64)n) h.x = 0u;
-            if (g + 1 >= (i64)n) h.y = 0u;
-            if (g + 2 >= (i64)n) h.z = 0u;
-            if (g + 3 >= (i64)n) h.w = 0u;
-            *reinterpret_cast<uint4 *>(&tile[left ? 4 * q : ANN_HALO + ANN_TILE + 4 * q]) = h;
+            *reinterpret_cast<uint4 *>(&tile[at]) = h;
+            if ((threadIdx.x & 3u) == 0) gmin[at >> PYR_SHIFT] = m;
         }
     }
     __syncthreads();
-    // level 1 of the min pyramid: entry e = min of the 16 ranks 16e .. 16e+15 (entries past the table: NONE)
-    if (threadIdx.x < ANN_TILE / PYR_FAN) {
-        const u32 e = tile_base / PYR_FAN + threadIdx.x;
+    // the row of group minima from either end, one wavefront each: a lane takes ANN_GROUPS_PER_LANE consecutive groups
+    if (wave_id() < 2) {
+        const bool fwd = wave_id() == 0;
+        const u32 lane = lane_id();
+        u32 mine[ANN_GROUPS_PER_LANE], all = NONE_U32;
+#pragma unroll
+        for (u32 i = 0; i < ANN_GROUPS_PER_LANE; i++) {
+            const u32 gi = lane * ANN_GROUPS_PER_LANE + i;
+            mine[i] = gi < ANN_GROUPS ? gmin[gi] : NONE_U32;
+            all = min(all, mine[i]);
+        }
+        // run = minimum over the lanes before this one (fwd) / behind it
+        u32 inc = all;
+#pragma unroll
+        for (u32 d = 1; d < 64; d <<= 1) {
+            const u32 other = fwd ? (u32)__shfl_up((int)inc, d) : (u32)__shfl_down((int)inc, d);
+            if (fwd ? lane >= d : lane + d < 64u) inc = min(inc, other);
+        }
+        u32 run = fwd ? (u32)__shfl_up((int)inc, 1) : (u32)__shfl_down((int)inc, 1);
+        if (fwd ? lane == 0 : lane == 63u) run = NONE_U32;
+#pragma unroll
+        for (u32 i = 0; i < ANN_GROUPS_PER_LANE; i++) {
+            const u32 ii = fwd ? i : ANN_GROUPS_PER_LANE - 1u - i;
+            const u32 gi = lane * ANN_GROUPS_PER_LANE + ii;
+            if (gi < ANN_GROUPS) (fwd ? gbefore : gbehind)[gi] = run;
+            run = min(run, mine[ii]);
+        }
+    }
+    // level 1 of the min pyramid: entry e = min of the 16 ranks 16e .. 16e+15 (entries past the table: NONE); the last
+    // threads write it, the first ones are busy above
+    if (threadIdx.x >= BLOCK - ANN_TILE / PYR_FAN) {
+        const u32 i = threadIdx.x - (BLOCK - ANN_TILE / PYR_FAN);
+        const u32 e = tile_base / PYR_FAN + i;
         if (e < len1_padded) {
             u32 m = NONE_U32;
             if (e < len1) {
-                const uint4 *g = reinterpret_cast<const uint4 *>(&tile[ANN_HALO + threadIdx.x * PYR_FAN]);
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const uint4 y = g[q];
-                    const u32 r = e * PYR_FAN + 4u * q;          // (ranks past n hold 0 in the tile: not part of the minimum)
-                    if (r + 0 < n) m = min(m, y.x);
-                    if (r + 1 < n) m = min(m, y.y);
-                    if (r + 2 < n) m = min(m, y.z);
-                    if (r + 3 < n) m = min(m, y.w);
+                if ((e + 1u) * PYR_FAN <= n) m = gmin[ANN_HALO / PYR_FAN + i];
+                else {
+                    // (the table ends inside this group: its ranks past n hold 0 in the tile and are not part of the minimum)
+                    for (u32 r = e * PYR_FAN; r < n; r++) m = min(m, tile[ANN_HALO + (r - tile_base)]);
                 }
             }
             lvl1[e] = m;
         }
     }
-    if (k0 < n) {
-        // c[i] = lcp[k0 - ANN_NEAR + i]: the thread's 4 ranks and ANN_NEAR ranks to either side
-        u32 c[ANN_IPT + 2 * ANN_NEAR];
 #pragma unroll
-        for (int q = 0; q < (ANN_IPT + 2 * ANN_NEAR) / 4; q++) {
-            const uint4 x = *reinterpret_cast<const uint4 *>(&tile[ANN_HALO + threadIdx.x * ANN_IPT - ANN_NEAR + 4 * q]);
+    for (int j = 0; j < ANN_QUADS; j++) {
+        const u32 local0 = (u32)j * 4u * BLOCK + threadIdx.x * 4u, k0 = tile_base + local0;
+        if (k0 >= n) continue;
+        // c[i] = lcp[k0 - ANN_NEAR + i]: the quad's 4 ranks and ANN_NEAR ranks to either side
+        u32 c[4 + 2 * ANN_NEAR];
+#pragma unroll
+        for (int q = 0; q < (4 + 2 * ANN_NEAR) / 4; q++) {
+            const uint4 x = *reinterpret_cast<const uint4 *>(&tile[ANN_HALO + local0 - ANN_NEAR + 4 * q]);
             c[4 * q] = x.x; c[4 * q + 1] = x.y; c[4 * q + 2] = x.z; c[4 * q + 3] = x.w;
         }
-        u32 out[ANN_IPT];
-        bool direct[ANN_IPT];
+        u32 out[4];
+        bool direct[4];
 #pragma unroll
-        for (int e = 0; e < ANN_IPT; e++) {
+        for (int e = 0; e < 4; e++) {
             const u32 k = k0 + e;
             const int i = ANN_NEAR + e;                  // c[i] = lcp[k]
             const u32 v = c[i];
@@ -700,72 +804,82 @@ __global__ __launch_bounds__(BLOCK) void ann_stream_kernel(const u32 *__restrict
                 else out[e] = fwd + back;
             }
         }
-        if (direct[0] && direct[1] && direct[2] && direct[3] && k0 + ANN_IPT <= n) {
+        if (direct[0] && direct[1] && direct[2] && direct[3] && k0 + 4 <= n) {
             *reinterpret_cast<uint4 *>(ann + k0) = uint4{out[0], out[1], out[2], out[3]};
         } else {
 #pragma unroll
-            for (int e = 0; e < ANN_IPT; e++) {
+            for (int e = 0; e < 4; e++) {
                 if (k0 + e >= n) break;
                 if (direct[e]) ann[k0 + e] = out[e];
-                else work[atomicAdd(&work_count, 1u)] = threadIdx.x * ANN_IPT + e;
+                else work[atomicAdd(&work_count, 1u)] = (uint16_t)(local0 + e);
             }
         }
     }
     __syncthreads();
-    // phase 2: EIGHT lanes per rank -- lane q looks at the distances q + 1, q + 9, q + 17, ... to either side, the nearest hit
-    // of the eight comes from three shuffles.  (One rank per thread left a tile's two or three dozen ranks to the first
-    // lanes of ONE wavefront, each walking up to 2 x ANN_LOCAL dependent LDS reads while the other wavefronts waited at the
-    // barrier; a whole wavefront per rank was measured before and is slower still: the ranks queue up.)
+    // phase 2: EIGHT lanes per rank, and every wavefront goes through the steps as one (the eight lanes of a rank put
+    // their answers together with ballots).  (One rank per thread left a tile's two or three dozen ranks to the first
+    // lanes of ONE wavefront while the other wavefronts waited at the barrier; a whole wavefront per rank was measured
+    // before and is slower still: the ranks queue up.)
     const u32 count = work_count;
-    const u32 sub = threadIdx.x & 7u;
-    for (u32 wi = threadIdx.x >> 3; wi < count; wi += BLOCK / 8) {
-        const u32 local = work[wi], at = ANN_HALO + local;
+    const u32 sub = threadIdx.x & 7u, sh = lane_id() & 56u;
+    for (u32 first_wi = 0; first_wi < count; first_wi += BLOCK / 8) {
+        const u32 wi = first_wi + (threadIdx.x >> 3);
+        const bool on = wi < count;
+        const u32 local = on ? work[wi] : 0u, at = ANN_HALO + local;
         const u32 v = tile[at];
-        constexpr u32 NONE_D = ANN_LOCAL + 1;
-        u32 d = NONE_D;
-#pragma unroll
-        for (u32 t = 0; t < (ANN_LOCAL + 7) / 8; t++) {
-            const u32 dist = 1u + sub + 8u * t;
-            if (dist <= ANN_LOCAL && d == NONE_D && tile[at - dist] <= v) d = dist;
-        }
-        d = min(d, (u32)__shfl_xor((int)d, 1, 8));
-        d = min(d, (u32)__shfl_xor((int)d, 2, 8));
-        d = min(d, (u32)__shfl_xor((int)d, 4, 8));
-        bool far = d == NONE_D;
-        u32 a = 0;
-        if (!far && tile[at - d] < v) {                     // first l-index: width = NSV - PSV
-            u32 e = NONE_D;
-#pragma unroll
-            for (u32 t = 0; t < (ANN_LOCAL + 7) / 8; t++) {
-                const u32 dist = 1u + sub + 8u * t;
-                if (dist <= ANN_LOCAL && e == NONE_D && tile[at + dist] < v) e = dist;
-            }
-            e = min(e, (u32)__shfl_xor((int)e, 1, 8));
-            e = min(e, (u32)__shfl_xor((int)e, 2, 8));
-            e = min(e, (u32)__shfl_xor((int)e, 4, 8));
-            if (e == NONE_D) far = true;
-            else a = d + e;
-        }
-        if (sub == 0) {
+        // the rank's own group, once for both sides
+        const u32 g0 = at & ~(PYR_FAN - 1u);
+        const u32 y0 = tile[g0 + sub], y1 = tile[g0 + 8u + sub];
+        const u32 le = ann_ballot8(y0 <= v, sh) | ann_ballot8(y1 <= v, sh) << 8;
+        const u32 lt = ann_ballot8(y0 < v, sh) | ann_ballot8(y1 < v, sh) << 8;
+        const u32 p = ann_window_search<true>(tile, gmin, gbefore, on, at, v, le, sub, sh);
+        const bool first = on && p != NONE_U32 && tile[p] < v;       // first l-index: width = NSV - PSV; a later one carries 0
+        const u32 q = ann_window_search<false>(tile, gmin, gbehind, first, at, v, lt, sub, sh);
+        if (on && sub == 0) {
             // (the tile's own stretch of the list: a single counter for all workgroups would serialise them)
-            if (far) wide_list[tile_base + atomicAdd(&far_count, 1u)] = tile_base + local;
-            else ann[tile_base + local] = a;
+            if (p == NONE_U32 || (first && q == NONE_U32)) wide_list[tile_base + atomicAdd(&far_count, 1u)] = tile_base + local;
+            else ann[tile_base + local] = first ? q - p : 0u;
         }
     }
     __syncthreads();
     if (threadIdx.x == 0) wide_count[blockIdx.x] = far_count;
 }
 
-#define ANN_WIDE_SLOTS 16                // threads per tile in ann_wide_kernel
+// The listed ranks are few and unevenly spread (0.6 per tile of the 64 MiB word stream, every rank of a one-letter
+// text): ANN_WIDE_SLICES workgroups share a run of ANN_WIDE_RUN tiles.  Each scans the run's counts and takes every
+// ANN_WIDE_SLICES-th stretch of BLOCK entries of the run -- entry j belongs to the tile t with off[t] <= j < off[t + 1].
+// A short list is dealt out evenly over the threads of the first workgroups, and where every rank is listed a thread
+// has as many searches to do one after the other as it had with 16 threads for every tile of 1 024.
+#define ANN_WIDE_RUN 64                  // tiles per run: one wavefront scans their counts
+#define ANN_WIDE_SLICES 8                // workgroups per run
 __global__ __launch_bounds__(BLOCK) void ann_wide_kernel(Pyramid P, u32 n, u32 n_tiles, const u32 *__restrict__ wide_list,
-                                                         const u32 *__restrict__ wide_count, u32 *__restrict__ ann)
+                                                         const u32 *__restrict__ wide_count, u32 *__restrict__ ann,
+                                                         u32 *__restrict__ listed_total)      // != nullptr (tests): + the ranks that came through here
 {
+    __shared__ u32 off[ANN_WIDE_RUN + 1];
     const u32 *lcp = P.ptr[0];
-    const u32 tile = blockIdx.x * (BLOCK / ANN_WIDE_SLOTS) + threadIdx.x / ANN_WIDE_SLOTS;
-    if (tile >= n_tiles) return;
-    const u32 count = wide_count[tile];
-    for (u32 i = threadIdx.x % ANN_WIDE_SLOTS; i < count; i += ANN_WIDE_SLOTS) {
-        const u32 k = wide_list[tile * ANN_TILE + i];
+    const u32 tile0 = blockIdx.x / ANN_WIDE_SLICES * ANN_WIDE_RUN, slice = blockIdx.x % ANN_WIDE_SLICES;
+    if (threadIdx.x < ANN_WIDE_RUN) {
+        const u32 t = tile0 + threadIdx.x;
+        u32 inc = t < n_tiles ? wide_count[t] : 0u;
+#pragma unroll
+        for (u32 d = 1; d < ANN_WIDE_RUN; d <<= 1) {
+            const u32 other = (u32)__shfl_up((int)inc, d);
+            if (threadIdx.x >= d) inc += other;
+        }
+        off[threadIdx.x + 1] = inc;
+        if (threadIdx.x == 0) off[0] = 0;
+    }
+    __syncthreads();
+    const u32 total = off[ANN_WIDE_RUN];
+    if (listed_total && slice == 0 && threadIdx.x == 0 && total) atomicAdd(listed_total, total);
+    for (u32 j = slice * BLOCK + threadIdx.x; j < total; j += ANN_WIDE_SLICES * BLOCK) {
+        u32 lo = 0, hi = ANN_WIDE_RUN;                          // invariant: off[lo] <= j < off[hi]
+        while (hi - lo > 1) {
+            const u32 mid = (lo + hi) >> 1;
+            if (off[mid] <= j) lo = mid; else hi = mid;
+        }
+        const u32 k = wide_list[(size_t)(tile0 + lo) * ANN_TILE + (j - off[lo])];
         const u32 v = lcp[k];
         u32 pse, nsv;                                           // pse exists: the segment start holds 0;
         pyr_find_both(P, k, v, pse, nsv);                       // the search to the right stops at the next segment start
@@ -775,6 +889,7 @@ __global__ __launch_bounds__(BLOCK) void ann_wide_kernel(Pyramid P, u32 n, u32 n
         ann[k] = a;
     }
 }
+static_assert(ANN_WIDE_RUN == 64, "one wavefront scans a run's counts");
 
 // The three child tables, positions local to the document, 0 = none (easa.py:268-304), in two launches like the
 // annotation table.  child_stream_kernel stages 1024 LCP values + CH_HALO to either side in LDS.  For every rank: the

@@ -75,6 +75,8 @@ SIGNATURES = {
                                                       ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int,
                                                       ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint8), _c_u32p, _c_u32p,
                                                       _c_u32p, _c_u32p]),
+    "east_hip_debug_annotate": (ctypes.c_int, [ctypes.c_int, _c_u32p, ctypes.c_int64, _c_i64p, ctypes.c_int32, _c_i32p,
+                                               _c_u32p, _c_u32p, _c_u32p]),
     "east_hip_debug_set_score_scratch": (ctypes.c_int, [ctypes.c_int64]),
     "east_hip_debug_set_score_path": (ctypes.c_int, [ctypes.c_int]),
     "east_hip_debug_set_score_grid": (ctypes.c_int, [ctypes.c_int64]),

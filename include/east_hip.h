@@ -581,6 +581,13 @@ int east_hip_debug_set_speculation(int enabled);
 int east_hip_debug_first_pass_hist(int device, const uint32_t *symbols, int64_t n, const uint32_t *code_map, int key_bytes,
                                    int w, int b, int spare, uint32_t term_first, int shift, uint32_t mask, uint8_t *s8,
                                    uint32_t *present, uint32_t *hist, uint32_t *group_sum, uint32_t *digit_total);
+/* Kernel-level test of the annotation pass (csrc/build.h: annotate -- ann_stream_kernel, the upper levels of the min
+ * pyramid, ann_wide_kernel): the pass the build runs, on the caller's table lcp[n] of n_docs documents (doc_off: n_docs + 1
+ * rank offsets, n_strings per document as in east_hip_build).  The table need not be an LCP table.  ann_out[n]: the
+ * annotation table; geometry_out[3]: the tile, the halo and the near reach the library was compiled with (csrc/tables.h:
+ * ANN_TILE, ANN_HALO, ANN_NEAR); listed_out: the number of ranks that went through ann_wide_kernel. */
+int east_hip_debug_annotate(int device, const uint32_t *lcp, int64_t n, const int64_t *doc_off, int32_t n_docs,
+                            const int32_t *n_strings, uint32_t *ann_out, uint32_t *geometry_out, uint32_t *listed_out);
 /* Test knob: bytes of per-suffix scratch a score call may use (default 1 GiB; 0 restores it); a table over
  * more documents than fit is scored a stretch of documents at a time.  Takes effect at the next
  * east_hip_set_keyphrases / east_hip_score_table. */
