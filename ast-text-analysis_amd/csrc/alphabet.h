@@ -46,13 +46,13 @@ __global__ __launch_bounds__(BLOCK) void presence_kernel(const u32 *__restrict__
 
 // Dense codes of the text alphabet from the presence bitmap: code point c -> its rank (1 ..) among the code
 // points present, 0 if absent; flags[FLAG_SIGMA] = their number.  One workgroup, ten code points per thread.
-// `assumed` != NONE: the host went ahead with that alphabet size (speculative build); a different one, or a
-// document that does not end in a terminator (doc_status), is recorded in flags[FLAG_STATUS].
+// `assumed` != NONE: the host went ahead with that alphabet size (speculative build); a different one is recorded in
+// flags[FLAG_STATUS].
 #define FLAG_CAPPED 0
 #define FLAG_STATUS 1
 #define FLAG_SIGMA 2
-#define FLAG_KEEP 3
-#define FLAG_FAIL 4
+#define FLAG_KEEP 3              // a boolean: a speculative build that expected no rounds left suffixes in large groups (set by the placement's workgroups)
+#define FLAG_FAIL 4              // ... and its placement gave up on a long repeat, where that is not FLAG_PLACE_FAIL itself (spec_counts_kernel)
 #define FLAG_SIGMA_HI 5
 #define FLAG_PLACE_FAIL 6        // the placement pass's "a repeat too long to order directly" (window_sort.h: fail), zeroed with the flags
 #define FLAG_KG_BAD 7            // the fused finish could not mark every k-gram bucket start (Ctx::kg_bad)
@@ -66,9 +66,8 @@ __global__ __launch_bounds__(BLOCK) void presence_kernel(const u32 *__restrict__
 // kept outside the arena.  A speculative build has already turned the symbols into bytes with that map
 // (presence_remap_kernel); `check` then compares the bitmaps -- any difference, and the bytes are wrong: STATUS_SIGMA_GUESS --,
 // and in any case the guess is replaced by what this build found.
-__global__ __launch_bounds__(BLOCK) void codemap_kernel(const u32 *__restrict__ present, u32 assumed,
-                                                        u32 *__restrict__ code_map, u32 *__restrict__ flags,
-                                                        u32 *__restrict__ guess = nullptr, int check = 0)
+__device__ __forceinline__ void codemap_block(const u32 *__restrict__ present, u32 assumed, u32 *__restrict__ code_map,
+                                              u32 *__restrict__ flags, u32 *__restrict__ guess, int check)
 {
     if (guess && threadIdx.x < PRESENT_WORDS) {
         u32 *gp = guess + TEXT_SYMBOLS;
@@ -95,10 +94,26 @@ __global__ __launch_bounds__(BLOCK) void codemap_kernel(const u32 *__restrict__ 
     }
     if (threadIdx.x == 0) {
         flags[FLAG_SIGMA] = total;
-        u32 st = present[PRESENT_WORDS] & STATUS_NO_TERMINATOR;
+        u32 st = 0;
         if (assumed != 0xFFFFFFFFu && assumed != total) st |= STATUS_SIGMA_GUESS;
         if (st) atomicOr(&flags[FLAG_STATUS], st);
     }
+}
+
+// The code map and, in the same launch, the check that every document ends in a terminator (memory safety: it stops every
+// suffix comparison).  Every workgroup looks at its BLOCK documents and ORs what it finds straight into the status flag --
+// nothing crosses workgroups --, and workgroup 0 makes the code map besides.
+__global__ __launch_bounds__(BLOCK) void validate_codemap_kernel(const u32 *__restrict__ sym, const u32 *__restrict__ doc_off,
+                                                                 u32 n_docs, u32 tagged, const u32 *__restrict__ present,
+                                                                 u32 assumed, u32 *__restrict__ code_map,
+                                                                 u32 *__restrict__ flags, u32 *__restrict__ guess, int check)
+{
+    const u32 d = blockIdx.x * BLOCK + threadIdx.x;
+    if (d < n_docs) {
+        const u32 c = sym[doc_off[d + 1] - 1];
+        if (tagged ? !(c >> 31) : c < TEXT_SYMBOLS) atomicOr(&flags[FLAG_STATUS], STATUS_NO_TERMINATOR);
+    }
+    if (blockIdx.x == 0) codemap_block(present, assumed, code_map, flags, guess, check);
 }
 
 // Planning sample ("The plan of a first build"): SAMPLE_N consecutive suffixes of the raw symbol stream;
@@ -170,7 +185,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_prefix_kernel(const u32
 }
 
 // Speculative build: presence bitmap AND byte stream in one pass over the symbols, the bytes through the code map of
-// the handle's last build (guess; codemap_kernel finds out whether that was right).  16-byte aligned input only.
+// the handle's last build (guess; validate_codemap_kernel finds out whether that was right).  16-byte aligned input only.
 __global__ __launch_bounds__(BLOCK) void presence_remap_kernel(const u32 *__restrict__ sym, u32 n,
                                                                const u32 *__restrict__ guess, u32 *__restrict__ present,
                                                                uint8_t *__restrict__ s8)
@@ -332,17 +347,6 @@ __global__ __launch_bounds__(BLOCK) void remap_bytes_kernel(const u32 *__restric
             s8[j] = v;
         }
     }
-}
-
-// memory safety: every document must end in a terminator (it stops every suffix comparison)
-__global__ __launch_bounds__(BLOCK) void validate_last_symbol_kernel(const u32 *__restrict__ sym,
-                                                                     const u32 *__restrict__ doc_off, u32 n_docs,
-                                                                     u32 tagged, u32 *__restrict__ status)
-{
-    const u32 d = blockIdx.x * BLOCK + threadIdx.x;
-    if (d >= n_docs) return;
-    const u32 c = sym[doc_off[d + 1] - 1];
-    if (tagged ? !(c >> 31) : c < TEXT_SYMBOLS) atomicOr(status, STATUS_NO_TERMINATOR);
 }
 
 // n_strings[d] must equal the terminators of document d.  Terminators sort above every text

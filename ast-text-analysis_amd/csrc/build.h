@@ -10,7 +10,7 @@
 static bool kgram_reserve(east_hip_index *h, u64 bins, u32 n_docs);      // (score_host.h: the build marks the score walk's k-gram tables)
 
 // min pyramid over the LCP table and the annotation table: the streaming pass decides all but the widest
-// intervals and writes pyramid level 1 on the way, the upper levels follow, then the listed wide ones
+// intervals and writes pyramid levels 1 and 2 on the way, the upper levels follow, then the listed wide ones
 // (listed_total != nullptr, a test's: a zeroed device word that takes the number of ranks ann_wide_kernel decided)
 static void annotate(east_hip_index *h, Ctx &ctx, u32 *listed_total = nullptr)
 {
@@ -21,12 +21,14 @@ static void annotate(east_hip_index *h, Ctx &ctx, u32 *listed_total = nullptr)
     const u32 n_tiles = ceil_div_u32(n, ANN_TILE);
     u32 *wide_list = ar.alloc<u32>((size_t)n_tiles * ANN_TILE);       // every tile has its own stretch
     u32 *wide_count = ar.alloc<u32>(n_tiles);
-    const bool has_lvl1 = pyr.levels > 1;                // (a table of at most 16 entries has no level 1)
+    const bool has_lvl1 = pyr.levels > 1;                // (a table of at most 16 entries has no level 1,
+    const bool has_lvl2 = pyr.levels > 2;                // one of at most 256 no level 2)
     LAUNCH(ctx, ann_stream_kernel, n_tiles, pyr.ptr[0], (const u32 *)h->doc_off, (const u32 *)h->n_strings,
            h->build_docs, n, h->ann, has_lvl1 ? (u32 *)pyr.ptr[1] : (u32 *)nullptr, has_lvl1 ? pyr.len[1] : 0u,
-           has_lvl1 ? pyr_padded(pyr.len[1]) : 0u, wide_list, wide_count, h->lcp);
-    // the levels above: one launch each while they are large, the top of the pyramid in a single one
-    int l = 2;
+           has_lvl1 ? pyr_padded(pyr.len[1]) : 0u, wide_list, wide_count, h->lcp,
+           has_lvl2 ? (u32 *)pyr.ptr[2] : (u32 *)nullptr, has_lvl2 ? pyr.len[2] : 0u, has_lvl2 ? pyr_padded(pyr.len[2]) : 0u);
+    // the levels above those two: one launch each while they are large, the top of the pyramid in a single one
+    int l = 3;
     for (; l < pyr.levels && pyr.len[l] > PYR_TOP; l++)
         LAUNCH(ctx, pyramid_level_kernel, ceil_div_u32(pyr_padded(pyr.len[l]), BLOCK), pyr.ptr[l - 1], pyr.len[l],
                pyr_padded(pyr.len[l]), (u32 *)pyr.ptr[l]);
@@ -124,8 +126,8 @@ static void build_impl(east_hip_index *h, Ctx &ctx, const u32 *d_sym, u32 n, u32
     h->up = ar.alloc<u32>(n);
     h->down = ar.alloc<u32>(n);
     h->next = ar.alloc<u32>(n);
-    h->doc_off = ar.alloc<u32>((size_t)n_docs + 1);
-    h->n_strings = ar.alloc<u32>(n_docs);
+    h->doc_off = ar.alloc<u32>(2 * (size_t)n_docs + 1);  // (one block, n_strings behind the offsets: they go up in one copy)
+    h->n_strings = h->doc_off + n_docs + 1;
     // + the flag words (FLAG_*) + the presence bitmap and its status word + the budget of deep LCP comparisons + the digit
     // totals of the first-level sort (a row set for the pass counted ahead, two for the sort): everything one fill zeroes
     constexpr size_t ZEROED_WORDS = FLAG_WORDS + PRESENT_WORDS + 1 + LCP_BUDGET_SLOTS, TOTAL_WORDS = (size_t)RS_TOTAL_SHARDS * RS_BINS;
@@ -147,14 +149,13 @@ static void build_impl(east_hip_index *h, Ctx &ctx, const u32 *d_sym, u32 n, u32
     h->build_docs = n_docs;
 
     // ---- host-side small tables ---------------------------------------------
-    std::vector<u32> off32((size_t)n_docs + 1), m32(n_docs);
+    std::vector<u32> off32(2 * (size_t)n_docs + 1);       // the offsets, then n_strings: the device block's layout
     u32 longest_doc = ctx.dry ? n : 0;                    // (sizing run: as if one document held everything)
     if (!ctx.dry) {
         for (u32 d = 0; d <= n_docs; d++) off32[d] = (u32)doc_offsets[d];
         for (u32 d = 0; d < n_docs; d++) longest_doc = std::max(longest_doc, off32[d + 1] - off32[d]);
-        for (u32 d = 0; d < n_docs; d++) m32[d] = (u32)n_strings[d];
+        for (u32 d = 0; d < n_docs; d++) off32[(size_t)n_docs + 1 + d] = (u32)n_strings[d];
         HIP_CHECK(hipMemcpyAsync(h->doc_off, off32.data(), off32.size() * 4, hipMemcpyHostToDevice, ctx.stream));
-        HIP_CHECK(hipMemcpyAsync(h->n_strings, m32.data(), m32.size() * 4, hipMemcpyHostToDevice, ctx.stream));
     }
 
     const u32 gn = ceil_div_u32(n, BLOCK);
@@ -162,7 +163,7 @@ static void build_impl(east_hip_index *h, Ctx &ctx, const u32 *d_sym, u32 n, u32
     u32 sigma_hi = tagged ? HI_SYMBOLS : 0;
     u32 *flags = h->code_map + TEXT_SYMBOLS;              // flag words behind the code map
     u32 *capped = flags + FLAG_CAPPED, *status = flags + FLAG_STATUS;
-    u32 *present = flags + FLAG_WORDS;                    // PRESENT_WORDS + 1 (status word): zeroed in the same fill
+    u32 *present = flags + FLAG_WORDS;                    // PRESENT_WORDS + 1 (a spare word): zeroed in the same fill
     if (!ctx.dry) HIP_CHECK(hipMemsetAsync(flags, 0, (ZEROED_WORDS + 3 * TOTAL_WORDS) * sizeof(u32), ctx.stream));
     ctx.zeroed_totals = ctx.dry ? nullptr : flags + ZEROED_WORDS + TOTAL_WORDS;
     // Speculative build of one document whose first level the build before sorted on fixed-width text keys: the remap
@@ -184,6 +185,7 @@ static void build_impl(east_hip_index *h, Ctx &ctx, const u32 *d_sym, u32 n, u32
     ctx.lcp_budget.per_slot = std::max<u32>(n / 256u / LCP_BUDGET_SLOTS, 4u);
     ctx.spec_out = flags + FLAG_KEEP;
     ctx.zeroed_word = ctx.dry ? nullptr : flags + FLAG_PLACE_FAIL;
+    ctx.spec_fail = flags + FLAG_PLACE_FAIL;
     ctx.kg_bad = ctx.dry ? nullptr : flags + FLAG_KG_BAD;
     {
         // ---- alphabet, dense remap ---------------------------------------------
@@ -191,6 +193,7 @@ static void build_impl(east_hip_index *h, Ctx &ctx, const u32 *d_sym, u32 n, u32
         u32 *term_ex = ar.alloc<u32>((size_t)n + 1);      // wide-alphabet path only
         const int vec = ((uintptr_t)d_sym & 15u) == 0;
         const bool fused = ctx.spec && vec && h->guess.p;     // (the bytes come out of the same pass, through the last build's map)
+        ctx.map_checked = fused && !ctx.dry;                  // (only then does the code map's kernel compare the two bitmaps)
         if (fused && fp.valid && !ctx.dry) {
             first_hist.s8 = h->s8;
             first_hist.key_bytes = fp.key_bytes; first_hist.w = fp.w; first_hist.b = fp.b; first_hist.spare = fp.spare;
@@ -208,16 +211,15 @@ static void build_impl(east_hip_index *h, Ctx &ctx, const u32 *d_sym, u32 n, u32
             ctx.first_hist = &first_hist;
         } else if (fused) LAUNCH(ctx, presence_remap_kernel, std::min<u32>(gn, 2048), d_sym, n, h->guess.as<const u32>(), present, h->s8);
         else LAUNCH(ctx, presence_kernel, std::min<u32>(gn, 2048), d_sym, n, vec, present);
-        LAUNCH(ctx, validate_last_symbol_kernel, ceil_div_u32(n_docs, BLOCK), d_sym, (const u32 *)h->doc_off, n_docs,
-               (u32)tagged, present + PRESENT_WORDS);
         if (tagged) {
             if (!ctx.dry) HIP_CHECK(hipMemsetAsync(h->hi_bits, 0, HI_WORDS * 4, ctx.stream));
             LAUNCH_BLOCK(ctx, presence_hi_kernel, std::min<u32>(ceil_div_u32(n, PRESENCE_HI_THREADS), 256), PRESENCE_HI_THREADS,
                          d_sym, n, h->hi_bits, status);
             LAUNCH(ctx, hi_rank_kernel, 1, (const u32 *)h->hi_bits, h->hi_rank, flags);
         }
-        LAUNCH(ctx, codemap_kernel, 1, (const u32 *)present, ctx.spec ? spec_sigma : 0xFFFFFFFFu, h->code_map, flags, h->guess.as<u32>(),
-               (int)fused);
+        // (+ every document's last symbol: one launch for the check and the code map)
+        LAUNCH(ctx, validate_codemap_kernel, ceil_div_u32(n_docs, BLOCK), d_sym, (const u32 *)h->doc_off, n_docs, (u32)tagged,
+               (const u32 *)present, ctx.spec ? spec_sigma : 0xFFFFFFFFu, h->code_map, flags, h->guess.as<u32>(), (int)fused);
         ctx.sample_n = 0;
         ctx.rep_n = ctx.rep_dup = 0;
         bool sample_plans = false;                          // the sample is large enough to plan the window and the fused finish from
@@ -516,6 +518,7 @@ static void build_common(east_hip_index *h, const u32 *sym, bool sym_on_host, i6
     use_device(h);
     h->built = false;
     h->table_scored = false;
+    const u64 map_epoch_before = h->map_epoch++;         // (handle.h; put back below by a build that confirms the code map)
     const Knobs kn = knobs_snapshot();                   // (the test knobs of this call, from its sizing run to its last launch)
     const u32 n = (u32)n_total;
     // (host symbols of the reference encoding go up as 16-bit words where that pays: upload_symbols_narrow)
@@ -613,12 +616,16 @@ static void build_common(east_hip_index *h, const u32 *sym, bool sym_on_host, i6
     const bool speculate = kn.speculate && kn.window_sort && h->hint_valid && h->hint_window && h->hint_sigma <= 254 && !tagged;
     const bool spec_rounds = speculate && h->hint_no_rounds;
     const bool went_through = run(speculate, spec_rounds);
-    if (speculate && (!went_through || (flags[FLAG_STATUS] & STATUS_SIGMA_GUESS) ||
-                      (spec_rounds && (flags[FLAG_KEEP] || flags[FLAG_FAIL])))) {
+    const bool repeat = speculate && (!went_through || (flags[FLAG_STATUS] & STATUS_SIGMA_GUESS) ||
+                                      (spec_rounds && (flags[FLAG_KEEP] || flags[FLAG_FAIL] || flags[FLAG_PLACE_FAIL])));
+    if (repeat) {
         if (g_trace) fprintf(stderr, "[east_hip] speculative build guessed wrong: building again\n");
         h->stats = Stats();
         run(false, false);
     }
+    // (the presence bitmap of the build before, hence its code map -- where the two bitmaps were compared: a speculative
+    // build from a symbol pointer that is not 16-byte aligned only has its alphabet SIZE checked)
+    const bool map_confirmed = speculate && !repeat && ctx.map_checked;
     const u32 status = flags[FLAG_STATUS];
     if (status & STATUS_NO_TERMINATOR)
         east_throw(EAST_HIP_ERR_DOMAIN, "a document does not end in a string terminator (>= U+0A00)");
@@ -656,6 +663,7 @@ static void build_common(east_hip_index *h, const u32 *sym, bool sym_on_host, i6
     h->n_docs = (u32)n_docs;
     h->h_doc_off.assign(doc_offsets, doc_offsets + n_docs + 1);
     h->h_n_strings.assign(n_strings, n_strings + n_docs);
+    if (map_confirmed) h->map_epoch = map_epoch_before;
     h->built = true;
     ring_pin_later(h);
 }

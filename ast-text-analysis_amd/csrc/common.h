@@ -256,7 +256,10 @@ struct Ctx {
     // end of the build finds out; a wrong guess costs a second, non-speculative build.
     bool spec = false;          // the build does not wait for the alphabet (it uses the last build's)
     bool spec_rounds = false;   // ... nor for the placement pass's counts (it goes on as if no tie group were large)
-    u32 *spec_out = nullptr;    // [0] suffixes left in large groups, [1] placement gave up on a long repeat
+    u32 *spec_out = nullptr;    // [0] != 0: suffixes were left in large groups, [1] placement gave up on a long repeat
+    bool map_checked = false;   // this build compared its presence bitmap with the build before's (validate_codemap_kernel, check): no
+                                // STATUS_SIGMA_GUESS then means the same code map
+    u32 *spec_fail = nullptr;   // the flag word build_common reads for the latter besides [1]: the placement's own fail word, where it is that word
     u32 *zeroed_word = nullptr; // one word the build has already zeroed: the first level-0 pass takes it for its fail flag
     u32 *zeroed_totals = nullptr;   // 2 * RS_TOTAL_SHARDS * RS_BINS words likewise: the digit totals of the first unsegmented radix sort
     // Speculative build: the first level's first radix pass as the build before ran it (FirstPassPlan), and -- where the

@@ -310,6 +310,25 @@ int east_hip_debug_annotate(int device, const uint32_t *lcp, int64_t n, const in
     return guarded([&] { debug_annotate(device, lcp, n, doc_off, n_docs, n_strings, ann_out, geometry_out, listed_out); });
 }
 
+int east_hip_debug_pyramid_level(east_hip_handle_t h, int32_t level, uint32_t *out, int64_t capacity, int64_t *geometry_out)
+{
+    return guarded([&] {
+        if (!h || !geometry_out) east_throw(EAST_HIP_ERR_INVALID, "null handle or output");
+        if (!h->built) east_throw(EAST_HIP_ERR_NOT_BUILT, "no index has been built on this handle");
+        geometry_out[0] = h->pyr.levels;
+        geometry_out[1] = geometry_out[2] = 0;
+        if (level < 0 || level >= h->pyr.levels) return;     // (the caller learns the number of levels)
+        const u32 len = h->pyr.len[level], padded = pyr_padded(len);
+        geometry_out[1] = len;
+        geometry_out[2] = padded;
+        if (!out) return;
+        if (capacity < (i64)padded) east_throw(EAST_HIP_ERR_INVALID, "the output is smaller than the padded level");
+        use_device(h);
+        HIP_CHECK(hipMemcpyAsync(out, h->pyr.ptr[level], (size_t)padded * 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+    });
+}
+
 int east_hip_debug_radix_sort_u64(int device, uint64_t *keys, uint32_t *vals, int64_t n, int bits)
 {
     return guarded([&] { debug_sort<u64>(device, keys, vals, n, bits); });

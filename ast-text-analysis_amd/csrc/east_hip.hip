@@ -231,8 +231,12 @@ int east_hip_set_keyphrases(east_hip_handle_t h, const uint32_t *q_symbols, cons
 int east_hip_score_resident(east_hip_handle_t h, int normalized, double *d_out)
 {
     return guarded([&] {
-        score_resident(h, normalized);
-        if (d_out)
+        // A small table goes to the caller's block from the score kernels themselves (every score written twice: a copy's
+        // launch costs more than its bytes).  A large one is copied behind the walk: its 8-byte stores are the strided side
+        // of the kernel, and doubling them cost 29 us at 10 000 x 256 where the copy takes 13.
+        const bool direct = d_out && h && (u64)h->n_kp * h->n_docs <= SCORE_DIRECT_OUT_MAX;
+        score_resident(h, normalized, nullptr, nullptr, direct ? d_out : nullptr);
+        if (d_out && !direct)
             HIP_CHECK(hipMemcpyAsync(d_out, h->table, (size_t)h->n_kp * h->n_docs * 8, hipMemcpyDeviceToDevice,
                                      h->stream));
         HIP_CHECK(hipStreamSynchronize(h->stream));
@@ -330,6 +334,7 @@ int east_hip_reset(east_hip_handle_t h)
         h->n_docs = 0;
         h->n_kp = 0;
         h->n_q = 0;
+        h->q_code_epoch = 0;
         h->kg_built = false;
         h->child_built = false;
         h->prep_n = 0;

@@ -52,6 +52,10 @@ struct east_hip_index {
     DevBuf q_buf;
     u32 n_kp = 0, n_q = 0, score_chunk = 0;     // score_chunk: documents per stretch the scratch was sized for
     u32 *q_raw = nullptr, *q_code = nullptr, *q_end = nullptr, *q_off = nullptr, *group_off = nullptr;
+    // q_code is a function of the resident keyphrases and the code map: map_epoch advances with every build that may have
+    // changed the map (all but a speculative build whose alphabet guess was confirmed: same presence bitmap, same map),
+    // q_code_epoch is the epoch q_code was made under (0: not made -- new keyphrases)
+    u64 map_epoch = 1, q_code_epoch = 0;
     u32 *q_blk = nullptr;        // whole keyphrases per workgroup of the score walk: [q_blk[i], q_blk[i + 1]), n_blk of them
     u32 n_blk = 0;               // (0: a keyphrase is longer than a workgroup -- the walk writes per-suffix results, a second kernel sums)
     double *suffix = nullptr, *table = nullptr, *table_g = nullptr;

@@ -561,7 +561,8 @@ __global__ __launch_bounds__(BLOCK) void score_walk_kernel(
     const u32 *__restrict__ n_strings, u32 n_docs, const u32 *__restrict__ q_code,
     const u32 *__restrict__ q_end, u32 n_q, int normalized, KgTables kt, int xcd_order, u32 doc_first, u32 doc_count,
     double *__restrict__ suffix_out, unsigned long long *__restrict__ probe_count, const u32 *__restrict__ blk, u32 n_blk,
-    const u32 *__restrict__ q_off, double *__restrict__ table)
+    const u32 *__restrict__ q_off, double *__restrict__ table,
+    double *__restrict__ table2 = nullptr)               // != nullptr: the caller's block takes every score too (same index)
 {
     // XCD-aware work order: workgroups go round-robin over the 8 XCDs, each with its own 4 MB L2.  All the
     // keyphrase suffixes of ONE document are walked by ONE XCD (document d belongs to XCD d mod 8, which takes
@@ -627,7 +628,9 @@ __global__ __launch_bounds__(BLOCK) void score_walk_kernel(
         const u32 b = q_off[k] - s0, e = q_off[k + 1] - s0;
         double total = 0.0;
         for (u32 i = b; i < e; i++) total += res[i];      // easa.py:130, in suffix order
-        table[(u64)k * n_docs + d] = total / (double)(e - b);   // easa.py:134
+        const double score = total / (double)(e - b);     // easa.py:134
+        table[(u64)k * n_docs + d] = score;
+        if (table2) table2[(u64)k * n_docs + d] = score;
     }
 }
 
@@ -660,7 +663,8 @@ __global__ __launch_bounds__(BLOCK) void kgram_pairs_end_kernel(const u32 *__res
 __global__ __launch_bounds__(BLOCK) void score_reduce_kernel(const double *__restrict__ suffix,
                                                              const u32 *__restrict__ q_off,
                                                              u32 n_kp, u32 n_docs, u32 n_q, u32 doc_first, u32 doc_count,
-                                                             double *__restrict__ out)
+                                                             double *__restrict__ out,
+                                                             double *__restrict__ out2 = nullptr)    // (as score_walk_kernel's table2)
 {
     // neighbouring threads take neighbouring keyphrases of ONE document: their suffix results lie side by
     // side in that document's row (the 8-byte stores into the K x D table are the strided side: 13x fewer)
@@ -672,7 +676,9 @@ __global__ __launch_bounds__(BLOCK) void score_reduce_kernel(const double *__res
     const double *row = suffix + (u64)d * n_q;
     double total = 0.0;
     for (u32 i = b; i < e; i++) total += row[i];          // easa.py:130
-    out[(u64)k * n_docs + doc_first + d] = total / (double)(e - b);   // easa.py:134
+    const double score = total / (double)(e - b);         // easa.py:134
+    out[(u64)k * n_docs + doc_first + d] = score;
+    if (out2) out2[(u64)k * n_docs + doc_first + d] = score;
 }
 
 // Synonym-expanded scoring (easa.py:27-34): every keyphrase was expanded into its variants (the product of the

@@ -26,6 +26,7 @@ static void set_keyphrases(east_hip_index *h, const u32 *q_symbols, const i64 *q
         east_throw(EAST_HIP_ERR_INVALID, "keyphrase set too large");
     use_device(h);
     h->table_scored = false;
+    h->q_code_epoch = 0;
     const u32 n_q = (u32)S;
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const Knobs kn = knobs_snapshot();
@@ -149,9 +150,12 @@ static void ensure_kgram(east_hip_index *h, Ctx &ctx)
     h->kg_bins = (u32)bins;
 }
 
-// queues the score kernels; result in h->table (K x D) / h->suffix (D x S)
+#define SCORE_DIRECT_OUT_MAX ((u64)1 << 18)     // scores (2 MiB): up to here east_hip_score_resident's block is written by the kernels
+
+// queues the score kernels; result in h->table (K x D) / h->suffix (D x S), and -- table_out != nullptr, device memory --
+// in the caller's block as well: the kernels write every score to both
 static void score_resident(east_hip_index *h, int normalized, unsigned long long *probe_count = nullptr,
-                           double *suffix_host = nullptr)
+                           double *suffix_host = nullptr, double *table_out = nullptr)
 {
     if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
     if (!h->built) east_throw(EAST_HIP_ERR_NOT_BUILT, "no index has been built on this handle");
@@ -160,9 +164,12 @@ static void score_resident(east_hip_index *h, int normalized, unsigned long long
     Ctx ctx = handle_ctx(h);
     HIP_CHECK(hipEventRecord(h->ev0, h->stream));
     ensure_kgram(h, ctx);
-    LAUNCH(ctx, query_map_kernel, ceil_div_u32(h->n_q, BLOCK), (const u32 *)h->q_raw, h->n_q,
-           (const u32 *)h->code_map, (const u32 *)h->hi_bits, (const u32 *)h->hi_rank,
-           h->sigma_hi ? h->sigma_t - h->sigma_hi + 1u : 0u, h->q_code);
+    if (h->q_code_epoch != h->map_epoch) {               // (the same keyphrases under the same code map: q_code stands)
+        LAUNCH(ctx, query_map_kernel, ceil_div_u32(h->n_q, BLOCK), (const u32 *)h->q_raw, h->n_q,
+               (const u32 *)h->code_map, (const u32 *)h->hi_bits, (const u32 *)h->hi_rank,
+               h->sigma_hi ? h->sigma_t - h->sigma_hi + 1u : 0u, h->q_code);
+        h->q_code_epoch = h->map_epoch;
+    }
     KgTables kt;
     kt.kg = h->kg.as<u32>(); kt.kg3 = h->kg3; kt.k = h->kg_k; kt.pairs = h->kg_k > 0 && h->kg_pairs; kt.A = h->kg_A; kt.bins = h->kg_bins;
     if (kt.pairs && h->kg_up_stride && h->kg_up) {
@@ -197,15 +204,15 @@ static void score_resident(east_hip_index *h, int normalized, unsigned long long
             LAUNCH_NAMED(ctx, "score_walk_kernel", (score_walk_kernel<uint8_t>), walk_grid, (const uint8_t *)h->s8,
                          (const u32 *)h->sa, (const u32 *)h->doc_off, (const u32 *)h->n_strings, h->n_docs,
                          (const u32 *)h->q_code, (const u32 *)h->q_end, h->n_q, normalized, kt, xcd_order, first, count, suffix,
-                         probe_count, blk, h->n_blk, (const u32 *)h->q_off, h->table);
+                         probe_count, blk, h->n_blk, (const u32 *)h->q_off, h->table, fused ? table_out : (double *)nullptr);
         else
             LAUNCH_NAMED(ctx, "score_walk_kernel", (score_walk_kernel<u32>), walk_grid, (const u32 *)h->s,
                          (const u32 *)h->sa, (const u32 *)h->doc_off, (const u32 *)h->n_strings, h->n_docs,
                          (const u32 *)h->q_code, (const u32 *)h->q_end, h->n_q, normalized, kt, xcd_order, first, count, suffix,
-                         probe_count, blk, h->n_blk, (const u32 *)h->q_off, h->table);
+                         probe_count, blk, h->n_blk, (const u32 *)h->q_off, h->table, fused ? table_out : (double *)nullptr);
         if (!fused)
             LAUNCH(ctx, score_reduce_kernel, ceil_div_u32((u64)h->n_kp * count, BLOCK), (const double *)h->suffix,
-                   (const u32 *)h->q_off, h->n_kp, h->n_docs, h->n_q, first, count, h->table);
+                   (const u32 *)h->q_off, h->n_kp, h->n_docs, h->n_q, first, count, h->table, table_out);
         if (suffix_host)                                  // the per-suffix results of this stretch of documents (D x S, row-major)
             HIP_CHECK(hipMemcpyAsync(suffix_host + (size_t)first * h->n_q, h->suffix, (size_t)count * h->n_q * 8,
                                      hipMemcpyDeviceToHost, h->stream));

@@ -582,8 +582,8 @@ __device__ __forceinline__ u32 pyr_leftmost_argmin(const Pyramid &P, u32 a, u32 
 //            from the prefix / suffix minimum of its group and is listed without a search.
 //   Only the ranks whose PSE -- or, for a first l-index, whose NSV -- lies outside the window are appended to the
 //   tile's list for ann_wide_kernel (the top levels of the tree: 6 ranks in 10 000 of the 64 MiB word stream).
-//   The kernel also writes level 1 of the min pyramid (it has the values in LDS): the LCP table is read
-//   once for both.
+//   The kernel also writes levels 1 and 2 of the min pyramid (it has the values in LDS): the LCP table is read
+//   once for all three, and the upper pyramid starts at level 3.
 // ann_wide_kernel: the listed ranks, one per thread, through the pyramid (O(log16 n) groups each).
 // Document starts carry lcp == 0, which bounds every search inside the document; ranks outside
 // [0, n) read as 0.
@@ -616,6 +616,8 @@ __device__ __forceinline__ u32 pyr_leftmost_argmin(const Pyramid &P, u32 a, u32 
 static_assert(ANN_IPT == 4 || ANN_IPT == 8, "a thread holds one or two quads");
 static_assert(ANN_HALO % PYR_FAN == 0 && ANN_HALO >= ANN_NEAR + 4 && 2 * ANN_HALO / 4 <= BLOCK, "the halo: whole groups, one quad per thread");
 static_assert(ANN_TILE <= 65536, "the work list holds 16-bit tile offsets");
+static_assert(ANN_TILE % (PYR_FAN * PYR_FAN) == 0 && (ANN_TILE / PYR_FAN) % 64 == 0,
+              "a tile is whole level-2 groups, and whole wavefronts hold its level-1 entries");
 
 // bits [sh, sh + 8) of a ballot: the answers of the eight lanes that share a rank
 __device__ __forceinline__ u32 ann_ballot8(bool pred, u32 sh) { return (u32)(__ballot(pred) >> sh) & 0xFFu; }
@@ -657,7 +659,8 @@ __global__ __launch_bounds__(BLOCK) void ann_stream_kernel(const u32 *__restrict
                                                            u32 *__restrict__ ann, u32 *__restrict__ lvl1, u32 len1,
                                                            u32 len1_padded, u32 *__restrict__ wide_list,
                                                            u32 *__restrict__ wide_count,      // per tile: its own stretch / count
-                                                           u32 *__restrict__ lcp_pad)         // != nullptr: the table's padding is still to be written
+                                                           u32 *__restrict__ lcp_pad,         // != nullptr: the table's padding is still to be written
+                                                           u32 *__restrict__ lvl2, u32 len2, u32 len2_padded)   // != nullptr: level 2 of the pyramid
 {
     __shared__ __attribute__((aligned(16))) u32 tile[ANN_WINDOW];
     // minimum of every 16-rank group of the window (over the staged values: ranks outside [0, n) count as 0), and per
@@ -747,19 +750,30 @@ __global__ __launch_bounds__(BLOCK) void ann_stream_kernel(const u32 *__restrict
     }
     // level 1 of the min pyramid: entry e = min of the 16 ranks 16e .. 16e+15 (entries past the table: NONE); the last
     // threads write it, the first ones are busy above
-    if (threadIdx.x >= BLOCK - ANN_TILE / PYR_FAN) {
+    if (threadIdx.x >= BLOCK - ANN_TILE / PYR_FAN) {        // (whole wavefronts: the shuffles below)
         const u32 i = threadIdx.x - (BLOCK - ANN_TILE / PYR_FAN);
         const u32 e = tile_base / PYR_FAN + i;
-        if (e < len1_padded) {
-            u32 m = NONE_U32;
-            if (e < len1) {
-                if ((e + 1u) * PYR_FAN <= n) m = gmin[ANN_HALO / PYR_FAN + i];
-                else {
-                    // (the table ends inside this group: its ranks past n hold 0 in the tile and are not part of the minimum)
-                    for (u32 r = e * PYR_FAN; r < n; r++) m = min(m, tile[ANN_HALO + (r - tile_base)]);
-                }
+        u32 m = NONE_U32;
+        if (e < len1) {
+            if ((e + 1u) * PYR_FAN <= n) m = gmin[ANN_HALO / PYR_FAN + i];
+            else {
+                // (the table ends inside this group: its ranks past n hold 0 in the tile and are not part of the minimum)
+                for (u32 r = e * PYR_FAN; r < n; r++) m = min(m, tile[ANN_HALO + (r - tile_base)]);
             }
-            lvl1[e] = m;
+        }
+        if (e < len1_padded) lvl1[e] = m;
+        // level 2 (lvl2 != nullptr: the pyramid has one): a tile is ANN_TILE / 256 aligned groups of 16 level-1 entries,
+        // each held by 16 consecutive lanes -- entries past the level count as NONE, as its padding does
+        if (lvl2) {
+            u32 m2 = m;
+#pragma unroll
+            for (u32 d = 1; d < PYR_FAN; d <<= 1) m2 = min(m2, (u32)__shfl_xor((int)m2, (int)d));
+            const u32 e2 = tile_base / (PYR_FAN * PYR_FAN) + i / PYR_FAN;
+            if ((i & (PYR_FAN - 1u)) == 0 && e2 < len2_padded) lvl2[e2] = e2 < len2 ? m2 : NONE_U32;
+            // (the tiles cover a multiple of ANN_TILE / 256 entries, the level is padded to a multiple of 16: the last tile
+            // writes what is left of the padding)
+            if (blockIdx.x == gridDim.x - 1)
+                for (u32 p = gridDim.x * (ANN_TILE / (PYR_FAN * PYR_FAN)) + i; p < len2_padded; p += ANN_TILE / PYR_FAN) lvl2[p] = NONE_U32;
         }
     }
 #pragma unroll
@@ -852,13 +866,22 @@ __global__ __launch_bounds__(BLOCK) void ann_stream_kernel(const u32 *__restrict
 // has as many searches to do one after the other as it had with 16 threads for every tile of 1 024.
 #define ANN_WIDE_RUN 64                  // tiles per run: one wavefront scans their counts
 #define ANN_WIDE_SLICES 8                // workgroups per run
+#define ANN_WIDE_GROUP 8u                // runs per group of the block order = the XCDs workgroups are dealt over (not the slices)
 __global__ __launch_bounds__(BLOCK) void ann_wide_kernel(Pyramid P, u32 n, u32 n_tiles, const u32 *__restrict__ wide_list,
                                                          const u32 *__restrict__ wide_count, u32 *__restrict__ ann,
                                                          u32 *__restrict__ listed_total)      // != nullptr (tests): + the ranks that came through here
 {
     __shared__ u32 off[ANN_WIDE_RUN + 1];
     const u32 *lcp = P.ptr[0];
-    const u32 tile0 = blockIdx.x / ANN_WIDE_SLICES * ANN_WIDE_RUN, slice = blockIdx.x % ANN_WIDE_SLICES;
+    // Workgroups are dealt round-robin over the 8 XCDs, and a short list only has work for slice 0 of every run: with the
+    // slice as blockIdx.x % 8 all of those sat on ONE XCD.  Slice-major inside groups of ANN_WIDE_GROUP runs (64 consecutive workgroups;
+    // the last group: what is left): the slice-0 workgroups are 8 consecutive ones of every 64, one per XCD, and the eight
+    // slices of a run still run side by side (slice-major over the whole grid starts them far apart: measured + 8 % where
+    // every rank is listed)
+    const u32 n_runs = gridDim.x / ANN_WIDE_SLICES;
+    const u32 group = blockIdx.x / (ANN_WIDE_GROUP * ANN_WIDE_SLICES), j = blockIdx.x % (ANN_WIDE_GROUP * ANN_WIDE_SLICES);
+    const u32 group_runs = min(ANN_WIDE_GROUP, n_runs - group * ANN_WIDE_GROUP);
+    const u32 tile0 = (group * ANN_WIDE_GROUP + j % group_runs) * ANN_WIDE_RUN, slice = j / group_runs;
     if (threadIdx.x < ANN_WIDE_RUN) {
         const u32 t = tile0 + threadIdx.x;
         u32 inc = t < n_tiles ? wide_count[t] : 0u;

@@ -764,7 +764,8 @@ __global__ __launch_bounds__(BLOCK) void lvl0_place_kernel(KeyNeqWindowIn<K> f, 
                                                           u32 *__restrict__ names_g, u32 *__restrict__ lcp_g,
                                                           u64 *__restrict__ keep, u32 *__restrict__ block_keep,
                                                           u32 *__restrict__ fail, LongRepeats lr_arg, KgMark km,
-                                                          uint8_t *__restrict__ xdep0 = nullptr, SegRanks sr = SegRanks())
+                                                          uint8_t *__restrict__ xdep0 = nullptr, SegRanks sr = SegRanks(),
+                                                          u32 *__restrict__ spec_keep = nullptr)      // (as FinishArgs::spec_keep)
 {
     const LongRepeats lr = OPTIMISTIC ? LongRepeats() : lr_arg;
     constexpr u32 limit = ENDGAME_LIMITS ? REFINE_ENDGAME_GROUP : REFINE_SMALL_GROUP;
@@ -1037,7 +1038,10 @@ __global__ __launch_bounds__(BLOCK) void lvl0_place_kernel(KeyNeqWindowIn<K> f, 
     if (threadIdx.x < BLOCK * PLACE_IPT / 64)
         keep[(size_t)blockIdx.x * (BLOCK * PLACE_IPT / 64) + threadIdx.x] =
             ((u64)keep_bits[2 * threadIdx.x + 1] << 32) | keep_bits[2 * threadIdx.x];
-    if (threadIdx.x == 0) block_keep[blockIdx.x] = n_keep;
+    if (threadIdx.x == 0) {
+        block_keep[blockIdx.x] = n_keep;
+        if (spec_keep && n_keep) spec_keep[0] = 1u;
+    }
 }
 
 // ---- the fused end of the sort: last digit + placement in one pass ---------------------------------
@@ -1085,6 +1089,7 @@ template <class K> struct FinishArgs {
     u32 *order_g, *lcp_g;
     u64 *keep, *gstart;                     // one bit per rank (zeroed; OR-ed into): left to the rounds / first of its group
     u32 *block_keep, *fail, *kg_bad;
+    u32 *spec_keep = nullptr;               // != nullptr (a speculative build that expects no rounds): set to 1 by every workgroup that keeps a suffix
     KgMark km;
     // variable-length code words in the keys (ht_code.h; ht_sb = 0: fixed-width fields): stream bits, the least whole
     // symbols the TOP part of a key holds (the depth the rounds start from), the decode table, and per rank handed to the
@@ -1600,7 +1605,10 @@ __global__ __launch_bounds__(BLOCK) void lvl0_finish_kernel(FinishArgs<K> a)
         if (kb) atomicOr(reinterpret_cast<u32 *>(a.keep) + (bit0 >> 5), kb);
         if (gb) atomicOr(reinterpret_cast<u32 *>(a.gstart) + (bit0 >> 5), gb);
     }
-    if (tid == 0) a.block_keep[blockIdx.x] = n_keep;
+    if (tid == 0) {
+        a.block_keep[blockIdx.x] = n_keep;
+        if (a.spec_keep && n_keep) a.spec_keep[0] = 1u;
+    }
 }
 
 // group starts kept as one bit per rank (the fused finish): the naming predicate of the first compaction
@@ -2122,9 +2130,15 @@ static bool dc3_level0_bytes(Ctx &ctx, const uint8_t *s8, u32 n0, u32 n02, int w
         clear_add(ctx, clears, gstart_bits, (((size_t)n02 >> 6) + 2) * sizeof(u64), 0);
     }
     clear_run(ctx, clears);
+    // A speculative build that expects no rounds only asks "was anything kept, did the placement give up?" at its very end:
+    // where `fail` already is the flag word build_common reads for the second, the workgroups that keep a suffix set the
+    // first themselves and no launch has to sum their counts (otherwise: spec_counts_kernel)
+    const bool spec_direct = ctx.spec_rounds && n0 == 0 && !ctx.dry && ctx.spec_out && fail_is_zero && fail == ctx.spec_fail;
     auto place = [&](int mode) {
+        u32 *spec_keep = spec_direct && mode == 0 ? ctx.spec_out : nullptr;
         if (fused) {
             if (mode != 0) throw FusedAbort();
+            fa.spec_keep = spec_keep;
             const bool sg = sr.n_docs != 0;
             if (ht && small_input && sg) LAUNCH_NAMED(ctx, "lvl0_finish_kernel", (lvl0_finish_kernel<K, true, 64, true, true>), gp, fa);
             else if (ht && small_input) LAUNCH_NAMED(ctx, "lvl0_finish_kernel", (lvl0_finish_kernel<K, true, 64, true>), gp, fa);
@@ -2138,29 +2152,30 @@ static bool dc3_level0_bytes(Ctx &ctx, const uint8_t *s8, u32 n0, u32 n02, int w
             else LAUNCH_NAMED(ctx, "lvl0_finish_kernel", (lvl0_finish_kernel<K, false, 64>), gp, fa);
         } else if (ht && small_input)
             LAUNCH_NAMED(ctx, "lvl0_place_kernel", (lvl0_place_kernel<K, true, false, true>), gp, starts, sorted_vals, n02, s8, n0, w,
-                         bt, spare, sa12, names_g, lcp_out, keep, block_keep, fail, LongRepeats{bad, mode}, KgMark(), xdep0, sr);
+                         bt, spare, sa12, names_g, lcp_out, keep, block_keep, fail, LongRepeats{bad, mode}, KgMark(), xdep0, sr, spec_keep);
         else if (ht && mode == 0)
             LAUNCH_NAMED(ctx, "lvl0_place_kernel", (lvl0_place_kernel<K, false, true, true>), gp, starts, sorted_vals, n02, s8, n0, w,
-                         bt, spare, sa12, names_g, lcp_out, keep, block_keep, fail, LongRepeats{bad, mode}, KgMark(), xdep0, sr);
+                         bt, spare, sa12, names_g, lcp_out, keep, block_keep, fail, LongRepeats{bad, mode}, KgMark(), xdep0, sr, spec_keep);
         else if (ht)
             LAUNCH_NAMED(ctx, "lvl0_place_kernel", (lvl0_place_kernel<K, false, false, true>), gp, starts, sorted_vals, n02, s8, n0, w,
-                         bt, spare, sa12, names_g, lcp_out, keep, block_keep, fail, LongRepeats{bad, mode}, KgMark(), xdep0, sr);
+                         bt, spare, sa12, names_g, lcp_out, keep, block_keep, fail, LongRepeats{bad, mode}, KgMark(), xdep0, sr, spec_keep);
         else if (small_input)
             LAUNCH_NAMED(ctx, "lvl0_place_kernel", (lvl0_place_kernel<K, true, false>), gp, starts, sorted_vals, n02, s8, n0, w,
-                         bt, spare, sa12, names_g, lcp_out, keep, block_keep, fail, LongRepeats{bad, mode}, KgMark(), (uint8_t *)nullptr, sr);
+                         bt, spare, sa12, names_g, lcp_out, keep, block_keep, fail, LongRepeats{bad, mode}, KgMark(), (uint8_t *)nullptr, sr, spec_keep);
         else if (mode == 0)
             LAUNCH_NAMED(ctx, "lvl0_place_kernel", (lvl0_place_kernel<K, false, true>), gp, starts, sorted_vals, n02, s8, n0, w,
-                         bt, spare, sa12, names_g, lcp_out, keep, block_keep, fail, LongRepeats{bad, mode}, km, (uint8_t *)nullptr, sr);
+                         bt, spare, sa12, names_g, lcp_out, keep, block_keep, fail, LongRepeats{bad, mode}, km, (uint8_t *)nullptr, sr, spec_keep);
         else
             LAUNCH_NAMED(ctx, "lvl0_place_kernel", (lvl0_place_kernel<K, false, false>), gp, starts, sorted_vals, n02, s8, n0, w,
-                         bt, spare, sa12, names_g, lcp_out, keep, block_keep, fail, LongRepeats{bad, mode}, KgMark(), (uint8_t *)nullptr, sr);
+                         bt, spare, sa12, names_g, lcp_out, keep, block_keep, fail, LongRepeats{bad, mode}, KgMark(), (uint8_t *)nullptr, sr, spec_keep);
         if (mode == 1 || ctx.dry) return;
         if (ctx.spec_rounds && mode == 0 && n0 == 0) {
             // speculative build: the host goes on as if nothing were left in large groups; the counts are
             // put next to the build's other flags and read at the end (build_common repeats the build if
             // they are not zero)
-            LAUNCH(ctx, spec_counts_kernel, ceil_div_u32(gp, SPEC_COUNT_TILE), (const u32 *)block_keep, gp, (const u32 *)fail,
-                   ctx.spec_out);
+            if (!spec_direct)
+                LAUNCH(ctx, spec_counts_kernel, ceil_div_u32(gp, SPEC_COUNT_TILE), (const u32 *)block_keep, gp, (const u32 *)fail,
+                       ctx.spec_out);
             m_next = 0;
             h_fail = 0;
             return;

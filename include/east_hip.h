@@ -588,6 +588,11 @@ int east_hip_debug_first_pass_hist(int device, const uint32_t *symbols, int64_t 
  * ANN_TILE, ANN_HALO, ANN_NEAR); listed_out: the number of ranks that went through ann_wide_kernel. */
 int east_hip_debug_annotate(int device, const uint32_t *lcp, int64_t n, const int64_t *doc_off, int32_t n_docs,
                             const int32_t *n_strings, uint32_t *ann_out, uint32_t *geometry_out, uint32_t *listed_out);
+/* One level of a built handle's min pyramid over the LCP table (csrc/tables.h: Pyramid; level 0 is the table itself, level
+ * l + 1 holds the minima of level l's aligned groups of 16), padding included.  geometry_out[3]: the number of levels, the
+ * level's length and its padded length (0, 0 for a level the pyramid does not have); out (may be null: the geometry alone)
+ * takes the padded length, which `capacity` (in words) must cover. */
+int east_hip_debug_pyramid_level(east_hip_handle_t h, int32_t level, uint32_t *out, int64_t capacity, int64_t *geometry_out);
 /* Test knob: bytes of per-suffix scratch a score call may use (default 1 GiB; 0 restores it); a table over
  * more documents than fit is scored a stretch of documents at a time.  Takes effect at the next
  * east_hip_set_keyphrases / east_hip_score_table. */
