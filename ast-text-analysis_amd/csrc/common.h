@@ -229,6 +229,7 @@ struct Knobs {
     int term_hash_bits = 0;                                             // east_hip_debug_set_term_hash_bits (0: all 61 bits)
     int syn_chunk = 128;                                                // east_hip_debug_set_synonyms_chunk (synonyms.h: SY_MAX_CHUNK)
     int top_tile = 64;                                                  // east_hip_debug_set_top_tile (top.h: TOP_TILE)
+    i64 related_chunk = 0;                                              // east_hip_debug_set_related_chunk (related.h: 0 = REL_CHUNK_BYTES of table)
     u32 plan_epoch = 1;                                                 // bumped by the knobs that change what a build allocates
 };
 static Knobs g_knobs;

@@ -1,5 +1,5 @@
 // consumer.h -- the host frame of the handle's consumers: the cosine term index, the keyphrase graph, the synonyms, the
-// ranking and the similarity.  A consumer is a struct of device buffers and results that the handle owns beside its arena,
+// ranking, the similarity and the text-to-text relatedness.  A consumer is a struct of device buffers and results that the handle owns beside its arena,
 // made by the consumer's first call.  Nothing in here knows one consumer from another ("The consumer frame").
 #pragma once
 #include "handle.h"
@@ -95,8 +95,9 @@ struct UploadedTable {
 
 // ---- which table a *_build_resident call reads ----------------------------------------------------------------------------
 // who: the consumer's name in front of its messages; own: the caller's uploaded copy (nullptr before its first call);
-// similarity_ok: the similarity matrix is a source too (the ranking alone).
-static TableRef resolve_table(const east_hip_index *h, int32_t source, const UploadedTable *own, const char *who, bool similarity_ok = false)
+// matrices_ok: the square matrices other consumers built -- the similarity's, the relatedness' -- are sources too (the
+// ranking alone).
+static TableRef resolve_table(const east_hip_index *h, int32_t source, const UploadedTable *own, const char *who, bool matrices_ok = false)
 {
     auto offered = [&](int slot) { return h->consumers[slot] ? h->consumers[slot]->offers() : TableRef(); };
     TableRef t;
@@ -110,9 +111,12 @@ static TableRef resolve_table(const east_hip_index *h, int32_t source, const Upl
     } else if (source == EAST_HIP_GRAPH_SOURCE_UPLOADED) {
         if (own) t = own->ref();
         missing = ": no host table has been uploaded to this handle";
-    } else if (source == EAST_HIP_GRAPH_SOURCE_SIMILARITY && similarity_ok) {
+    } else if (source == EAST_HIP_GRAPH_SOURCE_SIMILARITY && matrices_ok) {
         t = offered(east_hip_index::SLOT_SIM);
         missing = ": no similarity matrix has been built on this handle";
+    } else if (source == EAST_HIP_GRAPH_SOURCE_RELATED && matrices_ok) {
+        t = offered(east_hip_index::SLOT_REL);
+        missing = ": no relatedness matrix has been built on this handle";
     } else {
         east_throw(EAST_HIP_ERR_INVALID, std::string(who) + ": unknown table source");
     }

@@ -454,3 +454,4 @@ double east_hip_last_score_ms(east_hip_handle_t h) { return h ? (double)h->last_
 #include "synonyms.h"       // synonym extraction from dependency triples
 #include "similarity.h"     // similar texts and keyphrases
 #include "top.h"            // ranked keyphrases
+#include "related.h"        // text-to-text relatedness

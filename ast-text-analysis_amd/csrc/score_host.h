@@ -12,6 +12,62 @@ static u32 score_doc_chunk(u32 n_q, u32 n_docs, size_t scratch_bytes)
     return (u32)std::min<size_t>(n_docs, std::max<size_t>(fit, 1));
 }
 
+// The score scratch for n_kp keyphrases of n_q suffixes in all, over n_docs documents scored `chunk` at a time.
+static size_t keyphrase_scratch_bytes(u32 n_kp, u32 n_q, u32 n_docs, u32 chunk)
+{
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    return 256 + al((size_t)n_q * 4) * 3 + al(((size_t)n_kp + 1) * 4) * 3 + al((size_t)n_q * chunk * 8) +
+           al((size_t)n_kp * n_docs * 8) * 2;
+}
+
+// The device half of setting keyphrases: the scratch is laid out for n_kp keyphrases of n_q suffixes, fill() queues on the
+// handle's stream whatever writes q_raw (or q_code, with q_code_epoch), q_end, q_off[n_kp + 1] and -- n_blk > 0 -- q_blk[n_blk + 1]
+// (score.h: score_walk_kernel, blk; n_blk == 0: a keyphrase is longer than a workgroup), from host arrays or from device
+// arrays alike.  The caller waits for the stream where its sources are host memory.
+template <class Fill>
+static void set_keyphrases_device(east_hip_index *h, u32 n_kp, u32 n_q, u32 n_blk, const Knobs &kn, Fill fill)
+{
+    h->table_scored = false;
+    h->q_code_epoch = 0;
+    h->n_kp = h->n_q = 0;                                  // (until the arrays are queued: a refused call leaves no keyphrases)
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const u32 chunk = score_doc_chunk(n_q, h->n_docs, kn.score_scratch_bytes);
+    h->q_buf.ensure(keyphrase_scratch_bytes(n_kp, n_q, h->n_docs, chunk), "the score scratch", h->stream);
+    char *p = h->q_buf.p + 256;                            // (the first bytes hold the probe counter of east_hip_score_probes)
+    h->q_raw = (u32 *)p;  p += al((size_t)n_q * 4);
+    h->q_code = (u32 *)p; p += al((size_t)n_q * 4);
+    h->q_end = (u32 *)p;  p += al((size_t)n_q * 4);
+    h->q_off = (u32 *)p;  p += al(((size_t)n_kp + 1) * 4);
+    h->group_off = (u32 *)p; p += al(((size_t)n_kp + 1) * 4);      // synonym-expanded scoring: variants per keyphrase
+    h->q_blk = (u32 *)p;  p += al(((size_t)n_kp + 1) * 4);
+    h->suffix = (double *)p; p += al((size_t)n_q * chunk * 8);
+    h->table = (double *)p; p += al((size_t)n_kp * h->n_docs * 8);
+    h->table_g = (double *)p;
+    h->n_blk = n_blk;
+    fill();
+    h->n_kp = n_kp;
+    h->n_q = n_q;
+    h->score_chunk = chunk;
+}
+
+// The score walk's workgroups take whole keyphrases (score.h: score_walk_kernel, blk): consecutive keyphrases packed into
+// stretches of at most BLOCK suffixes.  len(k) = the suffixes of keyphrase k.  blk comes back as the stretches' bounds
+// (n_blk + 1 of them), or empty where a keyphrase is longer than a workgroup or the sums run in a kernel of their own.
+template <class Len> static void pack_keyphrase_blocks(u32 n_kp, bool fused, Len len, std::vector<u32> &blk)
+{
+    blk.clear();
+    if (!fused) return;
+    blk.push_back(0);
+    u32 used = 0;
+    for (u32 k = 0; k < n_kp; k++) {
+        const u64 l = len(k);
+        if (l > BLOCK) { blk.clear(); return; }
+        if (used + l > BLOCK) { blk.push_back(k); used = 0; }
+        used += (u32)l;
+    }
+    blk.push_back(n_kp);
+}
+
 static void set_keyphrases(east_hip_index *h, const u32 *q_symbols, const i64 *q_offsets, int32_t n_kp)
 {
     if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
@@ -25,52 +81,23 @@ static void set_keyphrases(east_hip_index *h, const u32 *q_symbols, const i64 *q
     if (S >= (i64)0x7FFFFFF0 || (i64)n_kp * h->n_docs >= ((i64)1 << 40))
         east_throw(EAST_HIP_ERR_INVALID, "keyphrase set too large");
     use_device(h);
-    h->table_scored = false;
-    h->q_code_epoch = 0;
     const u32 n_q = (u32)S;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const Knobs kn = knobs_snapshot();
-    const u32 chunk = score_doc_chunk(n_q, h->n_docs, kn.score_scratch_bytes);
-    const size_t bytes = 256 + al((size_t)n_q * 4) * 3 + al(((size_t)n_kp + 1) * 4) * 3 +
-                         al((size_t)n_q * chunk * 8) + al((size_t)n_kp * h->n_docs * 8) * 2;
-    h->q_buf.ensure(bytes, "the score scratch", h->stream);
-    char *p = h->q_buf.p + 256;                            // (the first bytes hold the probe counter of east_hip_score_probes)
-    h->q_raw = (u32 *)p;  p += al((size_t)n_q * 4);
-    h->q_code = (u32 *)p; p += al((size_t)n_q * 4);
-    h->q_end = (u32 *)p;  p += al((size_t)n_q * 4);
-    h->q_off = (u32 *)p;  p += al(((size_t)n_kp + 1) * 4);
-    h->group_off = (u32 *)p; p += al(((size_t)n_kp + 1) * 4);      // synonym-expanded scoring: variants per keyphrase
-    h->q_blk = (u32 *)p;  p += al(((size_t)n_kp + 1) * 4);
-    h->suffix = (double *)p; p += al((size_t)n_q * chunk * 8);
-    h->table = (double *)p; p += al((size_t)n_kp * h->n_docs * 8);
-    h->table_g = (double *)p;
     std::vector<u32> end(n_q), off((size_t)n_kp + 1);
     for (int32_t k = 0; k < n_kp; k++) {
         off[k] = (u32)q_offsets[k];
         for (i64 i = q_offsets[k]; i < q_offsets[k + 1]; i++) end[i] = (u32)q_offsets[k + 1];
     }
     off[n_kp] = n_q;
-    // the score walk's workgroups take whole keyphrases (score.h: score_walk_kernel, blk): consecutive keyphrases packed
-    // into stretches of at most BLOCK suffixes
     std::vector<u32> blk;
-    blk.push_back(0);
-    bool fits = kn.score_fused;
-    for (int32_t k = 0, used = 0; k < n_kp && fits; k++) {
-        const i64 len = q_offsets[k + 1] - q_offsets[k];
-        if (len > BLOCK) { fits = false; break; }
-        if (used + len > BLOCK) { blk.push_back((u32)k); used = 0; }
-        used += (int32_t)len;
-    }
-    blk.push_back((u32)n_kp);
-    h->n_blk = fits ? (u32)blk.size() - 1 : 0;
-    if (fits) HIP_CHECK(hipMemcpyAsync(h->q_blk, blk.data(), blk.size() * 4, hipMemcpyHostToDevice, h->stream));
-    HIP_CHECK(hipMemcpyAsync(h->q_raw, q_symbols, (size_t)n_q * 4, hipMemcpyHostToDevice, h->stream));
-    HIP_CHECK(hipMemcpyAsync(h->q_end, end.data(), (size_t)n_q * 4, hipMemcpyHostToDevice, h->stream));
-    HIP_CHECK(hipMemcpyAsync(h->q_off, off.data(), off.size() * 4, hipMemcpyHostToDevice, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    h->n_kp = (u32)n_kp;
-    h->n_q = n_q;
-    h->score_chunk = chunk;
+    pack_keyphrase_blocks((u32)n_kp, kn.score_fused, [&](u32 k) { return (u64)(q_offsets[k + 1] - q_offsets[k]); }, blk);
+    set_keyphrases_device(h, (u32)n_kp, n_q, blk.empty() ? 0u : (u32)blk.size() - 1, kn, [&] {
+        if (!blk.empty()) HIP_CHECK(hipMemcpyAsync(h->q_blk, blk.data(), blk.size() * 4, hipMemcpyHostToDevice, h->stream));
+        HIP_CHECK(hipMemcpyAsync(h->q_raw, q_symbols, (size_t)n_q * 4, hipMemcpyHostToDevice, h->stream));
+        HIP_CHECK(hipMemcpyAsync(h->q_end, end.data(), (size_t)n_q * 4, hipMemcpyHostToDevice, h->stream));
+        HIP_CHECK(hipMemcpyAsync(h->q_off, off.data(), off.size() * 4, hipMemcpyHostToDevice, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+    });
 }
 
 // device memory for n_docs rows of bins + 1 entries plus the fill's chunk scratch; false if it cannot be had

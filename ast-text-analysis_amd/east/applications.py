@@ -442,3 +442,74 @@ def keyphrases_similar(keyphrases, texts, n=10, by="text", similarity_threshold=
         lists = _top_select(_similarity_matrix(scores, axis), 1, n, threshold)
     names = titles if axis == 0 else wanted
     return _top_named(lists, names, names)
+
+
+# ---- text-to-text relatedness --------------------------------------------------------------------------------------------
+_RELATED_ORIENTATIONS = ("directed", "symmetric")
+_RELATED_HOST_CHUNK = 4096                  # strings a relevance_table call of the host path scores at a time
+
+
+def _related_matrix(collections, score_rows, orientation):
+    """The contract of include/east_hip.h ("Text-to-text relatedness") in numpy: collections[A] = the scored strings of
+    text A, score_rows(strings) = their len(strings) x D scores.  F[A] = the mean of A's rows (+0.0 for a text without
+    one), summed in numpy's order.  -> (R[D, D] with NaN on the diagonal, self[D], scored[D])."""
+    D = len(collections)
+    forward = np.zeros((D, D), dtype=np.float64)
+    scored = np.array([len(strings) for strings in collections], dtype=np.int32)
+    flat = [(a, s) for a, strings in enumerate(collections) for s in strings]
+    for b in range(0, len(flat), _RELATED_HOST_CHUNK):
+        part = flat[b:b + _RELATED_HOST_CHUNK]
+        rows = np.asarray(score_rows([s for _, s in part]), dtype=np.float64).reshape(len(part), D)
+        owner = np.array([a for a, _ in part], dtype=np.int64)
+        for a in np.unique(owner).tolist():
+            forward[a] += rows[owner == a].sum(axis=0)
+    has = scored > 0
+    forward[has] /= scored[has, None].astype(np.float64)
+    own = forward.diagonal().copy()
+    matrix = (forward + forward.T) * 0.5 if orientation == 1 else forward
+    np.fill_diagonal(matrix, np.nan)
+    return matrix, own, scored
+
+
+def _related_on_host(texts, orientation, measure, language):
+    """texts_related's matrix on the host: the strings of utils.text_to_strings_collection per text (the " " placeholder
+    of a text without a kept token dropped), scored as keyphrases through relevance_table."""
+    collections = [[s for s in utils.text_to_strings_collection(text) if s.replace(" ", "")] for text in texts.values()]
+    measure.set_text_collection(list(texts.values()), language)
+    return _related_matrix(collections, measure.relevance_table, orientation)
+
+
+def texts_related(texts, n=10, orientation="symmetric", relatedness_threshold=None, similarity_measure=None,
+                  language=consts.Language.ENGLISH):
+    """The texts most related to every text, from the texts alone: no keyphrase file.  Every string of text A (its groups
+    of three kept tokens, as the index holds them) is scored against the annotated suffix tree of text B as a keyphrase
+    is; F[A][B] = the mean of those scores says how much of A's wording is found in B.
+
+    :param texts: {text name: text}
+    :param n: entries per text at most, 1 .. 1024
+    :param orientation: "directed" -- F[A][B] as it is; "symmetric" -- (F[A][B] + F[B][A]) / 2
+    :param relatedness_threshold: only values >= it are listed (None: every value that is a number)
+    :returns: {text name: [(other text name, relatedness), ...]}, best first: by relatedness descending and, among equal
+              values, in the order of `texts`; a text never lists itself; plain Python values
+
+    The strings are scored out of the index, summed and ranked on the device (csrc/related.h, csrc/top.h) when the measure
+    has `relevance_related`, the text titles are distinct and EAST_HIP_RELATED is not `host`; in every other case on the
+    host: the strings go through relevance_table in chunks and the formula runs in numpy.  The two paths sum in different
+    orders: their values agree to (max(c_A, c_B) + 4) * 2^-53 relative (c = a text's strings) and they name the same texts
+    in the same order wherever neighbouring values lie further apart than twice that -- they are NOT promised to be the
+    same bytes.
+    """
+    if orientation not in _RELATED_ORIENTATIONS:
+        raise ValueError("texts_related: orientation must be 'symmetric' or 'directed', not %r" % (orientation,))
+    _, n, threshold = _ranking_arguments("texts_related", "text", n, relatedness_threshold, "relatedness")
+    measure = similarity_measure or relevance.ASTRelevanceMeasure()
+    titles = list(texts.keys())
+    if not titles:
+        return {}
+    code = _RELATED_ORIENTATIONS.index(orientation)
+    if _device_applies(measure, texts, None, "relevance_related", "EAST_HIP_RELATED"):
+        measure.set_text_collection(list(texts.values()), language)
+        lists = _top_lists(measure.relevance_related(code, n, threshold))
+    else:
+        lists = _top_select(_related_on_host(texts, code, measure, language)[0], 1, n, threshold)
+    return _top_named(lists, titles, titles)

@@ -142,6 +142,32 @@ def similar2csv(result, by):
                    for member in sorted(result) for rank, (other, similarity) in enumerate(result[member], 1))
 
 
+def format_related(result, format):
+    """Related texts (applications.texts_related: {text: [(other text, relatedness), ...]}), in the layout of
+    format_similar(..., "text", ...) under the root element <related>."""
+    renderers = {"xml": related2xml, "csv": related2csv}
+    if format not in renderers:
+        raise Exception("Unknown relatedness format: '%s'. Please use one of: 'xml', 'csv'." % format)
+    return renderers[format](result)
+
+
+def related2xml(result):
+    """<related> / <text name=..> / <text name=.. rank=..>relatedness</text>; texts sorted by name, entries in rank order."""
+    lines = ["<related>"]
+    for text in sorted(result):
+        lines.append('  <text name="%s">' % text)
+        lines.extend('    <text name="%s" rank="%d">%s</text>' % (other, rank, _SCORE % value)
+                     for rank, (other, value) in enumerate(result[text], 1))
+        lines.append("  </text>")
+    lines.append("</related>")
+    return "\n".join(lines) + "\n"
+
+
+def related2csv(result):
+    """One line per entry: "text","other",rank,relatedness; texts sorted by name, entries in rank order."""
+    return similar2csv(result, "text")
+
+
 def format_graph(graph, format):
     renderers = {"gml": graph2gml, "edges": graph2edges}
     if format not in renderers:

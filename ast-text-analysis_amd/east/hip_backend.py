@@ -148,6 +148,10 @@ SIGNATURES = {
                                                       _c_i64p]),
     "east_hip_similarity_fetch": (ctypes.c_int, [ctypes.c_void_p, _c_dblp, _c_dblp]),
     "east_hip_last_similarity_ms": (ctypes.c_double, [ctypes.c_void_p]),
+    "east_hip_related_build": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int32, _c_i64p]),
+    "east_hip_related_fetch": (ctypes.c_int, [ctypes.c_void_p, _c_dblp, _c_dblp, _c_i32p]),
+    "east_hip_last_related_ms": (ctypes.c_double, [ctypes.c_void_p]),
+    "east_hip_debug_set_related_chunk": (ctypes.c_int, [ctypes.c_int64]),
 }
 
 BUILD_INFO_FIELDS = ("n_total", "n_docs", "n_strings", "sigma_text", "bits_level0", "dc3_levels", "arena_bytes",
@@ -161,6 +165,8 @@ COSINE_INFO_FIELDS = ("built", "n_docs", "kept_tokens", "words", "terms", "class
 
 GRAPH_SOURCE_AST, GRAPH_SOURCE_COSINE, GRAPH_SOURCE_UPLOADED = 0, 1, 2      # east_hip_graph_build_resident: which resident table
 GRAPH_SOURCE_SIMILARITY = 3                 # east_hip_top_build_resident only: the matrix the last similarity build left
+GRAPH_SOURCE_RELATED = 4                    # east_hip_top_build_resident only: the matrix the last related build left
+RELATED_DIRECTED, RELATED_SYMMETRIC = 0, 1                                  # east_hip_related_build: the orientation
 TOP_BY_TEXT, TOP_BY_KEYPHRASE = 0, 1                                        # east_hip_top_build_*: what a segment is
 TOP_MAX_N = 1024
 
@@ -663,6 +669,37 @@ class HipIndex(_ResidentTableConsumers):
     @property
     def last_score_ms(self):
         return float(self._lib.east_hip_last_score_ms(self._h))
+
+    # -- text-to-text relatedness ----------------------------------------------
+    def related_build(self, normalized=True, orientation=RELATED_SYMMETRIC):
+        """The D x D relatedness matrix of the index's own texts (include/east_hip.h, "Text-to-text relatedness"): every
+        string of text A scored against the tree of text B, averaged per A; it stays on the device.  The call replaces the
+        resident keyphrases.  -> (D, scored strings, score launches)"""
+        out = np.zeros(3, dtype=np.int64)
+        _check(self._lib.east_hip_related_build(self._h, int(bool(normalized)), int(orientation), _ptr(out, _c_i64p)))
+        self._rel_D = int(out[0])
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def related_matrix(self):
+        """The last relatedness matrix of this handle -> (matrix[D, D] with NaN on the diagonal, self[D] = F[A][A],
+        scored[D] = the scored strings of every text, int32)."""
+        D = getattr(self, "_rel_D", 0)
+        matrix, own, scored = np.empty((D, D), dtype=np.float64), np.empty(D, dtype=np.float64), np.empty(D, dtype=np.int32)
+        _check(self._lib.east_hip_related_fetch(self._h, _ptr(matrix, _c_dblp), _ptr(own, _c_dblp), _ptr(scored, _c_i32p)))
+        return matrix, own, scored
+
+    def rank_related(self, n, threshold=-np.inf):
+        """A ranking of the last relatedness matrix by row (other n, other threshold: no new matrix) -> TopArrays."""
+        return _top_build(self._lib, self._h, GRAPH_SOURCE_RELATED, None, TOP_BY_KEYPHRASE, n, threshold)
+
+    def related(self, normalized=True, orientation=RELATED_SYMMETRIC, n=10, threshold=-np.inf):
+        """related_build, then the n most related other texts of every text (the NaN on the diagonal is never eligible)
+        -> TopArrays.  It is the handle's one ranking: it replaces top()'s and similar()'s."""
+        self.related_build(normalized, orientation)
+        return self.rank_related(n, threshold)
+
+    def last_related_ms(self):
+        return float(self._lib.east_hip_last_related_ms(self._h))
 
     # -- tables from elsewhere: each consumer keeps an uploaded copy of its own ------
     def graph_from_table(self, table, rows, relevance_threshold, support_threshold, referral_confidence):

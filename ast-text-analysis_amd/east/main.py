@@ -12,6 +12,10 @@ README.rst:27-63; the shipped reference main crashes with a NameError, SURVEY.md
         the N texts most like every text (-b text: the cosine of their keyphrase profiles, the columns of the score table) or
         the N keyphrases most like every keyphrase (-b keyphrase: of their text profiles, the rows), best first, matrix and
         ranking on the device (csrc/similarity.h); -r: only similarities that reach it (default: no threshold)
+    east [-n N] [-r threshold] [-o symmetric|directed] [-d] [-f xml|csv] texts related <directory with .txt files | single file>
+        the N texts most related to every text, from the texts alone (no keyphrase file): every string of text A is scored
+        against the tree of text B out of the index, the scores are averaged per A (-o directed) and with the opposite
+        direction (-o symmetric, the default), best first, on the device (csrc/related.h); one device, the AST measure
     east -s cosine [-w tf|tf-idf] [-v stems|words] keyphrases table|graph|top|similar ...
         the cosine measure (relevance.CosineRelevanceMeasure) on one device; `-v stems` (the default) needs nltk's
         Snowball stemmer, and without nltk's stopword list no stopwords are removed (said on stderr)
@@ -42,7 +46,7 @@ def _read(path):
         return f.read()
 
 
-_OPTIONS = "s:a:w:v:l:f:c:r:p:g:t:n:b:dy"
+_OPTIONS = "s:a:w:v:l:f:c:r:p:g:t:n:b:o:dy"
 _VALUE_OPTIONS = frozenset(c for c, nxt in zip(_OPTIONS, _OPTIONS[1:] + " ") if nxt == ":")
 
 
@@ -82,6 +86,8 @@ def main(argv=None, measure_factory=None):
             if rank == 0:
                 print(refusal)
             return 1
+    if args[:1] == ["texts"]:
+        return _texts_main(opts, args, world, rank)
     cosine = opts.get("-s", "").lower() == consts.RelevanceMeasure.COSINE
     if world > 1 and cosine:
         if rank == 0:
@@ -138,13 +144,13 @@ def _main(opts, args, world, measure_factory):
     if len(args) < 2:
         print("Invalid syntax: EAST should be called as:\n\n"
               "    east [options] <command> <subcommand> args\n\n"
-              "Commands available: keyphrases.\n"
+              "Commands available: keyphrases, texts.\n"
               "Subcommands available: table/graph/top/similar.")
         return 1
 
     command, subcommand = args[0], args[1]
     if command != "keyphrases":
-        print("Invalid command: '%s'. Please use one of: 'keyphrases'." % command)
+        print("Invalid command: '%s'. Please use one of: 'keyphrases', 'texts'." % command)
         return 1
     if len(args) < 4:
         print('Invalid syntax. For keyphrases analysis, EAST should be called as:\n\n'
@@ -236,6 +242,81 @@ def _main(opts, args, world, measure_factory):
         if group_up:
             import torch.distributed as dist
             dist.destroy_process_group()
+
+
+def _read_texts(path):
+    """{text name: text} of a directory of .txt files (the name: the file's without .txt) or of a single file (a text a
+    line, named by its number), as _main reads them (main.py:67-89)."""
+    path = os.path.abspath(path)
+    if os.path.isdir(path):
+        text_files = [os.path.join(path, filename) for filename in sorted(os.listdir(path)) if filename.endswith(".txt")]
+    else:
+        text_files = [path]
+    texts = {}
+    if len(text_files) == 1:      # a single file: one text per line
+        lines = _read(text_files[0]).splitlines()
+        for i in range(len(lines)):
+            texts[str(i)] = lines[i]
+    else:
+        for filename in text_files:
+            texts[os.path.basename(filename)[:-4]] = _read(filename)
+    return texts
+
+
+def _related_options(opts):
+    """(n, orientation, threshold, None) of `texts related`, or (None, None, None, the one line that says what is wrong)."""
+    n, _, threshold, refusal = _top_options({key: value for key, value in opts.items() if key != "-b"})
+    if refusal:
+        return None, None, None, refusal.replace("relevance threshold", "relatedness threshold")
+    orientation = opts.get("-o", "symmetric").lower()
+    if orientation not in ("symmetric", "directed"):
+        return None, None, None, "Invalid orientation: '%s'. Please use one of: 'symmetric', 'directed'." % opts["-o"]
+    return n, orientation, threshold, None
+
+
+def _texts_main(opts, args, world, rank):
+    """`east texts related <texts>`.  Everything that cannot be done is refused with one line before a file is read or
+    anything touches a device."""
+    def refuse(line):
+        if rank == 0:
+            print(line)
+        return 1
+
+    if len(args) < 2 or args[1] != "related":
+        return refuse("Invalid subcommand: '%s'. Please use one of: 'related'." % (args[1] if len(args) > 1 else ""))
+    if len(args) < 3:
+        return refuse('Invalid syntax. For text analysis, EAST should be called as:\n\n'
+                      '    east [options] texts related "path/to/texts/dir"')
+    n, orientation, threshold, refusal = _related_options(opts)
+    if refusal:
+        return refuse(refusal)
+    if opts.get("-s", consts.RelevanceMeasure.AST).lower() != consts.RelevanceMeasure.AST.lower():
+        return refuse("Text relatedness is defined by the AST measure: -s %s is not supported." % opts["-s"])
+    if "-y" in opts:
+        return refuse("Text relatedness takes no synonyms: -y is not supported.")
+    if world > 1:
+        return refuse("Text relatedness runs on one device: a launcher with WORLD_SIZE=%d is not supported." % world)
+    if os.environ.get("EAST_HIP_FORCE_DIST") == "1":
+        return refuse("Text relatedness runs on one device: the collective path is not supported.")
+    devices = opts.get("-g", os.environ.get("EAST_HIP_DEVICES", "1"))
+    try:
+        n_ranks = int(devices)
+    except ValueError:
+        return refuse("Invalid number of GPUs: '%s'." % devices)
+    if n_ranks > 1:
+        return refuse("Text relatedness runs on one device: -g %d is not supported." % n_ranks)
+    texts = _read_texts(args[2])
+    try:
+        measure = relevance.ASTRelevanceMeasure(opts.get("-a", consts.ASTAlgorithm.EASA), "-d" not in opts)
+        related = applications.texts_related(texts, n, orientation, threshold, measure, opts.get("-l", consts.Language.ENGLISH))
+        print(formatting.format_related(related, opts.get("-f", "xml").lower()))
+    except exceptions.EastException as e:       # (no device, a failed build ...): a message, not a traceback
+        print(e)
+        return 1
+    except Exception as e:                      # (an unknown format)
+        print(e)
+        return 1
+    return 0
 
 
 def _run_cosine(subcommand, keyphrases, texts, opts, synonimizer=None):

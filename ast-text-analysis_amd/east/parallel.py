@@ -104,6 +104,8 @@ class DistributedASTRelevanceMeasure(relevance.ASTRelevanceMeasure):
     relevance_graph = None       # (every rank holds a block of the table: keyphrases_graph keeps its host path)
     relevance_top = None         # (... and keyphrases_top too)
     relevance_similar = None     # (... and keyphrases_similar)
+    relevance_related = None     # (... and a rank holds the trees of its own documents only: texts_related is refused by the CLI)
+    relatedness_matrix = None
 
     def _on_gpu(self):
         import torch.distributed as dist

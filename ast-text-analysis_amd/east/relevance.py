@@ -239,6 +239,17 @@ class ASTRelevanceMeasure(RelevanceMeasure):
         self._score_resident(prepared_keyphrases)
         return self.index.similar(axis, n, threshold)
 
+    def relevance_related(self, orientation, n, threshold=-np.inf):
+        """The n most related other texts of every text of the collection: every string of text A is scored against the
+        tree of text B as a keyphrase is, straight out of the index (csrc/related.h); orientation
+        hip_backend.RELATED_DIRECTED or RELATED_SYMMETRIC.  -> hip_backend.TopArrays."""
+        return self.index.related(self.normalized, orientation, n, threshold)
+
+    def relatedness_matrix(self, orientation):
+        """The D x D matrix relevance_related ranks -> (matrix, self, scored) of HipIndex.related_matrix."""
+        self.index.related_build(self.normalized, orientation)
+        return self.index.related_matrix()
+
 
 class MultiDeviceASTRelevanceMeasure(ASTRelevanceMeasure):
     """ASTRelevanceMeasure over several GPUs of this process (`east -g N`): the documents are sharded over the devices --
@@ -258,6 +269,8 @@ class MultiDeviceASTRelevanceMeasure(ASTRelevanceMeasure):
     relevance_graph = None       # (the table is spread over the devices: keyphrases_graph keeps its host path)
     relevance_top = None         # (... and so does keyphrases_top)
     relevance_similar = None     # (... and keyphrases_similar)
+    relevance_related = None     # (every shard holds its own documents' trees only: texts_related keeps its host path)
+    relatedness_matrix = None
 
     def _after_build(self, n_docs):
         self._shards = []

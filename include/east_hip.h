@@ -435,6 +435,56 @@ int east_hip_similarity_fetch(east_hip_handle_t h, double *matrix, double *norm2
 double east_hip_last_similarity_ms(east_hip_handle_t h);
 
 /*
+ * Text-to-text relatedness (`east texts related`): how much of text A's wording is found in text B, for every two documents
+ * of the index, and -- through the ranking above -- the n most related others of each.  (How: csrc/related.h)
+ *
+ * Let the index hold D documents.  The STRINGS of document A are the strings of its collection as the index holds them: the
+ * runs of text symbols between the terminators of its EASA string, m_A = n_strings[A] of them (in both encodings, on the
+ * byte and on the 32-bit code stream).  A string is SCORED when it is not empty once U+0020 is removed -- in practice only
+ * the [" "] placeholder of a text without a kept token is not --; c_A = the scored strings of A.
+ * score(s, B) is exactly what east_hip_score_table returns for the keyphrase s against document B with the same
+ * `normalized` flag: the same 8 bytes.  The forward matrix is F[A][B] = (the sum over the scored strings s of A of
+ * score(s, B)) / c_A, and +0.0 for every B when c_A = 0.  The result R is D x D doubles, row-major:
+ *   orientation EAST_HIP_RELATED_DIRECTED:  R[A][B] = F[A][B]
+ *   orientation EAST_HIP_RELATED_SYMMETRIC: R[A][B] = (F[A][B] + F[B][A]) * 0.5 -- R[A][B] and R[B][A] are the same bytes
+ * In both R[A][A] = NaN, and self[A] = F[A][A] is reported separately.
+ * Order of the sums: the sum over a document's strings is a fixed tree whose shape depends on c_A alone -- tiles of a fixed
+ * number of scored strings, aligned to the document's first, added in tile order.  It depends neither on how the strings
+ * are cut into score launches nor on D; no atomic is used.  Two builds of the same input give the same bytes, under any
+ * chunk setting (east_hip_debug_set_related_chunk).
+ * Accuracy: the scores are finite and >= 0, so summing c of them in any order is off by less than gamma_(c-1) relative;
+ * one rounding for the division, one for the addition of the symmetric form, the halving is exact:
+ * |R[A][B] - exact| <= (max(c_A, c_B) + 4) * 2^-53 * exact, `exact` being the formula without rounding on the device's own
+ * per-string scores.
+ *
+ * The build call: out[0] = D, out[1] = the scored strings (the sum of c_A), out[2] = the score launches (chunks).
+ * EAST_HIP_ERR_NOT_BUILT before a build of the index; EAST_HIP_ERR_INVALID for an unknown orientation or a null handle;
+ * EAST_HIP_ERR_OOM with D and the bytes in the message when the matrix or a chunk cannot be had.  The call uses the score
+ * scratch: it REPLACES the handle's resident keyphrases and withdraws its resident score table, exactly as a new
+ * east_hip_set_keyphrases does, and afterwards east_hip_score_resident answers "no keyphrases set" until new ones are set.
+ * The fetch call gives the last result (each pointer nullable): matrix[D * D], self[D], scored[D] = c_A.
+ * EAST_HIP_ERR_NOT_BUILT before a related build.
+ * Ranking the matrix: east_hip_top_build_resident accepts the source EAST_HIP_GRAPH_SOURCE_RELATED = the D x D matrix the
+ * last related build of this handle left, ranked like any table (callers use EAST_HIP_TOP_BY_KEYPHRASE: a segment is a row;
+ * the NaN on the diagonal keeps a text from listing itself); EAST_HIP_ERR_NOT_BUILT before a related build.  The handle
+ * still has ONE ranking.
+ * The matrix, self and scored live in buffers of their own -- not the EASA arena, the score scratch, the ranking's buffers
+ * or the similarity's; a later score call or keyphrase set leaves a finished matrix valid; the reset call releases them,
+ * destroying the handle too.
+ * Device time of the last related build in milliseconds (events on the handle's stream around the whole build, the one
+ * read-back of the strings' lengths included), -1 when there is none.
+ * Test knob (process-wide, read when a build starts): the scored strings per score launch, rounded up to whole tiles; 0 =
+ * the default (as many as keep a launch's score table at or below 256 MiB).  The result does not depend on it.
+ */
+#define EAST_HIP_RELATED_DIRECTED 0
+#define EAST_HIP_RELATED_SYMMETRIC 1
+#define EAST_HIP_GRAPH_SOURCE_RELATED 4
+int east_hip_related_build(east_hip_handle_t h, int normalized, int32_t orientation, int64_t *out);
+int east_hip_related_fetch(east_hip_handle_t h, double *matrix, double *self, int32_t *scored);
+double east_hip_last_related_ms(east_hip_handle_t h);
+int east_hip_debug_set_related_chunk(int64_t strings);
+
+/*
  * Several devices in one process ("single-process/8-device fits the one-process CLI best").
  * Every document is an independent AST (east/relevance.py:41-46) and every (keyphrase, document) score is independent
  * (east/applications.py:43-52): a GROUP shards a collection at document granularity -- contiguous blocks of documents
