@@ -38,6 +38,40 @@ static void annotate(east_hip_index *h, Ctx &ctx, u32 *listed_total = nullptr)
     ar.release(mark);
 }
 
+// childtab_up / down / next_l_index of the whole shard: the streaming pass, then the ranks it listed through the pyramid
+// (the lists live in the arena's temporary region).
+// (listed_total != nullptr, a test's: a host word that takes the number of ranks child_wide_kernel decided -- the call
+// then waits for the stream)
+static void child_tables(east_hip_index *h, Ctx &ctx, u32 *listed_total = nullptr)
+{
+    const Pyramid &pyr = h->pyr;
+    const u32 n = pyr.len[0];
+    Arena &ar = *ctx.arena;
+    const size_t mark = ar.mark();
+    const u32 n_tiles = ceil_div_u32(n, CH_TILE);
+    u32 *wide_list = ar.alloc<u32>((size_t)n_tiles * CH_TILE);        // every tile has its own stretch
+    u32 *wide_count = ar.alloc<u32>(n_tiles);
+    LAUNCH(ctx, child_stream_kernel, n_tiles, pyr, (const u32 *)h->doc_off, h->build_docs, n, h->up, h->down, h->next,
+           wide_list, wide_count);
+    LAUNCH(ctx, child_wide_kernel, ceil_div_u32(n_tiles, BLOCK / CH_WIDE_SLOTS), pyr, (const u32 *)h->doc_off,
+           h->build_docs, n, n_tiles, (const u32 *)wide_list, (const u32 *)wide_count, h->up, h->down, h->next);
+    if (listed_total) {
+        std::vector<u32> counts(n_tiles);
+        HIP_CHECK(hipMemcpyAsync(counts.data(), wide_count, (size_t)n_tiles * 4, hipMemcpyDeviceToHost, ctx.stream));
+        HIP_CHECK(hipStreamSynchronize(ctx.stream));
+        u64 sum = 0;
+        for (u32 c : counts) sum += c;
+        *listed_total = (u32)sum;
+    }
+    ar.release(mark);
+}
+
+// the lcp-interval lefts of the document of nd ranks from rank seg on, into left[nd] (device memory)
+static void interval_lefts(east_hip_index *h, Ctx &ctx, u32 seg, u32 nd, u32 *left)
+{
+    LAUNCH(ctx, interval_left_kernel, ceil_div_u32(nd, BLOCK), h->pyr, (const u32 *)h->ann, seg, nd, left);
+}
+
 // symbol counts of the byte stream (the weights of the variable-length code, ht_code.h): 16 bytes per thread and step,
 // per-lane-class counters in LDS
 __global__ __launch_bounds__(BLOCK) void byte_hist_kernel(const uint8_t *__restrict__ s8, u32 n, u32 *__restrict__ counts)

@@ -93,30 +93,20 @@ static void debug_first_pass_hist(int device, const u32 *symbols, i64 n64, const
     HIP_CHECK(hipStreamSynchronize(sc.stream));
 }
 
-// The annotation pass (build.h: annotate -- ann_stream_kernel, the upper pyramid, ann_wide_kernel) on a caller's table
-static void debug_annotate(int device, const u32 *lcp, i64 n64, const i64 *doc_off, int32_t n_docs, const int32_t *n_strings,
-                           u32 *ann_out, u32 *geometry_out, u32 *listed_out)
+// what annotate() and the passes behind it read of a handle, in the scope's arena: the caller's table with the levels of
+// its pyramid, the annotation, the document tables
+static void debug_table_handle(DebugScope &sc, east_hip_index &h, const u32 *lcp, u32 n, const i64 *doc_off, int32_t n_docs,
+                               const int32_t *n_strings)
 {
-    if (!lcp || !doc_off || !n_strings || !ann_out || !geometry_out || !listed_out || n64 < 1 || n64 >= (i64)0x7FFFFFF0 ||
-        n_docs < 1 || doc_off[0] != 0 || doc_off[n_docs] != n64)
-        east_throw(EAST_HIP_ERR_INVALID, "bad annotation arguments");
-    for (int32_t d = 0; d < n_docs; d++)
-        if (doc_off[d + 1] <= doc_off[d]) east_throw(EAST_HIP_ERR_INVALID, "document offsets must increase");
-    const u32 n = (u32)n64;
+    Arena &ar = sc.arena;
     std::vector<u32> off32((size_t)n_docs + 1), m32(n_docs);
     for (int32_t d = 0; d <= n_docs; d++) off32[d] = (u32)doc_off[d];
     for (int32_t d = 0; d < n_docs; d++) m32[d] = (u32)n_strings[d];
-    // table, annotation, the pyramid's upper levels (a sixteenth each), the tiles' lists and counts, the document tables
-    DebugScope sc(device, ((size_t)pyr_padded(n) * 2 + (size_t)n / 8 + (size_t)ceil_div_u32(n, ANN_TILE) * (ANN_TILE + 1) + 2 * (size_t)n_docs) * 4 +
-                              (1u << 20));
-    Arena &ar = sc.arena;
-    east_hip_index h;                   // (what annotate() reads of a handle, and no more)
     h.lcp = ar.alloc<u32>(pyr_padded(n));
     h.ann = ar.alloc<u32>(n);
     h.doc_off = ar.alloc<u32>((size_t)n_docs + 1);
     h.n_strings = ar.alloc<u32>(n_docs);
     h.build_docs = (u32)n_docs;
-    u32 *listed = ar.alloc<u32>(1);
     Pyramid &pyr = h.pyr;
     pyr.levels = 1;
     pyr.ptr[0] = h.lcp;
@@ -130,10 +120,29 @@ static void debug_annotate(int device, const u32 *lcp, i64 n64, const i64 *doc_o
     // (the table's padding and the annotation start out as something no result is: the pass writes both)
     HIP_CHECK(hipMemsetAsync(h.lcp, 0x5A, (size_t)pyr_padded(n) * 4, sc.stream));
     HIP_CHECK(hipMemsetAsync(h.ann, 0xEE, (size_t)n * 4, sc.stream));
-    HIP_CHECK(hipMemsetAsync(listed, 0, 4, sc.stream));
     HIP_CHECK(hipMemcpyAsync(h.lcp, lcp, (size_t)n * 4, hipMemcpyHostToDevice, sc.stream));
     HIP_CHECK(hipMemcpyAsync(h.doc_off, off32.data(), off32.size() * 4, hipMemcpyHostToDevice, sc.stream));
     HIP_CHECK(hipMemcpyAsync(h.n_strings, m32.data(), m32.size() * 4, hipMemcpyHostToDevice, sc.stream));
+    HIP_CHECK(hipStreamSynchronize(sc.stream));     // (the two small tables go up out of this frame)
+}
+
+// The annotation pass (build.h: annotate -- ann_stream_kernel, the upper pyramid, ann_wide_kernel) on a caller's table
+static void debug_annotate(int device, const u32 *lcp, i64 n64, const i64 *doc_off, int32_t n_docs, const int32_t *n_strings,
+                           u32 *ann_out, u32 *geometry_out, u32 *listed_out)
+{
+    if (!lcp || !doc_off || !n_strings || !ann_out || !geometry_out || !listed_out || n64 < 1 || n64 >= (i64)0x7FFFFFF0 ||
+        n_docs < 1 || doc_off[0] != 0 || doc_off[n_docs] != n64)
+        east_throw(EAST_HIP_ERR_INVALID, "bad annotation arguments");
+    for (int32_t d = 0; d < n_docs; d++)
+        if (doc_off[d + 1] <= doc_off[d]) east_throw(EAST_HIP_ERR_INVALID, "document offsets must increase");
+    const u32 n = (u32)n64;
+    // table, annotation, the pyramid's upper levels (a sixteenth each), the tiles' lists and counts, the document tables
+    DebugScope sc(device, ((size_t)pyr_padded(n) * 2 + (size_t)n / 8 + (size_t)ceil_div_u32(n, ANN_TILE) * (ANN_TILE + 1) + 2 * (size_t)n_docs) * 4 +
+                              (1u << 20));
+    east_hip_index h;                   // (what annotate() reads of a handle, and no more)
+    u32 *listed = sc.arena.alloc<u32>(1);
+    HIP_CHECK(hipMemsetAsync(listed, 0, 4, sc.stream));
+    debug_table_handle(sc, h, lcp, n, doc_off, n_docs, n_strings);
     annotate(&h, sc.ctx, listed);
     HIP_CHECK(hipMemcpyAsync(ann_out, h.ann, (size_t)n * 4, hipMemcpyDeviceToHost, sc.stream));
     HIP_CHECK(hipMemcpyAsync(listed_out, listed, 4, hipMemcpyDeviceToHost, sc.stream));
@@ -141,6 +150,48 @@ static void debug_annotate(int device, const u32 *lcp, i64 n64, const i64 *doc_o
     geometry_out[0] = ANN_TILE;
     geometry_out[1] = ANN_HALO;
     geometry_out[2] = ANN_NEAR;
+}
+
+// The child tables and the lcp-interval lefts (build.h: child_tables, interval_lefts) behind the annotation pass, on a
+// caller's table: the raw device values, positions local to the document, 0 = none, NONE_U32 = no left
+static void debug_child_tables(int device, const u32 *lcp, i64 n64, const i64 *doc_off, int32_t n_docs, const int32_t *n_strings,
+                               u32 *up_out, u32 *down_out, u32 *next_out, u32 *left_out, u32 *geometry_out, u32 *listed_out)
+{
+    if (!lcp || !doc_off || !n_strings || !up_out || !down_out || !next_out || !left_out || !geometry_out || !listed_out ||
+        n64 < 1 || n64 >= (i64)0x7FFFFFF0 || n_docs < 1 || doc_off[0] != 0 || doc_off[n_docs] != n64)
+        east_throw(EAST_HIP_ERR_INVALID, "bad child table arguments");
+    for (int32_t d = 0; d < n_docs; d++) {
+        // (checked in this order: an offset is an index into lcp only once it is known to lie below n)
+        if (doc_off[d + 1] <= doc_off[d] || doc_off[d + 1] > n64) east_throw(EAST_HIP_ERR_INVALID, "document offsets must increase");
+        if (lcp[doc_off[d]] != 0) east_throw(EAST_HIP_ERR_INVALID, "the table must hold 0 at a document's first rank: it bounds the searches");
+    }
+    for (i64 k = 0; k < n64; k++)
+        if (lcp[k] > 0x7FFFFFEFu) east_throw(EAST_HIP_ERR_INVALID, "a value above 0x7FFFFFEF: an LCP value is below n");
+    const u32 n = (u32)n64;
+    // as above + the three child tables and the lefts, and the child pass's lists and counts (behind the annotation's)
+    DebugScope sc(device, ((size_t)pyr_padded(n) * 6 + (size_t)n / 8 + (size_t)ceil_div_u32(n, ANN_TILE) * (ANN_TILE + 1) +
+                           (size_t)ceil_div_u32(n, CH_TILE) * (CH_TILE + 1) + 2 * (size_t)n_docs) * 4 + (1u << 20));
+    Arena &ar = sc.arena;
+    east_hip_index h;                   // (what annotate(), child_tables() and interval_lefts() read of a handle, and no more)
+    h.up = ar.alloc<u32>(n);
+    h.down = ar.alloc<u32>(n);
+    h.next = ar.alloc<u32>(n);
+    u32 *left = ar.alloc<u32>(n);
+    for (u32 *t : {h.up, h.down, h.next, left}) HIP_CHECK(hipMemsetAsync(t, 0xEE, (size_t)n * 4, sc.stream));   // (an unwritten rank shows)
+    debug_table_handle(sc, h, lcp, n, doc_off, n_docs, n_strings);
+    annotate(&h, sc.ctx);
+    child_tables(&h, sc.ctx, listed_out);
+    for (int32_t d = 0; d < n_docs; d++)
+        interval_lefts(&h, sc.ctx, (u32)doc_off[d], (u32)(doc_off[d + 1] - doc_off[d]), left + doc_off[d]);
+    HIP_CHECK(hipMemcpyAsync(up_out, h.up, (size_t)n * 4, hipMemcpyDeviceToHost, sc.stream));
+    HIP_CHECK(hipMemcpyAsync(down_out, h.down, (size_t)n * 4, hipMemcpyDeviceToHost, sc.stream));
+    HIP_CHECK(hipMemcpyAsync(next_out, h.next, (size_t)n * 4, hipMemcpyDeviceToHost, sc.stream));
+    HIP_CHECK(hipMemcpyAsync(left_out, left, (size_t)n * 4, hipMemcpyDeviceToHost, sc.stream));
+    HIP_CHECK(hipStreamSynchronize(sc.stream));
+    geometry_out[0] = CH_TILE;
+    geometry_out[1] = CH_HALO;
+    geometry_out[2] = CH_NEAR;
+    geometry_out[3] = CH_LOCAL;
 }
 
 extern "C" {
@@ -308,6 +359,15 @@ int east_hip_debug_annotate(int device, const uint32_t *lcp, int64_t n, const in
                             const int32_t *n_strings, uint32_t *ann_out, uint32_t *geometry_out, uint32_t *listed_out)
 {
     return guarded([&] { debug_annotate(device, lcp, n, doc_off, n_docs, n_strings, ann_out, geometry_out, listed_out); });
+}
+
+int east_hip_debug_child_tables(int device, const uint32_t *lcp, int64_t n, const int64_t *doc_off, int32_t n_docs,
+                                const int32_t *n_strings, uint32_t *up_out, uint32_t *down_out, uint32_t *next_out,
+                                uint32_t *left_out, uint32_t *geometry_out, uint32_t *listed_out)
+{
+    return guarded([&] {
+        debug_child_tables(device, lcp, n, doc_off, n_docs, n_strings, up_out, down_out, next_out, left_out, geometry_out, listed_out);
+    });
 }
 
 int east_hip_debug_pyramid_level(east_hip_handle_t h, int32_t level, uint32_t *out, int64_t capacity, int64_t *geometry_out)

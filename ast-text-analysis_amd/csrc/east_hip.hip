@@ -197,17 +197,8 @@ int east_hip_get_tables(east_hip_handle_t h, int32_t doc, int32_t *suftab, int32
         if (doc < 0 || (u32)doc >= h->n_docs) east_throw(EAST_HIP_ERR_INVALID, "document index out of range");
         use_device(h);
         if ((childtab_up || childtab_down || childtab_next_l_index) && !h->child_built) {
-            // (the lists of the ranks the streaming pass leaves to the pyramid live in the arena's temporary region)
             Ctx ctx = handle_ctx(h, &h->arena);
-            const size_t mark = h->arena.mark();
-            const u32 n_tiles = ceil_div_u32(h->n, CH_TILE);
-            u32 *wide_list = h->arena.alloc<u32>((size_t)n_tiles * CH_TILE);
-            u32 *wide_count = h->arena.alloc<u32>(n_tiles);
-            LAUNCH(ctx, child_stream_kernel, n_tiles, h->pyr, (const u32 *)h->doc_off, h->n_docs, h->n, h->up, h->down,
-                   h->next, wide_list, wide_count);
-            LAUNCH(ctx, child_wide_kernel, ceil_div_u32(n_tiles, BLOCK / CH_WIDE_SLOTS), h->pyr, (const u32 *)h->doc_off,
-                   h->n_docs, h->n, n_tiles, (const u32 *)wide_list, (const u32 *)wide_count, h->up, h->down, h->next);
-            h->arena.release(mark);
+            child_tables(h, ctx);
             h->child_built = true;
         }
         const size_t b = (size_t)h->h_doc_off[doc], nd = (size_t)(h->h_doc_off[doc + 1] - h->h_doc_off[doc]);
@@ -315,7 +306,7 @@ int east_hip_get_lcp_intervals(east_hip_handle_t h, int32_t doc, int32_t *left)
         // (scratch from the arena's temporary region, idle between builds: the child tables stay as they are)
         const size_t mark = h->arena.mark();
         u32 *scratch = h->arena.alloc<u32>(nd);
-        LAUNCH(ctx, interval_left_kernel, ceil_div_u32(nd, BLOCK), h->pyr, (const u32 *)h->ann, seg, nd, scratch);
+        interval_lefts(h, ctx, seg, nd, scratch);
         HIP_CHECK(hipMemcpyAsync(left, scratch, (size_t)nd * 4, hipMemcpyDeviceToHost, h->stream));
         HIP_CHECK(hipStreamSynchronize(h->stream));
         h->arena.release(mark);

@@ -932,6 +932,9 @@ static_assert(ANN_WIDE_RUN == 64, "one wavefront scans a run's counts");
 #endif
 #define CH_IPT 4
 #define CH_TILE (BLOCK * CH_IPT)
+static_assert(CH_LOCAL <= CH_HALO && CH_NEAR <= CH_HALO, "phases 1 and 2 read tile[at +- dist] up to CH_NEAR / CH_LOCAL out of a halo of CH_HALO");
+static_assert(CH_NEAR % 4 == 0 && CH_HALO % 4 == 0, "a thread's registers and the halo are staged in quads");
+static_assert(2 * CH_HALO / 4 <= BLOCK, "the halo: one quad per thread");
 
 __device__ __forceinline__ void child_of_rank(const Pyramid &P, u32 k, u32 seg, u32 seg_end, u32 &u, u32 &dn, u32 &nx)
 {

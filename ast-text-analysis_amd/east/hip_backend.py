@@ -77,6 +77,8 @@ SIGNATURES = {
                                                       _c_u32p, _c_u32p]),
     "east_hip_debug_annotate": (ctypes.c_int, [ctypes.c_int, _c_u32p, ctypes.c_int64, _c_i64p, ctypes.c_int32, _c_i32p,
                                                _c_u32p, _c_u32p, _c_u32p]),
+    "east_hip_debug_child_tables": (ctypes.c_int, [ctypes.c_int, _c_u32p, ctypes.c_int64, _c_i64p, ctypes.c_int32, _c_i32p,
+                                                   _c_u32p, _c_u32p, _c_u32p, _c_u32p, _c_u32p, _c_u32p]),
     "east_hip_debug_pyramid_level": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _c_u32p, ctypes.c_int64, _c_i64p]),
     "east_hip_debug_set_score_scratch": (ctypes.c_int, [ctypes.c_int64]),
     "east_hip_debug_set_score_path": (ctypes.c_int, [ctypes.c_int]),

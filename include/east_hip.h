@@ -638,6 +638,16 @@ int east_hip_debug_first_pass_hist(int device, const uint32_t *symbols, int64_t 
  * ANN_TILE, ANN_HALO, ANN_NEAR); listed_out: the number of ranks that went through ann_wide_kernel. */
 int east_hip_debug_annotate(int device, const uint32_t *lcp, int64_t n, const int64_t *doc_off, int32_t n_docs,
                             const int32_t *n_strings, uint32_t *ann_out, uint32_t *geometry_out, uint32_t *listed_out);
+/* Kernel-level test of the child tables and the lcp-interval lefts (csrc/build.h: child_tables -- child_stream_kernel,
+ * child_wide_kernel --, interval_lefts -- interval_left_kernel), run behind annotate() on the caller's table as the calls
+ * above take it.  Unlike there the table must hold 0 at every document's first rank (the kernels' searches end at that
+ * zero) and no value above 0x7FFFFFEF; anything else is EAST_HIP_ERR_INVALID before a launch.  up_out / down_out /
+ * next_out[n]: the raw device tables, positions local to the document, 0 = none; left_out[n]: the lefts of every
+ * document, local, 0xFFFFFFFF = none; geometry_out[4]: CH_TILE, CH_HALO, CH_NEAR, CH_LOCAL of csrc/tables.h; listed_out:
+ * the number of ranks that went through child_wide_kernel. */
+int east_hip_debug_child_tables(int device, const uint32_t *lcp, int64_t n, const int64_t *doc_off, int32_t n_docs,
+                                const int32_t *n_strings, uint32_t *up_out, uint32_t *down_out, uint32_t *next_out,
+                                uint32_t *left_out, uint32_t *geometry_out, uint32_t *listed_out);
 /* One level of a built handle's min pyramid over the LCP table (csrc/tables.h: Pyramid; level 0 is the table itself, level
  * l + 1 holds the minima of level l's aligned groups of 16), padding included.  geometry_out[3]: the number of levels, the
  * level's length and its padded length (0, 0 for a level the pyramid does not have); out (may be null: the geometry alone)
