@@ -230,6 +230,7 @@ struct Knobs {
     int syn_chunk = 128;                                                // east_hip_debug_set_synonyms_chunk (synonyms.h: SY_MAX_CHUNK)
     int top_tile = 64;                                                  // east_hip_debug_set_top_tile (top.h: TOP_TILE)
     i64 related_chunk = 0;                                              // east_hip_debug_set_related_chunk (related.h: 0 = REL_CHUNK_BYTES of table)
+    i64 cosine_texts_batch = 0;                                         // east_hip_debug_set_text_similarity_batch (cosine_texts.h: 0 = COSTEXT_SCRATCH_BYTES of partial tiles)
     u32 plan_epoch = 1;                                                 // bumped by the knobs that change what a build allocates
 };
 static Knobs g_knobs;

@@ -587,6 +587,13 @@ struct CosState : Consumer {
     }
 };
 
+// the text-to-text cosine matrix (cosine_texts.h) is a function of the index and of its vector space: every build and every
+// change of the classes withdraws it
+static void cos_withdraw_texts_matrix(east_hip_index *h)
+{
+    if (Consumer *t = h->consumers[east_hip_index::SLOT_COSTEXT]) { t->valid = false; t->ms = -1.f; }
+}
+
 static CosState &cos_built(east_hip_index *h)
 {
     if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
@@ -628,6 +635,7 @@ static void cos_build(east_hip_index *h, HostTexts in, const UnicodeTablesHost &
         if (stop_offsets[w + 1] < stop_offsets[w]) east_throw(EAST_HIP_ERR_INVALID, "stopword offsets must not decrease");
     use_device(h);
     CosState &c = consumer_state<CosState>(h);
+    cos_withdraw_texts_matrix(h);
     c.built = c.use_classes = false;
     c.table_valid = false;
     c.terms.w_valid[0] = c.terms.w_valid[1] = c.cls.w_valid[0] = c.cls.w_valid[1] = false;
@@ -816,6 +824,7 @@ static void cos_build(east_hip_index *h, HostTexts in, const UnicodeTablesHost &
 static void cos_set_classes(east_hip_index *h, const int32_t *term_class, int32_t n_classes)
 {
     CosState &c = cos_built(h);
+    cos_withdraw_texts_matrix(h);
     if (n_classes == 0) {                                   // back to the terms
         c.use_classes = false;
         return;
@@ -907,6 +916,20 @@ static void cos_weight_ptrs(CosUnits &U, u32 D, int wt, double **w, double **nor
     *norm = (double *)(U.weights.p + wt * (wb + nb) + wb);
 }
 
+// The weights and norms of weighting wt into their place (cos_weight_ptrs), unless they are there: two launches on the
+// context's stream, the squares' scratch (P + 1 doubles) out of its arena.  The caller sets U.w_valid[wt] once it has
+// waited for the stream.  Shared by the score call and the text-to-text cosine (cosine_texts.h): the same doubles.
+static void cos_make_weights(Ctx &ctx, const CosState &c, CosUnits &U, int wt, double *w, double *norm)
+{
+    if (U.w_valid[wt]) return;
+    const u32 D = c.n_docs;
+    double *sq = ctx.arena->alloc<double>((size_t)U.P + 1);
+    if (U.P)
+        LAUNCH(ctx, cos_weights_kernel, ceil_div_u32(U.P, BLOCK), (const u32 *)U.post_doc, (const u32 *)U.post_unit,
+               (const u32 *)U.post_cnt, (const u32 *)U.unit_off, (const u32 *)c.n_d, (const u32 *)U.inv_perm, U.P, D, wt, w, sq);
+    LAUNCH(ctx, cos_norms_kernel, ceil_div_u32(D, WAVES_PER_BLOCK), (const double *)sq, (const u32 *)U.doc_off, D, norm);
+}
+
 static void cos_score(east_hip_index *h, const int32_t *q_ids, const i64 *q_offsets, i64 q_len, int32_t K, int32_t weighting,
                       double *out)
 {
@@ -939,13 +962,7 @@ static void cos_score(east_hip_index *h, const int32_t *q_ids, const i64 *q_offs
     Arena a = c.text.arena();             // (the build's first scratch: 6 bytes and more per byte of text, P <= bytes / 4)
     Ctx ctx = handle_ctx(h, &a, &stats);
     HIP_CHECK(hipEventRecord(h->ev0, h->stream));
-    if (!U.w_valid[weighting]) {
-        double *sq = a.alloc<double>((size_t)U.P + 1);
-        if (U.P)
-            LAUNCH(ctx, cos_weights_kernel, ceil_div_u32(U.P, BLOCK), (const u32 *)U.post_doc, (const u32 *)U.post_unit,
-                   (const u32 *)U.post_cnt, (const u32 *)U.unit_off, (const u32 *)c.n_d, (const u32 *)U.inv_perm, U.P, D, weighting, w, sq);
-        LAUNCH(ctx, cos_norms_kernel, ceil_div_u32(D, WAVES_PER_BLOCK), (const double *)sq, (const u32 *)U.doc_off, D, norm);
-    }
+    cos_make_weights(ctx, c, U, weighting, w, norm);
     if (total) HIP_CHECK(hipMemcpyAsync(d_ids, q_ids, (size_t)total * 4, hipMemcpyHostToDevice, h->stream));
     HIP_CHECK(hipMemcpyAsync(d_off, off32.data(), off32.size() * 4, hipMemcpyHostToDevice, h->stream));
     if (total)

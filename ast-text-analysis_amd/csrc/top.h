@@ -27,8 +27,9 @@
 // back are the table's own bytes, read again by the merge kernel (the key has lost the sign of a zero).  The tile length
 // is a test knob (east_hip_debug_set_top_tile); the result does not depend on it.
 //
-// The host half is a consumer of the handle (consumer.h); it alone also ranks the matrices of other consumers, two more table
-// sources: the similarity's (EAST_HIP_GRAPH_SOURCE_SIMILARITY) and the relatedness' (EAST_HIP_GRAPH_SOURCE_RELATED).
+// The host half is a consumer of the handle (consumer.h); it alone also ranks the matrices of other consumers, three more table
+// sources: the similarity's (EAST_HIP_GRAPH_SOURCE_SIMILARITY), the relatedness' (EAST_HIP_GRAPH_SOURCE_RELATED) and the
+// text-to-text cosine's (EAST_HIP_GRAPH_SOURCE_COSINE_TEXTS).
 #pragma once
 #include "consumer.h"
 

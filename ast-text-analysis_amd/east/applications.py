@@ -513,3 +513,107 @@ def texts_related(texts, n=10, orientation="symmetric", relatedness_threshold=No
     else:
         lists = _top_select(_related_on_host(texts, code, measure, language)[0], 1, n, threshold)
     return _top_named(lists, titles, titles)
+
+
+# ---- text-to-text cosine similarity --------------------------------------------------------------------------------------
+_TEXTS_SIMILAR_HOST_BLOCK = 4096            # units of the vector space a dense D x block array of the host path holds at a time
+
+
+def _texts_cosine_matrix(doc_units, n_units, tfidf):
+    """The contract of include/east_hip.h ("Text-to-text cosine similarity") in numpy: doc_units[d] = the units of text d's
+    kept tokens, one entry a token, units numbered 0 .. n_units - 1.  x = count / max(n_d, 1), times 1 + ln(D / df) under
+    tf-idf; norm = the root of the sum of the squares, 1.0 for a text without a posting; the products over the unit axis in
+    column blocks of _TEXTS_SIMILAR_HOST_BLOCK.  -> (C[D, D] with NaN on the diagonal, self[D], postings[D])."""
+    D = len(doc_units)
+    doc, unit, weight = [], [], []
+    df = np.zeros(n_units, dtype=np.int64)
+    postings = np.zeros(D, dtype=np.int32)
+    for d, ids in enumerate(doc_units):
+        u, count = np.unique(np.asarray(ids, dtype=np.int64), return_counts=True)
+        df[u] += 1
+        postings[d] = u.size
+        doc.append(np.full(u.size, d, dtype=np.int64))
+        unit.append(u)
+        weight.append(count.astype(np.float64) / float(max(len(ids), 1)))
+    doc = np.concatenate(doc) if doc else np.zeros(0, np.int64)
+    unit = np.concatenate(unit) if unit else np.zeros(0, np.int64)
+    weight = np.concatenate(weight) if weight else np.zeros(0, np.float64)
+    if tfidf and unit.size:
+        weight = weight * (1.0 + np.log(float(D) / df[unit].astype(np.float64)))
+    order = np.argsort(unit, kind="stable")
+    doc, unit, weight = doc[order], unit[order], weight[order]
+    gram = np.zeros((D, D), dtype=np.float64)
+    square = np.zeros(D, dtype=np.float64)
+    for lo in range(0, n_units, _TEXTS_SIMILAR_HOST_BLOCK):
+        a, e = np.searchsorted(unit, [lo, lo + _TEXTS_SIMILAR_HOST_BLOCK])
+        if a == e:
+            continue
+        block = np.zeros((D, min(_TEXTS_SIMILAR_HOST_BLOCK, n_units - lo)), dtype=np.float64)
+        block[doc[a:e], unit[a:e] - lo] = weight[a:e]
+        gram += block @ block.T
+        square += np.einsum("du,du->d", block, block)
+    norm = np.where(postings > 0, np.sqrt(square), 1.0)
+    matrix = gram / (norm[:, None] * norm[None, :])
+    own = matrix.diagonal().copy()
+    np.fill_diagonal(matrix, np.nan)
+    return matrix, own, postings
+
+
+def _texts_similar_on_host(texts, measure, language):
+    """texts_similar's matrix on the host, without a device: the tokens of utils.tokenize(utils.prepare_text(text)) through
+    the measure's own filter (at least 3 code points, not a stopword) and, in the stems space, its stemmer; the units
+    numbered by first occurrence."""
+    stems = measure.vector_space == consts.VectorSpace.STEMS
+    stemmer = None
+    if stems:
+        stemmer = measure.stemmer if measure._snowball is None else measure._snowball.SnowballStemmer(language)
+    number, stem_of, doc_units = {}, {}, []
+    for text in texts.values():
+        ids = []
+        for token in utils.tokenize(utils.prepare_text(text)):
+            if len(token) < 3 or token in measure.stopwords:
+                continue
+            if stems:
+                if token not in stem_of:
+                    stem_of[token] = stemmer.stem(token)
+                token = stem_of[token]
+            ids.append(number.setdefault(token, len(number)))
+        doc_units.append(ids)
+    return _texts_cosine_matrix(doc_units, len(number), measure.term_weighting == consts.TermWeighting.TF_IDF)
+
+
+def texts_similar(texts, n=10, similarity_threshold=None, similarity_measure=None, language=consts.Language.ENGLISH):
+    """The texts most like every text, from the texts alone: no keyphrase file.  Alike means the cosine of two texts' term
+    vectors -- tf or tf-idf weights over the words or the stems, as the cosine measure is set up (+0.0 for two texts without
+    a common term).
+
+    :param texts: {text name: text}
+    :param n: entries per text at most, 1 .. 1024
+    :param similarity_threshold: only cosines >= it are listed (None: every cosine that is a number)
+    :param similarity_measure: a relevance.CosineRelevanceMeasure (None: CosineRelevanceMeasure()); any other measure raises
+                               ValueError -- the AST measure's answer to the same question is texts_related
+    :returns: {text name: [(other text name, cosine), ...]}, best first: by cosine descending and, among equal cosines, in
+              the order of `texts`; a text never lists itself; plain Python values
+
+    The matrix and its ranking are made on the device, straight out of the term index (csrc/cosine_texts.h, csrc/top.h),
+    when the text titles are distinct and EAST_HIP_TEXTS_SIMILAR is not `host`; in every other case on the host, which then
+    touches no device at all: the same tokens, the formula in numpy over column blocks of the term axis.  The two paths sum in
+    different orders: their cosines agree to (t_ab + ceil(p_a / 64) + ceil(p_b / 64) + 176) * 2^-52 relative (t_ab = the
+    common terms of two texts, p = a text's distinct terms) and they name the same texts in the same order wherever
+    neighbouring cosines lie further apart than twice that -- they are NOT promised to be the same bytes.  (Python's
+    upper() and the device's 1:1 upper-casing agree on every character but a few such as U+00DF.)
+    """
+    _, n, threshold = _ranking_arguments("texts_similar", "text", n, similarity_threshold, "similarity")
+    measure = relevance.CosineRelevanceMeasure() if similarity_measure is None else similarity_measure
+    if not isinstance(measure, relevance.CosineRelevanceMeasure):
+        raise ValueError("texts_similar: the cosine of term vectors needs a CosineRelevanceMeasure, not %s (texts_related "
+                         "answers with the AST measure)" % type(measure).__name__)
+    titles = list(texts.keys())
+    if not titles:
+        return {}
+    if _device_applies(measure, texts, None, "relevance_texts_similar", "EAST_HIP_TEXTS_SIMILAR"):
+        measure.set_text_collection(list(texts.values()), language)
+        lists = _top_lists(measure.relevance_texts_similar(n, threshold))
+    else:
+        lists = _top_select(_texts_similar_on_host(texts, measure, language)[0], 1, n, threshold)
+    return _top_named(lists, titles, titles)

@@ -154,6 +154,10 @@ SIGNATURES = {
     "east_hip_related_fetch": (ctypes.c_int, [ctypes.c_void_p, _c_dblp, _c_dblp, _c_i32p]),
     "east_hip_last_related_ms": (ctypes.c_double, [ctypes.c_void_p]),
     "east_hip_debug_set_related_chunk": (ctypes.c_int, [ctypes.c_int64]),
+    "east_hip_text_similarity_build": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _c_i64p]),
+    "east_hip_text_similarity_fetch": (ctypes.c_int, [ctypes.c_void_p, _c_dblp, _c_dblp, _c_i32p]),
+    "east_hip_last_text_similarity_ms": (ctypes.c_double, [ctypes.c_void_p]),
+    "east_hip_debug_set_text_similarity_batch": (ctypes.c_int, [ctypes.c_int64]),
 }
 
 BUILD_INFO_FIELDS = ("n_total", "n_docs", "n_strings", "sigma_text", "bits_level0", "dc3_levels", "arena_bytes",
@@ -168,7 +172,10 @@ COSINE_INFO_FIELDS = ("built", "n_docs", "kept_tokens", "words", "terms", "class
 GRAPH_SOURCE_AST, GRAPH_SOURCE_COSINE, GRAPH_SOURCE_UPLOADED = 0, 1, 2      # east_hip_graph_build_resident: which resident table
 GRAPH_SOURCE_SIMILARITY = 3                 # east_hip_top_build_resident only: the matrix the last similarity build left
 GRAPH_SOURCE_RELATED = 4                    # east_hip_top_build_resident only: the matrix the last related build left
-RELATED_DIRECTED, RELATED_SYMMETRIC = 0, 1                                  # east_hip_related_build: the orientation
+GRAPH_SOURCE_COSINE_TEXTS = 5               # east_hip_top_build_resident only: the matrix the last cosine texts build left
+COSINE_TEXTS_CHUNK, COSINE_TEXTS_SEG = 32, 8192      # csrc/cosine_texts.h: the units of a staged chunk and of a segment (texts_build reports them)
+COSINE_TEXTS_INFO_FIELDS = ("n_docs", "units", "postings", "tiles", "segments", "launches", "chunk_units", "segment_units")
+RELATED_DIRECTED, RELATED_SYMMETRIC = 0, 1                               # east_hip_related_build: the orientation
 TOP_BY_TEXT, TOP_BY_KEYPHRASE = 0, 1                                        # east_hip_top_build_*: what a segment is
 TOP_MAX_N = 1024
 
@@ -813,6 +820,36 @@ class HipCosineIndex(_ResidentTableConsumers):
         _check(self._lib.east_hip_cosine_score_table(self._h, _ptr(q_ids, _c_i32p), _ptr(q_offsets, _c_i64p), q_ids.size, K,
                                                      1 if tfidf else 0, _ptr(out, _c_dblp) if fetch else None))
         return out
+
+    # -- text-to-text cosine similarity ------------------------------------------
+    def texts_build(self, tfidf=True):
+        """The D x D cosine matrix of the index's own texts in the vector space the score call uses (include/east_hip.h,
+        "Text-to-text cosine similarity"); it stays on the device.  -> {COSINE_TEXTS_INFO_FIELDS: value}"""
+        out = np.zeros(len(COSINE_TEXTS_INFO_FIELDS), dtype=np.int64)
+        _check(self._lib.east_hip_text_similarity_build(self._h, 1 if tfidf else 0, _ptr(out, _c_i64p)))
+        self._texts_D = int(out[0])
+        return dict(zip(COSINE_TEXTS_INFO_FIELDS, (int(x) for x in out)))
+
+    def texts_matrix(self):
+        """The last text-to-text cosine matrix of this handle -> (matrix[D, D] with NaN on the diagonal, self[D] = the
+        diagonal before the NaN, postings[D] = the postings of every text, int32)."""
+        D = getattr(self, "_texts_D", 0)
+        matrix, own, postings = np.empty((D, D), dtype=np.float64), np.empty(D, dtype=np.float64), np.empty(D, dtype=np.int32)
+        _check(self._lib.east_hip_text_similarity_fetch(self._h, _ptr(matrix, _c_dblp), _ptr(own, _c_dblp), _ptr(postings, _c_i32p)))
+        return matrix, own, postings
+
+    def rank_texts(self, n, threshold=-np.inf):
+        """A ranking of the last text-to-text cosine matrix by row (other n, other threshold: no new matrix) -> TopArrays."""
+        return _top_build(self._lib, self._h, GRAPH_SOURCE_COSINE_TEXTS, None, TOP_BY_KEYPHRASE, n, threshold)
+
+    def texts_similar(self, tfidf=True, n=10, threshold=-np.inf):
+        """texts_build, then the n most similar other texts of every text (the NaN on the diagonal is never eligible)
+        -> TopArrays.  It is the handle's one ranking: it replaces top()'s and similar()'s."""
+        self.texts_build(tfidf)
+        return self.rank_texts(n, threshold)
+
+    def last_texts_ms(self):
+        return float(self._lib.east_hip_last_text_similarity_ms(self._h))
 
 
 SYNONYMS_INFO_FIELDS = ("raw_triples", "distinct_triples", "words", "relations", "features", "longest_row")

@@ -16,6 +16,10 @@ README.rst:27-63; the shipped reference main crashes with a NameError, SURVEY.md
         the N texts most related to every text, from the texts alone (no keyphrase file): every string of text A is scored
         against the tree of text B out of the index, the scores are averaged per A (-o directed) and with the opposite
         direction (-o symmetric, the default), best first, on the device (csrc/related.h); one device, the AST measure
+    east [-w tf|tf-idf] [-v stems|words] [-n N] [-r threshold] [-l language] [-f xml|csv] texts similar <directory | single file>
+        the N texts most like every text, from the texts alone: the cosine of their tf or tf-idf term vectors (the cosine
+        measure's own index, stopwords and stemmer), best first, matrix and ranking on the device (csrc/cosine_texts.h); one
+        device; `-s ast` is refused (that question is `texts related`)
     east -s cosine [-w tf|tf-idf] [-v stems|words] keyphrases table|graph|top|similar ...
         the cosine measure (relevance.CosineRelevanceMeasure) on one device; `-v stems` (the default) needs nltk's
         Snowball stemmer, and without nltk's stopword list no stopwords are removed (said on stderr)
@@ -275,15 +279,17 @@ def _related_options(opts):
 
 
 def _texts_main(opts, args, world, rank):
-    """`east texts related <texts>`.  Everything that cannot be done is refused with one line before a file is read or
+    """`east texts related <texts>` (and `east texts similar <texts>`: _texts_similar_main).  Everything that cannot be done is refused with one line before a file is read or
     anything touches a device."""
     def refuse(line):
         if rank == 0:
             print(line)
         return 1
 
-    if len(args) < 2 or args[1] != "related":
-        return refuse("Invalid subcommand: '%s'. Please use one of: 'related'." % (args[1] if len(args) > 1 else ""))
+    if len(args) < 2 or args[1] not in ("related", "similar"):
+        return refuse("Invalid subcommand: '%s'. Please use one of: 'related', 'similar'." % (args[1] if len(args) > 1 else ""))
+    if args[1] == "similar":
+        return _texts_similar_main(opts, args, world, refuse)
     if len(args) < 3:
         return refuse('Invalid syntax. For text analysis, EAST should be called as:\n\n'
                       '    east [options] texts related "path/to/texts/dir"')
@@ -311,6 +317,53 @@ def _texts_main(opts, args, world, rank):
         related = applications.texts_related(texts, n, orientation, threshold, measure, opts.get("-l", consts.Language.ENGLISH))
         print(formatting.format_related(related, opts.get("-f", "xml").lower()))
     except exceptions.EastException as e:       # (no device, a failed build ...): a message, not a traceback
+        print(e)
+        return 1
+    except Exception as e:                      # (an unknown format)
+        print(e)
+        return 1
+    return 0
+
+
+def _texts_similar_main(opts, args, world, refuse):
+    """`east texts similar <texts>`: the cosine of the texts' term vectors.  Everything that cannot be done is refused with one
+    line (refuse) before a file is read or a measure is made."""
+    if len(args) < 3:
+        return refuse('Invalid syntax. For text analysis, EAST should be called as:\n\n'
+                      '    east [options] texts similar "path/to/texts/dir"')
+    n, _, threshold, refusal = _top_options({key: value for key, value in opts.items() if key != "-b"})
+    if refusal:
+        return refuse(refusal.replace("relevance threshold", "similarity threshold"))
+    measure_name = opts.get("-s", consts.RelevanceMeasure.COSINE).lower()
+    if measure_name == consts.RelevanceMeasure.AST.lower():
+        return refuse("Text similarity is the cosine of term vectors: -s %s is not supported (see `texts related`)." % opts["-s"])
+    if measure_name != consts.RelevanceMeasure.COSINE:
+        return refuse("Relevance measure '%s' is not available for `texts similar` (use 'cosine')." % opts["-s"])
+    if opts.get("-v", consts.VectorSpace.STEMS).lower() == consts.VectorSpace.LEMMATA:
+        return refuse("Text similarity has no lemmatizer: -v %s is not supported (use 'stems' or 'words')." % opts["-v"])
+    if "-y" in opts:
+        return refuse("Text similarity takes no synonyms: -y is not supported.")
+    if "-o" in opts:
+        return refuse("Text similarity is symmetric: -o %s is not supported (an orientation belongs to `texts related`)." % opts["-o"])
+    if world > 1:
+        return refuse("Text similarity runs on one device: a launcher with WORLD_SIZE=%d is not supported." % world)
+    if os.environ.get("EAST_HIP_FORCE_DIST") == "1":
+        return refuse("Text similarity runs on one device: the collective path is not supported.")
+    devices = opts.get("-g", os.environ.get("EAST_HIP_DEVICES", "1"))
+    try:
+        n_ranks = int(devices)
+    except ValueError:
+        return refuse("Invalid number of GPUs: '%s'." % devices)
+    if n_ranks > 1:
+        return refuse("Text similarity runs on one device: -g %d is not supported." % n_ranks)
+    try:
+        measure = relevance.CosineRelevanceMeasure(opts.get("-v", consts.VectorSpace.STEMS), opts.get("-w", consts.TermWeighting.TF_IDF))
+        if measure.stopwords_source == "none":
+            sys.stderr.write("nltk's English stopword list is not available: no stopwords are removed.\n")
+        texts = _read_texts(args[2])
+        similar = applications.texts_similar(texts, n, threshold, measure, opts.get("-l", consts.Language.ENGLISH))
+        print(formatting.format_similar(similar, "text", opts.get("-f", "xml").lower()))
+    except exceptions.EastException as e:       # (a missing stemmer, no device, a failed build ...): a message, not a traceback
         print(e)
         return 1
     except Exception as e:                      # (an unknown format)

@@ -21,6 +21,9 @@ from east.asts import utils as ast_utils
 
 class RelevanceMeasure(object):
 
+    relevance_texts_similar = None      # (the cosine of two texts' term vectors: the cosine measure alone)
+    text_similarity_matrix = None
+
     def set_text_collection(self, texts, language=consts.Language.ENGLISH):
         raise NotImplementedError()
 
@@ -427,6 +430,17 @@ class CosineRelevanceMeasure(RelevanceMeasure):
         """The n most similar other members of every text or keyphrase (ASTRelevanceMeasure.relevance_similar)."""
         self._score(prepared_keyphrases, False)
         return self.index.similar(axis, n, threshold)
+
+    def relevance_texts_similar(self, n, threshold=-np.inf):
+        """The n most similar other texts of every text of the collection: the cosine of their term vectors in this
+        measure's vector space and weighting, straight out of the term index (csrc/cosine_texts.h); after
+        set_text_collection.  -> hip_backend.TopArrays."""
+        return self.index.texts_similar(self.term_weighting == consts.TermWeighting.TF_IDF, n, threshold)
+
+    def text_similarity_matrix(self):
+        """The D x D matrix relevance_texts_similar ranks -> (matrix, self, postings) of HipCosineIndex.texts_matrix."""
+        self.index.texts_build(self.term_weighting == consts.TermWeighting.TF_IDF)
+        return self.index.texts_matrix()
 
     def _score(self, prepared_keyphrases, fetch):
         per_query = [self._query_terms(q) for q in prepared_keyphrases]

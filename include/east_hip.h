@@ -485,6 +485,63 @@ double east_hip_last_related_ms(east_hip_handle_t h);
 int east_hip_debug_set_related_chunk(int64_t strings);
 
 /*
+ * Text-to-text cosine similarity (`east texts similar`): the cosine of the tf or tf-idf vectors of every two texts of the
+ * cosine term index, and -- through the ranking above -- the n most similar others of each.  (How: csrc/cosine_texts.h,
+ * DESIGN.md 15.)  Not to be confused with "Similar texts and keyphrases" above, the cosine of score-table profiles: these
+ * entry points are named east_hip_text_similarity_*, those east_hip_similarity_*.
+ *
+ * A cosine index has been built on the handle; the vector space is the one the score call uses: the terms, or the classes
+ * after east_hip_cosine_set_classes.  For a weighting (0 tf, 1 tf-idf) and documents a, b of the D of the index:
+ *   x_d[u]   = the weight of posting (u, d): count / max(n_d, 1), times 1 + ln(D / df_u) under tf-idf -- the same double the
+ *              score call uses;
+ *   norm_d   = the norm the score call divides by: the squares of x_d in ascending unit order cut into 64 consecutive
+ *              slices, the 64 partial sums added in order, the square root; 1.0 for a document without postings;
+ *   G_ab     = the sum over the units u common to a and b of x_a[u] * x_b[u];
+ *   C[a][b]  = G_ab / (norm_a * norm_b) for a != b: one product, one quotient; +0.0 when a and b share no unit (a document
+ *              without postings shares none with anybody); C[a][a] = NaN, so that nobody lists itself;
+ *   self[d]  = G_dd / (norm_d * norm_d), the diagonal before the NaN: 1 up to rounding for a document with postings, +0.0
+ *              for one without (the two sums take different orders: their agreement is a check);
+ *   postings[d] = the postings of document d in the vector space.
+ * The matrix is D x D doubles, row-major.
+ * Guaranteed: no atomic is used and the order of every sum is fixed by the collection alone -- the units of a pair in
+ * ascending order inside fixed segments of the unit range, the segments' sums added in segment order; two builds give the
+ * same bytes, under any value of the batch knob below; C[a][b] and C[b][a] are the same bytes (one value written to two
+ * places); an exact value of 0 is +0.0 bit for bit.
+ * Accuracy: all weights are non-negative, so no order of the sum cancels.  With t_ab the units common to a and b and
+ * p_d = postings[d], for a != b
+ *   |C[a][b] - exact| <= (t_ab + ceil(p_a / 64) + ceil(p_b / 64) + 128 + 48) * 2^-52 * exact
+ * (t_ab roundings of the dot product; per norm a slice of ceil(p / 64) and 64 partial sums; 48 ulp for log, sqrt, the
+ * divisions and the products, a weight entering a product on both sides), and the same with t_aa = p_a bounds |self[a] - 1|.
+ *
+ * The build call: out (at least 8 entries, nullable) = D, the units of the vector space, its postings, the 64 x 64 tiles of
+ * document pairs computed (tile_a <= tile_b), the segments of the unit range, the kernel launches, the units of a staged
+ * chunk (32), the units of a segment.  EAST_HIP_ERR_NOT_BUILT without a cosine index; EAST_HIP_ERR_INVALID for a null
+ * handle or an unknown weighting; EAST_HIP_ERR_OOM with D and the bytes in the message when the matrix or its scratch
+ * cannot be had.  A build that fails leaves no matrix.
+ * The fetch call gives the last result (each pointer nullable): matrix[D * D], self[D], postings[D].
+ * EAST_HIP_ERR_NOT_BUILT without a matrix.
+ * The matrix is withdrawn by east_hip_reset, by every east_hip_cosine_build_texts* call and by every
+ * east_hip_cosine_set_classes call (the space changed under it), whether or not that call succeeds.  A score call, a
+ * similarity build, an EASA build or a ranking leaves it alone.
+ * Ranking the matrix: east_hip_top_build_resident accepts the source EAST_HIP_GRAPH_SOURCE_COSINE_TEXTS = the D x D matrix
+ * the last build left, ranked like any table (callers use EAST_HIP_TOP_BY_KEYPHRASE: a segment is a row; the NaN on the
+ * diagonal is never eligible); EAST_HIP_ERR_NOT_BUILT without a matrix.  The handle still has ONE ranking.
+ * The matrix, self, postings, the postings in document order and the partial tiles live in buffers of their own -- not the
+ * cosine index's, the EASA arena or another consumer's; the weights and norms are the cosine index's, made on first use by
+ * this call or by the score call, whichever comes first.  Memory: 12 bytes a posting, the matrix, and partial tiles of at
+ * most 256 MiB or of one segment (half the matrix's size), whichever is more.
+ * Device time of the last build in milliseconds (events on the handle's stream around all launches), -1 before a build,
+ * after a failed one and once the matrix has been withdrawn.
+ * Test knob (process-wide, read when a build starts): the segments per launch of the tile kernel; 0 = the default (as many
+ * as keep the partial tiles at or below 256 MiB).  The result does not depend on it.
+ */
+#define EAST_HIP_GRAPH_SOURCE_COSINE_TEXTS 5
+int east_hip_text_similarity_build(east_hip_handle_t h, int32_t weighting, int64_t *out);
+int east_hip_text_similarity_fetch(east_hip_handle_t h, double *matrix, double *self, int32_t *postings);
+double east_hip_last_text_similarity_ms(east_hip_handle_t h);
+int east_hip_debug_set_text_similarity_batch(int64_t segments);
+
+/*
  * Several devices in one process ("single-process/8-device fits the one-process CLI best").
  * Every document is an independent AST (east/relevance.py:41-46) and every (keyphrase, document) score is independent
  * (east/applications.py:43-52): a GROUP shards a collection at document granularity -- contiguous blocks of documents
