@@ -1,5 +1,5 @@
 // consumer.h -- the host frame of the handle's consumers: the cosine term index, the keyphrase graph, the synonyms, the
-// ranking, the similarity, the text-to-text relatedness and the text-to-text cosine.  A consumer is a struct of device buffers and results that the handle owns beside its arena,
+// ranking, the similarity, the text-to-text relatedness, the text-to-text cosine and the clusters.  A consumer is a struct of device buffers and results that the handle owns beside its arena,
 // made by the consumer's first call.  Nothing in here knows one consumer from another ("The consumer frame").
 #pragma once
 #include "handle.h"
@@ -96,7 +96,7 @@ struct UploadedTable {
 // ---- which table a *_build_resident call reads ----------------------------------------------------------------------------
 // who: the consumer's name in front of its messages; own: the caller's uploaded copy (nullptr before its first call);
 // matrices_ok: the square matrices other consumers built -- the similarity's, the relatedness', the text-to-text cosine's --
-// are sources too (the ranking alone).
+// are sources too (the ranking and the clusters).
 static TableRef resolve_table(const east_hip_index *h, int32_t source, const UploadedTable *own, const char *who, bool matrices_ok = false)
 {
     auto offered = [&](int slot) { return h->consumers[slot] ? h->consumers[slot]->offers() : TableRef(); };

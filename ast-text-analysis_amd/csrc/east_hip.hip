@@ -447,3 +447,4 @@ double east_hip_last_score_ms(east_hip_handle_t h) { return h ? (double)h->last_
 #include "top.h"            // ranked keyphrases
 #include "related.h"        // text-to-text relatedness
 #include "cosine_texts.h"   // text-to-text cosine similarity
+#include "clusters.h"       // single-linkage clusters of a square matrix

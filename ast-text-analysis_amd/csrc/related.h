@@ -183,6 +183,7 @@ __global__ __launch_bounds__(BLOCK) void rel_finish_kernel(double *__restrict__ 
 struct RelState : Consumer {
     static constexpr int SLOT = east_hip_index::SLOT_REL;
     u32 D = 0;
+    bool symmetric = false;                 // the matrix is the symmetric form (clusters.h takes no other)
     DevBuf scan_tmp, dir, partial, out;    // the terminator counts (released after the directory); the directory and the lists; partial[tile][D]; matrix, self, scored
     double *matrix = nullptr, *self = nullptr;
     int32_t *scored = nullptr;
@@ -375,6 +376,7 @@ static void rel_build(east_hip_index *h, int normalized, int32_t orientation, i6
     LAUNCH(ctx, rel_finish_kernel, (u32)std::min<u64>(((u64)D * D + BLOCK - 1) / BLOCK, REL_MAX_GRID), g.matrix, D, (const int32_t *)g.scored, (int)(orientation == EAST_HIP_RELATED_SYMMETRIC),
            g.self);
     timer.finish();
+    g.symmetric = orientation == EAST_HIP_RELATED_SYMMETRIC;
     g.valid = true;
     if (out) { out[0] = (i64)D; out[1] = (i64)c_total; out[2] = (i64)chunks.size(); }
 }

@@ -617,3 +617,209 @@ def texts_similar(texts, n=10, similarity_threshold=None, similarity_measure=Non
     else:
         lists = _top_select(_texts_similar_on_host(texts, measure, language)[0], 1, n, threshold)
     return _top_named(lists, titles, titles)
+
+
+# ---- clusters ------------------------------------------------------------------------------------------------------------
+def _strongest_first(matrix):
+    """The pairs a < b of a symmetric M x M array that are not NaN in the order of include/east_hip.h ("Clusters"): by
+    weight descending (-0.0 == +0.0), then a, then b ascending.  -> (a, b, w); w is the upper triangle's own bytes."""
+    a, b = np.triu_indices(matrix.shape[0], 1)
+    w = matrix[a, b]
+    edge = ~np.isnan(w)
+    a, b, w = a[edge], b[edge], w[edge]
+    order = np.lexsort((b, a, -(w + 0.0)))                  # (-0.0 + 0.0 is +0.0: the zeros tie)
+    return a[order], b[order], w[order]
+
+
+class _Sets(object):
+    """Disjoint sets of 0 .. M - 1; the root of a set is its smallest member."""
+
+    def __init__(self, M):
+        self.parent = list(range(M))
+
+    def find(self, v):
+        parent = self.parent
+        while parent[v] != v:
+            parent[v] = parent[parent[v]]
+            v = parent[v]
+        return v
+
+    def union(self, a, b):
+        """-> (the root that stays, the root that went), or None when a and b are in one set already."""
+        a, b = self.find(a), self.find(b)
+        if a == b:
+            return None
+        a, b = min(a, b), max(a, b)
+        self.parent[b] = a
+        return a, b
+
+
+def _roots(M, merge_a, merge_b, n):
+    """labels[v] = the smallest member of v's cluster after the first n merges."""
+    sets = _Sets(M)
+    for i in range(n):
+        sets.union(int(merge_a[i]), int(merge_b[i]))
+    return [sets.find(v) for v in range(M)]
+
+
+def _single_linkage(matrix):
+    """The contract of include/east_hip.h ("Clusters") in plain Python: Kruskal's algorithm over the edges strongest
+    first.  -> (merge_a, merge_b, merge_w), the forest's edges in that order."""
+    matrix = np.asarray(matrix, dtype=np.float64)
+    M = matrix.shape[0]
+    a, b, w = _strongest_first(matrix)
+    sets, took = _Sets(M), []
+    for i in range(a.size):
+        if len(took) == M - 1:
+            break                                           # (a spanning tree: every later edge closes a cycle)
+        if sets.union(int(a[i]), int(b[i])):
+            took.append(i)
+    took = np.asarray(took, dtype=np.int64)
+    return a[took].astype(np.int32), b[took].astype(np.int32), w[took]
+
+
+class Clustering(object):
+    """Single-linkage clusters of named members.
+
+    names     the members, in index order
+    merges    the dendrogram, [(name_a, name_b, similarity)], strongest merge first (index of a < index of b);
+              merge_a, merge_b (int32), merge_w (float64) hold the same as arrays of member indexes
+    labels    per member the smallest member index of its cluster -- None when neither a threshold nor k was given
+    clusters  lists of names: the clusters ordered by their smallest member, the members in index order -- or None
+    """
+
+    def __init__(self, names, merge_a, merge_b, merge_w, labels=None):
+        self.names = list(names)
+        self.merge_a = np.asarray(merge_a, dtype=np.int32)
+        self.merge_b = np.asarray(merge_b, dtype=np.int32)
+        self.merge_w = np.asarray(merge_w, dtype=np.float64)
+        self.merges = [(self.names[a], self.names[b], w) for a, b, w in
+                       zip(self.merge_a.tolist(), self.merge_b.tolist(), self.merge_w.tolist())]
+        self.labels = None if labels is None else [int(x) for x in labels]
+        self.clusters = None
+        if self.labels is not None:
+            members = {}
+            for v, root in enumerate(self.labels):
+                members.setdefault(root, []).append(self.names[v])
+            self.clusters = [members[root] for root in sorted(members)]
+
+    def to_linkage(self):
+        """The (M - 1) x 4 array of scipy.cluster.hierarchy: per merge the two clusters joined (a member is its index,
+        the cluster merge i made is M + i; the smaller id first), the SIMILARITY in the distance column -- it falls where
+        SciPy's distances rise -- and the size of the new cluster.  Defined when the dendrogram is one tree."""
+        M = len(self.names)
+        if len(self.merge_a) != M - 1 or M < 1:
+            raise ValueError("to_linkage: the dendrogram is not one tree (%d merges of %d members)" % (len(self.merge_a), M))
+        sets, cluster, size = _Sets(M), list(range(M)), [1] * M
+        Z = np.zeros((M - 1, 4), dtype=np.float64)
+        for i in range(M - 1):
+            a, b = sets.find(int(self.merge_a[i])), sets.find(int(self.merge_b[i]))
+            ids = sorted((cluster[a], cluster[b]))
+            kept, gone = sets.union(a, b)
+            size[kept] += size[gone]
+            cluster[kept] = M + i
+            Z[i] = (ids[0], ids[1], self.merge_w[i], size[kept])
+        return Z
+
+
+def _cut_arguments(who, threshold, k):
+    if threshold is not None and k is not None:
+        raise ValueError("%s: give a threshold or a number of clusters k, not both" % who)
+    if threshold is not None:
+        threshold = float(threshold)
+        if threshold != threshold:
+            raise ValueError("%s: the threshold is not a number" % who)
+    if k is not None:
+        if isinstance(k, bool) or int(k) != k or k < 1:
+            raise ValueError("%s: k must be an integer of at least 1, not %r" % (who, k))
+        k = int(k)
+    return threshold, k
+
+
+def _clustering_of_index(names, index, threshold, k):
+    """The Clustering of the clusters `index` (a hip_backend index) has just built."""
+    merge_a, merge_b, merge_w = index.clusters_merges()
+    labels = None
+    if threshold is not None or k is not None:
+        labels = index.clusters_cut(threshold, k)[0]
+    return Clustering(names, merge_a, merge_b, merge_w, labels)
+
+
+def _clustering_of_matrix(names, matrix, threshold, k):
+    """The same on the host, from an M x M array."""
+    merge_a, merge_b, merge_w = _single_linkage(matrix)
+    M, F = len(names), len(merge_a)
+    labels = None
+    if threshold is not None:
+        n = 0
+        while n < F and merge_w[n] >= threshold:
+            n += 1
+        labels = _roots(M, merge_a, merge_b, n)
+    elif k is not None:
+        labels = _roots(M, merge_a, merge_b, max(0, min(F, M - k)))
+    return Clustering(names, merge_a, merge_b, merge_w, labels)
+
+
+def texts_clusters(texts, threshold=None, k=None, similarity_measure=None, language=consts.Language.ENGLISH):
+    """The groups the texts fall into, from the texts alone: single-linkage agglomerative clustering of the matrix
+    texts_related (an AST measure: the symmetric relatedness) or texts_similar (a CosineRelevanceMeasure: the cosine of
+    the term vectors) ranks.
+
+    :param texts: {text name: text}
+    :param threshold: flat clusters = the connected components of "similarity >= threshold"
+    :param k: flat clusters by number: the strongest merges are applied until k clusters are left (there are never fewer
+              than the matrix has connected components); at most one of threshold and k -- with neither, only the
+              dendrogram is filled
+    :param similarity_measure: None: relevance.ASTRelevanceMeasure()
+    :returns: a Clustering
+
+    The matrix is built and clustered on the device (csrc/clusters.h) when the measure has `relevance_clusters`, the text
+    titles are distinct and EAST_HIP_CLUSTERS is not `host`; in every other case the matrix comes from the host paths of
+    texts_related / texts_similar and Kruskal's algorithm runs here.  The two matrices differ in their last bits by their
+    own contracts, so a near-tie may merge differently; on ONE matrix both give the same bytes.
+    """
+    threshold, k = _cut_arguments("texts_clusters", threshold, k)
+    measure = similarity_measure or relevance.ASTRelevanceMeasure()
+    titles = list(texts.keys())
+    if not titles:
+        return Clustering([], [], [], [], None if threshold is None and k is None else [])
+    if _device_applies(measure, texts, None, "relevance_clusters", "EAST_HIP_CLUSTERS"):
+        measure.set_text_collection(list(texts.values()), language)
+        return _clustering_of_index(titles, measure.relevance_clusters(), threshold, k)
+    if isinstance(measure, relevance.CosineRelevanceMeasure):
+        matrix = _texts_similar_on_host(texts, measure, language)[0]
+    else:
+        matrix = _related_on_host(texts, 1, measure, language)[0]
+    return _clustering_of_matrix(titles, matrix, threshold, k)
+
+
+def keyphrases_clusters(keyphrases, texts, by="text", threshold=None, k=None, similarity_measure=None, synonimizer=None,
+                        language=consts.Language.ENGLISH):
+    """The groups the texts (by="text") or the keyphrases (by="keyphrase") fall into by their profiles in the keyphrase x
+    text score table: single-linkage agglomerative clustering of the cosine matrix keyphrases_similar ranks.
+
+    :param keyphrases: raw keyphrase strings, taken as keyphrases_table takes them (empty ones are skipped, duplicates
+                       collapse)
+    :param texts: {text name: text}
+    :param threshold, k: as texts_clusters takes them
+    :returns: a Clustering of the text names or of the keyphrases
+
+    On the device (csrc/similarity.h, csrc/clusters.h) when the measure has `relevance_clusters`, no synonimizer is given,
+    the text titles are distinct and EAST_HIP_CLUSTERS is not `host`; in every other case on the host, from
+    keyphrases_table's array.
+    """
+    if by not in _TOP_AXES:
+        raise ValueError("keyphrases_clusters: by must be 'text' or 'keyphrase', not %r" % (by,))
+    axis = _TOP_AXES.index(by)
+    threshold, k = _cut_arguments("keyphrases_clusters", threshold, k)
+    measure = similarity_measure or relevance.ASTRelevanceMeasure()
+    titles = list(texts.keys())
+    wanted = [kp for kp in dict.fromkeys(keyphrases) if kp]              # applications.py:44-45
+    if not wanted or not titles:
+        return Clustering([], [], [], [], None if threshold is None and k is None else [])
+    if _device_applies(measure, texts, synonimizer, "relevance_clusters", "EAST_HIP_CLUSTERS"):
+        measure.set_text_collection(list(texts.values()), language)
+        index = measure.relevance_clusters([utils.prepare_text(kp) for kp in wanted], axis)
+        return _clustering_of_index(titles if axis == 0 else wanted, index, threshold, k)
+    scores, titles = _score_array(keyphrases_table(wanted, texts, measure, synonimizer, language), wanted, titles)
+    return _clustering_of_matrix(titles if axis == 0 else wanted, _similarity_matrix(scores, axis), threshold, k)

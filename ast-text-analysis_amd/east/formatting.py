@@ -168,6 +168,40 @@ def related2csv(result):
     return similar2csv(result, "text")
 
 
+def format_clusters(clustering, format):
+    """Clusters (applications.Clustering).  xml and csv list the flat clusters and need a cut (a threshold or k); merges
+    lists the dendrogram and needs none."""
+    renderers = {"xml": clusters2xml, "csv": clusters2csv, "merges": clusters2merges}
+    if format not in renderers:
+        raise Exception("Unknown clusters format: '%s'. Please use one of: 'xml', 'csv', 'merges'." % format)
+    if format != "merges" and clustering.clusters is None:
+        raise Exception("Clusters format '%s' lists flat clusters: give a threshold or a number of clusters." % format)
+    return renderers[format](clustering)
+
+
+def clusters2xml(clustering):
+    """<clusters count=..> / <cluster id=.. size=..> / <member name=../>; the clusters by their smallest member, numbered
+    from 1, the members in index order."""
+    lines = ['<clusters count="%d">' % len(clustering.clusters)]
+    for number, members in enumerate(clustering.clusters, 1):
+        lines.append('  <cluster id="%d" size="%d">' % (number, len(members)))
+        lines.extend('    <member name="%s"/>' % member for member in members)
+        lines.append("  </cluster>")
+    lines.append("</clusters>")
+    return "\n".join(lines) + "\n"
+
+
+def clusters2csv(clustering):
+    """One line per member: "member",cluster number,"the cluster's first member"; in the order of clusters2xml."""
+    return "".join("%s,%d,%s\n" % (_csv_quote(member), number, _csv_quote(members[0]))
+                   for number, members in enumerate(clustering.clusters, 1) for member in members)
+
+
+def clusters2merges(clustering):
+    """One line per merge of the dendrogram, strongest first: "member","member",similarity."""
+    return "".join("%s,%s,%s\n" % (_csv_quote(a), _csv_quote(b), _SCORE % similarity) for a, b, similarity in clustering.merges)
+
+
 def format_graph(graph, format):
     renderers = {"gml": graph2gml, "edges": graph2edges}
     if format not in renderers:

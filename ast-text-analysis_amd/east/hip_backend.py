@@ -158,6 +158,12 @@ SIGNATURES = {
     "east_hip_text_similarity_fetch": (ctypes.c_int, [ctypes.c_void_p, _c_dblp, _c_dblp, _c_i32p]),
     "east_hip_last_text_similarity_ms": (ctypes.c_double, [ctypes.c_void_p]),
     "east_hip_debug_set_text_similarity_batch": (ctypes.c_int, [ctypes.c_int64]),
+    "east_hip_clusters_build_resident": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _c_i64p]),
+    "east_hip_clusters_build_host": (ctypes.c_int, [ctypes.c_void_p, _c_dblp, ctypes.c_int32, _c_i64p]),
+    "east_hip_clusters_fetch": (ctypes.c_int, [ctypes.c_void_p, _c_i32p, _c_i32p, _c_dblp]),
+    "east_hip_clusters_cut_threshold": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, _c_i32p, _c_i64p]),
+    "east_hip_clusters_cut_count": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _c_i32p, _c_i64p]),
+    "east_hip_last_clusters_ms": (ctypes.c_double, [ctypes.c_void_p]),
 }
 
 BUILD_INFO_FIELDS = ("n_total", "n_docs", "n_strings", "sigma_text", "bits_level0", "dc3_levels", "arena_bytes",
@@ -175,6 +181,7 @@ GRAPH_SOURCE_RELATED = 4                    # east_hip_top_build_resident only: 
 GRAPH_SOURCE_COSINE_TEXTS = 5               # east_hip_top_build_resident only: the matrix the last cosine texts build left
 COSINE_TEXTS_CHUNK, COSINE_TEXTS_SEG = 32, 8192      # csrc/cosine_texts.h: the units of a staged chunk and of a segment (texts_build reports them)
 COSINE_TEXTS_INFO_FIELDS = ("n_docs", "units", "postings", "tiles", "segments", "launches", "chunk_units", "segment_units")
+CLUSTERS_INFO_FIELDS = ("members", "merges", "rounds", "launches")      # east_hip_clusters_build_*: out
 RELATED_DIRECTED, RELATED_SYMMETRIC = 0, 1                               # east_hip_related_build: the orientation
 TOP_BY_TEXT, TOP_BY_KEYPHRASE = 0, 1                                        # east_hip_top_build_*: what a segment is
 TOP_MAX_N = 1024
@@ -454,6 +461,57 @@ class _ResidentTableConsumers(object):
     @property
     def last_similarity_ms(self):
         return float(self._lib.east_hip_last_similarity_ms(self._h))
+
+    # -- clusters ----------------------------------------------------------------
+    def _clusters_built(self, out):
+        info = dict(zip(CLUSTERS_INFO_FIELDS, (int(x) for x in out)))
+        self._sim_holder._clu_info = info
+        return info
+
+    def clusters_build(self, source):
+        """Single-linkage clusters (include/east_hip.h, "Clusters") of a square matrix that lies on the device of this
+        handle: GRAPH_SOURCE_SIMILARITY, GRAPH_SOURCE_RELATED (symmetric), GRAPH_SOURCE_COSINE_TEXTS, or
+        GRAPH_SOURCE_UPLOADED = the copy the last clusters_build_host left -> {CLUSTERS_INFO_FIELDS: value}."""
+        out = np.zeros(len(CLUSTERS_INFO_FIELDS), dtype=np.int64)
+        _check(self._lib.east_hip_clusters_build_resident(self._h, int(source), _ptr(out, _c_i64p)))
+        return self._clusters_built(out)
+
+    def clusters_build_host(self, matrix):
+        """The same of an M x M host array, which is uploaded and checked for symmetry first."""
+        matrix = np.ascontiguousarray(matrix, dtype=np.float64)
+        if matrix.ndim != 2 or matrix.shape[0] != matrix.shape[1]:
+            raise exceptions.HipBackendError(reason="the matrix of clusters is an M x M array")
+        out = np.zeros(len(CLUSTERS_INFO_FIELDS), dtype=np.int64)
+        _check(self._lib.east_hip_clusters_build_host(self._h, _ptr(matrix, _c_dblp) if matrix.size else None, matrix.shape[0],
+                                                      _ptr(out, _c_i64p)))
+        return self._clusters_built(out)
+
+    def clusters_merges(self):
+        """The dendrogram of the last clusters build, strongest merge first -> (merge_a int32, merge_b int32, merge_w
+        float64: the matrix's own bytes of S[a][b], a < b)."""
+        info = getattr(self._sim_holder, "_clu_info", None) or {"merges": 0}
+        F = info["merges"]
+        a, b, w = np.empty(F, dtype=np.int32), np.empty(F, dtype=np.int32), np.empty(F, dtype=np.float64)
+        _check(self._lib.east_hip_clusters_fetch(self._h, _ptr(a, _c_i32p), _ptr(b, _c_i32p), _ptr(w, _c_dblp)))
+        return a, b, w
+
+    def clusters_cut(self, threshold=None, k=None):
+        """Flat clusters of the last build: the merges with similarity >= threshold, or the first merges that leave k
+        clusters (exactly one of the two) -> (labels int32: the smallest member of every member's cluster, clusters,
+        merges applied)."""
+        if (threshold is None) == (k is None):
+            raise exceptions.HipBackendError(reason="a cut of clusters takes a threshold or a number of clusters, one of the two")
+        info = getattr(self._sim_holder, "_clu_info", None) or {"members": 0}
+        labels, out = np.empty(info["members"], dtype=np.int32), np.zeros(2, dtype=np.int64)
+        if threshold is not None:
+            _check(self._lib.east_hip_clusters_cut_threshold(self._h, float(threshold), _ptr(labels, _c_i32p), _ptr(out, _c_i64p)))
+        else:
+            _check(self._lib.east_hip_clusters_cut_count(self._h, int(k), _ptr(labels, _c_i32p), _ptr(out, _c_i64p)))
+        return labels, int(out[0]), int(out[1])
+
+    @property
+    def last_clusters_ms(self):
+        return float(self._lib.east_hip_last_clusters_ms(self._h))
 
 
 class HipIndex(_ResidentTableConsumers):

@@ -20,7 +20,13 @@ README.rst:27-63; the shipped reference main crashes with a NameError, SURVEY.md
         the N texts most like every text, from the texts alone: the cosine of their tf or tf-idf term vectors (the cosine
         measure's own index, stopwords and stemmer), best first, matrix and ranking on the device (csrc/cosine_texts.h); one
         device; `-s ast` is refused (that question is `texts related`)
-    east -s cosine [-w tf|tf-idf] [-v stems|words] keyphrases table|graph|top|similar ...
+    east [-s ast|cosine] [-r threshold | -k clusters] [-w tf|tf-idf] [-v stems|words] [-d] [-f xml|csv|merges] texts clusters <texts>
+        the groups the texts fall into: single-linkage clusters of the symmetric relatedness (-s ast, the default) or of the
+        term-vector cosine (-s cosine), built where the matrix lies (csrc/clusters.h); -r: the texts joined by similarities
+        that reach it, -k: that many clusters, one of the two -- or neither with -f merges, the dendrogram a merge a line
+    east [-s ast|cosine] [-b text|keyphrase] [-r threshold | -k clusters] [-f xml|csv|merges] keyphrases clusters <keyphrases file> <texts>
+        the same of the texts (-b text) or the keyphrases (-b keyphrase) by the profile cosines of `keyphrases similar`
+    east -s cosine [-w tf|tf-idf] [-v stems|words] keyphrases table|graph|top|similar|clusters ...
         the cosine measure (relevance.CosineRelevanceMeasure) on one device; `-v stems` (the default) needs nltk's
         Snowball stemmer, and without nltk's stopword list no stopwords are removed (said on stderr)
     east -y -t <triples file> keyphrases table|graph ...
@@ -50,7 +56,7 @@ def _read(path):
         return f.read()
 
 
-_OPTIONS = "s:a:w:v:l:f:c:r:p:g:t:n:b:o:dy"
+_OPTIONS = "s:a:w:v:l:f:c:r:p:g:t:n:b:o:k:dy"
 _VALUE_OPTIONS = frozenset(c for c, nxt in zip(_OPTIONS, _OPTIONS[1:] + " ") if nxt == ":")
 
 
@@ -92,6 +98,8 @@ def main(argv=None, measure_factory=None):
             return 1
     if args[:1] == ["texts"]:
         return _texts_main(opts, args, world, rank)
+    if args[:2] == ["keyphrases", "clusters"]:
+        return _clusters_main(opts, args, world, rank)
     cosine = opts.get("-s", "").lower() == consts.RelevanceMeasure.COSINE
     if world > 1 and cosine:
         if rank == 0:
@@ -149,7 +157,7 @@ def _main(opts, args, world, measure_factory):
         print("Invalid syntax: EAST should be called as:\n\n"
               "    east [options] <command> <subcommand> args\n\n"
               "Commands available: keyphrases, texts.\n"
-              "Subcommands available: table/graph/top/similar.")
+              "Subcommands available: table/graph/top/similar/clusters.")
         return 1
 
     command, subcommand = args[0], args[1]
@@ -286,10 +294,12 @@ def _texts_main(opts, args, world, rank):
             print(line)
         return 1
 
-    if len(args) < 2 or args[1] not in ("related", "similar"):
-        return refuse("Invalid subcommand: '%s'. Please use one of: 'related', 'similar'." % (args[1] if len(args) > 1 else ""))
+    if len(args) < 2 or args[1] not in ("related", "similar", "clusters"):
+        return refuse("Invalid subcommand: '%s'. Please use one of: 'related', 'similar', 'clusters'." % (args[1] if len(args) > 1 else ""))
     if args[1] == "similar":
         return _texts_similar_main(opts, args, world, refuse)
+    if args[1] == "clusters":
+        return _clusters_main(opts, args, world, rank)
     if len(args) < 3:
         return refuse('Invalid syntax. For text analysis, EAST should be called as:\n\n'
                       '    east [options] texts related "path/to/texts/dir"')
@@ -367,6 +377,98 @@ def _texts_similar_main(opts, args, world, refuse):
         print(e)
         return 1
     except Exception as e:                      # (an unknown format)
+        print(e)
+        return 1
+    return 0
+
+
+def _clusters_options(opts):
+    """(threshold, k, format, None) of `texts clusters` and `keyphrases clusters`, or (None, None, None, the one line that
+    says what is wrong)."""
+    fmt = opts.get("-f", "xml").lower()
+    if fmt not in ("xml", "csv", "merges"):
+        return None, None, None, "Unknown clusters format: '%s'. Please use one of: 'xml', 'csv', 'merges'." % opts["-f"]
+    if "-r" in opts and "-k" in opts:
+        return None, None, None, "Clusters are cut by a threshold (-r) or by their number (-k): please give one of the two."
+    if "-r" not in opts and "-k" not in opts and fmt != "merges":
+        return None, None, None, "Clusters need a threshold (-r) or their number (-k); without either only -f merges has something to print."
+    threshold = k = None
+    if "-r" in opts:
+        try:
+            threshold = float(opts["-r"])
+        except ValueError:
+            threshold = float("nan")
+        if threshold != threshold:
+            return None, None, None, "Invalid similarity threshold: '%s'." % opts["-r"]
+    if "-k" in opts:
+        try:
+            k = int(opts["-k"])
+        except ValueError:
+            k = 0
+        if k < 1:
+            return None, None, None, "Invalid number of clusters: '%s'. Please use an integer of at least 1." % opts["-k"]
+    return threshold, k, fmt, None
+
+
+def _clusters_main(opts, args, world, rank):
+    """`east texts clusters <texts>` and `east keyphrases clusters <keyphrases file> <texts>`.  Everything that cannot be done
+    is refused with one line before a file is read or anything touches a device."""
+    def refuse(line):
+        if rank == 0:
+            print(line)
+        return 1
+
+    of_texts = args[0] == "texts"
+    if len(args) < (3 if of_texts else 4):
+        return refuse('Invalid syntax. For clusters, EAST should be called as:\n\n'
+                      '    east [options] texts clusters "path/to/texts/dir"\n'
+                      '    east [options] keyphrases clusters "path/to/keyphrases.txt" "path/to/texts/dir"')
+    threshold, k, fmt, refusal = _clusters_options(opts)
+    if refusal:
+        return refuse(refusal)
+    measure_name = opts.get("-s", consts.RelevanceMeasure.AST).lower()
+    cosine = measure_name == consts.RelevanceMeasure.COSINE
+    if measure_name != consts.RelevanceMeasure.AST.lower() and not cosine:
+        return refuse("Relevance measure '%s' is not available (use 'ast' or 'cosine')." % opts["-s"])
+    by = opts.get("-b", "text").lower()
+    if by not in ("text", "keyphrase"):
+        return refuse("Invalid clustering direction: '%s'. Please use one of: 'text', 'keyphrase'." % opts["-b"])
+    if of_texts and "-b" in opts:
+        return refuse("`texts clusters` groups the texts: -b %s is not supported (a direction belongs to `keyphrases clusters`)." % opts["-b"])
+    if "-o" in opts:
+        return refuse("Clusters need a symmetric matrix: -o %s is not supported." % opts["-o"])
+    if "-n" in opts:
+        return refuse("Clusters are not ranked: -n %s is not supported (use -k for their number)." % opts["-n"])
+    if "-y" in opts:
+        return refuse("Clusters take no synonyms: -y is not supported.")
+    if opts.get("-v", consts.VectorSpace.STEMS).lower() == consts.VectorSpace.LEMMATA:
+        return refuse("Clusters have no lemmatizer: -v %s is not supported (use 'stems' or 'words')." % opts["-v"])
+    if world > 1:
+        return refuse("Clusters run on one device: a launcher with WORLD_SIZE=%d is not supported." % world)
+    if os.environ.get("EAST_HIP_FORCE_DIST") == "1":
+        return refuse("Clusters run on one device: the collective path is not supported.")
+    devices = opts.get("-g", os.environ.get("EAST_HIP_DEVICES", "1"))
+    try:
+        n_ranks = int(devices)
+    except ValueError:
+        return refuse("Invalid number of GPUs: '%s'." % devices)
+    if n_ranks > 1:
+        return refuse("Clusters run on one device: -g %d is not supported." % n_ranks)
+    language = opts.get("-l", consts.Language.ENGLISH)
+    try:
+        if cosine:
+            measure = relevance.CosineRelevanceMeasure(opts.get("-v", consts.VectorSpace.STEMS), opts.get("-w", consts.TermWeighting.TF_IDF))
+            if measure.stopwords_source == "none":
+                sys.stderr.write("nltk's English stopword list is not available: no stopwords are removed.\n")
+        else:
+            measure = relevance.ASTRelevanceMeasure(opts.get("-a", consts.ASTAlgorithm.EASA), "-d" not in opts)
+        if of_texts:
+            found = applications.texts_clusters(_read_texts(args[2]), threshold, k, measure, language)
+        else:
+            keyphrases = _read(os.path.abspath(args[2])).decode("utf-8", errors="replace").splitlines()
+            found = applications.keyphrases_clusters(keyphrases, _read_texts(args[3]), by, threshold, k, measure, None, language)
+        print(formatting.format_clusters(found, fmt))
+    except exceptions.EastException as e:       # (a missing stemmer, no device, a failed build ...): a message, not a traceback
         print(e)
         return 1
     return 0
@@ -452,7 +554,7 @@ def _run(subcommand, keyphrases, texts, similarity_measure, opts, synonimizer=No
             print(e)
             return 1
         return 0
-    print("Invalid subcommand: '%s'. Please use one of: 'table', 'graph', 'top', 'similar'." % subcommand)
+    print("Invalid subcommand: '%s'. Please use one of: 'table', 'graph', 'top', 'similar', 'clusters'." % subcommand)
     return 1
 
 

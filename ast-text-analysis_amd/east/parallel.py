@@ -106,6 +106,7 @@ class DistributedASTRelevanceMeasure(relevance.ASTRelevanceMeasure):
     relevance_similar = None     # (... and keyphrases_similar)
     relevance_related = None     # (... and a rank holds the trees of its own documents only: texts_related is refused by the CLI)
     relatedness_matrix = None
+    relevance_clusters = None    # (... and no rank holds a whole matrix: the clusters are refused by the CLI)
 
     def _on_gpu(self):
         import torch.distributed as dist

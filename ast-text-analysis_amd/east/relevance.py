@@ -23,6 +23,7 @@ class RelevanceMeasure(object):
 
     relevance_texts_similar = None      # (the cosine of two texts' term vectors: the cosine measure alone)
     text_similarity_matrix = None
+    relevance_clusters = None           # (single-linkage clusters on the device: the single-device measures)
 
     def set_text_collection(self, texts, language=consts.Language.ENGLISH):
         raise NotImplementedError()
@@ -253,6 +254,21 @@ class ASTRelevanceMeasure(RelevanceMeasure):
         self.index.related_build(self.normalized, orientation)
         return self.index.related_matrix()
 
+    def relevance_clusters(self, prepared_keyphrases=None, axis=None):
+        """Single-linkage clusters of a matrix of this measure, built and clustered where it lies (csrc/clusters.h).
+        Without keyphrases: the texts, by their symmetric relatedness (relatedness_matrix).  With keyphrases: the texts
+        (axis hip_backend.TOP_BY_TEXT) or the keyphrases (TOP_BY_KEYPHRASE) by the cosine of their score profiles, the
+        matrix relevance_similar ranks.  -> the index: its clusters_merges(), clusters_cut(), similarity_matrix() /
+        related_matrix() speak of what was built."""
+        if prepared_keyphrases is None:
+            self.index.related_build(self.normalized, hip_backend.RELATED_SYMMETRIC)
+            self.index.clusters_build(hip_backend.GRAPH_SOURCE_RELATED)
+        else:
+            self._score_resident(prepared_keyphrases)
+            self.index.similarity(axis)
+            self.index.clusters_build(hip_backend.GRAPH_SOURCE_SIMILARITY)
+        return self.index
+
 
 class MultiDeviceASTRelevanceMeasure(ASTRelevanceMeasure):
     """ASTRelevanceMeasure over several GPUs of this process (`east -g N`): the documents are sharded over the devices --
@@ -274,6 +290,7 @@ class MultiDeviceASTRelevanceMeasure(ASTRelevanceMeasure):
     relevance_similar = None     # (... and keyphrases_similar)
     relevance_related = None     # (every shard holds its own documents' trees only: texts_related keeps its host path)
     relatedness_matrix = None
+    relevance_clusters = None    # (no device holds a whole matrix: the clusters keep their host path)
 
     def _after_build(self, n_docs):
         self._shards = []
@@ -441,6 +458,20 @@ class CosineRelevanceMeasure(RelevanceMeasure):
         """The D x D matrix relevance_texts_similar ranks -> (matrix, self, postings) of HipCosineIndex.texts_matrix."""
         self.index.texts_build(self.term_weighting == consts.TermWeighting.TF_IDF)
         return self.index.texts_matrix()
+
+    def relevance_clusters(self, prepared_keyphrases=None, axis=None):
+        """Single-linkage clusters of a matrix of this measure, built and clustered where it lies
+        (ASTRelevanceMeasure.relevance_clusters).  Without keyphrases: the texts, by the cosine of their term vectors
+        (text_similarity_matrix).  With keyphrases: the texts or the keyphrases by the cosine of their score profiles.
+        -> the index."""
+        if prepared_keyphrases is None:
+            self.index.texts_build(self.term_weighting == consts.TermWeighting.TF_IDF)
+            self.index.clusters_build(hip_backend.GRAPH_SOURCE_COSINE_TEXTS)
+        else:
+            self._score(prepared_keyphrases, False)
+            self.index.similarity(axis)
+            self.index.clusters_build(hip_backend.GRAPH_SOURCE_SIMILARITY)
+        return self.index
 
     def _score(self, prepared_keyphrases, fetch):
         per_query = [self._query_terms(q) for q in prepared_keyphrases]

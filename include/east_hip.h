@@ -542,6 +542,52 @@ double east_hip_last_text_similarity_ms(east_hip_handle_t h);
 int east_hip_debug_set_text_similarity_batch(int64_t segments);
 
 /*
+ * Clusters (`east texts clusters`, `east keyphrases clusters`): single-linkage agglomerative clustering -- the maximum
+ * spanning forest -- of a square matrix of similarities that is on the device already, and its flat cuts.  (How:
+ * csrc/clusters.h)
+ *
+ * Input: S, M x M doubles, row-major, M >= 0.  The diagonal is never read for its value.  S is symmetric: for a != b
+ * S[a][b] == S[b][a] as doubles (+0.0 against -0.0 is symmetric), or both are NaN.  The pair {a, b}, a < b, is an EDGE
+ * when S[a][b] is not a NaN; its weight w is S[a][b], the upper triangle's bytes.  Plus and minus infinity are ordinary
+ * weights.
+ * Order: edge e is STRONGER than f when w_e > w_f (-0.0 and +0.0 are equal), or the weights are equal and a_e < a_f, or
+ * the weights and a are equal and b_e < b_f.  A strict total order: the maximum spanning forest under it is unique.
+ * The merges (the dendrogram): the forest's F edges, strongest first, as merge_a[i] < merge_b[i] and merge_w[i] -- the
+ * edges Kruskal's algorithm accepts when it visits all edges in that order.  F = M minus the number of connected components
+ * of the edge graph.  merge_w[i] is S[a][b]'s own bytes: a -0.0 comes back as -0.0.
+ * Flat clusters, two cuts of the same dendrogram: by threshold t (not a NaN; minus infinity = every merge) the merges with
+ * w >= t are applied, a prefix of the list; by count k >= 1 the first max(0, min(F, M - k)) merges are applied -- the order
+ * above decides among equal weights, and there are never fewer than M - F clusters.  labels[v] (M entries, nullable) = the
+ * smallest member of v's cluster; out (2 entries, nullable) = the clusters, the merges applied.
+ * Guaranteed: only comparisons are made, no atomic is used; two builds give the same bytes; the result does not depend on
+ * the grid, on timing or on the number of rounds, and equals Kruskal's on the same matrix bytes.
+ *
+ * east_hip_clusters_build_resident reads a matrix another call left on the device: source
+ * EAST_HIP_GRAPH_SOURCE_SIMILARITY, EAST_HIP_GRAPH_SOURCE_RELATED or EAST_HIP_GRAPH_SOURCE_COSINE_TEXTS (each symmetric by
+ * its own contract: not checked; EAST_HIP_ERR_NOT_BUILT where there is none), or EAST_HIP_GRAPH_SOURCE_UPLOADED = the copy
+ * the last east_hip_clusters_build_host left (the clusters' OWN copy, not the ranking's or the graph's).  A relatedness
+ * matrix built with EAST_HIP_RELATED_DIRECTED is EAST_HIP_ERR_INVALID ("directed" in the message), as are
+ * EAST_HIP_GRAPH_SOURCE_AST, EAST_HIP_GRAPH_SOURCE_COSINE and unknown sources: those are not square matrices of members.
+ * east_hip_clusters_build_host uploads m x m doubles first and checks the copy for symmetry on the device; a matrix that
+ * is not symmetric is EAST_HIP_ERR_INVALID with the first offending pair (in row-major order) in the message, and neither
+ * a result nor an uploaded copy is left.  m = 0 (matrix may be null) and m = 1 succeed with F = 0.
+ * out (at least 4 entries, nullable) = M, F, the rounds, the kernel launches.
+ * The matrix is read during the build only: the merges are kept on the host side of the handle, so a later rebuild of
+ * the source matrix, a score call or a ranking leaves finished clusters valid; east_hip_reset releases them, and a build
+ * that fails leaves none.  east_hip_clusters_fetch copies the merges out (each pointer nullable, F entries); the cuts run
+ * on the host.  Fetch and cuts before a build are EAST_HIP_ERR_NOT_BUILT; a NaN threshold and k < 1 are
+ * EAST_HIP_ERR_INVALID.  The work arrays (64 bytes a member) and the uploaded copy are buffers of the clusters' own.
+ * Device time of the last build in milliseconds (events on the handle's stream around all launches and the read-backs
+ * between the rounds), -1 before a build and after a failed one.
+ */
+int east_hip_clusters_build_resident(east_hip_handle_t h, int32_t source, int64_t *out);
+int east_hip_clusters_build_host(east_hip_handle_t h, const double *matrix, int32_t m, int64_t *out);
+int east_hip_clusters_fetch(east_hip_handle_t h, int32_t *merge_a, int32_t *merge_b, double *merge_w);
+int east_hip_clusters_cut_threshold(east_hip_handle_t h, double t, int32_t *labels, int64_t *out);
+int east_hip_clusters_cut_count(east_hip_handle_t h, int32_t k, int32_t *labels, int64_t *out);
+double east_hip_last_clusters_ms(east_hip_handle_t h);
+
+/*
  * Several devices in one process ("single-process/8-device fits the one-process CLI best").
  * Every document is an independent AST (east/relevance.py:41-46) and every (keyphrase, document) score is independent
  * (east/applications.py:43-52): a GROUP shards a collection at document granularity -- contiguous blocks of documents
