@@ -35,21 +35,12 @@
 // on the host, and the matrix is not needed again.
 #pragma once
 #include "consumer.h"
-#include "related.h"
 
 #define CLU_UNROLL 8u                      // 512-byte pieces of a row requested before the first comparison
 #define CLU_NONE 0xFFFFFFFFu
 #define CLU_SYM_TILE 64u
 #define CLU_SYM_STRIDE 65u                 // doubles from one row of the turned tile to the next (top.h: TOP_LDS_STRIDE)
 #define CLU_MAX_M 0x7FFFFFF0u
-
-// the order of the doubles as the order of unsigned integers, -0.0 folded onto +0.0 (no NaN gets here)
-__device__ __forceinline__ u64 clu_key(double v)
-{
-    u64 b = (u64)__double_as_longlong(v);
-    if (b == 0x8000000000000000ull) b = 0ull;
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
 
 // ---- the strongest edge of every member ----------------------------------------------------------------------------------
 __global__ __launch_bounds__(BLOCK) void clu_best_kernel(const double *__restrict__ S, u32 M, const u32 *__restrict__ comp,
@@ -150,7 +141,7 @@ __global__ __launch_bounds__(BLOCK) void clu_merge_kernel(u32 M, u32 *comp, cons
             const u32 t = tgt[c];                                 // (a root that is not done has picked: t is another root, not done either)
             if (!(tgt[t] == c && c < t)) {
                 p = t;
-                ekey[c] = clu_key(cw[c]);
+                ekey[c] = ordered_key(cw[c]);
                 ea[c] = clo[c];
                 eb[c] = chi[c];
             }
@@ -319,9 +310,7 @@ static void clusters_check_symmetry(east_hip_index *h, ClustersState &g, const d
 // S: M x M doubles on the handle's device, symmetric (checked first when it is the caller's).
 static void clusters_build(east_hip_index *h, const double *S, u32 M, bool check, i64 *out)
 {
-    ClustersState &g = consumer_state<ClustersState>(h);
-    g.valid = false;
-    g.ms = -1.f;
+    ClustersState &g = consumer_begin<ClustersState>(h);
     g.M = 0;
     g.rounds = g.launches = 0;
     g.merge_a.clear();
@@ -331,9 +320,8 @@ static void clusters_build(east_hip_index *h, const double *S, u32 M, bool check
     ConsumerTimer timer(h, g);
     if (M >= 2) {
         if (check) clusters_check_symmetry(h, g, S, M);
-        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
         // 12 arrays of 4 bytes a member, 4 of 8, the read-back words
-        const size_t bytes = 12 * al((size_t)M * 4) + 4 * al((size_t)M * 8) + 2 * 256;
+        const size_t bytes = 12 * align256((size_t)M * 4) + 4 * align256((size_t)M * 8) + 2 * 256;
         if (!g.work.try_ensure(bytes, h->stream)) {
             char msg[200];
             snprintf(msg, sizeof(msg), "clusters: the work arrays of %u members need %zu bytes, which the device does not have", M, bytes);
@@ -405,10 +393,7 @@ static void clusters_cut(const ClustersState &g, size_t n_merges, int32_t *label
 
 static const ClustersState &clusters_built(east_hip_index *h)
 {
-    if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
-    const ClustersState *g = consumer_peek<ClustersState>(h);
-    if (!g || !g->valid) east_throw(EAST_HIP_ERR_NOT_BUILT, "no clusters have been built on this handle");
-    return *g;
+    return consumer_built<ClustersState>(h, "no clusters have been built on this handle");
 }
 
 extern "C" {
@@ -420,10 +405,8 @@ int east_hip_clusters_build_resident(east_hip_handle_t h, int32_t source, int64_
         if (source != EAST_HIP_GRAPH_SOURCE_SIMILARITY && source != EAST_HIP_GRAPH_SOURCE_RELATED &&
             source != EAST_HIP_GRAPH_SOURCE_COSINE_TEXTS && source != EAST_HIP_GRAPH_SOURCE_UPLOADED)
             east_throw(EAST_HIP_ERR_INVALID, "clusters: the source is not a square matrix of members");
-        use_device(h);
-        const ClustersState *g = consumer_peek<ClustersState>(h);
-        const TableRef t = resolve_table(h, source, g ? &g->table : nullptr, "clusters", true);
-        if (source == EAST_HIP_GRAPH_SOURCE_RELATED && !consumer_peek<RelState>(h)->symmetric)
+        const TableRef t = consumer_resident<ClustersState>(h, source, "clusters", true);
+        if (t.directed)
             east_throw(EAST_HIP_ERR_INVALID, "clusters: the relatedness matrix is directed (build it with EAST_HIP_RELATED_SYMMETRIC)");
         if (t.K != t.D) east_throw(EAST_HIP_ERR_INTERNAL, "clusters: the source matrix is not square");
         clusters_build(h, t.p, t.K, false, out);
@@ -435,17 +418,17 @@ int east_hip_clusters_build_host(east_hip_handle_t h, const double *matrix, int3
     return guarded([&] {
         if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
         if (m < 0 || (u32)m >= CLU_MAX_M || (m > 0 && !matrix)) east_throw(EAST_HIP_ERR_INVALID, "clusters: null matrix or bad size");
-        use_device(h);
-        ClustersState &g = consumer_state<ClustersState>(h);
-        g.valid = false;
-        g.ms = -1.f;
-        g.table.withdraw();
-        if (m == 0) { clusters_build(h, nullptr, 0, false, out); return; }
-        const TableRef t = g.table.upload(h, matrix, (u32)m, (u32)m, "the clusters' matrix");
+        if (m == 0) {                                             // (no members: nothing to upload, and no uploaded matrix left)
+            use_device(h);
+            consumer_begin<ClustersState>(h).table.withdraw();
+            clusters_build(h, nullptr, 0, false, out);
+            return;
+        }
+        const TableRef t = consumer_upload<ClustersState>(h, matrix, m, m, "clusters: null matrix or bad size", "the clusters' matrix", [] {});
         try {
             clusters_build(h, t.p, t.K, true, out);
         } catch (...) {
-            g.table.withdraw();                                   // (a matrix that was refused is no source either)
+            consumer_peek<ClustersState>(h)->table.withdraw();   // (a matrix that was refused is no source either)
             throw;
         }
     });

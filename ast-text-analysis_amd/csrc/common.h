@@ -66,6 +66,8 @@ struct EastError {
 // (mark/release).  In dry mode nothing is backed by memory: the same host
 // orchestration code is run to measure the high-water mark before the real
 // arena is allocated, so a build never calls hipMalloc in its timed region.
+static inline size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }      // up to the next multiple of 256
+
 struct Arena {
     char *base = nullptr;
     size_t cap = 0, off = 0, high = 0;
@@ -75,7 +77,7 @@ struct Arena {
     void release(size_t m) { off = m; }
     void *alloc_bytes(size_t bytes)
     {
-        size_t a = (off + 255) & ~(size_t)255;
+        size_t a = align256(off);
         size_t end = a + bytes;
         if (!dry && end > cap) east_throw(EAST_HIP_ERR_INTERNAL, "device arena exhausted");
         off = end;
@@ -446,6 +448,14 @@ __device__ __forceinline__ u32 wave_min(u32 x)
         x = y < x ? y : x;
     }
     return x;
+}
+
+// The order of the doubles as the order of unsigned integers, -0.0 folded onto +0.0.  (Only a NaN with every bit set maps to 0.)
+__device__ __forceinline__ u64 ordered_key(double v)
+{
+    u64 b = (u64)__double_as_longlong(v);
+    if (b == 0x8000000000000000ull) b = 0ull;
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
 
 __device__ __forceinline__ u32 wave_sum(u32 x)

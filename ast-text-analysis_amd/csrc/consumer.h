@@ -1,6 +1,10 @@
 // consumer.h -- the host frame of the handle's consumers: the cosine term index, the keyphrase graph, the synonyms, the
-// ranking, the similarity, the text-to-text relatedness, the text-to-text cosine and the clusters.  A consumer is a struct of device buffers and results that the handle owns beside its arena,
-// made by the consumer's first call.  Nothing in here knows one consumer from another ("The consumer frame").
+// ranking, the similarity, the text-to-text relatedness, the text-to-text cosine and the clusters.  A consumer is a struct
+// of device buffers and results that the handle owns beside its arena, made by the consumer's first call.  The frame has
+// the state and its lifetime, the timer, the front of every entry point (consumer_begin, consumer_built, the two halves
+// of a *_build_resident / *_build_host pair), the table a source names (resolve_table), the M x M matrix of the consumers
+// that produce one (MatrixConsumer) and the count-scan-fill of a list of unknown length.  Nothing in here knows one
+// consumer from another but the table of sources in resolve_table ("The consumer frame").
 #pragma once
 #include "handle.h"
 #include "scan.h"
@@ -9,6 +13,7 @@
 struct TableRef {               // K x D doubles on the handle's device, ordered behind everything queued on its stream
     const double *p = nullptr;  // (nullptr: no table)
     u32 K = 0, D = 0;
+    bool directed = false;      // a square matrix whose [a][b] and [b][a] are two values (the clusters take no such)
 };
 
 // ---- state, lifetime, timing ----------------------------------------------------------------------------------------------
@@ -23,10 +28,14 @@ struct Consumer {
     Consumer(const Consumer &) = delete;    // (bufs points into the object)
     virtual void clear() = 0;               // the consumer's own fields, back to "nothing built"
     virtual TableRef offers() const { return TableRef(); }      // the score table other consumers may read where it lies
-    void reset()
+    void withdraw()                         // the result is no longer there to fetch; the buffers stay
     {
         valid = false;
         ms = -1.f;
+    }
+    void reset()
+    {
+        withdraw();
         clear();
         for (DevBuf *b : bufs)
             if (b->cap > keep_bytes) b->release();
@@ -45,6 +54,22 @@ template <class T> static T &consumer_state(east_hip_index *h)
 {
     if (!h->consumers[T::SLOT]) h->consumers[T::SLOT] = new T();
     return *consumer_peek<T>(h);
+}
+// The front of a build: T's state, its last result withdrawn.
+template <class T> static T &consumer_begin(east_hip_index *h)
+{
+    T &g = consumer_state<T>(h);
+    g.withdraw();
+    return g;
+}
+// The front of a fetch: T's state with a result to fetch, on the handle's device; none: the message of EAST_HIP_ERR_NOT_BUILT.
+template <class T> static T &consumer_built(east_hip_index *h, const char *none)
+{
+    if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
+    T *g = consumer_peek<T>(h);
+    if (!g || !g->valid) east_throw(EAST_HIP_ERR_NOT_BUILT, none);
+    use_device(h);
+    return *g;
 }
 template <class T> static double consumer_ms(const east_hip_index *h) { return h && h->consumers[T::SLOT] ? (double)h->consumers[T::SLOT]->ms : -1.0; }
 
@@ -99,32 +124,108 @@ struct UploadedTable {
 // are sources too (the ranking and the clusters).
 static TableRef resolve_table(const east_hip_index *h, int32_t source, const UploadedTable *own, const char *who, bool matrices_ok = false)
 {
-    auto offered = [&](int slot) { return h->consumers[slot] ? h->consumers[slot]->offers() : TableRef(); };
+    static const struct { int32_t source; int slot; bool matrix; const char *missing; } OFFERED[] = {       // what a consumer offers()
+        {EAST_HIP_GRAPH_SOURCE_COSINE, east_hip_index::SLOT_COS, false, ": no cosine score table is resident (score the keyphrases first)"},
+        {EAST_HIP_GRAPH_SOURCE_SIMILARITY, east_hip_index::SLOT_SIM, true, ": no similarity matrix has been built on this handle"},
+        {EAST_HIP_GRAPH_SOURCE_RELATED, east_hip_index::SLOT_REL, true, ": no relatedness matrix has been built on this handle"},
+        {EAST_HIP_GRAPH_SOURCE_COSINE_TEXTS, east_hip_index::SLOT_COSTEXT, true, ": no text similarity matrix has been built on this handle"},
+    };
     TableRef t;
     const char *missing = nullptr;
     if (source == EAST_HIP_GRAPH_SOURCE_AST) {
         if (h->built && h->table_scored) { t.p = h->table; t.K = h->n_kp; t.D = h->n_docs; }
         missing = ": no score table is resident (score the keyphrases first)";
-    } else if (source == EAST_HIP_GRAPH_SOURCE_COSINE) {
-        t = offered(east_hip_index::SLOT_COS);
-        missing = ": no cosine score table is resident (score the keyphrases first)";
     } else if (source == EAST_HIP_GRAPH_SOURCE_UPLOADED) {
         if (own) t = own->ref();
         missing = ": no host table has been uploaded to this handle";
-    } else if (source == EAST_HIP_GRAPH_SOURCE_SIMILARITY && matrices_ok) {
-        t = offered(east_hip_index::SLOT_SIM);
-        missing = ": no similarity matrix has been built on this handle";
-    } else if (source == EAST_HIP_GRAPH_SOURCE_RELATED && matrices_ok) {
-        t = offered(east_hip_index::SLOT_REL);
-        missing = ": no relatedness matrix has been built on this handle";
-    } else if (source == EAST_HIP_GRAPH_SOURCE_COSINE_TEXTS && matrices_ok) {
-        t = offered(east_hip_index::SLOT_COSTEXT);
-        missing = ": no text similarity matrix has been built on this handle";
-    } else {
-        east_throw(EAST_HIP_ERR_INVALID, std::string(who) + ": unknown table source");
     }
+    for (const auto &o : OFFERED)
+        if (o.source == source && (matrices_ok || !o.matrix)) {
+            if (h->consumers[o.slot]) t = h->consumers[o.slot]->offers();
+            missing = o.missing;
+        }
+    if (!missing) east_throw(EAST_HIP_ERR_INVALID, std::string(who) + ": unknown table source");
     if (!t.p) east_throw(EAST_HIP_ERR_NOT_BUILT, std::string(who) + missing);
     return t;
+}
+
+// ---- the two halves of a *_build_resident / *_build_host pair ---------------------------------------------------------------
+// T has an UploadedTable `table`.  The resident half: the table the source names, on the handle's device.
+template <class T> static TableRef consumer_resident(east_hip_index *h, int32_t source, const char *who, bool matrices_ok = false)
+{
+    if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
+    use_device(h);
+    const T *g = consumer_peek<T>(h);
+    return resolve_table(h, source, g ? &g->table : nullptr, who, matrices_ok);
+}
+
+// The host half: the host table's copy on the device, T's last result withdrawn.  empty: the message for no table; check()
+// throws for what else can be refused BEFORE the upload (a call refused there leaves the uploaded table alone); what the
+// caller checks on the TableRef that comes back is checked AFTER it (the new table is the uploaded one by then).
+template <class T, class Check>
+static TableRef consumer_upload(east_hip_index *h, const double *table, int32_t n_keyphrases, int32_t n_docs, const char *empty,
+                                const char *what, Check check)
+{
+    if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
+    if (!table || n_keyphrases < 1 || n_docs < 1) east_throw(EAST_HIP_ERR_INVALID, empty);
+    check();
+    use_device(h);
+    return consumer_begin<T>(h).table.upload(h, table, (u32)n_keyphrases, (u32)n_docs, what);
+}
+
+// ---- an M x M matrix of members ------------------------------------------------------------------------------------------
+// The similarity, the relatedness and the text-to-text cosine: a matrix the ranking and the clusters read where it lies, a
+// double a member (the similarity's squared norms, the others' diagonal before the NaN) and, for two of them, a count a
+// member (the relatedness' scored strings, the text cosine's postings).
+#define MATRIX_MAX_M (1u << 20)            // (8 TiB of matrix: more than any device holds; 2^14 tiles a grid dimension)
+
+struct MatrixConsumer : Consumer {
+    u32 M = 0;
+    DevBuf out;                             // matrix, per_member, count
+    double *matrix = nullptr, *per_member = nullptr;
+    int32_t *count = nullptr;               // (nullptr: the consumer has none)
+    MatrixConsumer() { bufs = {&out}; }     // (a derived state adds its own)
+    void clear() override
+    {
+        M = 0;
+        matrix = per_member = nullptr;
+        count = nullptr;
+    }
+    TableRef offers() const override        // (the ranking and the clusters read the matrix where it lies)
+    {
+        TableRef t;
+        if (valid) { t.p = matrix; t.K = t.D = M; }
+        return t;
+    }
+};
+
+// EAST_HIP_ERR_OOM in the one wording; of: the size in the consumer's own nouns ("12 texts")
+[[noreturn]] static void consumer_oom(const char *who, const char *what, const std::string &of, double bytes)
+{
+    char msg[240];
+    snprintf(msg, sizeof(msg), "%s: %s of %s needs %.0f bytes, which the device does not have", who, what, of.c_str(), bytes);
+    east_throw(EAST_HIP_ERR_OOM, msg);
+}
+
+// Room for M members in g.out, carved; the limit is tested before anything is allocated.
+static void matrix_reserve(east_hip_index *h, MatrixConsumer &g, u32 M, bool with_count, const char *who, const std::string &of)
+{
+    const size_t bytes = align256((size_t)M * M * 8) + align256((size_t)M * 8) + (with_count ? align256((size_t)M * 4) : 0) + 256;
+    if (M > MATRIX_MAX_M || !g.out.try_ensure(bytes, h->stream)) consumer_oom(who, "the matrix", of, (double)M * (double)M * 8.0);
+    Arena a = g.out.arena();
+    g.matrix = a.alloc<double>((size_t)M * M);
+    g.per_member = a.alloc<double>(M);
+    g.count = with_count ? a.alloc<int32_t>(M) : nullptr;
+    g.M = M;
+}
+
+// what the caller has room for; g comes from consumer_built
+static void matrix_fetch(east_hip_index *h, const MatrixConsumer &g, double *matrix, double *per_member, int32_t *count)
+{
+    if (matrix) HIP_CHECK(hipMemcpyAsync(matrix, g.matrix, (size_t)g.M * g.M * 8, hipMemcpyDeviceToHost, h->stream));
+    if (per_member) HIP_CHECK(hipMemcpyAsync(per_member, g.per_member, (size_t)g.M * 8, hipMemcpyDeviceToHost, h->stream));
+    if (count) HIP_CHECK(hipMemcpyAsync(count, g.count, (size_t)g.M * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(hipStreamSynchronize(h->stream));
 }
 
 // ---- count, scan, fill ----------------------------------------------------------------------------------------------------

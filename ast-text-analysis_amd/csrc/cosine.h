@@ -591,7 +591,7 @@ struct CosState : Consumer {
 // change of the classes withdraws it
 static void cos_withdraw_texts_matrix(east_hip_index *h)
 {
-    if (Consumer *t = h->consumers[east_hip_index::SLOT_COSTEXT]) { t->valid = false; t->ms = -1.f; }
+    if (Consumer *t = h->consumers[east_hip_index::SLOT_COSTEXT]) t->withdraw();
 }
 
 static CosState &cos_built(east_hip_index *h)
@@ -620,8 +620,6 @@ static void cos_doc_order(Ctx &ctx, CosUnits &U, u32 D)
     LAUNCH(ctx, cos_doc_offsets_kernel, ceil_div_u32((u64)D + 1, BLOCK), (const u32 *)sb.keys[r], P, D, U.doc_off);
     ctx.arena->release(mark);
 }
-
-static size_t cos_align(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
 static void cos_build(east_hip_index *h, HostTexts in, const UnicodeTablesHost &tables, const u32 *stop_cps, const i64 *stop_offsets, int32_t n_stop)
 {
@@ -847,7 +845,7 @@ static void cos_set_classes(east_hip_index *h, const int32_t *term_class, int32_
     U.inv_perm = ac.alloc<u32>(K1);
     U.doc_off = ac.alloc<u32>((size_t)D + 1);
     Stats stats;
-    c.work.ensure(cos_align(((size_t)c.V + 1) * 4) + ((size_t)P + 2) * 64 + ((size_t)4 << 20), "the cosine index");
+    c.work.ensure(align256(((size_t)c.V + 1) * 4) + ((size_t)P + 2) * 64 + ((size_t)4 << 20), "the cosine index");
     Arena a = c.work.arena();
     Ctx ctx = handle_ctx(h, &a, &stats);
     u32 *d_tc = a.alloc<u32>((size_t)c.V + 1);
@@ -890,7 +888,7 @@ static void cos_lookup(east_hip_index *h, const u32 *cps, const i64 *offsets, in
     }
     use_device(h);
     Stats stats;
-    c.work.ensure(cos_align(((size_t)n_cps + 1) * 4) + cos_align(((size_t)n_words + 1) * 4) * 2 + 4096, "the cosine index");
+    c.work.ensure(align256(((size_t)n_cps + 1) * 4) + align256(((size_t)n_words + 1) * 4) * 2 + 4096, "the cosine index");
     Arena a = c.work.arena();
     Ctx ctx = handle_ctx(h, &a, &stats);
     u32 *d_w = a.alloc<u32>((size_t)n_cps + 1), *d_off = a.alloc<u32>((size_t)n_words + 1);
@@ -907,7 +905,7 @@ static void cos_lookup(east_hip_index *h, const u32 *cps, const i64 *offsets, in
 // where the weights and norms of weighting wt live (CosUnits::weights)
 static void cos_weight_ptrs(CosUnits &U, u32 D, int wt, double **w, double **norm)
 {
-    const size_t wb = cos_align(((size_t)U.P + 1) * 8), nb = cos_align(((size_t)D + 1) * 8);
+    const size_t wb = align256(((size_t)U.P + 1) * 8), nb = align256(((size_t)D + 1) * 8);
     if (U.weights.cap < 2 * (wb + nb)) {
         U.w_valid[0] = U.w_valid[1] = false;
         U.weights.ensure(2 * (wb + nb), "the cosine index");
@@ -950,8 +948,8 @@ static void cos_score(east_hip_index *h, const int32_t *q_ids, const i64 *q_offs
     use_device(h);
     c.table_valid = false;
     const u32 D = c.n_docs, total = (u32)q_len;
-    const size_t b_ids = cos_align(((size_t)total + 1) * 4), b_off = cos_align(((size_t)K + 1) * 4),
-                 b_qw = cos_align(((size_t)total + 1) * 8), table = (size_t)K * D * 8;
+    const size_t b_ids = align256(((size_t)total + 1) * 4), b_off = align256(((size_t)K + 1) * 4),
+                 b_qw = align256(((size_t)total + 1) * 8), table = (size_t)K * D * 8;
     c.score.ensure(b_ids + b_off + b_qw + table, "the cosine index");
     int32_t *d_ids = (int32_t *)c.score.p;
     u32 *d_off = (u32 *)(c.score.p + b_ids);

@@ -34,7 +34,7 @@
 // Memory: du, dw (12 bytes a posting), the matrix, and partial tiles of at most COSTEXT_SCRATCH_BYTES -- or of one segment
 // where a single segment's tiles take more: half the matrix's own size.
 //
-// The host half is a consumer of the handle (consumer.h); its matrix is what it offers() the ranking (top.h) as a table.
+// The host half is a MatrixConsumer of the handle (consumer.h: the matrix, its limit, its fetch, what it offers()).
 #pragma once
 #include "consumer.h"
 #include "cosine.h"
@@ -43,7 +43,6 @@
 #define COSTEXT_SEG 8192u                          // units of a segment
 #define COSTEXT_CHUNK SIM_CHUNK                    // units staged at a time
 #define COSTEXT_TILE_WORDS (SIM_TILE * SIM_TILE)   // doubles of a partial tile
-#define COSTEXT_MAX_D (1u << 20)                   // (8 TiB of matrix: more than any device holds; 2^14 tiles a grid dimension)
 #define COSTEXT_MAX_BATCH 65535u                   // segments of a launch at most: the grid's third dimension
 #define COSTEXT_SCRATCH_BYTES ((size_t)256 << 20)  // the default batch: as many segments as keep the partial tiles at or below this
 #define COSTEXT_MAX_GRID (1u << 22)                // workgroups of the fold at most (it loops)
@@ -84,10 +83,7 @@ __global__ __launch_bounds__(BLOCK) void cost_tile_kernel(const u32 *__restrict_
     const u32 lo_u = (seg0 + blockIdx.z) * COSTEXT_SEG;           // (the host launches segments that start below n_units only)
     const u32 hi_u = min(n_units, lo_u + COSTEXT_SEG);
     sim_v4d acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-        for (int j = 0; j < 2; j++) acc[i][j] = (sim_v4d){0.0, 0.0, 0.0, 0.0};
+    sim_acc_zero(acc);
 
     // this thread's member: its cursor, the end of its postings and the unit under the cursor (COS_NONE: none left in the segment)
     u32 cur = 0, end = 0, nu = COS_NONE;
@@ -106,9 +102,7 @@ __global__ __launch_bounds__(BLOCK) void cost_tile_kernel(const u32 *__restrict_
     double *row = lds + threadIdx.x * SIM_LDS_STRIDE;             // (members only: strip a's rows, then strip b's)
     const double *la = lds, *lb = diag ? lds : lds + SIM_TILE * SIM_LDS_STRIDE;
     for (;;) {
-        u32 m = nu;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) m = min(m, (u32)__shfl_xor((int)m, off, WAVE));
+        u32 m = wave_min(nu);
         if (lane == 0u) wmin[wv] = m;
         __syncthreads();                                          // (and: the chunk before has been read)
         m = min(min(wmin[0], wmin[1]), min(wmin[2], wmin[3]));
@@ -124,7 +118,7 @@ __global__ __launch_bounds__(BLOCK) void cost_tile_kernel(const u32 *__restrict_
         }
         __syncthreads();
 #pragma unroll
-        for (u32 s = 0; s < COSTEXT_CHUNK / 4u; s++) {
+        for (u32 s = 0; s < SIM_CHUNK / 4u; s++) {
             const u32 e = 4u * s + lk;
             const double a[2] = {la[(ra + lr) * SIM_LDS_STRIDE + e], la[(ra + 16u + lr) * SIM_LDS_STRIDE + e]};
             const double b[2] = {lb[(cb + lr) * SIM_LDS_STRIDE + e], lb[(cb + 16u + lr) * SIM_LDS_STRIDE + e]};
@@ -164,7 +158,6 @@ __global__ __launch_bounds__(BLOCK) void cost_finish_kernel(double *__restrict__
     __shared__ double tile[SIM_TILE * SIM_EPI_STRIDE];
     const u32 t = pair_tiles[blockIdx.x];
     const u32 a0 = (t >> 16) * SIM_TILE, b0 = (t & 0xFFFFu) * SIM_TILE;
-    const bool diag = a0 == b0;
     const u32 lane = lane_id(), wv = wave_id();
     for (u32 r = wv; r < SIM_TILE; r += WAVES_PER_BLOCK) {
         const u32 a = a0 + r, b = b0 + lane;
@@ -176,38 +169,15 @@ __global__ __launch_bounds__(BLOCK) void cost_finish_kernel(double *__restrict__
         tile[r * SIM_EPI_STRIDE + lane] = v;
     }
     __syncthreads();
-    for (u32 r = wv; r < SIM_TILE; r += WAVES_PER_BLOCK) {        // the tile, row by row (a diagonal tile: its upper half's values)
-        const u32 a = a0 + r, b = b0 + lane;
-        if (a < D && b < D) M[(size_t)a * D + b] = diag && lane < r ? tile[lane * SIM_EPI_STRIDE + r] : tile[r * SIM_EPI_STRIDE + lane];
-    }
-    if (diag) return;
-    for (u32 c = wv; c < SIM_TILE; c += WAVES_PER_BLOCK) {        // its mirror image, column by column
-        const u32 b = b0 + c, a = a0 + lane;
-        if (a < D && b < D) M[(size_t)b * D + a] = tile[lane * SIM_EPI_STRIDE + c];
-    }
+    sim_tile_store(M, D, a0, b0, a0 == b0, tile, lane, wv);
 }
 
 // ============================================================================================================ host ==
 // The buffers belong to the handle and to nothing else: not the cosine index's, the EASA arena or another consumer's.
-struct CosTextsState : Consumer {
+struct CosTextsState : MatrixConsumer {      // per_member: self; count: postings
     static constexpr int SLOT = east_hip_index::SLOT_COSTEXT;
-    u32 D = 0;
-    DevBuf ops, scratch, out;               // du, dw, the tile pairs and the squares' scratch; the partial tiles; matrix, self, postings
-    double *matrix = nullptr, *self = nullptr;
-    int32_t *postings = nullptr;
-    CosTextsState() { bufs = {&ops, &scratch, &out}; }
-    void clear() override
-    {
-        D = 0;
-        matrix = self = nullptr;
-        postings = nullptr;
-    }
-    TableRef offers() const override        // (the ranking reads the matrix where it lies)
-    {
-        TableRef t;
-        if (valid) { t.p = matrix; t.K = t.D = D; }
-        return t;
-    }
+    DevBuf ops, scratch;                    // du, dw, the tile pairs and the squares' scratch; the partial tiles
+    CosTextsState() { bufs.insert(bufs.end(), {&ops, &scratch}); }
 };
 
 __global__ __launch_bounds__(BLOCK) void cost_postings_kernel(const u32 *__restrict__ doc_off, u32 D, int32_t *__restrict__ postings)
@@ -216,28 +186,19 @@ __global__ __launch_bounds__(BLOCK) void cost_postings_kernel(const u32 *__restr
     if (d < D) postings[d] = (int32_t)(doc_off[d + 1u] - doc_off[d]);
 }
 
-[[noreturn]] static void cost_oom(u32 D, const char *what, double bytes)
-{
-    char msg[240];
-    snprintf(msg, sizeof(msg), "text similarity: %s of %u texts needs %.0f bytes, which the device does not have", what, D, bytes);
-    east_throw(EAST_HIP_ERR_OOM, msg);
-}
-
 static void cost_build(east_hip_index *h, int32_t weighting, i64 *out)
 {
     if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
     if (weighting < 0 || weighting > 1) east_throw(EAST_HIP_ERR_INVALID, "text similarity: unknown weighting");
     CosState &c = cos_built(h);
     use_device(h);
-    CosTextsState &g = consumer_state<CosTextsState>(h);
-    g.valid = false;
-    g.ms = -1.f;
+    CosTextsState &g = consumer_begin<CosTextsState>(h);
     CosUnits &U = c.use_classes ? c.cls : c.terms;
     const u32 D = c.n_docs, P = U.P, n_units = U.n_units;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const std::string texts = std::to_string(D) + " texts";
+    auto cost_oom = [&](const char *what, double bytes) { consumer_oom("text similarity", what, texts, bytes); };
     if (D < 1) east_throw(EAST_HIP_ERR_INVALID, "text similarity: the index holds no text");
-    if (D > COSTEXT_MAX_D || !g.out.try_ensure(al((size_t)D * D * 8) + al((size_t)D * 8) + al((size_t)D * 4) + 256, h->stream))
-        cost_oom(D, "the matrix", (double)D * (double)D * 8.0);
+    matrix_reserve(h, g, D, true, "text similarity", texts);
     const u32 NT = ceil_div_u32(D, SIM_TILE);
     const u64 n_pairs = cost_pair_index(NT, NT, NT);
     const u32 n_seg = ceil_div_u32(n_units, COSTEXT_SEG);
@@ -246,14 +207,10 @@ static void cost_build(east_hip_index *h, int32_t weighting, i64 *out)
     u32 batch = kn.cosine_texts_batch > 0 ? (u32)std::min<i64>(kn.cosine_texts_batch, COSTEXT_MAX_BATCH)
                                           : (u32)std::min<size_t>(std::max<size_t>(COSTEXT_SCRATCH_BYTES / tile_bytes, 1), COSTEXT_MAX_BATCH);
     batch = std::max(std::min(batch, n_seg), 1u);
-    const size_t ops_bytes = al(((size_t)P + 1) * 4) + 2 * al(((size_t)P + 1) * 8) + al((size_t)n_pairs * 4) + 256;
-    if (!g.ops.try_ensure(ops_bytes, h->stream)) cost_oom(D, "the postings in document order", (double)ops_bytes);
-    if (!g.scratch.try_ensure((size_t)batch * tile_bytes + 256, h->stream)) cost_oom(D, "a batch's partial tiles", (double)batch * (double)tile_bytes);
-    Arena oa = g.out.arena(), pa = g.ops.arena();
-    g.matrix = oa.alloc<double>((size_t)D * D);
-    g.self = oa.alloc<double>(D);
-    g.postings = oa.alloc<int32_t>(D);
-    g.D = D;
+    const size_t ops_bytes = align256(((size_t)P + 1) * 4) + 2 * align256(((size_t)P + 1) * 8) + align256((size_t)n_pairs * 4) + 256;
+    if (!g.ops.try_ensure(ops_bytes, h->stream)) cost_oom("the postings in document order", (double)ops_bytes);
+    if (!g.scratch.try_ensure((size_t)batch * tile_bytes + 256, h->stream)) cost_oom("a batch's partial tiles", (double)batch * (double)tile_bytes);
+    Arena pa = g.ops.arena();
     u32 *du = pa.alloc<u32>((size_t)P + 1), *d_pairs = pa.alloc<u32>((size_t)n_pairs);
     double *dw = pa.alloc<double>((size_t)P + 1);
     std::vector<u32> pairs;
@@ -269,7 +226,7 @@ static void cost_build(east_hip_index *h, int32_t weighting, i64 *out)
     cos_make_weights(ctx, c, U, weighting, w, norm);
     if (P)
         LAUNCH(ctx, cost_scatter_kernel, ceil_div_u32(P, BLOCK), (const u32 *)U.post_unit, (const double *)w, (const u32 *)U.inv_perm, P, du, dw);
-    LAUNCH(ctx, cost_postings_kernel, ceil_div_u32(D, BLOCK), (const u32 *)U.doc_off, D, g.postings);
+    LAUNCH(ctx, cost_postings_kernel, ceil_div_u32(D, BLOCK), (const u32 *)U.doc_off, D, g.count);
     double *partial = g.scratch.as<double>();
     const u32 fold_grid = (u32)std::min<u64>((n_pairs * COSTEXT_TILE_WORDS + BLOCK - 1) / BLOCK, COSTEXT_MAX_GRID);
     i64 launches = 0;
@@ -282,7 +239,7 @@ static void cost_build(east_hip_index *h, int32_t weighting, i64 *out)
         LAUNCH(ctx, cost_fold_kernel, fold_grid, (const double *)partial, (const u32 *)d_pairs, n_pairs, nb, (int)(s0 == 0), D, g.matrix);
         launches++;
     }
-    LAUNCH(ctx, cost_finish_kernel, (u32)n_pairs, g.matrix, (const u32 *)d_pairs, D, (const double *)norm, g.self);
+    LAUNCH(ctx, cost_finish_kernel, (u32)n_pairs, g.matrix, (const u32 *)d_pairs, D, (const double *)norm, g.per_member);
     launches++;
     timer.finish();
     U.w_valid[weighting] = true;
@@ -303,15 +260,7 @@ int east_hip_text_similarity_build(east_hip_handle_t h, int32_t weighting, int64
 int east_hip_text_similarity_fetch(east_hip_handle_t h, double *matrix, double *self, int32_t *postings)
 {
     return guarded([&] {
-        if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
-        CosTextsState *gp = consumer_peek<CosTextsState>(h);
-        if (!gp || !gp->valid) east_throw(EAST_HIP_ERR_NOT_BUILT, "no text similarity matrix has been built on this handle");
-        use_device(h);
-        CosTextsState &g = *gp;
-        if (matrix) HIP_CHECK(hipMemcpyAsync(matrix, g.matrix, (size_t)g.D * g.D * 8, hipMemcpyDeviceToHost, h->stream));
-        if (self) HIP_CHECK(hipMemcpyAsync(self, g.self, (size_t)g.D * 8, hipMemcpyDeviceToHost, h->stream));
-        if (postings) HIP_CHECK(hipMemcpyAsync(postings, g.postings, (size_t)g.D * 4, hipMemcpyDeviceToHost, h->stream));
-        HIP_CHECK(hipStreamSynchronize(h->stream));
+        matrix_fetch(h, consumer_built<CosTextsState>(h, "no text similarity matrix has been built on this handle"), matrix, self, postings);
     });
 }
 

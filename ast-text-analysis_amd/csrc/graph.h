@@ -221,9 +221,7 @@ static void graph_build(east_hip_index *h, TableRef t, const int32_t *rows, i64 
     if (n_pos < 0 || n_pos >= (i64)0x7FFFFFF0 || (n_pos > 0 && !rows)) east_throw(EAST_HIP_ERR_INVALID, "bad node positions");
     for (i64 p = 0; p < n_pos; p++)
         if (rows[p] < 0 || (u32)rows[p] >= t.K) east_throw(EAST_HIP_ERR_INVALID, "a node position names a row outside the score table");
-    GraphState &g = consumer_state<GraphState>(h);
-    g.valid = false;
-    g.ms = -1.f;
+    GraphState &g = consumer_begin<GraphState>(h);
     const u32 n = (u32)n_pos, D = t.D, W = ceil_div_u32(D, 64);
     g.n = n;
     g.M = 0;
@@ -265,7 +263,7 @@ static void graph_build(east_hip_index *h, TableRef t, const int32_t *rows, i64 
                     graph_launch_pairs<false>(ctx, grid, cbits, csup, g.kept, M, W, TB, referral_confidence, cnt, nullptr, nullptr, nullptr, nullptr);
                 },
                 [&](u64 E) {
-                    const size_t eb = (((size_t)E * 4) + 255) & ~(size_t)255;
+                    const size_t eb = align256((size_t)E * 4);
                     g.edges.ensure(eb * 3, "the keyphrase graph's edges");
                     g.e_src = (int32_t *)g.edges.p;
                     g.e_dst = (int32_t *)(g.edges.p + eb);
@@ -288,10 +286,7 @@ int east_hip_graph_build_resident(east_hip_handle_t h, int32_t source, const int
                                   double relevance_threshold, double support_threshold, double referral_confidence, int64_t *out)
 {
     return guarded([&] {
-        if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
-        use_device(h);
-        const GraphState *g = consumer_peek<GraphState>(h);
-        graph_build(h, resolve_table(h, source, g ? &g->table : nullptr, "keyphrase graph"), rows, n_positions, relevance_threshold, support_threshold,
+        graph_build(h, consumer_resident<GraphState>(h, source, "keyphrase graph"), rows, n_positions, relevance_threshold, support_threshold,
                     referral_confidence, out);
     });
 }
@@ -301,13 +296,10 @@ int east_hip_graph_build_host(east_hip_handle_t h, const double *table, int32_t 
                               int64_t *out)
 {
     return guarded([&] {
-        if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
-        if (!table || n_keyphrases < 1 || n_docs < 1) east_throw(EAST_HIP_ERR_INVALID, "keyphrase graph: null or empty score table");
-        use_device(h);
-        GraphState &g = consumer_state<GraphState>(h);
-        g.valid = false;                                      // (the rows are checked after the upload: the new table is the uploaded one)
-        graph_build(h, g.table.upload(h, table, (u32)n_keyphrases, (u32)n_docs, "the keyphrase graph's score table"), rows, n_positions,
-                    relevance_threshold, support_threshold, referral_confidence, out);
+        // (nothing to refuse before the upload: the rows are checked after it, the new table is the uploaded one)
+        const TableRef t = consumer_upload<GraphState>(h, table, n_keyphrases, n_docs, "keyphrase graph: null or empty score table",
+                                                       "the keyphrase graph's score table", [] {});
+        graph_build(h, t, rows, n_positions, relevance_threshold, support_threshold, referral_confidence, out);
     });
 }
 
@@ -315,11 +307,7 @@ int east_hip_graph_fetch(east_hip_handle_t h, int32_t *support, int32_t *kept, i
                          int32_t *edge_shared)
 {
     return guarded([&] {
-        if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
-        GraphState *gp = consumer_peek<GraphState>(h);
-        if (!gp || !gp->valid) east_throw(EAST_HIP_ERR_NOT_BUILT, "no keyphrase graph has been built on this handle");
-        use_device(h);
-        GraphState &g = *gp;
+        const GraphState &g = consumer_built<GraphState>(h, "no keyphrase graph has been built on this handle");
         const size_t eb = (size_t)g.E * 4;
         if (support && g.n) HIP_CHECK(hipMemcpyAsync(support, g.support, (size_t)g.n * 4, hipMemcpyDeviceToHost, h->stream));
         if (kept && g.M) HIP_CHECK(hipMemcpyAsync(kept, g.kept, (size_t)g.M * 4, hipMemcpyDeviceToHost, h->stream));

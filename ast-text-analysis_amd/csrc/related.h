@@ -30,7 +30,8 @@
 // score against a walk of dozens of dependent gathers a score.  Parallelism comes from the (tile, strip) pairs -- one
 // document of 64 MiB is ~12 000 tiles --, the rows are read as whole 512-byte pieces (a wavefront: 64 consecutive columns).
 //
-// The host half is a consumer of the handle (consumer.h); its matrix is what it offers() the ranking (top.h) as a table.
+// The host half is a MatrixConsumer of the handle (consumer.h: the matrix, its limit, its fetch, what it offers()); it
+// adds whether the matrix is the directed form.
 #pragma once
 #include "consumer.h"
 #include "score_host.h"
@@ -38,7 +39,6 @@
 #define REL_TILE 256u                              // scored strings of a tile
 #define REL_STRIP 64u                              // columns of a strip: a lane each
 #define REL_MAX_CHUNK_TILES ((1u << 22) / REL_TILE) // (score_resident: a launch of the walk takes fewer than 2^24 workgroups)
-#define REL_MAX_D (1u << 20)                        // (8 TiB of matrix: more than any device holds)
 #define REL_MAX_GRID (1u << 22)                     // workgroups of a launch at most: 2^30 threads, below HIP's 2^32 a grid dimension (the sums loop)
 #define REL_CHUNK_BYTES ((size_t)256 << 20)        // the default chunk: as many tiles as keep K_c x D x 8 bytes at or below this ("Measured": flat from 64 MiB up)
 
@@ -180,34 +180,18 @@ __global__ __launch_bounds__(BLOCK) void rel_finish_kernel(double *__restrict__ 
 // ============================================================================================================ host ==
 // The relatedness' device buffers belong to the handle and to nothing else: not the EASA arena, the score scratch, the
 // ranking's buffers or the similarity's.
-struct RelState : Consumer {
+struct RelState : MatrixConsumer {           // per_member: self; count: scored
     static constexpr int SLOT = east_hip_index::SLOT_REL;
-    u32 D = 0;
-    bool symmetric = false;                 // the matrix is the symmetric form (clusters.h takes no other)
-    DevBuf scan_tmp, dir, partial, out;    // the terminator counts (released after the directory); the directory and the lists; partial[tile][D]; matrix, self, scored
-    double *matrix = nullptr, *self = nullptr;
-    int32_t *scored = nullptr;
-    RelState() { bufs = {&scan_tmp, &dir, &partial, &out}; }
-    void clear() override
+    bool symmetric = false;                 // the matrix is the symmetric form
+    DevBuf scan_tmp, dir, partial;          // the terminator counts (released after the directory); the directory and the lists; partial[tile][D]
+    RelState() { bufs.insert(bufs.end(), {&scan_tmp, &dir, &partial}); }
+    TableRef offers() const override
     {
-        D = 0;
-        matrix = self = nullptr;
-        scored = nullptr;
-    }
-    TableRef offers() const override        // (the ranking reads the matrix where it lies)
-    {
-        TableRef t;
-        if (valid) { t.p = matrix; t.K = t.D = D; }
+        TableRef t = MatrixConsumer::offers();
+        t.directed = !symmetric;
         return t;
     }
 };
-
-[[noreturn]] static void rel_oom(u32 D, const char *what, double bytes)
-{
-    char msg[240];
-    snprintf(msg, sizeof(msg), "relatedness: %s of %u texts needs %.0f bytes, which the device does not have", what, D, bytes);
-    east_throw(EAST_HIP_ERR_OOM, msg);
-}
 
 static void rel_build(east_hip_index *h, int normalized, int32_t orientation, i64 *out)
 {
@@ -216,9 +200,7 @@ static void rel_build(east_hip_index *h, int normalized, int32_t orientation, i6
         east_throw(EAST_HIP_ERR_INVALID, "relatedness: unknown orientation");
     if (!h->built) east_throw(EAST_HIP_ERR_NOT_BUILT, "no index has been built on this handle");
     use_device(h);
-    RelState &g = consumer_state<RelState>(h);
-    g.valid = false;
-    g.ms = -1.f;
+    RelState &g = consumer_begin<RelState>(h);
     // the handle's resident keyphrases are replaced, its score table withdrawn -- whatever becomes of this call
     h->table_scored = false;
     h->q_code_epoch = 0;
@@ -227,17 +209,11 @@ static void rel_build(east_hip_index *h, int normalized, int32_t orientation, i6
     u64 m_sum = 0;
     for (u32 d = 0; d < D; d++) m_sum += h->h_n_strings[d];
     if (m_sum != m || m < 1) east_throw(EAST_HIP_ERR_INTERNAL, "relatedness: the documents' strings do not add up");
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t scan_scratch = al(((size_t)ceil_div_u32((u64)n + 1, SCAN_TILE) + 1) * 8) + 16 * 256;
-    if (D > REL_MAX_D || !g.out.try_ensure(al((size_t)D * D * 8) + al((size_t)D * 8) + al((size_t)D * 4) + 256, h->stream))
-        rel_oom(D, "the matrix", (double)D * (double)D * 8.0);
-    if (!g.scan_tmp.try_ensure(al(((size_t)n + 1) * 4) + scan_scratch, h->stream))
-        rel_oom(D, "the string directory", ((double)n + 1) * 4.0);
-    Arena oa = g.out.arena();
-    g.matrix = oa.alloc<double>((size_t)D * D);
-    g.self = oa.alloc<double>(D);
-    g.scored = oa.alloc<int32_t>(D);
-    g.D = D;
+    const std::string texts = std::to_string(D) + " texts";
+    auto rel_oom = [&](const char *what, double bytes) { consumer_oom("relatedness", what, texts, bytes); };
+    const size_t scan_scratch = align256(((size_t)ceil_div_u32((u64)n + 1, SCAN_TILE) + 1) * 8) + 16 * 256;
+    matrix_reserve(h, g, D, true, "relatedness", texts);
+    if (!g.scan_tmp.try_ensure(align256(((size_t)n + 1) * 4) + scan_scratch, h->stream)) rel_oom("the string directory", ((double)n + 1) * 4.0);
     Stats stats;
     const Knobs kn = knobs_snapshot();
     ConsumerTimer timer(h, g);
@@ -246,9 +222,9 @@ static void rel_build(east_hip_index *h, int normalized, int32_t orientation, i6
     std::vector<u32> len((size_t)m + 1);
     // (room for the lists below too: tile_row and doc_tile, at most m + D + 2 words, and the packed q_blk lists, at most
     // one bound a scored string and one more a chunk -- chunks are whole tiles, of which there are at most m)
-    const size_t dir_bytes = al((size_t)m * 4) + 3 * al(((size_t)m + 1) * 4) + al(((size_t)m + D + 2) * 4) + al(((size_t)D + 1) * 4) +
-                             al((2 * (size_t)m + 2) * 4) + scan_scratch + 256;
-    if (!g.dir.try_ensure(dir_bytes, h->stream)) rel_oom(D, "the string directory", (double)dir_bytes);
+    const size_t dir_bytes = align256((size_t)m * 4) + 3 * align256(((size_t)m + 1) * 4) + align256(((size_t)m + D + 2) * 4) +
+                             align256(((size_t)D + 1) * 4) + align256((2 * (size_t)m + 2) * 4) + scan_scratch + 256;
+    if (!g.dir.try_ensure(dir_bytes, h->stream)) rel_oom("the string directory", (double)dir_bytes);
     Arena da = g.dir.arena();
     u32 *d_end = da.alloc<u32>(m), *d_len = da.alloc<u32>((size_t)m + 1), *d_q = da.alloc<u32>((size_t)m + 1),
         *d_rank = da.alloc<u32>((size_t)m + 1);
@@ -339,14 +315,14 @@ static void rel_build(east_hip_index *h, int normalized, int32_t orientation, i6
         q_bytes = std::max(q_bytes, keyphrase_scratch_bytes(c.K, c.n_q, D, score_doc_chunk(c.n_q, D, kn.score_scratch_bytes)));
     }
     const u32 most_tiles = std::min(chunk_tiles, NT);
-    if (!g.partial.try_ensure((size_t)most_tiles * D * 8 + 256, h->stream)) rel_oom(D, "a chunk's partial sums", (double)most_tiles * D * 8.0);
-    if (!h->q_buf.try_ensure(q_bytes, h->stream)) rel_oom(D, "a chunk's score table", (double)q_bytes);
+    if (!g.partial.try_ensure((size_t)most_tiles * D * 8 + 256, h->stream)) rel_oom("a chunk's partial sums", (double)most_tiles * D * 8.0);
+    if (!h->q_buf.try_ensure(q_bytes, h->stream)) rel_oom("a chunk's score table", (double)q_bytes);
     u32 *d_tile_row = da.alloc<u32>(tile_row.size()), *d_doc_tile = da.alloc<u32>(doc_tile.size()),
         *d_blk = da.alloc<u32>(std::max<size_t>(blk_all.size(), 1));
     HIP_CHECK(hipMemcpyAsync(d_tile_row, tile_row.data(), tile_row.size() * 4, hipMemcpyHostToDevice, h->stream));
     HIP_CHECK(hipMemcpyAsync(d_doc_tile, doc_tile.data(), doc_tile.size() * 4, hipMemcpyHostToDevice, h->stream));
     if (!blk_all.empty()) HIP_CHECK(hipMemcpyAsync(d_blk, blk_all.data(), blk_all.size() * 4, hipMemcpyHostToDevice, h->stream));
-    HIP_CHECK(hipMemcpyAsync(g.scored, scored.data(), (size_t)D * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(hipMemcpyAsync(g.count, scored.data(), (size_t)D * 4, hipMemcpyHostToDevice, h->stream));
     HIP_CHECK(hipStreamSynchronize(h->stream));
 
     Ctx ctx = handle_ctx(h, nullptr, &stats);
@@ -373,8 +349,8 @@ static void rel_build(east_hip_index *h, int normalized, int32_t orientation, i6
         h->q_code_epoch = 0;
         h->n_kp = h->n_q = 0;
     }
-    LAUNCH(ctx, rel_finish_kernel, (u32)std::min<u64>(((u64)D * D + BLOCK - 1) / BLOCK, REL_MAX_GRID), g.matrix, D, (const int32_t *)g.scored, (int)(orientation == EAST_HIP_RELATED_SYMMETRIC),
-           g.self);
+    LAUNCH(ctx, rel_finish_kernel, (u32)std::min<u64>(((u64)D * D + BLOCK - 1) / BLOCK, REL_MAX_GRID), g.matrix, D, (const int32_t *)g.count, (int)(orientation == EAST_HIP_RELATED_SYMMETRIC),
+           g.per_member);
     timer.finish();
     g.symmetric = orientation == EAST_HIP_RELATED_SYMMETRIC;
     g.valid = true;
@@ -391,15 +367,7 @@ int east_hip_related_build(east_hip_handle_t h, int normalized, int32_t orientat
 int east_hip_related_fetch(east_hip_handle_t h, double *matrix, double *self, int32_t *scored)
 {
     return guarded([&] {
-        if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
-        RelState *gp = consumer_peek<RelState>(h);
-        if (!gp || !gp->valid) east_throw(EAST_HIP_ERR_NOT_BUILT, "no relatedness matrix has been built on this handle");
-        use_device(h);
-        RelState &g = *gp;
-        if (matrix) HIP_CHECK(hipMemcpyAsync(matrix, g.matrix, (size_t)g.D * g.D * 8, hipMemcpyDeviceToHost, h->stream));
-        if (self) HIP_CHECK(hipMemcpyAsync(self, g.self, (size_t)g.D * 8, hipMemcpyDeviceToHost, h->stream));
-        if (scored) HIP_CHECK(hipMemcpyAsync(scored, g.scored, (size_t)g.D * 4, hipMemcpyDeviceToHost, h->stream));
-        HIP_CHECK(hipStreamSynchronize(h->stream));
+        matrix_fetch(h, consumer_built<RelState>(h, "no relatedness matrix has been built on this handle"), matrix, self, scored);
     });
 }
 

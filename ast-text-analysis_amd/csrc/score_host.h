@@ -15,9 +15,8 @@ static u32 score_doc_chunk(u32 n_q, u32 n_docs, size_t scratch_bytes)
 // The score scratch for n_kp keyphrases of n_q suffixes in all, over n_docs documents scored `chunk` at a time.
 static size_t keyphrase_scratch_bytes(u32 n_kp, u32 n_q, u32 n_docs, u32 chunk)
 {
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    return 256 + al((size_t)n_q * 4) * 3 + al(((size_t)n_kp + 1) * 4) * 3 + al((size_t)n_q * chunk * 8) +
-           al((size_t)n_kp * n_docs * 8) * 2;
+    return 256 + align256((size_t)n_q * 4) * 3 + align256(((size_t)n_kp + 1) * 4) * 3 + align256((size_t)n_q * chunk * 8) +
+           align256((size_t)n_kp * n_docs * 8) * 2;
 }
 
 // The device half of setting keyphrases: the scratch is laid out for n_kp keyphrases of n_q suffixes, fill() queues on the
@@ -30,18 +29,17 @@ static void set_keyphrases_device(east_hip_index *h, u32 n_kp, u32 n_q, u32 n_bl
     h->table_scored = false;
     h->q_code_epoch = 0;
     h->n_kp = h->n_q = 0;                                  // (until the arrays are queued: a refused call leaves no keyphrases)
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const u32 chunk = score_doc_chunk(n_q, h->n_docs, kn.score_scratch_bytes);
     h->q_buf.ensure(keyphrase_scratch_bytes(n_kp, n_q, h->n_docs, chunk), "the score scratch", h->stream);
     char *p = h->q_buf.p + 256;                            // (the first bytes hold the probe counter of east_hip_score_probes)
-    h->q_raw = (u32 *)p;  p += al((size_t)n_q * 4);
-    h->q_code = (u32 *)p; p += al((size_t)n_q * 4);
-    h->q_end = (u32 *)p;  p += al((size_t)n_q * 4);
-    h->q_off = (u32 *)p;  p += al(((size_t)n_kp + 1) * 4);
-    h->group_off = (u32 *)p; p += al(((size_t)n_kp + 1) * 4);      // synonym-expanded scoring: variants per keyphrase
-    h->q_blk = (u32 *)p;  p += al(((size_t)n_kp + 1) * 4);
-    h->suffix = (double *)p; p += al((size_t)n_q * chunk * 8);
-    h->table = (double *)p; p += al((size_t)n_kp * h->n_docs * 8);
+    h->q_raw = (u32 *)p;  p += align256((size_t)n_q * 4);
+    h->q_code = (u32 *)p; p += align256((size_t)n_q * 4);
+    h->q_end = (u32 *)p;  p += align256((size_t)n_q * 4);
+    h->q_off = (u32 *)p;  p += align256(((size_t)n_kp + 1) * 4);
+    h->group_off = (u32 *)p; p += align256(((size_t)n_kp + 1) * 4);      // synonym-expanded scoring: variants per keyphrase
+    h->q_blk = (u32 *)p;  p += align256(((size_t)n_kp + 1) * 4);
+    h->suffix = (double *)p; p += align256((size_t)n_q * chunk * 8);
+    h->table = (double *)p; p += align256((size_t)n_kp * h->n_docs * 8);
     h->table_g = (double *)p;
     h->n_blk = n_blk;
     fill();

@@ -33,7 +33,12 @@
 //
 // Determinism: no atomic, no split of L across workgroups or wavefronts; the order of every sum is fixed by the code.
 //
-// The host half is a consumer of the handle (consumer.h); its matrix is what it offers() the ranking (top.h) as a table.
+// The tile's geometry is this file's, and so are its pieces that cosine_texts.h runs too: sim_mfma_step, sim_acc_zero and
+// sim_tile_store (the tile and its mirror image).  The eight steps over a staged chunk stand in both kernels: as a shared
+// function they cost cost_tile_kernel 1.6 % on its largest measured case (profiles/matrix_frame_refactor.json).
+//
+// The host half is a MatrixConsumer of the handle (consumer.h): the frame has the matrix, its limit, its fetch and what it
+// offers() the ranking (top.h) and the clusters as a table; here are the axis, the uploaded table and the launches.
 #pragma once
 #include "consumer.h"
 
@@ -42,7 +47,6 @@
 #define SIM_LDS_STRIDE 33u                 // 8-byte words from one member's chunk to the next (see above)
 #define SIM_EPI_STRIDE 65u                 // ... from one row of the finished tile to the next
 #define SIM_NORM_COLS 16u                  // by text: columns a workgroup of the norm kernel sums (x 16 groups of rows)
-#define SIM_MAX_M (1u << 20)               // (8 TiB of matrix: more than any device holds, and the 2-D grid stays small)
 
 typedef double sim_v4d __attribute__((ext_vector_type(4)));
 
@@ -91,6 +95,29 @@ __device__ __forceinline__ void sim_mfma_step(sim_v4d (&acc)[2][2], const double
         for (int j = 0; j < 2; j++) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, 0);
 }
 
+__device__ __forceinline__ void sim_acc_zero(sim_v4d (&acc)[2][2])
+{
+#pragma unroll
+    for (int i = 0; i < 2; i++)
+#pragma unroll
+        for (int j = 0; j < 2; j++) acc[i][j] = (sim_v4d){0.0, 0.0, 0.0, 0.0};
+}
+
+// The finished tile (rows of SIM_EPI_STRIDE words in LDS) to S[a0 ..][b0 ..], row by row, and its mirror image to
+// S[b0 ..][a0 ..], column by column; a diagonal tile stores the values of its upper half to both places.
+__device__ __forceinline__ void sim_tile_store(double *__restrict__ S, u32 M, u32 a0, u32 b0, bool diag, const double *tile, u32 lane, u32 wv)
+{
+    for (u32 r = wv; r < SIM_TILE; r += WAVES_PER_BLOCK) {
+        const u32 a = a0 + r, b = b0 + lane;
+        if (a < M && b < M) S[(size_t)a * M + b] = diag && lane < r ? tile[lane * SIM_EPI_STRIDE + r] : tile[r * SIM_EPI_STRIDE + lane];
+    }
+    if (diag) return;
+    for (u32 c = wv; c < SIM_TILE; c += WAVES_PER_BLOCK) {
+        const u32 b = b0 + c, a = a0 + lane;
+        if (a < M && b < M) S[(size_t)b * M + a] = tile[lane * SIM_EPI_STRIDE + c];
+    }
+}
+
 // Workgroup (blockIdx.y = tile_a, blockIdx.x = tile_b), tile_a <= tile_b: S[64 tile_a ..][64 tile_b ..] and its mirror image.
 template <bool BY_TEXT>
 __global__ __launch_bounds__(BLOCK) void sim_gram_kernel(const double *__restrict__ t, u32 K, u32 D, const double *__restrict__ q,
@@ -107,10 +134,7 @@ __global__ __launch_bounds__(BLOCK) void sim_gram_kernel(const double *__restric
     const u32 ra = (wv >> 1) * 32u, cb = (wv & 1u) * 32u;         // this wavefront's quadrant inside the tile
     const u32 a0 = ta * SIM_TILE, b0 = tb * SIM_TILE;
     sim_v4d acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-        for (int j = 0; j < 2; j++) acc[i][j] = (sim_v4d){0.0, 0.0, 0.0, 0.0};
+    sim_acc_zero(acc);
 
     if (BY_TEXT) {
         const u32 ma[2] = {a0 + ra + lr, a0 + ra + 16u + lr}, mb[2] = {b0 + cb + lr, b0 + cb + 16u + lr};
@@ -189,38 +213,22 @@ __global__ __launch_bounds__(BLOCK) void sim_gram_kernel(const double *__restric
             }
         }
     __syncthreads();
-    for (u32 r = wv; r < SIM_TILE; r += WAVES_PER_BLOCK) {        // the tile, row by row
-        const u32 a = a0 + r, b = b0 + lane;
-        if (a < M && b < M) S[(size_t)a * M + b] = diag && lane < r ? lds[lane * SIM_EPI_STRIDE + r] : lds[r * SIM_EPI_STRIDE + lane];
-    }
-    if (diag) return;
-    for (u32 c = wv; c < SIM_TILE; c += WAVES_PER_BLOCK) {        // its mirror image, column by column
-        const u32 b = b0 + c, a = a0 + lane;
-        if (a < M && b < M) S[(size_t)b * M + a] = lds[lane * SIM_EPI_STRIDE + c];
-    }
+    sim_tile_store(S, M, a0, b0, diag, lds, lane, wv);
 }
 
 // ============================================================================================================ host ==
 // The similarity's device buffers belong to the handle and to nothing else: not the EASA arena, the cosine buffers, the
 // graph's or the ranking's.
-struct SimState : Consumer {
+struct SimState : MatrixConsumer {           // per_member: q
     static constexpr int SLOT = east_hip_index::SLOT_SIM;
-    u32 M = 0, L = 0;
+    u32 L = 0;
     UploadedTable table;                    // a host table's copy (east_hip_similarity_build_host)
-    DevBuf out;                             // q[M], matrix[M x M]
-    double *q = nullptr, *matrix = nullptr;
-    SimState() { bufs = {&table.buf, &out}; }
+    SimState() { bufs.push_back(&table.buf); }
     void clear() override
     {
-        M = L = 0;
+        MatrixConsumer::clear();
+        L = 0;
         table.withdraw();
-        q = matrix = nullptr;
-    }
-    TableRef offers() const override        // (the ranking reads the matrix where it lies)
-    {
-        TableRef t;
-        if (valid) { t.p = matrix; t.K = t.D = M; }
-        return t;
     }
 };
 
@@ -235,34 +243,22 @@ static void sim_build(east_hip_index *h, TableRef t, int32_t axis, i64 *out)
     const double *d_table = t.p;
     const u32 K = t.K, D = t.D;
     if (K < 1 || D < 1 || K >= 0x7FFFFFF0u || D >= 0x7FFFFFF0u) east_throw(EAST_HIP_ERR_INVALID, "similarity: empty score table");
-    SimState &g = consumer_state<SimState>(h);
-    g.valid = false;
-    g.ms = -1.f;
+    SimState &g = consumer_begin<SimState>(h);
     const bool by_text = axis == EAST_HIP_TOP_BY_TEXT;
     const u32 M = by_text ? D : K, L = by_text ? K : D;
-    const size_t q_bytes = ((size_t)M * 8 + 255) & ~(size_t)255;
-    const double matrix_bytes = (double)M * (double)M * 8.0;
-    if (M > SIM_MAX_M || !g.out.try_ensure(q_bytes + (size_t)M * M * 8 + 256, h->stream)) {
-        char msg[240];
-        snprintf(msg, sizeof(msg), "similarity: the matrix of %u x %u members needs %.0f bytes, which the device does not have", M, M,
-                 matrix_bytes);
-        east_throw(EAST_HIP_ERR_OOM, msg);
-    }
+    matrix_reserve(h, g, M, false, "similarity", std::to_string(M) + " x " + std::to_string(M) + " members");
+    g.L = L;
     Stats stats;
     Ctx ctx = handle_ctx(h, nullptr, &stats);
-    Arena a = g.out.arena();
-    g.q = a.alloc<double>(M);
-    g.matrix = a.alloc<double>((size_t)M * M);
-    g.M = M;
-    g.L = L;
+    double *q = g.per_member;
     const u32 NT = ceil_div_u32(M, SIM_TILE);
     ConsumerTimer timer(h, g);
     if (by_text) {
-        LAUNCH(ctx, sim_norm_col_kernel, ceil_div_u32(D, SIM_NORM_COLS), d_table, K, D, g.q);
-        LAUNCH_NAMED(ctx, "sim_gram_text_kernel", sim_gram_kernel<true>, dim3(NT, NT), d_table, K, D, (const double *)g.q, g.matrix);
+        LAUNCH(ctx, sim_norm_col_kernel, ceil_div_u32(D, SIM_NORM_COLS), d_table, K, D, q);
+        LAUNCH_NAMED(ctx, "sim_gram_text_kernel", sim_gram_kernel<true>, dim3(NT, NT), d_table, K, D, (const double *)q, g.matrix);
     } else {
-        LAUNCH(ctx, sim_norm_row_kernel, ceil_div_u32(K, WAVES_PER_BLOCK), d_table, K, D, g.q);
-        LAUNCH_NAMED(ctx, "sim_gram_keyphrase_kernel", sim_gram_kernel<false>, dim3(NT, NT), d_table, K, D, (const double *)g.q, g.matrix);
+        LAUNCH(ctx, sim_norm_row_kernel, ceil_div_u32(K, WAVES_PER_BLOCK), d_table, K, D, q);
+        LAUNCH_NAMED(ctx, "sim_gram_keyphrase_kernel", sim_gram_kernel<false>, dim3(NT, NT), d_table, K, D, (const double *)q, g.matrix);
     }
     timer.finish();
     g.valid = true;
@@ -273,38 +269,22 @@ extern "C" {
 
 int east_hip_similarity_build_resident(east_hip_handle_t h, int32_t source, int32_t axis, int64_t *out)
 {
-    return guarded([&] {
-        if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
-        use_device(h);
-        const SimState *g = consumer_peek<SimState>(h);
-        sim_build(h, resolve_table(h, source, g ? &g->table : nullptr, "similarity"), axis, out);
-    });
+    return guarded([&] { sim_build(h, consumer_resident<SimState>(h, source, "similarity"), axis, out); });
 }
 
 int east_hip_similarity_build_host(east_hip_handle_t h, const double *table, int32_t n_keyphrases, int32_t n_docs, int32_t axis, int64_t *out)
 {
     return guarded([&] {
-        if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
-        if (!table || n_keyphrases < 1 || n_docs < 1) east_throw(EAST_HIP_ERR_INVALID, "similarity: null or empty score table");
-        sim_check(axis);                                      // (before the upload: a refused call leaves the uploaded table alone)
-        use_device(h);
-        SimState &g = consumer_state<SimState>(h);
-        g.valid = false;
-        sim_build(h, g.table.upload(h, table, (u32)n_keyphrases, (u32)n_docs, "the similarity's score table"), axis, out);
+        const TableRef t = consumer_upload<SimState>(h, table, n_keyphrases, n_docs, "similarity: null or empty score table",
+                                                     "the similarity's score table", [&] { sim_check(axis); });
+        sim_build(h, t, axis, out);
     });
 }
 
 int east_hip_similarity_fetch(east_hip_handle_t h, double *matrix, double *norm2)
 {
     return guarded([&] {
-        if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
-        SimState *gp = consumer_peek<SimState>(h);
-        if (!gp || !gp->valid) east_throw(EAST_HIP_ERR_NOT_BUILT, "no similarity matrix has been built on this handle");
-        use_device(h);
-        SimState &g = *gp;
-        if (matrix) HIP_CHECK(hipMemcpyAsync(matrix, g.matrix, (size_t)g.M * g.M * 8, hipMemcpyDeviceToHost, h->stream));
-        if (norm2) HIP_CHECK(hipMemcpyAsync(norm2, g.q, (size_t)g.M * 8, hipMemcpyDeviceToHost, h->stream));
-        HIP_CHECK(hipStreamSynchronize(h->stream));
+        matrix_fetch(h, consumer_built<SimState>(h, "no similarity matrix has been built on this handle"), matrix, norm2, nullptr);
     });
 }
 

@@ -371,13 +371,7 @@ struct SynState : Consumer {             // valid: the feature rows; ms: the las
     }
 };
 
-static SynState &syn_built(east_hip_index *h)
-{
-    if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
-    SynState *g = consumer_peek<SynState>(h);
-    if (!g || !g->valid) east_throw(EAST_HIP_ERR_NOT_BUILT, "no synonym features have been built on this handle");
-    return *g;
-}
+static SynState &syn_built(east_hip_index *h) { return consumer_built<SynState>(h, "no synonym features have been built on this handle"); }
 
 static void syn_build(east_hip_index *h, const int32_t *w1, const int32_t *rel, const int32_t *w2, i64 n_triples, const int32_t *inv,
                       i64 n_words, i64 n_relations)
@@ -394,9 +388,8 @@ static void syn_build(east_hip_index *h, const int32_t *w1, const int32_t *rel, 
         if (w1[i] < 0 || w1[i] >= n_words || w2[i] < 0 || w2[i] >= n_words || rel[i] < 0 || rel[i] >= n_relations)
             east_throw(EAST_HIP_ERR_INVALID, "synonyms: a triple names a word or a relation outside the given counts");
     use_device(h);
-    SynState &g = consumer_state<SynState>(h);
-    g.valid = g.pairs_valid = false;
-    g.ms = -1.f;
+    SynState &g = consumer_begin<SynState>(h);
+    g.pairs_valid = false;
     const u32 N = (u32)n_triples, M = 2u * N, W = (u32)n_words, R = (u32)n_relations;
     Stats stats;
     Ctx ctx = handle_ctx(h, nullptr, &stats);
@@ -511,7 +504,7 @@ static void syn_pairs(east_hip_index *h, const int32_t *candidates, i64 n_candid
             ctx, e, true,                                     // (the tiles that leave early write no count)
             [&](u32 *cnt) { syn_launch_pairs<false>(ctx, grid, g, cand, C, L, TB, threshold, cnt, nullptr, nullptr, nullptr, nullptr); },
             [&](u64 E) {
-                const size_t ib = (((size_t)E * 4) + 255) & ~(size_t)255, db = (((size_t)E * 8) + 255) & ~(size_t)255;
+                const size_t ib = align256((size_t)E * 4), db = align256((size_t)E * 8);
                 g.out.ensure(2 * ib + db, "the synonym pairs", h->stream);
                 g.o_a = (int32_t *)g.out.p;
                 g.o_b = (int32_t *)(g.out.p + ib);

@@ -38,15 +38,9 @@
 #define TOP_COLS_PER_WAVE (64u / WAVES_PER_BLOCK)
 #define TOP_MAX_N 1024
 
-// the order of the doubles as the order of unsigned integers; 0 = not eligible (the only double that would map to 0 is a
-// NaN with every bit set, and a NaN is never eligible)
-__device__ __forceinline__ u64 top_key(double v, double threshold)
-{
-    if (!(v >= threshold)) return 0ull;
-    u64 b = (u64)__double_as_longlong(v);
-    if (b == 0x8000000000000000ull) b = 0ull;             // -0.0 == +0.0
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
+// ordered_key of an eligible score; 0 = not eligible (the only double that would map to 0 is a NaN with every bit set, and
+// a NaN is never eligible)
+__device__ __forceinline__ u64 top_key(double v, double threshold) { return v >= threshold ? ordered_key(v) : 0ull; }
 
 // list: the 64 keys of a tile in LDS (0 behind its end); the keys in front of (my, lane) -- the same address for every lane
 __device__ __forceinline__ u32 top_rank_in_tile(const u64 *list, u64 my, u32 lane)
@@ -210,9 +204,7 @@ static void top_build(east_hip_index *h, TableRef t, int32_t axis, int32_t n_bes
     const double *d_table = t.p;
     const u32 K = t.K, D = t.D;
     if (K < 1 || D < 1 || K >= 0x7FFFFFF0u || D >= 0x7FFFFFF0u) east_throw(EAST_HIP_ERR_INVALID, "ranked keyphrases: empty score table");
-    TopState &g = consumer_state<TopState>(h);
-    g.valid = false;
-    g.ms = -1.f;
+    TopState &g = consumer_begin<TopState>(h);
     g.total = 0;
     const bool by_text = axis == EAST_HIP_TOP_BY_TEXT;
     const u32 S = by_text ? D : K, L = by_text ? K : D, n = (u32)n_best;
@@ -258,36 +250,23 @@ extern "C" {
 
 int east_hip_top_build_resident(east_hip_handle_t h, int32_t source, int32_t axis, int32_t n, double threshold, int64_t *out)
 {
-    return guarded([&] {
-        if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
-        use_device(h);
-        const TopState *g = consumer_peek<TopState>(h);
-        top_build(h, resolve_table(h, source, g ? &g->table : nullptr, "ranked keyphrases", true), axis, n, threshold, out);
-    });
+    return guarded([&] { top_build(h, consumer_resident<TopState>(h, source, "ranked keyphrases", true), axis, n, threshold, out); });
 }
 
 int east_hip_top_build_host(east_hip_handle_t h, const double *table, int32_t n_keyphrases, int32_t n_docs, int32_t axis, int32_t n,
                             double threshold, int64_t *out)
 {
     return guarded([&] {
-        if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
-        if (!table || n_keyphrases < 1 || n_docs < 1) east_throw(EAST_HIP_ERR_INVALID, "ranked keyphrases: null or empty score table");
-        top_check(axis, n, threshold);                        // (before the upload: a refused call leaves the uploaded table alone)
-        use_device(h);
-        TopState &g = consumer_state<TopState>(h);
-        g.valid = false;
-        top_build(h, g.table.upload(h, table, (u32)n_keyphrases, (u32)n_docs, "the ranking's score table"), axis, n, threshold, out);
+        const TableRef t = consumer_upload<TopState>(h, table, n_keyphrases, n_docs, "ranked keyphrases: null or empty score table",
+                                                     "the ranking's score table", [&] { top_check(axis, n, threshold); });
+        top_build(h, t, axis, n, threshold, out);
     });
 }
 
 int east_hip_top_fetch(east_hip_handle_t h, int32_t *count, int32_t *index, double *score)
 {
     return guarded([&] {
-        if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
-        TopState *gp = consumer_peek<TopState>(h);
-        if (!gp || !gp->valid) east_throw(EAST_HIP_ERR_NOT_BUILT, "no keyphrase ranking has been built on this handle");
-        use_device(h);
-        TopState &g = *gp;
+        const TopState &g = consumer_built<TopState>(h, "no keyphrase ranking has been built on this handle");
         const size_t places = (size_t)g.S * g.n;
         if (count) HIP_CHECK(hipMemcpyAsync(count, g.count, (size_t)g.S * 4, hipMemcpyDeviceToHost, h->stream));
         if (index) HIP_CHECK(hipMemcpyAsync(index, g.index, places * 4, hipMemcpyDeviceToHost, h->stream));

@@ -395,11 +395,12 @@ def _similarity_build(lib, h, source, table, axis):
     return int(out[0]), int(out[1])
 
 
-def _similarity_fetch(lib, h, M):
-    """east_hip_similarity_fetch -> (matrix[M, M], norm2[M])."""
-    matrix, norm2 = np.empty((M, M), dtype=np.float64), np.empty(M, dtype=np.float64)
-    _check(lib.east_hip_similarity_fetch(h, _ptr(matrix, _c_dblp), _ptr(norm2, _c_dblp)))
-    return matrix, norm2
+def _matrix_fetch(fetch, h, M, count=True):
+    """The fetch entry point of an M x M matrix consumer -> (matrix[M, M], a double a member[M]) and, where the consumer
+    counts (count=True), an int32 a member[M]."""
+    found = (np.empty((M, M), dtype=np.float64), np.empty(M, dtype=np.float64)) + ((np.empty(M, dtype=np.int32),) if count else ())
+    _check(fetch(h, *(_ptr(x, _c_i32p if x.dtype == np.int32 else _c_dblp) for x in found)))
+    return found
 
 
 class _ResidentTableConsumers(object):
@@ -407,6 +408,7 @@ class _ResidentTableConsumers(object):
     self._h): the table `_table_source` names -- the AST table of a HipIndex, the cosine table of a HipCosineIndex."""
 
     _table_source = None
+    _sim_M = _rel_M = _texts_M = 0      # the members of the handle's last similarity / relatedness / text cosine matrix (0: none yet)
 
     @property
     def _sim_holder(self):
@@ -446,7 +448,7 @@ class _ResidentTableConsumers(object):
 
     def similarity_matrix(self):
         """The last similarity matrix of this handle and the squared norms of its profiles -> (matrix[M, M], norm2[M])."""
-        return _similarity_fetch(self._lib, self._h, getattr(self._sim_holder, "_sim_M", 0))
+        return _matrix_fetch(self._lib.east_hip_similarity_fetch, self._h, self._sim_holder._sim_M, count=False)
 
     def similar(self, axis, n, threshold=-np.inf):
         """similarity(axis), then the n most similar other members of every member (the ranking of the matrix by row: the
@@ -744,16 +746,13 @@ class HipIndex(_ResidentTableConsumers):
         resident keyphrases.  -> (D, scored strings, score launches)"""
         out = np.zeros(3, dtype=np.int64)
         _check(self._lib.east_hip_related_build(self._h, int(bool(normalized)), int(orientation), _ptr(out, _c_i64p)))
-        self._rel_D = int(out[0])
+        self._rel_M = int(out[0])
         return int(out[0]), int(out[1]), int(out[2])
 
     def related_matrix(self):
         """The last relatedness matrix of this handle -> (matrix[D, D] with NaN on the diagonal, self[D] = F[A][A],
         scored[D] = the scored strings of every text, int32)."""
-        D = getattr(self, "_rel_D", 0)
-        matrix, own, scored = np.empty((D, D), dtype=np.float64), np.empty(D, dtype=np.float64), np.empty(D, dtype=np.int32)
-        _check(self._lib.east_hip_related_fetch(self._h, _ptr(matrix, _c_dblp), _ptr(own, _c_dblp), _ptr(scored, _c_i32p)))
-        return matrix, own, scored
+        return _matrix_fetch(self._lib.east_hip_related_fetch, self._h, self._rel_M)
 
     def rank_related(self, n, threshold=-np.inf):
         """A ranking of the last relatedness matrix by row (other n, other threshold: no new matrix) -> TopArrays."""
@@ -885,16 +884,13 @@ class HipCosineIndex(_ResidentTableConsumers):
         "Text-to-text cosine similarity"); it stays on the device.  -> {COSINE_TEXTS_INFO_FIELDS: value}"""
         out = np.zeros(len(COSINE_TEXTS_INFO_FIELDS), dtype=np.int64)
         _check(self._lib.east_hip_text_similarity_build(self._h, 1 if tfidf else 0, _ptr(out, _c_i64p)))
-        self._texts_D = int(out[0])
+        self._texts_M = int(out[0])
         return dict(zip(COSINE_TEXTS_INFO_FIELDS, (int(x) for x in out)))
 
     def texts_matrix(self):
         """The last text-to-text cosine matrix of this handle -> (matrix[D, D] with NaN on the diagonal, self[D] = the
         diagonal before the NaN, postings[D] = the postings of every text, int32)."""
-        D = getattr(self, "_texts_D", 0)
-        matrix, own, postings = np.empty((D, D), dtype=np.float64), np.empty(D, dtype=np.float64), np.empty(D, dtype=np.int32)
-        _check(self._lib.east_hip_text_similarity_fetch(self._h, _ptr(matrix, _c_dblp), _ptr(own, _c_dblp), _ptr(postings, _c_i32p)))
-        return matrix, own, postings
+        return _matrix_fetch(self._lib.east_hip_text_similarity_fetch, self._h, self._texts_M)
 
     def rank_texts(self, n, threshold=-np.inf):
         """A ranking of the last text-to-text cosine matrix by row (other n, other threshold: no new matrix) -> TopArrays."""

@@ -79,6 +79,57 @@ def check_all_from_uploaded(index, graph_table, top_table, sim_table):
     check_top(index.top_from_uploaded(0, NS[0]), top_table, 0, NS[0])
 
 
+def test_frame_messages(hip):
+    """The messages of the consumer frame (csrc/consumer.h), word for word, through east_hip_last_error(): what a fetch and
+    a *_build_resident call say on a fresh handle, and what the matrix's limit says.  Nothing is launched; the one upload
+    is the (2^20 + 1) x 1 table whose matrix is refused before anything is allocated for it."""
+    lib = hip.load()
+    index = hip.HipIndex()
+    h = index._h
+    ERR_OOM = -3
+    out = np.zeros(4, dtype=np.int64)
+    out_p = out.ctypes.data_as(I64P)
+    rows = np.zeros(1, dtype=np.int32)
+
+    def said(rc, code, message):
+        assert (rc, lib.east_hip_last_error().decode()) == (code, message)
+
+    said(lib.east_hip_graph_fetch(h, None, None, None, None, None), ERR_NOT_BUILT, "no keyphrase graph has been built on this handle")
+    said(lib.east_hip_top_fetch(h, None, None, None), ERR_NOT_BUILT, "no keyphrase ranking has been built on this handle")
+    said(lib.east_hip_similarity_fetch(h, None, None), ERR_NOT_BUILT, "no similarity matrix has been built on this handle")
+    said(lib.east_hip_related_fetch(h, None, None, None), ERR_NOT_BUILT, "no relatedness matrix has been built on this handle")
+    said(lib.east_hip_text_similarity_fetch(h, None, None, None), ERR_NOT_BUILT, "no text similarity matrix has been built on this handle")
+    said(lib.east_hip_clusters_fetch(h, None, None, None), ERR_NOT_BUILT, "no clusters have been built on this handle")
+
+    resident = {
+        "keyphrase graph": lambda s: lib.east_hip_graph_build_resident(h, s, rows.ctypes.data_as(I32P), 1, RT, float(ST), RC, out_p),
+        "ranked keyphrases": lambda s: lib.east_hip_top_build_resident(h, s, 0, 3, 0.0, out_p),
+        "similarity": lambda s: lib.east_hip_similarity_build_resident(h, s, 0, out_p),
+        "clusters": lambda s: lib.east_hip_clusters_build_resident(h, s, out_p),
+    }
+    missing = {0: "no score table is resident (score the keyphrases first)",
+               1: "no cosine score table is resident (score the keyphrases first)",
+               2: "no host table has been uploaded to this handle",
+               3: "no similarity matrix has been built on this handle",
+               4: "no relatedness matrix has been built on this handle",
+               5: "no text similarity matrix has been built on this handle"}
+    for who, call in resident.items():
+        takes_matrices = who in ("ranked keyphrases", "clusters")
+        for source in (0, 1, 2, 3, 4, 5, 7):
+            if who == "clusters" and source in (0, 1, 7):       # (the clusters refuse what is no matrix in their own words)
+                said(call(source), ERR_INVALID, "clusters: the source is not a square matrix of members")
+            elif source in (0, 1, 2) or (takes_matrices and source in (3, 4, 5)):
+                said(call(source), ERR_NOT_BUILT, "%s: %s" % (who, missing[source]))
+            else:
+                said(call(source), ERR_INVALID, "%s: unknown table source" % who)
+
+    M = (1 << 20) + 1
+    column = np.zeros((M, 1))
+    said(lib.east_hip_similarity_build_host(h, column.ctypes.data_as(DBLP), M, 1, 1, out_p), ERR_OOM,
+         "similarity: the matrix of 1048577 x 1048577 members needs 8796109799432 bytes, which the device does not have")
+    index.close()
+
+
 def test_three_uploaded_tables_on_one_handle(hip):
     lib = hip.load()
     index = hip.HipIndex()
