@@ -74,9 +74,11 @@ template <class T> static T &consumer_built(east_hip_index *h, const char *none)
 template <class T> static double consumer_ms(const east_hip_index *h) { return h && h->consumers[T::SLOT] ? (double)h->consumers[T::SLOT]->ms : -1.0; }
 
 // Brackets a call's launches on the handle's stream: ev0 now; finish() records ev1, waits for the stream and stores the time.
+// stop() records ev1 early, for a call that queues behind its launches what it does not count (the copy of a table to the host).
 struct ConsumerTimer {
     east_hip_index *h;
     Consumer &c;
+    bool stopped = false;
     ConsumerTimer(east_hip_index *h_, Consumer &c_) : h(h_), c(c_)
     {
         if (!c.ev1) {
@@ -85,9 +87,14 @@ struct ConsumerTimer {
         }
         HIP_CHECK(hipEventRecord(c.ev0, h->stream));
     }
-    void finish()
+    void stop()
     {
         HIP_CHECK(hipEventRecord(c.ev1, h->stream));
+        stopped = true;
+    }
+    void finish()
+    {
+        if (!stopped) stop();
         HIP_CHECK(hipStreamSynchronize(h->stream));
         HIP_CHECK(hipEventElapsedTime(&c.ms, c.ev0, c.ev1));
     }

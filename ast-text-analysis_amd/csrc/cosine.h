@@ -88,14 +88,12 @@ static inline u64 cos_base_of_seed(u64 seed)
 }
 
 // ---- tokens --------------------------------------------------------------------------------------------------------
-// keep[k] = the token has at least COS_MIN_LEN code points (no isdigit filter and no U+0A00 limit here); keep[n_tok] = 0
-__global__ __launch_bounds__(BLOCK) void cos_keep_kernel(const u32 *__restrict__ tstart, const u32 *__restrict__ tend, u32 n_tok,
-                                                         u32 *__restrict__ keep)
-{
-    const u32 k = blockIdx.x * BLOCK + threadIdx.x;
-    if (k > n_tok) return;
-    keep[k] = k < n_tok && tend[k] - tstart[k] + 1u >= COS_MIN_LEN ? 1u : 0u;
-}
+// The predicates the build scans are inputs of the scan (scan.h) where they read what lies in a row; those that gather are
+// arrays (pflag, tn, ns).  Token k has at least COS_MIN_LEN code points (no isdigit filter and no U+0A00 limit here)
+struct CosKeepIn {
+    const u32 *tstart, *tend;
+    __device__ __forceinline__ u32 operator()(u32 k) const { return tend[k] - tstart[k] + 1u >= COS_MIN_LEN ? 1u : 0u; }
+};
 
 // the kept tokens, compacted: first code point, length, document, and the number of pieces
 __global__ __launch_bounds__(BLOCK) void cos_compact_kernel(const u32 *__restrict__ tstart, const u32 *__restrict__ tend,
@@ -157,27 +155,21 @@ __global__ __launch_bounds__(BLOCK) void cos_token_hash_kernel(const u64 *__rest
 }
 
 // ---- runs of equal hashes ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(BLOCK) void cos_run_flags_kernel(const u64 *__restrict__ skeys, u32 n, u32 *__restrict__ flag)
+// ri = inclusive scan of the run heads (RunHeadIn over the sorted keys): the run of sorted position i is ri[i] - 1, and i
+// is a head where ri steps.  Per run: its first sorted position (and n behind the last run), its key, and where its head
+// token -- the first occurrence: the sort is stable and the tokens went in ascending -- lies in the code points
+__global__ __launch_bounds__(BLOCK) void cos_run_heads_kernel(const u32 *__restrict__ ri, const u64 *__restrict__ skeys,
+                                                              const u32 *__restrict__ svals, const u32 *__restrict__ kstart,
+                                                              const u32 *__restrict__ klen, u32 n, u32 *__restrict__ run_start,
+                                                              u64 *__restrict__ run_key, u32 *__restrict__ run_hstart,
+                                                              u32 *__restrict__ run_hlen)
 {
     const u32 i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
-    flag[i] = i == 0 || skeys[i] != skeys[i - 1u] ? 1u : 0u;
-}
-
-// ri = inclusive scan of the flags: the run of sorted position i is ri[i] - 1.  Per run: its first sorted position (and
-// n behind the last run), its key, and where its head token -- the first occurrence: the sort is stable and the tokens
-// went in ascending -- lies in the code points
-__global__ __launch_bounds__(BLOCK) void cos_run_heads_kernel(const u32 *__restrict__ flag, const u32 *__restrict__ ri,
-                                                              const u64 *__restrict__ skeys, const u32 *__restrict__ svals,
-                                                              const u32 *__restrict__ kstart, const u32 *__restrict__ klen,
-                                                              u32 n, u32 *__restrict__ run_start, u64 *__restrict__ run_key,
-                                                              u32 *__restrict__ run_hstart, u32 *__restrict__ run_hlen)
-{
-    const u32 i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    if (i + 1u == n) run_start[ri[i]] = n;
-    if (!flag[i]) return;
-    const u32 r = ri[i] - 1u, t = svals[i];
+    const u32 r1 = ri[i];
+    if (i + 1u == n) run_start[r1] = n;
+    if (i > 0 && ri[i - 1u] == r1) return;
+    const u32 r = r1 - 1u, t = svals[i];
     run_start[r] = i;
     run_key[r] = skeys[i];
     run_hstart[r] = kstart[t];
@@ -274,25 +266,23 @@ __global__ __launch_bounds__(BLOCK) void cos_run_terms_kernel(const u32 *__restr
 
 // ---- postings -------------------------------------------------------------------------------------------------------
 // Inside a run the tokens are in collection order, so its segments of one document are its postings.  pflag[i] = sorted
-// position i starts a posting (stop runs have none); pflag[n] = 0
+// position i starts a posting (stop runs have none).  (Gathers: an array, since the scan evaluates its input twice)
 __global__ __launch_bounds__(BLOCK) void cos_posting_flags_kernel(const u32 *__restrict__ svals, const u32 *__restrict__ ri,
                                                                   const u32 *__restrict__ run_start, const u32 *__restrict__ run_term,
                                                                   const u32 *__restrict__ kdoc, u32 n, u32 *__restrict__ pflag)
 {
     const u32 i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i > n) return;
-    if (i == n) { pflag[i] = 0u; return; }
+    if (i >= n) return;
     const u32 r = ri[i] - 1u;
     pflag[i] = run_term[r] != COS_NONE && (i == run_start[r] || kdoc[svals[i - 1u]] != kdoc[svals[i]]) ? 1u : 0u;
 }
 
-// postings per term, in term order (tn[V] = 0 for the scan)
+// postings per term, in term order; px = exclusive scan of pflag.  (Gathers: an array, since the scan evaluates its input twice)
 __global__ __launch_bounds__(BLOCK) void cos_term_counts_kernel(const u32 *__restrict__ term_run, const u32 *__restrict__ run_start,
                                                                 const u32 *__restrict__ px, u32 V, u32 *__restrict__ tn)
 {
     const u32 t = blockIdx.x * BLOCK + threadIdx.x;
-    if (t > V) return;
-    if (t == V) { tn[t] = 0u; return; }
+    if (t >= V) return;
     const u32 r = term_run[t];
     tn[t] = px[run_start[r + 1u]] - px[run_start[r]];
 }
@@ -327,26 +317,22 @@ __global__ __launch_bounds__(BLOCK) void cos_counts_kernel(const u32 *__restrict
 }
 
 // ---- per document: the kept tokens that are not stopwords (n_d) -----------------------------------------------------
+// ns[j] = kept token j is no stopword (a gather: an array, as tn)
 __global__ __launch_bounds__(BLOCK) void cos_nonstop_kernel(const u32 *__restrict__ run_of_tok, const u32 *__restrict__ run_term,
                                                             u32 n_kept, u32 *__restrict__ ns)
 {
     const u32 j = blockIdx.x * BLOCK + threadIdx.x;
-    if (j > n_kept) return;
-    ns[j] = j < n_kept && run_term[run_of_tok[j]] != COS_NONE ? 1u : 0u;
+    if (j < n_kept) ns[j] = run_term[run_of_tok[j]] != COS_NONE ? 1u : 0u;
 }
 
-// the kept tokens of document d are [lower_bound(kdoc, d), lower_bound(kdoc, d + 1)); nsx = exclusive scan of ns
+// the kept tokens of document d are those from the first of a document >= d to the first of one >= d + 1 (kdoc ascends);
+// nsx = exclusive scan of ns
 __global__ __launch_bounds__(BLOCK) void cos_doc_lengths_kernel(const u32 *__restrict__ kdoc, u32 n_kept, const u32 *__restrict__ nsx,
                                                                 u32 n_docs, u32 *__restrict__ n_d)
 {
     const u32 d = blockIdx.x * BLOCK + threadIdx.x;
     if (d >= n_docs) return;
-    auto lower = [&](u32 x) {
-        u32 lo = 0, hi = n_kept;
-        while (lo < hi) { const u32 mid = (lo + hi) >> 1; if (kdoc[mid] < x) lo = mid + 1u; else hi = mid; }
-        return lo;
-    };
-    n_d[d] = nsx[lower(d + 1u)] - nsx[lower(d)];
+    n_d[d] = nsx[ascending_lower_bound(kdoc, n_kept, d + 1u)] - nsx[ascending_lower_bound(kdoc, n_kept, d)];
 }
 
 // ---- the terms' text (east_hip_cosine_get_terms, query look-ups) ----------------------------------------------------
@@ -354,8 +340,7 @@ __global__ __launch_bounds__(BLOCK) void cos_term_len_kernel(const u32 *__restri
                                                              u32 *__restrict__ tlen)
 {
     const u32 t = blockIdx.x * BLOCK + threadIdx.x;
-    if (t > V) return;
-    tlen[t] = t < V ? run_hlen[term_run[t]] : 0u;
+    if (t < V) tlen[t] = run_hlen[term_run[t]];
 }
 
 // a wavefront per term
@@ -380,15 +365,8 @@ __global__ __launch_bounds__(BLOCK) void cos_class_keys_kernel(const u32 *__rest
     vals[p] = p;
 }
 
-__global__ __launch_bounds__(BLOCK) void cos_key_flags_kernel(const u64 *__restrict__ skeys, u32 n, u32 *__restrict__ flag)
-{
-    const u32 i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i > n) return;
-    flag[i] = i < n && (i == 0 || skeys[i] != skeys[i - 1u]) ? 1u : 0u;
-}
-
-// one merged posting per segment of equal (class, document), fx = exclusive scan of the segment starts; the counts are
-// integers, added in term order
+// one merged posting per segment of equal (class, document), fx = exclusive scan of the segment starts (RunHeadIn over the
+// sorted keys); the counts are integers, added in term order
 __global__ __launch_bounds__(BLOCK) void cos_class_merge_kernel(const u64 *__restrict__ skeys, const u32 *__restrict__ svals,
                                                                 const u32 *__restrict__ post_cnt, const u32 *__restrict__ fx, u32 n,
                                                                 u32 *__restrict__ c_doc, u32 *__restrict__ c_unit,
@@ -402,17 +380,6 @@ __global__ __launch_bounds__(BLOCK) void cos_class_merge_kernel(const u64 *__res
     c_doc[slot] = (u32)skeys[i];
     c_unit[slot] = (u32)(skeys[i] >> 32);
     c_cnt[slot] = c;
-}
-
-// unit_off[u] = the first posting of unit u in postings sorted by unit (n_units + 1 entries; a unit without postings gets
-// an empty range)
-__global__ __launch_bounds__(BLOCK) void cos_unit_offsets_kernel(const u32 *__restrict__ post_unit, u32 P, u32 n_units,
-                                                                 u32 *__restrict__ unit_off)
-{
-    const u32 p = blockIdx.x * BLOCK + threadIdx.x;
-    if (p > P) return;
-    const u32 u0 = p == 0 ? 0u : post_unit[p - 1u] + 1u, u1 = p == P ? n_units : post_unit[p];
-    for (u32 u = u0; u <= u1; u++) unit_off[u] = p;
 }
 
 // ---- document order of the postings, weights and norms ---------------------------------------------------------------
@@ -429,16 +396,6 @@ __global__ __launch_bounds__(BLOCK) void cos_invert_perm_kernel(const u32 *__res
 {
     const u32 i = blockIdx.x * BLOCK + threadIdx.x;
     if (i < P) inv[perm[i]] = i;
-}
-
-// the postings of document d in document order are [doc_off[d], doc_off[d + 1])
-__global__ __launch_bounds__(BLOCK) void cos_doc_offsets_kernel(const u32 *__restrict__ sdoc, u32 P, u32 n_docs, u32 *__restrict__ doc_off)
-{
-    const u32 d = blockIdx.x * BLOCK + threadIdx.x;
-    if (d > n_docs) return;
-    u32 lo = 0, hi = P;
-    while (lo < hi) { const u32 mid = (lo + hi) >> 1; if (sdoc[mid] < d) lo = mid + 1u; else hi = mid; }
-    doc_off[d] = lo;
 }
 
 // w = tf * idf, tf = count / max(n_d, 1), idf = 1 + ln(D / df) under tf-idf and no factor under tf (relevance.py:105-141);
@@ -551,7 +508,7 @@ struct CosUnits {
 
 struct CosState : Consumer {
     static constexpr int SLOT = east_hip_index::SLOT_COS;
-    bool built = false, use_classes = false;
+    bool use_classes = false;                             // (valid: the index is built)
     u32 n_docs = 0, n_kept = 0, n_runs = 0, V = 0, attempts = 0;
     u64 B = 0, mask = 0;                                  // hash base and mask of the attempt that passed the verification
     DevBuf text;             // scratch: bytes, code points, tokens (after the build: the scratch of the weights)
@@ -563,7 +520,7 @@ struct CosState : Consumer {
     u64 *run_key = nullptr;
     u32 *run_term = nullptr, *term_off = nullptr, *term_len = nullptr, *tcp = nullptr, *n_d = nullptr;
     CosUnits terms, cls;
-    float build_ms = -1.f, score_ms = -1.f;
+    float build_ms = -1.f, score_ms = -1.f;               // the timer's ms of the last build and of the last score call
     double *table = nullptr;                              // the last score call's K x D table, where it lies in `score` (offers(): the graph, the ranking and the similarity read it there)
     u32 table_K = 0;
     bool table_valid = false;
@@ -574,15 +531,14 @@ struct CosState : Consumer {
     }
     void clear() override
     {
-        built = use_classes = false;
-        table_valid = false;
+        use_classes = table_valid = false;
         terms.w_valid[0] = terms.w_valid[1] = cls.w_valid[0] = cls.w_valid[1] = false;
         build_ms = score_ms = -1.f;
     }
     TableRef offers() const override
     {
         TableRef t;
-        if (built && table_valid) { t.p = table; t.K = table_K; t.D = n_docs; }
+        if (valid && table_valid) { t.p = table; t.K = table_K; t.D = n_docs; }
         return t;
     }
 };
@@ -594,12 +550,21 @@ static void cos_withdraw_texts_matrix(east_hip_index *h)
     if (Consumer *t = h->consumers[east_hip_index::SLOT_COSTEXT]) t->withdraw();
 }
 
-static CosState &cos_built(east_hip_index *h)
+static CosState &cos_built(east_hip_index *h) { return consumer_built<CosState>(h, "no cosine index has been built on this handle"); }
+
+// A ragged host array: n + 1 offsets into a payload of offsets[n] words, narrowed to 32 bits for the device.  bad: the
+// message where they do not start at 0, the payload has 2^31 - 16 words or more, or it is null and not empty; decreasing:
+// where an offset is below the one in front.
+static std::vector<u32> ragged_offsets_u32(const i64 *offsets, int32_t n, const void *payload, const char *bad, const char *decreasing)
 {
-    if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
-    CosState *c = consumer_peek<CosState>(h);
-    if (!c || !c->built) east_throw(EAST_HIP_ERR_NOT_BUILT, "no cosine index has been built on this handle");
-    return *c;
+    std::vector<u32> off32((size_t)n + 1, 0);
+    if (!n) return off32;
+    if (offsets[0] != 0 || offsets[n] >= (i64)0x7FFFFFF0 || (offsets[n] > 0 && !payload)) east_throw(EAST_HIP_ERR_INVALID, bad);
+    for (int32_t i = 0; i < n; i++) {
+        if (offsets[i + 1] < offsets[i]) east_throw(EAST_HIP_ERR_INVALID, decreasing);
+        off32[i + 1] = (u32)offsets[i + 1];
+    }
+    return off32;
 }
 
 // The postings in document order: a stable sort by document keeps the ascending unit order inside every document
@@ -612,12 +577,12 @@ static void cos_doc_order(Ctx &ctx, CosUnits &U, u32 D)
         return;
     }
     const size_t mark = ctx.arena->mark();
-    SortBufs<u32> sb;
-    for (int k = 0; k < 2; k++) { sb.keys[k] = ctx.arena->alloc<u32>(P); sb.vals[k] = ctx.arena->alloc<u32>(P); }
+    SortBufs<u32> sb = sort_bufs_alloc<u32>(*ctx.arena, P);
     LAUNCH(ctx, cos_doc_keys_kernel, ceil_div_u32(P, BLOCK), (const u32 *)U.post_doc, P, sb.keys[0], sb.vals[0]);
     const int r = radix_sort_pairs<u32>(ctx, sb, P, std::max(1, bit_width_u32(D - 1)));
     LAUNCH(ctx, cos_invert_perm_kernel, ceil_div_u32(P, BLOCK), (const u32 *)sb.vals[r], P, U.inv_perm);
-    LAUNCH(ctx, cos_doc_offsets_kernel, ceil_div_u32((u64)D + 1, BLOCK), (const u32 *)sb.keys[r], P, D, U.doc_off);
+    // (the postings of document d in document order are [doc_off[d], doc_off[d + 1]))
+    LAUNCH(ctx, ascending_offsets_kernel, ceil_div_u32((u64)D + 1, BLOCK), (const u32 *)sb.keys[r], P, D, U.doc_off);
     ctx.arena->release(mark);
 }
 
@@ -626,26 +591,22 @@ static void cos_build(east_hip_index *h, HostTexts in, const UnicodeTablesHost &
     if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
     host_texts_check(in, tables);
     if (n_stop < 0 || (n_stop > 0 && !stop_offsets)) east_throw(EAST_HIP_ERR_INVALID, "bad stopword arguments");
-    const i64 n_stop_cps = n_stop ? stop_offsets[n_stop] : 0;
-    if (n_stop && (stop_offsets[0] != 0 || n_stop_cps >= (i64)0x7FFFFFF0 || (n_stop_cps > 0 && !stop_cps)))
-        east_throw(EAST_HIP_ERR_INVALID, "bad stopword offsets");
-    for (int32_t w = 0; w < n_stop; w++)
-        if (stop_offsets[w + 1] < stop_offsets[w]) east_throw(EAST_HIP_ERR_INVALID, "stopword offsets must not decrease");
+    const std::vector<u32> stop_off32 = ragged_offsets_u32(stop_offsets, n_stop, stop_cps, "bad stopword offsets", "stopword offsets must not decrease");
+    const u32 n_stop_cps = stop_off32[n_stop];
     use_device(h);
-    CosState &c = consumer_state<CosState>(h);
+    CosState &c = consumer_begin<CosState>(h);
+    c.clear();
     cos_withdraw_texts_matrix(h);
-    c.built = c.use_classes = false;
-    c.table_valid = false;
-    c.terms.w_valid[0] = c.terms.w_valid[1] = c.cls.w_valid[0] = c.cls.w_valid[1] = false;
     const u32 N = (u32)in.n_bytes, D = (u32)in.D;
     Stats stats;
 
     // ---- bytes -> code points -> tokens (at most one token per two code points, plus one)
     const size_t n_tok_max = (size_t)N / 2 + 2;
-    c.text.ensure((size_t)N * 6 + n_tok_max * 20 + (size_t)N / 32 + (size_t)D * 16 + ((size_t)1 << 20), "the cosine index");
+    // (a token: its two bounds, tok_nd and keep_ex)
+    c.text.ensure((size_t)N * 6 + n_tok_max * 16 + (size_t)N / 32 + (size_t)D * 16 + ((size_t)1 << 20), "the cosine index");
     Arena a1 = c.text.arena();
     Ctx ctx = handle_ctx(h, &a1, &stats);
-    HIP_CHECK(hipEventRecord(h->ev0, h->stream));
+    ConsumerTimer timer(h, c);
     uint8_t *d_bytes = a1.alloc<uint8_t>((size_t)N + 32);
     u32 *d_text_off = a1.alloc<u32>((size_t)D + 1);
     upload_texts_whole(h, in, d_bytes, d_text_off);
@@ -654,12 +615,8 @@ static void cos_build(east_hip_index *h, HostTexts in, const UnicodeTablesHost &
     const TpTokens tk = tp_tokenize(ctx, D, N, d_bytes, d_text_off, tb, false);
     const u32 n_cp = tk.n_cp, n_tok = tk.n_tok;
     const u32 *cpu = tk.cpu, *doc_cp_off = tk.doc_cp_off, *tstart = tk.tstart, *tend = tk.tend;
-    u32 *keep = a1.alloc<u32>((size_t)n_tok + 1), *keep_ex = a1.alloc<u32>((size_t)n_tok + 1);
-    LAUNCH(ctx, cos_keep_kernel, ceil_div_u32((u64)n_tok + 1, BLOCK), (const u32 *)tstart, (const u32 *)tend, n_tok, keep);
-    device_scan<ArrIn, false>(ctx, ArrIn{keep}, n_tok + 1, keep_ex);
-    u32 n_kept = 0;
-    HIP_CHECK(hipMemcpyAsync(&n_kept, keep_ex + n_tok, 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
+    u32 *keep_ex = a1.alloc<u32>((size_t)n_tok + 1);
+    const u32 n_kept = device_scan_count(ctx, CosKeepIn{tstart, tend}, n_tok, keep_ex);
 
     // ---- what stays (runs, terms and postings are at most as many as the kept tokens)
     const size_t K1 = (size_t)n_kept + 2;
@@ -680,26 +637,23 @@ static void cos_build(east_hip_index *h, HostTexts in, const UnicodeTablesHost &
 
     // ---- the kept tokens and their pieces
     const size_t n_pc_max = (size_t)n_kept + n_cp / COS_PIECE + 2;
-    c.work.ensure(K1 * 160 + n_pc_max * 12 + ((size_t)n_stop_cps + 3 * (size_t)n_stop) * 4 + ((size_t)4 << 20), "the cosine index");
+    // (a kept token: 128 bytes -- the twenty-two arrays of a word each below, the term sort's two pairs of 12 bytes and
+    // cos_doc_order's two of 8 -- and 28 to spare for the sorts' scratch)
+    c.work.ensure(K1 * 156 + n_pc_max * 12 + ((size_t)n_stop_cps + 3 * (size_t)n_stop) * 4 + ((size_t)4 << 20), "the cosine index");
     Arena a2 = c.work.arena();
     ctx.arena = &a2;
     u32 *kstart = a2.alloc<u32>(K1), *klen = a2.alloc<u32>(K1), *kdoc = a2.alloc<u32>(K1), *npc = a2.alloc<u32>(K1),
         *pc_base = a2.alloc<u32>(K1);
-    HIP_CHECK(hipMemsetAsync(npc + n_kept, 0, 4, h->stream));
     if (n_tok)
         LAUNCH(ctx, cos_compact_kernel, ceil_div_u32(n_tok, BLOCK), (const u32 *)tstart, (const u32 *)tend, (const u32 *)keep_ex, n_tok,
                (const u32 *)doc_cp_off, D, kstart, klen, kdoc, npc);
-    device_scan<ArrIn, false>(ctx, ArrIn{npc}, n_kept + 1, pc_base);
-    u32 n_pieces = 0;
-    HIP_CHECK(hipMemcpyAsync(&n_pieces, pc_base + n_kept, 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
+    const u32 n_pieces = device_scan_count(ctx, ArrIn{npc}, n_kept, pc_base);
     u32 *piece_tok = a2.alloc<u32>((size_t)n_pieces + 1);
     u64 *piece_h = a2.alloc<u64>((size_t)n_pieces + 1);
     if (n_kept) LAUNCH(ctx, cos_piece_map_kernel, ceil_div_u32(n_kept, BLOCK), (const u32 *)pc_base, n_kept, piece_tok);
-    SortBufs<u64> sb;
-    for (int k = 0; k < 2; k++) { sb.keys[k] = a2.alloc<u64>(K1); sb.vals[k] = a2.alloc<u32>(K1); }
-    u32 *flag = a2.alloc<u32>(K1), *ri = a2.alloc<u32>(K1), *run_start = a2.alloc<u32>(K1), *run_hstart = a2.alloc<u32>(K1),
-        *run_hlen = a2.alloc<u32>(K1), *run_of_tok = a2.alloc<u32>(K1), *head_of = a2.alloc<u32>(K1), *bad = a2.alloc<u32>(1);
+    SortBufs<u64> sb = sort_bufs_alloc<u64>(a2, K1);
+    u32 *ri = a2.alloc<u32>(K1), *run_start = a2.alloc<u32>(K1), *run_hstart = a2.alloc<u32>(K1), *run_hlen = a2.alloc<u32>(K1),
+        *run_of_tok = a2.alloc<u32>(K1), *head_of = a2.alloc<u32>(K1), *bad = a2.alloc<u32>(1);
 
     // ---- term hashes: sort, runs, verification; the next seed while two different words share a hash
     int r = 0;
@@ -717,9 +671,8 @@ static void cos_build(east_hip_index *h, HostTexts in, const UnicodeTablesHost &
         LAUNCH(ctx, cos_token_hash_kernel, ceil_div_u32(n_kept, BLOCK), (const u64 *)piece_h, (const u32 *)pc_base, (const u32 *)klen,
                n_kept, B, cos_host_powmod(B, COS_PIECE), mask, sb.keys[0], sb.vals[0]);
         r = radix_sort_pairs<u64>(ctx, sb, n_kept, bits);
-        LAUNCH(ctx, cos_run_flags_kernel, ceil_div_u32(n_kept, BLOCK), (const u64 *)sb.keys[r], n_kept, flag);
-        device_scan<ArrIn, true>(ctx, ArrIn{flag}, n_kept, ri);
-        LAUNCH(ctx, cos_run_heads_kernel, ceil_div_u32(n_kept, BLOCK), (const u32 *)flag, (const u32 *)ri, (const u64 *)sb.keys[r],
+        device_scan<RunHeadIn<u64>, true>(ctx, RunHeadIn<u64>{sb.keys[r], 0}, n_kept, ri);
+        LAUNCH(ctx, cos_run_heads_kernel, ceil_div_u32(n_kept, BLOCK), (const u32 *)ri, (const u64 *)sb.keys[r],
                (const u32 *)sb.vals[r], (const u32 *)kstart, (const u32 *)klen, n_kept, run_start, c.run_key, run_hstart, run_hlen);
         LAUNCH(ctx, cos_token_runs_kernel, ceil_div_u32(n_kept, BLOCK), (const u32 *)sb.vals[r], (const u32 *)ri,
                (const u32 *)run_start, n_kept, run_of_tok, head_of);
@@ -727,9 +680,7 @@ static void cos_build(east_hip_index *h, HostTexts in, const UnicodeTablesHost &
         LAUNCH(ctx, cos_verify_kernel, ceil_div_u32(n_pieces, BLOCK), (const u32 *)cpu, (const u32 *)kstart, (const u32 *)klen,
                (const u32 *)pc_base, (const u32 *)piece_tok, (const u32 *)head_of, n_pieces, bad);
         u32 rb[2] = {0, 0};
-        HIP_CHECK(hipMemcpyAsync(&rb[0], bad, 4, hipMemcpyDeviceToHost, h->stream));
-        HIP_CHECK(hipMemcpyAsync(&rb[1], ri + n_kept - 1, 4, hipMemcpyDeviceToHost, h->stream));
-        HIP_CHECK(hipStreamSynchronize(h->stream));
+        device_read_words(ctx, {{&rb[0], bad}, {&rb[1], ri + n_kept - 1}});
         if (!rb[0]) {
             n_runs = rb[1];
             c.B = B;
@@ -742,9 +693,7 @@ static void cos_build(east_hip_index *h, HostTexts in, const UnicodeTablesHost &
     // ---- stopwords: their runs lose their postings
     u32 *is_stop = a2.alloc<u32>(K1);
     HIP_CHECK(hipMemsetAsync(is_stop, 0, K1 * 4, h->stream));
-    std::vector<u32> stop_off32((size_t)n_stop + 1, 0);
     if (n_stop && n_runs) {
-        for (int32_t w = 0; w <= n_stop; w++) stop_off32[w] = (u32)stop_offsets[w];
         u32 *d_sw = a2.alloc<u32>((size_t)n_stop_cps + 1), *d_sw_off = a2.alloc<u32>((size_t)n_stop + 1);
         int32_t *found = a2.alloc<int32_t>((size_t)n_stop);
         if (n_stop_cps) HIP_CHECK(hipMemcpyAsync(d_sw, stop_cps, (size_t)n_stop_cps * 4, hipMemcpyHostToDevice, h->stream));
@@ -761,26 +710,21 @@ static void cos_build(east_hip_index *h, HostTexts in, const UnicodeTablesHost &
     if (n_runs)
         LAUNCH(ctx, cos_term_heads_kernel, ceil_div_u32(n_runs, BLOCK), (const u32 *)run_start, svals, (const u32 *)is_stop, n_runs,
                head_flag);
-    device_scan<ArrIn, false>(ctx, ArrIn{head_flag}, n_kept + 1, th_ex);
+    // (head_flag is an array: the runs scatter to it)
+    const u32 V = device_scan_count(ctx, ArrIn{head_flag}, n_kept, th_ex);
     if (n_runs)
         LAUNCH(ctx, cos_run_terms_kernel, ceil_div_u32(n_runs, BLOCK), (const u32 *)run_start, svals, (const u32 *)is_stop,
                (const u32 *)th_ex, n_runs, c.run_term, term_run);
-    u32 V = 0;
-    HIP_CHECK(hipMemcpyAsync(&V, th_ex + n_kept, 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
 
     // ---- postings (term, document, count) in (term, document) order
-    u32 *pflag = a2.alloc<u32>(K1), *px = a2.alloc<u32>(K1), *tn = a2.alloc<u32>(K1), *post_beg = a2.alloc<u32>(K1),
-        *post_end = a2.alloc<u32>(K1);
-    LAUNCH(ctx, cos_posting_flags_kernel, ceil_div_u32((u64)n_kept + 1, BLOCK), svals, (const u32 *)ri, (const u32 *)run_start,
-           (const u32 *)c.run_term, (const u32 *)kdoc, n_kept, pflag);
-    device_scan<ArrIn, false>(ctx, ArrIn{pflag}, n_kept + 1, px);
-    LAUNCH(ctx, cos_term_counts_kernel, ceil_div_u32((u64)V + 1, BLOCK), (const u32 *)term_run, (const u32 *)run_start, (const u32 *)px,
-           V, tn);
-    device_scan<ArrIn, false>(ctx, ArrIn{tn}, V + 1, T.unit_off);
-    u32 P = 0;
-    HIP_CHECK(hipMemcpyAsync(&P, T.unit_off + V, 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
+    u32 *pflag = a2.alloc<u32>(K1), *px = a2.alloc<u32>(K1), *post_beg = a2.alloc<u32>(K1), *post_end = a2.alloc<u32>(K1);
+    if (n_kept)
+        LAUNCH(ctx, cos_posting_flags_kernel, ceil_div_u32(n_kept, BLOCK), svals, (const u32 *)ri, (const u32 *)run_start,
+               (const u32 *)c.run_term, (const u32 *)kdoc, n_kept, pflag);
+    device_scan_with_total(ctx, ArrIn{pflag}, n_kept, px);
+    u32 *tn = a2.alloc<u32>(K1);
+    if (V) LAUNCH(ctx, cos_term_counts_kernel, ceil_div_u32(V, BLOCK), (const u32 *)term_run, (const u32 *)run_start, (const u32 *)px, V, tn);
+    const u32 P = device_scan_count(ctx, ArrIn{tn}, V, T.unit_off);
     if (n_kept)
         LAUNCH(ctx, cos_postings_kernel, ceil_div_u32(n_kept, BLOCK), svals, (const u32 *)ri, (const u32 *)run_start,
                (const u32 *)c.run_term, (const u32 *)kdoc, (const u32 *)pflag, (const u32 *)px, (const u32 *)T.unit_off, n_kept,
@@ -788,17 +732,15 @@ static void cos_build(east_hip_index *h, HostTexts in, const UnicodeTablesHost &
     if (P) LAUNCH(ctx, cos_counts_kernel, ceil_div_u32(P, BLOCK), (const u32 *)post_beg, (const u32 *)post_end, P, T.post_cnt);
 
     // ---- n_d: the kept tokens of every document that are not stopwords
-    u32 *ns = a2.alloc<u32>(K1), *nsx = a2.alloc<u32>(K1);
-    LAUNCH(ctx, cos_nonstop_kernel, ceil_div_u32((u64)n_kept + 1, BLOCK), (const u32 *)run_of_tok, (const u32 *)c.run_term, n_kept, ns);
-    device_scan<ArrIn, false>(ctx, ArrIn{ns}, n_kept + 1, nsx);
+    u32 *nsx = a2.alloc<u32>(K1);
+    u32 *ns = a2.alloc<u32>(K1);
+    if (n_kept) LAUNCH(ctx, cos_nonstop_kernel, ceil_div_u32(n_kept, BLOCK), (const u32 *)run_of_tok, (const u32 *)c.run_term, n_kept, ns);
+    device_scan_with_total(ctx, ArrIn{ns}, n_kept, nsx);
     LAUNCH(ctx, cos_doc_lengths_kernel, ceil_div_u32(D, BLOCK), (const u32 *)kdoc, n_kept, (const u32 *)nsx, D, c.n_d);
 
-    // ---- the terms' text
-    LAUNCH(ctx, cos_term_len_kernel, ceil_div_u32((u64)V + 1, BLOCK), (const u32 *)term_run, (const u32 *)run_hlen, V, c.term_len);
-    device_scan<ArrIn, false>(ctx, ArrIn{c.term_len}, V + 1, c.term_off);
-    u32 n_tcp = 0;
-    HIP_CHECK(hipMemcpyAsync(&n_tcp, c.term_off + V, 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
+    // ---- the terms' text (term_len is part of the index: an array)
+    if (V) LAUNCH(ctx, cos_term_len_kernel, ceil_div_u32(V, BLOCK), (const u32 *)term_run, (const u32 *)run_hlen, V, c.term_len);
+    const u32 n_tcp = device_scan_count(ctx, ArrIn{c.term_len}, V, c.term_off);
     c.term_text.ensure(((size_t)n_tcp + 1) * 4, "the cosine index");
     c.tcp = (u32 *)c.term_text.p;
     if (V)
@@ -808,14 +750,13 @@ static void cos_build(east_hip_index *h, HostTexts in, const UnicodeTablesHost &
     T.n_units = V;
     T.P = P;
     cos_doc_order(ctx, T, D);
-    HIP_CHECK(hipEventRecord(h->ev1, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    HIP_CHECK(hipEventElapsedTime(&c.build_ms, h->ev0, h->ev1));
+    timer.finish();
+    c.build_ms = c.ms;
     c.n_docs = D;
     c.n_kept = n_kept;
     c.n_runs = n_runs;
     c.V = V;
-    c.built = true;
+    c.valid = true;
 }
 
 // the stems: the postings re-keyed by class (term_class[t], classes numbered by their smallest term id) and merged
@@ -830,7 +771,6 @@ static void cos_set_classes(east_hip_index *h, const int32_t *term_class, int32_
     if (n_classes < 0 || (u32)n_classes > c.V || !term_class) east_throw(EAST_HIP_ERR_INVALID, "bad class map");
     for (u32 t = 0; t < c.V; t++)
         if (term_class[t] < 0 || term_class[t] >= n_classes) east_throw(EAST_HIP_ERR_INVALID, "a term's class is out of range");
-    use_device(h);
     const u32 P = c.terms.P, D = c.n_docs, C = (u32)n_classes;
     CosUnits &U = c.cls;
     c.use_classes = false;
@@ -845,27 +785,25 @@ static void cos_set_classes(east_hip_index *h, const int32_t *term_class, int32_
     U.inv_perm = ac.alloc<u32>(K1);
     U.doc_off = ac.alloc<u32>((size_t)D + 1);
     Stats stats;
-    c.work.ensure(align256(((size_t)c.V + 1) * 4) + ((size_t)P + 2) * 64 + ((size_t)4 << 20), "the cosine index");
+    // (a posting: the sort's two pairs of 12 bytes, fx, cos_doc_order's two pairs of 8, and 16 to spare)
+    c.work.ensure(align256(((size_t)c.V + 1) * 4) + ((size_t)P + 2) * 60 + ((size_t)4 << 20), "the cosine index");
     Arena a = c.work.arena();
     Ctx ctx = handle_ctx(h, &a, &stats);
     u32 *d_tc = a.alloc<u32>((size_t)c.V + 1);
-    SortBufs<u64> sb;
-    for (int k = 0; k < 2; k++) { sb.keys[k] = a.alloc<u64>((size_t)P + 1); sb.vals[k] = a.alloc<u32>((size_t)P + 1); }
-    u32 *fl = a.alloc<u32>((size_t)P + 1), *fx = a.alloc<u32>((size_t)P + 1);
+    SortBufs<u64> sb = sort_bufs_alloc<u64>(a, (size_t)P + 1);
+    u32 *fx = a.alloc<u32>((size_t)P + 1);
     u32 Pc = 0;
     if (P) {
         HIP_CHECK(hipMemcpyAsync(d_tc, term_class, (size_t)c.V * 4, hipMemcpyHostToDevice, h->stream));
         LAUNCH(ctx, cos_class_keys_kernel, ceil_div_u32(P, BLOCK), (const u32 *)c.terms.post_unit, (const u32 *)c.terms.post_doc,
                (const u32 *)d_tc, P, sb.keys[0], sb.vals[0]);
         const int r = radix_sort_pairs<u64>(ctx, sb, P, 32 + std::max(1, bit_width_u32(C - 1)));
-        LAUNCH(ctx, cos_key_flags_kernel, ceil_div_u32((u64)P + 1, BLOCK), (const u64 *)sb.keys[r], P, fl);
-        device_scan<ArrIn, false>(ctx, ArrIn{fl}, P + 1, fx);
+        Pc = device_scan_count(ctx, RunHeadIn<u64>{sb.keys[r], 0}, P, fx);
         LAUNCH(ctx, cos_class_merge_kernel, ceil_div_u32(P, BLOCK), (const u64 *)sb.keys[r], (const u32 *)sb.vals[r],
                (const u32 *)c.terms.post_cnt, (const u32 *)fx, P, U.post_doc, U.post_unit, U.post_cnt);
-        HIP_CHECK(hipMemcpyAsync(&Pc, fx + P, 4, hipMemcpyDeviceToHost, h->stream));
-        HIP_CHECK(hipStreamSynchronize(h->stream));
     }
-    LAUNCH(ctx, cos_unit_offsets_kernel, ceil_div_u32((u64)Pc + 1, BLOCK), (const u32 *)U.post_unit, Pc, C, U.unit_off);
+    // (the postings of class u are [unit_off[u], unit_off[u + 1]): post_unit ascends)
+    LAUNCH(ctx, ascending_offsets_kernel, ceil_div_u32((u64)C + 1, BLOCK), (const u32 *)U.post_unit, Pc, C, U.unit_off);
     U.n_units = C;
     U.P = Pc;
     cos_doc_order(ctx, U, D);
@@ -879,14 +817,8 @@ static void cos_lookup(east_hip_index *h, const u32 *cps, const i64 *offsets, in
     CosState &c = cos_built(h);
     if (n_words < 0 || (n_words > 0 && (!offsets || !out))) east_throw(EAST_HIP_ERR_INVALID, "bad look-up arguments");
     if (n_words == 0) return;
-    const i64 n_cps = offsets[n_words];
-    if (offsets[0] != 0 || n_cps >= (i64)0x7FFFFFF0 || (n_cps > 0 && !cps)) east_throw(EAST_HIP_ERR_INVALID, "bad word offsets");
-    std::vector<u32> off32((size_t)n_words + 1);
-    for (int32_t w = 0; w <= n_words; w++) {
-        if (w < n_words && offsets[w + 1] < offsets[w]) east_throw(EAST_HIP_ERR_INVALID, "word offsets must not decrease");
-        off32[w] = (u32)offsets[w];
-    }
-    use_device(h);
+    const std::vector<u32> off32 = ragged_offsets_u32(offsets, n_words, cps, "bad word offsets", "word offsets must not decrease");
+    const u32 n_cps = off32[n_words];
     Stats stats;
     c.work.ensure(align256(((size_t)n_cps + 1) * 4) + align256(((size_t)n_words + 1) * 4) * 2 + 4096, "the cosine index");
     Arena a = c.work.arena();
@@ -934,18 +866,13 @@ static void cos_score(east_hip_index *h, const int32_t *q_ids, const i64 *q_offs
     CosState &c = cos_built(h);
     if (K < 0 || weighting < 0 || weighting > 1 || (K > 0 && !q_offsets)) east_throw(EAST_HIP_ERR_INVALID, "bad score arguments");
     if (K == 0) return;
-    if (q_offsets[0] != 0 || q_offsets[K] != q_len || q_len < 0 || q_len >= (i64)0x7FFFFFF0 || (q_len > 0 && !q_ids))
-        east_throw(EAST_HIP_ERR_INVALID, "q_offsets must start at 0 and end at q_len");
+    const char *bad_offsets = "q_offsets must start at 0 and end at q_len";
+    if (q_offsets[K] != q_len || q_len < 0) east_throw(EAST_HIP_ERR_INVALID, bad_offsets);
+    const std::vector<u32> off32 = ragged_offsets_u32(q_offsets, K, q_ids, bad_offsets, "q_offsets must not decrease");
     CosUnits &U = c.use_classes ? c.cls : c.terms;
-    std::vector<u32> off32((size_t)K + 1);
-    for (int32_t k = 0; k <= K; k++) {
-        if (k < K && q_offsets[k + 1] < q_offsets[k]) east_throw(EAST_HIP_ERR_INVALID, "q_offsets must not decrease");
-        off32[k] = (u32)q_offsets[k];
-    }
     for (i64 i = 0; i < q_len; i++)
         if (q_ids[i] < -1 || (q_ids[i] >= 0 && (u32)q_ids[i] >= U.n_units))
             east_throw(EAST_HIP_ERR_INVALID, "a query id is neither -1 nor a unit of the vector space");
-    use_device(h);
     c.table_valid = false;
     const u32 D = c.n_docs, total = (u32)q_len;
     const size_t b_ids = align256(((size_t)total + 1) * 4), b_off = align256(((size_t)K + 1) * 4),
@@ -959,7 +886,7 @@ static void cos_score(east_hip_index *h, const int32_t *q_ids, const i64 *q_offs
     Stats stats;
     Arena a = c.text.arena();             // (the build's first scratch: 6 bytes and more per byte of text, P <= bytes / 4)
     Ctx ctx = handle_ctx(h, &a, &stats);
-    HIP_CHECK(hipEventRecord(h->ev0, h->stream));
+    ConsumerTimer timer(h, c);
     cos_make_weights(ctx, c, U, weighting, w, norm);
     if (total) HIP_CHECK(hipMemcpyAsync(d_ids, q_ids, (size_t)total * 4, hipMemcpyHostToDevice, h->stream));
     HIP_CHECK(hipMemcpyAsync(d_off, off32.data(), off32.size() * 4, hipMemcpyHostToDevice, h->stream));
@@ -968,14 +895,14 @@ static void cos_score(east_hip_index *h, const int32_t *q_ids, const i64 *q_offs
                U.n_units, d_qw);
     LAUNCH(ctx, cos_score_kernel, std::min<u32>((u32)K, 1u << 16), (const int32_t *)d_ids, (const u32 *)d_off, (const double *)d_qw,
            (u32)K, (const u32 *)U.unit_off, (const u32 *)U.post_doc, (const double *)w, (const double *)norm, D, d_out);
-    HIP_CHECK(hipEventRecord(h->ev1, h->stream));
+    timer.stop();                           // (the time is the launches': the copy of the table is not in it)
     if (out) HIP_CHECK(hipMemcpyAsync(out, d_out, table, hipMemcpyDeviceToHost, h->stream));     // (null: the table stays on the device, graph.h)
-    HIP_CHECK(hipStreamSynchronize(h->stream));
+    timer.finish();
+    c.score_ms = c.ms;
     U.w_valid[weighting] = true;
     c.table = d_out;
     c.table_K = (u32)K;
     c.table_valid = true;
-    HIP_CHECK(hipEventElapsedTime(&c.score_ms, h->ev0, h->ev1));
 }
 
 extern "C" {
@@ -1004,7 +931,7 @@ int east_hip_cosine_info(east_hip_handle_t h, int64_t *out, int32_t cap)
 {
     if (!h || !out || cap < 0) return EAST_HIP_ERR_INVALID;
     const CosState *c = consumer_peek<CosState>(h);
-    const bool b = c && c->built;
+    const bool b = c && c->valid;
     const int64_t v[10] = {b ? 1 : 0,
                            b ? (int64_t)c->n_docs : 0,
                            b ? (int64_t)c->n_kept : 0,
@@ -1023,7 +950,6 @@ int east_hip_cosine_get_terms(east_hip_handle_t h, int64_t *offsets, uint32_t *c
 {
     return guarded([&] {
         CosState &c = cos_built(h);
-        use_device(h);
         std::vector<u32> off((size_t)c.V + 1);
         HIP_CHECK(hipMemcpyAsync(off.data(), c.term_off, off.size() * 4, hipMemcpyDeviceToHost, h->stream));
         HIP_CHECK(hipStreamSynchronize(h->stream));

@@ -689,6 +689,12 @@ template <class K> struct SortBufs {
     K *keys[2];
     u32 *vals[2];
 };
+template <class K> static SortBufs<K> sort_bufs_alloc(Arena &a, size_t n)       // both pairs of n out of the arena
+{
+    SortBufs<K> b;
+    for (int k = 0; k < 2; k++) { b.keys[k] = a.alloc<K>(n); b.vals[k] = a.alloc<u32>(n); }
+    return b;
+}
 
 struct NoGen {
     static constexpr int MODE = 0;

@@ -17,6 +17,25 @@ struct ArrIn {             // plain array
     __device__ __forceinline__ u32 operator()(u32 i) const { return p[i]; }
 };
 
+template <class K> struct RunHeadIn {      // 1 where sorted key i differs from the one in front of it above `shift`, and at i == 0
+    const K *k;
+    int shift;
+    __device__ __forceinline__ u32 operator()(u32 i) const { return i == 0u || (k[i] >> shift) != (k[i - 1u] >> shift) ? 1u : 0u; }
+};
+
+// `in` over [0, n), n > 0, and one 0 behind it: the exclusive scan over n + 1 elements leaves the sum of `in` in out[n]
+// (device_scan_with_total).  The kernels below ask for index n at most; `in` itself is never asked for it -- index n reads
+// element n - 1 and counts as 0: the read stays unconditional, as the kernels' own reads behind the end are.
+template <class In> struct ZeroBehind {
+    In in;
+    u32 n;
+    __device__ __forceinline__ u32 operator()(u32 i) const
+    {
+        const u32 v = in(i < n ? i : n - 1u);
+        return i < n ? v : 0u;
+    }
+};
+
 template <class In>
 __global__ __launch_bounds__(BLOCK) void scan_reduce_kernel(In in, u32 n, u32 *block_sums)
 {
@@ -61,6 +80,9 @@ __device__ __forceinline__ void scan_load4(const ArrIn &in, u32 i, u32 n, u32 x[
     x[2] = i + 2 < n ? v.z : 0u;
     x[3] = i + 3 < n ? v.w : 0u;
 }
+
+// (an array and a 0 behind it: the array's 16-byte groups, zeros from its end on)
+__device__ __forceinline__ void scan_load4(const ZeroBehind<ArrIn> &in, u32 i, u32, u32 x[4]) { scan_load4(in.in, i, in.n, x); }
 
 // out[i] = (exclusive or inclusive) prefix of in over [0, i], plus the scanned
 // sum of all earlier tiles.  block_offsets == nullptr means a single tile.
@@ -149,6 +171,51 @@ static void device_scan(Ctx &ctx, In in, u32 n, u32 *out)
     }
     LAUNCH(ctx, (scan_apply_kernel<In, INCLUSIVE>), nb, in, n, (const u32 *)sums, out, raw);
     ctx.arena->release(mark);
+}
+
+// Words of the device read back behind everything queued on the context's stream: {host, device} pairs, one wait for all.
+static void device_read_words(Ctx &ctx, std::initializer_list<std::pair<u32 *, const u32 *>> words)
+{
+    for (const auto &w : words) HIP_CHECK(hipMemcpyAsync(w.first, w.second, 4, hipMemcpyDeviceToHost, ctx.stream));
+    HIP_CHECK(hipStreamSynchronize(ctx.stream));
+}
+
+// out[0 .. n] = the exclusive scan of `in` over [0, n) and a 0 behind it: n + 1 words, out[n] the sum
+template <class In>
+static void device_scan_with_total(Ctx &ctx, In in, u32 n, u32 *out)
+{
+    if (n) device_scan<ZeroBehind<In>, false>(ctx, ZeroBehind<In>{in, n}, n + 1u, out);
+    else HIP_CHECK(hipMemsetAsync(out, 0, 4, ctx.stream));        // (nothing to ask `in` for: the sum of nothing)
+}
+
+// The count behind a compaction: device_scan_with_total, and the total comes back.  One wait.  (An inclusive scan's count
+// is inc[n - 1]: device_read_words.)
+template <class In>
+static u32 device_scan_count(Ctx &ctx, In in, u32 n, u32 *out)
+{
+    u32 count = 0;
+    device_scan_with_total(ctx, in, n, out);
+    device_read_words(ctx, {{&count, out + n}});
+    return count;
+}
+
+// ---- where every value starts in an ascending array --------------------------------------------------------------------
+// the first index whose element is >= v (n where there is none)
+__device__ __forceinline__ u32 ascending_lower_bound(const u32 *__restrict__ sorted, u32 n, u32 v)
+{
+    u32 lo = 0, hi = n;
+    while (lo < hi) {
+        const u32 mid = lo + ((hi - lo) >> 1);
+        if (sorted[mid] < v) lo = mid + 1u; else hi = mid;
+    }
+    return lo;
+}
+
+// off[v] = ascending_lower_bound(v) for v = 0 .. n_values: the elements equal to v are [off[v], off[v + 1])
+__global__ __launch_bounds__(BLOCK) void ascending_offsets_kernel(const u32 *__restrict__ sorted, u32 n, u32 n_values, u32 *__restrict__ off)
+{
+    const u32 v = blockIdx.x * BLOCK + threadIdx.x;
+    if (v <= n_values) off[v] = ascending_lower_bound(sorted, n, v);
 }
 
 // ---- two sums at once, over a length the DEVICE knows ------------------------------------------------------------------

@@ -60,13 +60,7 @@ __global__ __launch_bounds__(BLOCK) void syn_emit_kernel(const int32_t *__restri
     vals[2u * i + 1u] = 2u * i + 1u;
 }
 
-struct SynHeadIn {              // 1 where sorted key i differs from the one in front of it above `shift`
-    const u64 *k;
-    int shift;
-    __device__ __forceinline__ u32 operator()(u32 i) const { return i == 0u || (k[i] >> shift) != (k[i - 1u] >> shift) ? 1u : 0u; }
-};
-
-// d_inc / g_inc: inclusive sums of the heads of distinct triples / of groups (w1, r).  The head of run d writes the run's
+// d_inc / g_inc: inclusive sums of the heads (RunHeadIn, scan.h) of distinct triples / of groups (w1, r).  The head of run d writes the run's
 // key, where it starts and its group; the head of a group writes the group's key (w1 << 12 | r).  d_pos[D] = M.
 __global__ __launch_bounds__(BLOCK) void syn_runs_kernel(const u64 *__restrict__ keys, const u32 *__restrict__ d_inc,
                                                          const u32 *__restrict__ g_inc, u32 M, u64 *__restrict__ d_key,
@@ -126,7 +120,7 @@ __global__ __launch_bounds__(BLOCK) void syn_marginals_kernel(const u64 *__restr
 
 // ---- features ----------------------------------------------------------------------------------------------------------
 // synonyms.py:126-132 for every distinct triple: q with the reference's three operations in its order, kept iff q > 1.0
-// (what `I > 0` decides, without the logarithm), I = log(q).  keep[D] = 0 for the scan.
+// (what `I > 0` decides, without the logarithm), I = log(q).
 __global__ __launch_bounds__(BLOCK) void syn_features_kernel(const u64 *__restrict__ d_key, const u32 *__restrict__ d_pos,
                                                              const u32 *__restrict__ d_gid, const u64 *__restrict__ g_key, u32 G,
                                                              const unsigned long long *__restrict__ F_w1r,
@@ -135,8 +129,7 @@ __global__ __launch_bounds__(BLOCK) void syn_features_kernel(const u64 *__restri
                                                              double *__restrict__ value)
 {
     const u32 d = blockIdx.x * BLOCK + threadIdx.x;
-    if (d > D) return;
-    if (d == D) { keep[d] = 0u; return; }
+    if (d >= D) return;
     const u64 k = d_key[d];
     const u32 r = (u32)(k >> SY_WORD_BITS) & (u32)SY_REL_MASK, w2 = (u32)(k & SY_WORD_MASK);
     const u64 inverse_group = ((u64)w2 << SY_REL_BITS) | (u64)(u32)inv[r];       // F_rw2(r, w2) = F_w1r(w2, r')
@@ -165,19 +158,6 @@ __global__ __launch_bounds__(BLOCK) void syn_compact_kernel(const u64 *__restric
     feat[j] = k & SY_FEAT_MASK;
     val[j] = value[d];
     row_of[j] = (u32)(k >> SY_FEAT_BITS);
-}
-
-// row_off[w] = the first kept entry of a word >= w (row_of ascends), w = 0 .. W
-__global__ __launch_bounds__(BLOCK) void syn_row_off_kernel(const u32 *__restrict__ row_of, u32 F, u32 W, u32 *__restrict__ row_off)
-{
-    const u32 w = blockIdx.x * BLOCK + threadIdx.x;
-    if (w > W) return;
-    u32 lo = 0, hi = F;
-    while (lo < hi) {
-        const u32 mid = lo + ((hi - lo) >> 1);
-        if (row_of[mid] < w) lo = mid + 1u; else hi = mid;
-    }
-    row_off[w] = lo;
 }
 
 // the divisor's half of a word (synonyms.py:147-148), added in ascending column order
@@ -402,37 +382,30 @@ static void syn_build(east_hip_index *h, const int32_t *w1, const int32_t *rel, 
     HIP_CHECK(hipMemcpyAsync(d_rel, rel, (size_t)N * 4, hipMemcpyHostToDevice, h->stream));
     HIP_CHECK(hipMemcpyAsync(d_w2, w2, (size_t)N * 4, hipMemcpyHostToDevice, h->stream));
     HIP_CHECK(hipMemcpyAsync(d_inv, inv, (size_t)R * 4, hipMemcpyHostToDevice, h->stream));
-    SortBufs<u64> sb;
-    for (int k = 0; k < 2; k++) { sb.keys[k] = a.alloc<u64>(M); sb.vals[k] = a.alloc<u32>(M); }
+    SortBufs<u64> sb = sort_bufs_alloc<u64>(a, M);
     LAUNCH(ctx, syn_emit_kernel, ceil_div_u32(N, BLOCK), (const int32_t *)d_w1, (const int32_t *)d_rel, (const int32_t *)d_w2,
            (const int32_t *)d_inv, N, sb.keys[0], sb.vals[0]);
     const int sorted = radix_sort_pairs<u64>(ctx, sb, M, SY_FEAT_BITS + std::max(1, bit_width_u32(W - 1u)));
     const u64 *keys = sb.keys[sorted];
     u32 *d_inc = a.alloc<u32>(M), *g_inc = a.alloc<u32>(M);
-    device_scan<SynHeadIn, true>(ctx, SynHeadIn{keys, 0}, M, d_inc);
-    device_scan<SynHeadIn, true>(ctx, SynHeadIn{keys, SY_WORD_BITS}, M, g_inc);
-    u32 counts[2] = {0, 0};
-    HIP_CHECK(hipMemcpyAsync(&counts[0], d_inc + (M - 1u), 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(hipMemcpyAsync(&counts[1], g_inc + (M - 1u), 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    const u32 D = counts[0], G = counts[1];
+    device_scan<RunHeadIn<u64>, true>(ctx, RunHeadIn<u64>{keys, 0}, M, d_inc);
+    device_scan<RunHeadIn<u64>, true>(ctx, RunHeadIn<u64>{keys, SY_WORD_BITS}, M, g_inc);
+    u32 D = 0, G = 0;
+    device_read_words(ctx, {{&D, d_inc + (M - 1u)}, {&G, g_inc + (M - 1u)}});
     u64 *d_key = a.alloc<u64>(D), *g_key = a.alloc<u64>(G);
     u32 *d_pos = a.alloc<u32>((size_t)D + 1), *d_gid = a.alloc<u32>(D);
     unsigned long long *F_w1r = a.alloc<unsigned long long>(G), *F_r = a.alloc<unsigned long long>(R);
-    u32 *keep = a.alloc<u32>((size_t)D + 1), *keep_ex = a.alloc<u32>((size_t)D + 1);
+    u32 *keep = a.alloc<u32>(D), *keep_ex = a.alloc<u32>((size_t)D + 1);
     double *value = a.alloc<double>(D);
     LAUNCH(ctx, syn_runs_kernel, ceil_div_u32(M, BLOCK), keys, (const u32 *)d_inc, (const u32 *)g_inc, M, d_key, d_pos, d_gid, g_key);
     HIP_CHECK(hipMemsetAsync(F_w1r, 0, (size_t)G * 8, h->stream));
     HIP_CHECK(hipMemsetAsync(F_r, 0, (size_t)R * 8, h->stream));
     LAUNCH(ctx, syn_marginals_kernel, std::min<u32>(ceil_div_u32(D, BLOCK), 2048u), (const u64 *)d_key, (const u32 *)d_pos,
            (const u32 *)d_gid, D, R, F_w1r, F_r);
-    LAUNCH(ctx, syn_features_kernel, ceil_div_u32((u64)D + 1, BLOCK), (const u64 *)d_key, (const u32 *)d_pos, (const u32 *)d_gid,
+    LAUNCH(ctx, syn_features_kernel, ceil_div_u32(D, BLOCK), (const u64 *)d_key, (const u32 *)d_pos, (const u32 *)d_gid,
            (const u64 *)g_key, G, (const unsigned long long *)F_w1r, (const unsigned long long *)F_r, (const int32_t *)d_inv, D, keep,
            value);
-    device_scan<ArrIn, false>(ctx, ArrIn{keep}, D + 1u, keep_ex);
-    u32 F = 0;
-    HIP_CHECK(hipMemcpyAsync(&F, keep_ex + D, 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
+    const u32 F = device_scan_count(ctx, ArrIn{keep}, D, keep_ex);
     const size_t al = 256;
     g.csr.ensure(((size_t)W + 1) * 4 + (size_t)F * 16 + (size_t)W * 8 + 8 * al, "the synonyms' feature rows", h->stream);
     Arena c = g.csr.arena();
@@ -443,7 +416,8 @@ static void syn_build(east_hip_index *h, const int32_t *w1, const int32_t *rel, 
     u32 *row_of = a.alloc<u32>(std::max<u32>(F, 1u));
     LAUNCH(ctx, syn_compact_kernel, ceil_div_u32(D, BLOCK), (const u64 *)d_key, (const u32 *)keep_ex, (const double *)value, D, g.feat,
            g.val, row_of);
-    LAUNCH(ctx, syn_row_off_kernel, ceil_div_u32((u64)W + 1, BLOCK), (const u32 *)row_of, F, W, g.row_off);
+    // (row_of ascends: the kept entries of word w are [row_off[w], row_off[w + 1]))
+    LAUNCH(ctx, ascending_offsets_kernel, ceil_div_u32((u64)W + 1, BLOCK), (const u32 *)row_of, F, W, g.row_off);
     LAUNCH(ctx, syn_row_sum_kernel, ceil_div_u32(W, BLOCK), (const u32 *)g.row_off, (const double *)g.val, W, g.row_sum);
     std::vector<u32> off((size_t)W + 1);
     HIP_CHECK(hipMemcpyAsync(off.data(), g.row_off, ((size_t)W + 1) * 4, hipMemcpyDeviceToHost, h->stream));

@@ -473,6 +473,26 @@ def slice_documents():
 
 SLICE_QUERIES = ["W00000", "W00001 W00002", "W00064 W00063 W00000 W00000", "W05002 NOPE", "W00003 W00128 W04096"]
 
+SCAN_TILE = 4096                                 # elements a workgroup of the device's prefix sums takes (csrc/scan.h)
+SCAN_TILE_SIZES = (SCAN_TILE - 1, SCAN_TILE, SCAN_TILE + 1, 2 * SCAN_TILE, 2 * SCAN_TILE + 1)
+SCAN_TILE_STOP = ("the",)
+
+
+def scan_tile_collections(n):
+    """{name: (texts, stopwords)} whose counts lie at n: one document of n distinct words of six letters (tokens = kept
+    tokens = words = terms = postings = n); the same with the stopword and a token of two letters in its middle (tokens
+    n + 2, kept tokens and words n + 1, terms and postings n); the same words dealt over three documents."""
+    words = ["w%05d" % j for j in range(n)]
+    return {"one document": ([" ".join(words)], ()),
+            "a stopword and a short token": ([" ".join(words[: n // 2] + ["the", "ab"] + words[n // 2:])], SCAN_TILE_STOP),
+            "three documents": ([" ".join(words[i::3]) for i in range(3)], ())}
+
+
+def scan_tile_queries(n):
+    """The first and the last word, the two on either side of a tile, a stopword and a short token, a word that is absent."""
+    return ["W00000", "W%05d" % (n - 1), "W%05d W%05d" % (SCAN_TILE - 1, min(SCAN_TILE, n - 1)), "THE AB W00001 W00001",
+            "NOPE W00002 W%05d" % (n // 2)]
+
 
 def _zipf_words(rng, size):
     """A vocabulary in Zipf rank order: random bases (east.synthetic.zipf_vocabulary), every fifth rank an -S or -ING

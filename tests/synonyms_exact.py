@@ -433,6 +433,7 @@ def word_count_case(W, n_triples=200):
 
 
 DISTINCT_COUNTS = (255, 256, 257, 511, 512, 513)
+SCAN_TILE_DISTINCT = (4094, 4095, 4096, 4097)   # around the 4096 elements a workgroup of the device's prefix sums takes: 4094, 4096, 4096, 4098 sorted keys
 
 
 def distinct_count_case(D):

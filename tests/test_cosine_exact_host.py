@@ -177,6 +177,19 @@ def test_generators_cover_what_the_gpu_tests_claim():
         assert model.df[model.term_id["EVERY"]] == D and model.df[model.term_id["SECOND"]] == (D + 1) // 2
         assert model.df[model.term_id["ONLY7"]] == 1
 
+    # the counts around the tiles of the prefix sums: the five counts at n, or one apart from each other
+    assert cx.SCAN_TILE_SIZES == (4095, 4096, 4097, 8192, 8193)
+    for n in cx.SCAN_TILE_SIZES:
+        cases = cx.scan_tile_collections(n)
+        for name, (texts, stop) in cases.items():
+            model = cx.build_model(texts, stop, cx.ToyStemmer(), fast=True)
+            counts = (sum(len(cx.all_tokens(t)) for t in texts), model.kept_tokens, model.words, len(model.terms), model.postings)
+            assert counts == ((n + 2, n + 1, n + 1, n, n) if stop else (n, n, n, n, n)), (n, name)
+            assert min(len(t) for t in model.terms) >= 3 and model.cls_postings == model.n_classes == n
+            assert sum(model.n_d) == n and all(q and all(len(i) > 0 for i in model.query_ids([q])) for q in cx.scan_tile_queries(n))
+        assert [len(t) for t, _ in cases.values()] == [1, 1, 3] and [bool(s) for _, s in cases.values()] == [False, True, False]
+        assert [d for d in cx.build_model(*cases["three documents"]).n_d] == [len(range(i, n, 3)) for i in range(3)]
+
     # the Zipf collection: long lists, classes of several members in one document, non-ASCII terms
     texts, queries, top = cx.zipf_collection()
     assert len(texts) == 64 and len(queries) == 2000 and len(top) == 50

@@ -370,3 +370,19 @@ def test_easa_build_between_cosine_builds_on_a_shared_handle(hip):
     assert np.array_equal(idx.score_table(qs, qo), easa)
     assert cos.score_table(ids, offsets, True).tobytes() == table.tobytes()
     idx.close()
+
+
+# ---- k. counts on both sides of a tile of the prefix sums ------------------------------------------------------------------------
+@pytest.mark.parametrize("n", cx.SCAN_TILE_SIZES)
+def test_counts_on_both_sides_of_a_scan_tile(hip, n):
+    """Every count of a build is the last word of a prefix sum over one element more than it has inputs: tokens, kept
+    tokens, words, terms, postings (and, under stems, the classes' postings) at n, n + 1 and n + 2 around one and two
+    tiles of 4096, in one document and dealt over three."""
+    for name, (texts, stop) in cx.scan_tile_collections(n).items():
+        for space, weighting in (("words", "tf-idf"), ("stems", "tf")):
+            m, model, table = _run(texts, cx.scan_tile_queries(n), space, weighting, stop)
+            extra = 1 if stop else 0
+            assert _info(m.index)["kept_tokens"] == _info(m.index)["words"] == n + extra, name
+            assert _info(m.index)["terms"] == _info(m.index)["postings"] == n, name
+            assert (table[:3] > 0).any(axis=1).all() and (table[3:] > 0).any(axis=1).all(), name
+            assert m.index.lookup(["THE", "AB"]).tolist() == [-1, -1]

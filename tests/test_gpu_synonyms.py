@@ -168,6 +168,29 @@ def test_candidate_counts_around_the_tiles(hip, C):
         built.close()
 
 
+@pytest.mark.parametrize("D", synonyms_exact.SCAN_TILE_DISTINCT)
+def test_distinct_triples_around_a_tile_of_the_scan(hip, D):
+    """D distinct triples out of M = 2 N sorted keys (4094, 4096, 4096, 4098), both on both sides of the 4096 elements a
+    workgroup of the prefix sums takes: the numbers of the distinct triples and of their groups are prefix sums over the
+    M keys' run heads, the slots of the kept features one over the D triples.  Ids against the array model: info and the
+    features with ==, I and the row sums to 1e-12."""
+    w1, rel, w2, inverse, W = case = synonyms_exact.distinct_count_case(D)
+    model = synonyms_exact.array_model(*case)
+    assert model.key.size == D and 2 * w1.size == D + D % 2 and abs(2 * w1.size - 4096) <= 2
+    dev = hip.HipSynonyms()
+    try:
+        dev.build(w1, rel, w2, inverse, W)
+        assert dev.info() == model.info()
+        offsets, relation, word, value, row_sum = dev.rows()
+        assert np.array_equal(offsets, model.offsets())
+        assert np.array_equal(relation, model.relation) and np.array_equal(word, model.word)
+        want_I, want_sum = model.I.astype(np.float64), model.sums().astype(np.float64)
+        assert want_I.size > 0 and np.abs(value - want_I).max() <= TOL
+        assert (np.abs(row_sum - want_sum) <= 1e-12 * np.maximum(1.0, want_sum)).all()
+    finally:
+        dev.close()
+
+
 def _row_length_case():
     """Rows of 0, 1, CHUNK - 1, CHUNK, CHUNK + 1 and 2 CHUNK + 3 entries, a few others, and a hub whose row is longer
     than all the others together; plus the feature words' own short rows."""

@@ -401,7 +401,7 @@ def test_the_word_count_cases_hold_what_they_are_for(W):
         assert m.info()["features"] > 50
 
 
-@pytest.mark.parametrize("D", synonyms_exact.DISTINCT_COUNTS)
+@pytest.mark.parametrize("D", synonyms_exact.DISTINCT_COUNTS + synonyms_exact.SCAN_TILE_DISTINCT)
 def test_the_distinct_count_cases_hold_what_they_are_for(D):
     w1, rel, w2, inverse, W = synonyms_exact.distinct_count_case(D)
     m = synonyms_exact.array_model(w1, rel, w2, inverse, W)
