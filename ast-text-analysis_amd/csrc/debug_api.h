@@ -194,6 +194,222 @@ static void debug_child_tables(int device, const u32 *lcp, i64 n64, const i64 *d
     geometry_out[3] = CH_LOCAL;
 }
 
+// ---- radix sort, spine and scans in every form the library uses them in --------------------------------------------------
+// Every output lies in the arena with DBG_GUARD elements behind it, both filled with 0xEE before the run and both copied
+// back: a slot the kernels left out and a write behind the end show on the host.
+#define DBG_GUARD EAST_HIP_DEBUG_GUARD
+static_assert(DBG_GUARD >= RS_TILE && DBG_GUARD >= SCAN_TILE, "a guard of a tile or more");
+
+static void debug_sort_scan_geometry(u32 *geometry_out)
+{
+    geometry_out[0] = RS_TILE;
+    geometry_out[1] = RS_GROUP;
+    geometry_out[2] = RS_TOTAL_SHARDS;
+    geometry_out[3] = RS_SPINE_DOC_GROUPS;
+    geometry_out[4] = RS_SPINE_PARTS * RS_SPINE_HELD;
+    geometry_out[5] = SCAN_TILE;
+    geometry_out[6] = SCAN_RAW_TILES;
+    geometry_out[7] = DBG_GUARD;
+    geometry_out[8] = RS_SPINE_PARTS;
+}
+
+// n words (and the guard behind them) of the arena, filled with 0xEE
+template <class T> static T *debug_guarded(DebugScope &sc, size_t n)
+{
+    T *p = sc.arena.alloc<T>(n + DBG_GUARD);
+    HIP_CHECK(hipMemsetAsync(p, 0xEE, (n + DBG_GUARD) * sizeof(T), sc.stream));
+    return p;
+}
+
+static void debug_check_offsets(const i64 *doc_off, int32_t n_docs, i64 n)
+{
+    if (n_docs < 0 || n_docs > (int32_t)RS_SEG_MAX_DOCS) east_throw(EAST_HIP_ERR_INVALID, "more documents than a segmented sort takes");
+    if (!n_docs) return;
+    if (!doc_off || doc_off[0] != 0) east_throw(EAST_HIP_ERR_INVALID, "document offsets start at 0");
+    for (int32_t d = 0; d < n_docs; d++)
+        if (doc_off[d + 1] <= doc_off[d] || doc_off[d + 1] > n) east_throw(EAST_HIP_ERR_INVALID, "document offsets must increase");
+    if (doc_off[n_docs] != n) east_throw(EAST_HIP_ERR_INVALID, "document offsets end at n");
+}
+
+// the offsets on the device, and the segments' tables made by the function the build calls (off32: the host's copy, which
+// outlives the uploads)
+static RsSeg debug_seg(Ctx &ctx, const i64 *doc_off, int32_t n_docs, u32 n, std::vector<u32> &off32)
+{
+    if (!n_docs) return RsSeg();
+    u32 *d_off = ctx.arena->alloc<u32>((size_t)n_docs + 1);
+    if (!ctx.dry) {
+        off32.resize((size_t)n_docs + 1);
+        for (int32_t d = 0; d <= n_docs; d++) off32[d] = (u32)doc_off[d];
+        HIP_CHECK(hipMemcpyAsync(d_off, off32.data(), off32.size() * 4, hipMemcpyHostToDevice, ctx.stream));
+    }
+    return rs_seg_make(ctx, d_off, off32.data(), (u32)n_docs, n, ctx.seg_host);
+}
+
+// radix_sort_pairs<K> with exactly the caller's arguments; keys / vals: n pairs in, n + DBG_GUARD elements out
+template <class K>
+static void debug_sort_ex(int device, K *keys, u32 *vals, i64 n64, int bits, int begin_bit, int check_from_bit, const i64 *doc_off,
+                          int32_t n_docs, u32 *geometry_out)
+{
+    if (!keys || !vals || !geometry_out || n64 < 1 || n64 >= (i64)0x7FFFFFF0 || begin_bit < 0 || bits <= begin_bit ||
+        bits > (int)sizeof(K) * 8 || check_from_bit < 0)
+        east_throw(EAST_HIP_ERR_INVALID, "bad radix sort arguments");
+    debug_check_offsets(doc_off, n_docs, n64);
+    const u32 n = (u32)n64;
+    const size_t padded = (size_t)n + DBG_GUARD;
+    std::vector<u32> off32;
+    SortBufs<K> sb;
+    int r = 0;
+    auto run = [&](Ctx &ctx) {
+        for (int k = 0; k < 2; k++) {
+            sb.keys[k] = ctx.arena->alloc<K>(padded);
+            sb.vals[k] = ctx.arena->alloc<u32>(padded);
+            if (ctx.dry) continue;
+            HIP_CHECK(hipMemsetAsync(sb.keys[k], 0xEE, padded * sizeof(K), ctx.stream));
+            HIP_CHECK(hipMemsetAsync(sb.vals[k], 0xEE, padded * 4, ctx.stream));
+        }
+        if (!ctx.dry) {
+            HIP_CHECK(hipMemcpyAsync(sb.keys[0], keys, (size_t)n * sizeof(K), hipMemcpyHostToDevice, ctx.stream));
+            HIP_CHECK(hipMemcpyAsync(sb.vals[0], vals, (size_t)n * 4, hipMemcpyHostToDevice, ctx.stream));
+        }
+        const RsSeg seg = debug_seg(ctx, doc_off, n_docs, n, off32);
+        r = radix_sort_pairs<K>(ctx, sb, n, bits, begin_bit, NoGen(), check_from_bit, seg);
+    };
+    // (the arena is measured with the same code, then the sort runs in it)
+    Arena dry;
+    dry.dry = true;
+    Stats st;
+    Ctx dctx;
+    dctx.arena = &dry;
+    dctx.dry = true;
+    dctx.stats = &st;
+    run(dctx);
+    DebugScope sc(device, dry.high + (8u << 20));
+    run(sc.ctx);
+    // (a write behind the end of the pair of buffers the result is not in shows in the result's guard as well)
+    std::vector<K> gk(DBG_GUARD);
+    std::vector<u32> gv(DBG_GUARD);
+    HIP_CHECK(hipMemcpyAsync(keys, sb.keys[r], padded * sizeof(K), hipMemcpyDeviceToHost, sc.stream));
+    HIP_CHECK(hipMemcpyAsync(vals, sb.vals[r], padded * 4, hipMemcpyDeviceToHost, sc.stream));
+    HIP_CHECK(hipMemcpyAsync(gk.data(), sb.keys[r ^ 1] + n, DBG_GUARD * sizeof(K), hipMemcpyDeviceToHost, sc.stream));
+    HIP_CHECK(hipMemcpyAsync(gv.data(), sb.vals[r ^ 1] + n, DBG_GUARD * 4, hipMemcpyDeviceToHost, sc.stream));
+    HIP_CHECK(hipStreamSynchronize(sc.stream));
+    K untouched;
+    memset(&untouched, 0xEE, sizeof(K));
+    for (u32 i = 0; i < DBG_GUARD; i++) {
+        if (gk[i] != untouched) keys[n + i] = gk[i];
+        if (gv[i] != 0xEEEEEEEEu) vals[n + i] = gv[i];
+    }
+    debug_sort_scan_geometry(geometry_out);
+}
+
+// The spine step of one radix pass (radix_sort.h: radix_spine) on the caller's group sums and digit totals.  Segmented:
+// the documents' groups follow from doc_off as in a sort, n_groups must be their number; the totals are a row per
+// document and shard.  group_prefix_out: n_groups rows + DBG_GUARD words, next_total_out: as many rows as digit_total
+// holds + DBG_GUARD words.
+static void debug_spine(int device, const u32 *group_sum, i64 n_groups64, const u32 *digit_total, const i64 *doc_off, int32_t n_docs,
+                        u32 *group_prefix_out, u32 *next_total_out, u32 *geometry_out)
+{
+    if (!group_sum || !digit_total || !group_prefix_out || !next_total_out || !geometry_out || n_groups64 < 1 || n_groups64 > ((i64)1 << 20) ||
+        n_docs < 0 || n_docs > (int32_t)RS_SEG_MAX_DOCS || (n_docs && !doc_off))
+        east_throw(EAST_HIP_ERR_INVALID, "bad spine arguments");
+    const i64 n64 = n_docs ? doc_off[n_docs] : 1;       // (one segment: the spine does not ask for the number of pairs)
+    if (n64 < 1 || n64 >= (i64)0x7FFFFFF0) east_throw(EAST_HIP_ERR_INVALID, "bad spine arguments");
+    debug_check_offsets(doc_off, n_docs, n64);
+    const u32 n_groups = (u32)n_groups64, shards = (u32)n_docs < RS_TOTAL_SHARDS ? RS_TOTAL_SHARDS : 1;
+    if (n_docs) {
+        i64 g = 0;
+        for (int32_t d = 0; d < n_docs; d++) g += rs_doc_groups((u32)(doc_off[d + 1] - doc_off[d]));
+        if (g != n_groups64) east_throw(EAST_HIP_ERR_INVALID, "n_groups is not the number of the documents' groups");
+    }
+    const size_t sum_words = (size_t)n_groups * RS_BINS, total_words = (size_t)(n_docs ? (u32)n_docs * shards : RS_TOTAL_SHARDS) * RS_BINS;
+    DebugScope sc(device, (2 * (sum_words + total_words + DBG_GUARD) + 3 * ((size_t)n_docs + 64) + n_groups) * 4 + (1u << 20));
+    u32 *d_sum = sc.arena.alloc<u32>(sum_words), *d_total = sc.arena.alloc<u32>(total_words);
+    u32 *d_prefix = debug_guarded<u32>(sc, sum_words), *d_next = debug_guarded<u32>(sc, total_words);
+    HIP_CHECK(hipMemcpyAsync(d_sum, group_sum, sum_words * 4, hipMemcpyHostToDevice, sc.stream));
+    HIP_CHECK(hipMemcpyAsync(d_total, digit_total, total_words * 4, hipMemcpyHostToDevice, sc.stream));
+    std::vector<u32> off32;
+    const RsSeg seg = debug_seg(sc.ctx, doc_off, n_docs, (u32)n64, off32);
+    radix_spine(sc.ctx, d_sum, n_groups, d_total, d_next, d_prefix, seg);
+    HIP_CHECK(hipMemcpyAsync(group_prefix_out, d_prefix, (sum_words + DBG_GUARD) * 4, hipMemcpyDeviceToHost, sc.stream));
+    HIP_CHECK(hipMemcpyAsync(next_total_out, d_next, (total_words + DBG_GUARD) * 4, hipMemcpyDeviceToHost, sc.stream));
+    HIP_CHECK(hipStreamSynchronize(sc.stream));
+    debug_sort_scan_geometry(geometry_out);
+}
+
+// device_scan in the forms of include/east_hip.h (EAST_HIP_SCAN_*); out: n words (n + 1 with the total) + DBG_GUARD
+static void debug_scan_ex(int device, int form, const u32 *in, i64 n64, u32 *out, u32 *geometry_out)
+{
+    if (!in || !out || !geometry_out || n64 < 1 || n64 >= (i64)0x7FFFFFF0 || form < EAST_HIP_SCAN_EXCLUSIVE || form > EAST_HIP_SCAN_WITH_TOTAL)
+        east_throw(EAST_HIP_ERR_INVALID, "bad scan arguments");
+    const u32 n = (u32)n64;
+    const size_t n_out = (size_t)n + (form == EAST_HIP_SCAN_WITH_TOTAL ? 1 : 0);
+    const bool in_place = form == EAST_HIP_SCAN_EXCLUSIVE_IN_PLACE || form == EAST_HIP_SCAN_INCLUSIVE_IN_PLACE;
+    DebugScope sc(device, ((size_t)n * 2 + DBG_GUARD + ceil_div_u32(n_out, SCAN_TILE) * 2) * 4 + (8u << 20));
+    u32 *d_out = debug_guarded<u32>(sc, n_out), *d_in = in_place ? d_out : sc.arena.alloc<u32>(n);
+    HIP_CHECK(hipMemcpyAsync(d_in, in, (size_t)n * 4, hipMemcpyHostToDevice, sc.stream));
+    if (form == EAST_HIP_SCAN_WITH_TOTAL) device_scan_with_total(sc.ctx, ArrIn{d_in}, n, d_out);
+    else if (form == EAST_HIP_SCAN_INCLUSIVE || form == EAST_HIP_SCAN_INCLUSIVE_IN_PLACE) device_scan<ArrIn, true>(sc.ctx, ArrIn{d_in}, n, d_out);
+    else device_scan<ArrIn, false>(sc.ctx, ArrIn{d_in}, n, d_out);
+    HIP_CHECK(hipMemcpyAsync(out, d_out, (n_out + DBG_GUARD) * 4, hipMemcpyDeviceToHost, sc.stream));
+    HIP_CHECK(hipStreamSynchronize(sc.stream));
+    debug_sort_scan_geometry(geometry_out);
+}
+
+// The heads of the runs of sorted 64-bit keys above `shift` (scan.h: RunHeadIn): their inclusive scan, n + DBG_GUARD words,
+// and their number as device_scan_count returns it
+static void debug_run_heads(int device, const u64 *keys, i64 n64, int shift, u32 *inclusive_out, u32 *count_out)
+{
+    if (!keys || !inclusive_out || !count_out || n64 < 1 || n64 >= (i64)0x7FFFFFF0 || shift < 0 || shift > 63)
+        east_throw(EAST_HIP_ERR_INVALID, "bad run head arguments");
+    const u32 n = (u32)n64;
+    DebugScope sc(device, ((size_t)n * 4 + 2 * DBG_GUARD + ceil_div_u32((u64)n + 1, SCAN_TILE) * 2) * 4 + (8u << 20));
+    u64 *d_keys = sc.arena.alloc<u64>(n);
+    u32 *d_inc = debug_guarded<u32>(sc, n), *d_exc = debug_guarded<u32>(sc, (size_t)n + 1);
+    HIP_CHECK(hipMemcpyAsync(d_keys, keys, (size_t)n * 8, hipMemcpyHostToDevice, sc.stream));
+    const RunHeadIn<u64> heads{d_keys, shift};
+    device_scan<RunHeadIn<u64>, true>(sc.ctx, heads, n, d_inc);
+    const u32 count = device_scan_count(sc.ctx, heads, n, d_exc);
+    std::vector<u32> behind(DBG_GUARD);
+    HIP_CHECK(hipMemcpyAsync(inclusive_out, d_inc, ((size_t)n + DBG_GUARD) * 4, hipMemcpyDeviceToHost, sc.stream));
+    HIP_CHECK(hipMemcpyAsync(behind.data(), d_exc + n + 1, DBG_GUARD * 4, hipMemcpyDeviceToHost, sc.stream));
+    HIP_CHECK(hipStreamSynchronize(sc.stream));
+    for (u32 v : behind)
+        if (v != 0xEEEEEEEEu) east_throw(EAST_HIP_ERR_INTERNAL, "the counting scan wrote behind its n + 1 words");
+    *count_out = count;
+}
+
+// device_scan_pair_bounded with the bound in a word of the device; out_a / out_b: n + DBG_GUARD words each
+static void debug_scan_pair_bounded(int device, const u32 *a, const u32 *b, i64 n64, u32 n_dev_value, u32 extra, u32 *out_a, u32 *out_b)
+{
+    if (!a || !b || !out_a || !out_b || n64 < 1 || n64 >= (i64)0x7FFFFFF0 || (u64)n_dev_value + extra > 0xFFFFFFFFull)
+        east_throw(EAST_HIP_ERR_INVALID, "bad bounded scan arguments");
+    const u32 n = (u32)n64;
+    DebugScope sc(device, ((size_t)n * 4 + 2 * DBG_GUARD + ceil_div_u32(n, SCAN_TILE) * 2 + 64) * 4 + (8u << 20));
+    u32 *d_a = sc.arena.alloc<u32>(n), *d_b = sc.arena.alloc<u32>(n), *d_n = sc.arena.alloc<u32>(1);
+    u32 *d_out_a = debug_guarded<u32>(sc, n), *d_out_b = debug_guarded<u32>(sc, n);
+    HIP_CHECK(hipMemcpyAsync(d_a, a, (size_t)n * 4, hipMemcpyHostToDevice, sc.stream));
+    HIP_CHECK(hipMemcpyAsync(d_b, b, (size_t)n * 4, hipMemcpyHostToDevice, sc.stream));
+    HIP_CHECK(hipMemcpyAsync(d_n, &n_dev_value, 4, hipMemcpyHostToDevice, sc.stream));
+    device_scan_pair_bounded(sc.ctx, d_a, d_b, n, d_n, extra, d_out_a, d_out_b);
+    HIP_CHECK(hipMemcpyAsync(out_a, d_out_a, ((size_t)n + DBG_GUARD) * 4, hipMemcpyDeviceToHost, sc.stream));
+    HIP_CHECK(hipMemcpyAsync(out_b, d_out_b, ((size_t)n + DBG_GUARD) * 4, hipMemcpyDeviceToHost, sc.stream));
+    HIP_CHECK(hipStreamSynchronize(sc.stream));
+}
+
+// ascending_offsets_kernel as the consumers launch it; off_out: n_values + 1 + DBG_GUARD words
+static void debug_ascending_offsets(int device, const u32 *sorted, i64 n64, i64 n_values64, u32 *off_out)
+{
+    if (!sorted || !off_out || n64 < 1 || n64 >= (i64)0x7FFFFFF0 || n_values64 < 0 || n_values64 >= (i64)0x7FFFFFF0)
+        east_throw(EAST_HIP_ERR_INVALID, "bad offsets arguments");
+    const u32 n = (u32)n64, n_values = (u32)n_values64;
+    DebugScope sc(device, ((size_t)n + n_values + 1 + DBG_GUARD) * 4 + (1u << 20));
+    u32 *d_sorted = sc.arena.alloc<u32>(n), *d_off = debug_guarded<u32>(sc, (size_t)n_values + 1);
+    HIP_CHECK(hipMemcpyAsync(d_sorted, sorted, (size_t)n * 4, hipMemcpyHostToDevice, sc.stream));
+    LAUNCH(sc.ctx, ascending_offsets_kernel, ceil_div_u32((u64)n_values + 1, BLOCK), (const u32 *)d_sorted, n, n_values, d_off);
+    HIP_CHECK(hipMemcpyAsync(off_out, d_off, ((size_t)n_values + 1 + DBG_GUARD) * 4, hipMemcpyDeviceToHost, sc.stream));
+    HIP_CHECK(hipStreamSynchronize(sc.stream));
+}
+
 extern "C" {
 
 int east_hip_debug_set_rank_bucket_bytes(int64_t bytes)
@@ -411,6 +627,44 @@ int east_hip_debug_exclusive_scan(int device, const uint32_t *in, uint32_t *out,
         HIP_CHECK(hipMemcpyAsync(out, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, sc.stream));
         HIP_CHECK(hipStreamSynchronize(sc.stream));
     });
+}
+
+int east_hip_debug_radix_sort_ex(int device, int key_bytes, void *keys, uint32_t *vals, int64_t n, int bits, int begin_bit,
+                                 int check_from_bit, const int64_t *doc_off, int32_t n_docs, uint32_t *geometry_out)
+{
+    return guarded([&] {
+        if (key_bytes == 8) debug_sort_ex<u64>(device, (u64 *)keys, vals, n, bits, begin_bit, check_from_bit, doc_off, n_docs, geometry_out);
+        else if (key_bytes == 4) debug_sort_ex<u32>(device, (u32 *)keys, vals, n, bits, begin_bit, check_from_bit, doc_off, n_docs, geometry_out);
+        else east_throw(EAST_HIP_ERR_INVALID, "key_bytes must be 4 or 8");
+    });
+}
+
+int east_hip_debug_radix_spine(int device, const uint32_t *group_sum, int64_t n_groups, const uint32_t *digit_total,
+                               const int64_t *doc_off, int32_t n_docs, uint32_t *group_prefix_out, uint32_t *next_total_out,
+                               uint32_t *geometry_out)
+{
+    return guarded([&] { debug_spine(device, group_sum, n_groups, digit_total, doc_off, n_docs, group_prefix_out, next_total_out, geometry_out); });
+}
+
+int east_hip_debug_scan_ex(int device, int form, const uint32_t *in, int64_t n, uint32_t *out, uint32_t *geometry_out)
+{
+    return guarded([&] { debug_scan_ex(device, form, in, n, out, geometry_out); });
+}
+
+int east_hip_debug_run_heads(int device, const uint64_t *keys64, int64_t n, int shift, uint32_t *inclusive_out, uint32_t *count_out)
+{
+    return guarded([&] { debug_run_heads(device, (const u64 *)keys64, n, shift, inclusive_out, count_out); });
+}
+
+int east_hip_debug_scan_pair_bounded(int device, const uint32_t *a, const uint32_t *b, int64_t n, uint32_t n_dev_value,
+                                     uint32_t extra, uint32_t *out_a, uint32_t *out_b)
+{
+    return guarded([&] { debug_scan_pair_bounded(device, a, b, n, n_dev_value, extra, out_a, out_b); });
+}
+
+int east_hip_debug_ascending_offsets(int device, const uint32_t *sorted, int64_t n, int64_t n_values, uint32_t *off_out)
+{
+    return guarded([&] { debug_ascending_offsets(device, sorted, n, n_values, off_out); });
 }
 
 int east_hip_debug_suffix_array(int device, const uint32_t *symbols, int64_t n, uint32_t sigma, int32_t *sa_out,

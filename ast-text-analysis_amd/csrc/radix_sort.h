@@ -685,6 +685,66 @@ __global__ __launch_bounds__(RS_THREADS, (RS_IPT <= 4 ? 8 : 4)) void radix_scatt
         radix_scatter_tile<K, Src, false>(lds, src, keys_out, vals_out, shift, mask, hist, group_prefix, tile, tile_base, tile_count);
 }
 
+// The spine step of one pass: group_prefix from the groups' sums and the digit totals, next_total cleared.  One segment:
+// the column-parallel kernel over all groups; segmented: one workgroup per document of at most RS_SPINE_DOC_GROUPS groups,
+// the column-parallel kernel once per larger document (both in the same pass where a collection holds both kinds).
+static void radix_spine(Ctx &ctx, const u32 *group_sum, u32 n_groups, const u32 *digit_total, u32 *next_total, u32 *group_prefix,
+                        const RsSeg &seg)
+{
+    if (seg.n_docs) {
+        if (seg.n_big < seg.n_docs)
+            LAUNCH(ctx, radix_spine_docs_kernel, seg.n_docs, group_sum, digit_total, next_total, group_prefix, seg);
+        if (seg.n_big)
+            LAUNCH(ctx, radix_spine_kernel, dim3(RS_BINS / RS_SPINE_COLS, seg.n_big), group_sum, n_groups, digit_total, next_total,
+                   group_prefix, seg);
+    } else {
+        LAUNCH(ctx, radix_spine_kernel, dim3(RS_BINS / RS_SPINE_COLS, 1u), group_sum, n_groups, digit_total, next_total, group_prefix, seg);
+    }
+}
+
+// The tables of a segmented sort of n pairs in n_docs documents (1 .. RS_SEG_MAX_DOCS), out of the context's arena: the
+// documents' groups, the document of every group, the list of large documents for the spine.  doc_off: the n_docs + 1
+// offsets on the device; h_doc_off: the same on the host (not read in a sizing run, which reserves the most the tables can
+// take).  hs keeps the host's copies until the uploads, which are asynchronous, have run: it must outlive them.
+static inline u32 rs_doc_groups(u32 pairs) { return ceil_div_u32(ceil_div_u32(pairs, RS_TILE), RS_GROUP); }
+static RsSeg rs_seg_make(Ctx &ctx, const u32 *doc_off, const u32 *h_doc_off, u32 n_docs, u32 n, std::vector<u32> &hs)
+{
+    Arena &ar = *ctx.arena;
+    RsSeg seg;
+    seg.n_docs = n_docs;
+    seg.doc_off = doc_off;
+    seg.shards = n_docs < RS_TOTAL_SHARDS ? RS_TOTAL_SHARDS : 1;
+    u32 *d_group0 = ar.alloc<u32>((size_t)n_docs + 1);
+    seg.doc_group0 = d_group0;
+    if (ctx.dry) {
+        seg.n_groups = rs_doc_groups(n) + n_docs;
+        seg.group_doc = ar.alloc<u32>(seg.n_groups);
+        seg.big_docs = ar.alloc<u32>(n_docs);
+        return seg;
+    }
+    hs.assign((size_t)n_docs + 1, 0u);
+    for (u32 d = 0; d < n_docs; d++) hs[d + 1] = hs[d] + rs_doc_groups(h_doc_off[d + 1] - h_doc_off[d]);
+    seg.n_groups = hs[n_docs];
+    u32 *d_group_doc = ar.alloc<u32>(seg.n_groups);
+    seg.group_doc = d_group_doc;
+    hs.resize((size_t)n_docs + 1 + seg.n_groups);
+    for (u32 d = 0; d < n_docs; d++)
+        for (u32 g = hs[d]; g < hs[d + 1]; g++) hs[(size_t)n_docs + 1 + g] = d;
+    // (the documents of many groups, for the spine: see RsSeg)
+    const size_t big_at = hs.size();
+    for (u32 d = 0; d < n_docs; d++)
+        if (hs[d + 1] - hs[d] > (u32)RS_SPINE_DOC_GROUPS) hs.push_back(d);
+    seg.n_big = (u32)(hs.size() - big_at);
+    HIP_CHECK(hipMemcpyAsync(d_group0, hs.data(), ((size_t)n_docs + 1) * 4, hipMemcpyHostToDevice, ctx.stream));
+    HIP_CHECK(hipMemcpyAsync(d_group_doc, hs.data() + n_docs + 1, (size_t)seg.n_groups * 4, hipMemcpyHostToDevice, ctx.stream));
+    if (seg.n_big) {
+        u32 *d_big = ar.alloc<u32>(seg.n_big);
+        seg.big_docs = d_big;
+        HIP_CHECK(hipMemcpyAsync(d_big, hs.data() + big_at, (size_t)seg.n_big * 4, hipMemcpyHostToDevice, ctx.stream));
+    }
+    return seg;
+}
+
 template <class K> struct SortBufs {
     K *keys[2];
     u32 *vals[2];
@@ -785,16 +845,7 @@ static int radix_sort_pairs(Ctx &ctx, SortBufs<K> &b, u32 n, int bits, int begin
             HIP_CHECK(hipGetLastError());
             if (prof) ctx.prof->end(ctx.stream);
         }
-        if (seg.n_docs) {
-            if (seg.n_big < seg.n_docs)
-                LAUNCH(ctx, radix_spine_docs_kernel, seg.n_docs, (const u32 *)group_sum_p, (const u32 *)tot, tot_next, group_prefix, seg);
-            if (seg.n_big)
-                LAUNCH(ctx, radix_spine_kernel, dim3(RS_BINS / RS_SPINE_COLS, seg.n_big), (const u32 *)group_sum_p, n_groups,
-                       (const u32 *)tot, tot_next, group_prefix, seg);
-        } else {
-            LAUNCH(ctx, radix_spine_kernel, dim3(RS_BINS / RS_SPINE_COLS, 1u), (const u32 *)group_sum_p, n_groups, (const u32 *)tot,
-                   tot_next, group_prefix, seg);
-        }
+        radix_spine(ctx, group_sum_p, n_groups, tot, tot_next, group_prefix, seg);
         if (!ctx.dry) {
             if (prof) ctx.prof->begin(name_scatter, ctx.stream);
             const dim3 grid(8 * ((n_tiles + 7) / 8));

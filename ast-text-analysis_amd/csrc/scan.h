@@ -220,7 +220,8 @@ __global__ __launch_bounds__(BLOCK) void ascending_offsets_kernel(const u32 *__r
 
 // ---- two sums at once, over a length the DEVICE knows ------------------------------------------------------------------
 // out_a / out_b = exclusive prefix sums of a[] / b[] over the elements [0, min(n, *n_dev + extra)); tiles wholly behind
-// that bound return at once and their outputs stay unwritten (nobody reads them).  The streamed text preparation scans
+// that bound return at once and the bound's own tile stores below it only: no word at or behind the bound is written
+// (nobody reads them; tests/test_gpu_sort_scan_forms.py holds the kernels to it).  The streamed text preparation scans
 // per-token quantities this way: its kernels run on an upper bound of the token count (half the code points), the real
 // count -- a third to a quarter of that -- is on the device, and the two quantities (kept tokens, kept symbols) used to be
 // two scans of three launches each over the whole upper bound.

@@ -2622,40 +2622,8 @@ static bool window_suffix_sort(Ctx &ctx, const uint8_t *s8, u32 n, u32 term_firs
         // (... and five or more of them: the document number of two to four documents costs the key a bit or two, less than
         // the segments' short tiles cost the passes -- 2 x 32 MiB: 1.71 ms with, 1.68 without)
         if (can && ctx.knobs.seg_mode != 0 && (ctx.knobs.seg_mode == 1 || (docs.n_docs >= 5 && docs.n_docs <= flat_groups / per_groups + 1))) {
-            RsSeg &seg = docs.seg;
-            seg.n_docs = docs.n_docs;
-            seg.doc_off = docs.doc_off;
-            seg.shards = docs.n_docs < RS_TOTAL_SHARDS ? RS_TOTAL_SHARDS : 1;
-            u32 *d_group0 = ar.alloc<u32>((size_t)docs.n_docs + 1);
-            seg.doc_group0 = d_group0;
-            if (ctx.dry) {
-                seg.n_groups = flat_groups + docs.n_docs;
-                seg.group_doc = ar.alloc<u32>(seg.n_groups);
-                seg.big_docs = ar.alloc<u32>(docs.n_docs);
-            } else {
-                std::vector<u32> &hs = ctx.seg_host;        // (lives as long as the build: the copies below are asynchronous)
-                hs.assign((size_t)docs.n_docs + 1, 0u);
-                for (u32 d = 0; d < docs.n_docs; d++)
-                    hs[d + 1] = hs[d] + ceil_div_u32(ceil_div_u32(docs.h_doc_off[d + 1] - docs.h_doc_off[d], RS_TILE), RS_GROUP);
-                seg.n_groups = hs[docs.n_docs];
-                u32 *d_group_doc = ar.alloc<u32>(seg.n_groups);
-                seg.group_doc = d_group_doc;
-                hs.resize((size_t)docs.n_docs + 1 + seg.n_groups);
-                for (u32 d = 0; d < docs.n_docs; d++)
-                    for (u32 g = hs[d]; g < hs[d + 1]; g++) hs[(size_t)docs.n_docs + 1 + g] = d;
-                // (the documents of many groups, for the spine: see RsSeg)
-                const size_t big_at = hs.size();
-                for (u32 d = 0; d < docs.n_docs; d++)
-                    if (hs[d + 1] - hs[d] > (u32)RS_SPINE_DOC_GROUPS) hs.push_back(d);
-                seg.n_big = (u32)(hs.size() - big_at);
-                HIP_CHECK(hipMemcpyAsync(d_group0, hs.data(), ((size_t)docs.n_docs + 1) * 4, hipMemcpyHostToDevice, ctx.stream));
-                HIP_CHECK(hipMemcpyAsync(d_group_doc, hs.data() + docs.n_docs + 1, (size_t)seg.n_groups * 4, hipMemcpyHostToDevice, ctx.stream));
-                if (seg.n_big) {
-                    u32 *d_big = ar.alloc<u32>(seg.n_big);
-                    seg.big_docs = d_big;
-                    HIP_CHECK(hipMemcpyAsync(d_big, hs.data() + big_at, (size_t)seg.n_big * 4, hipMemcpyHostToDevice, ctx.stream));
-                }
-            }
+            // (the host's copies of the tables live as long as the build: the uploads are asynchronous)
+            docs.seg = rs_seg_make(ctx, docs.doc_off, docs.h_doc_off, docs.n_docs, n, ctx.seg_host);
             docs.bits = 0;                              // (no document number in the keys)
         }
     }

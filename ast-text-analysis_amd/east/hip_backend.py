@@ -79,6 +79,15 @@ SIGNATURES = {
                                                _c_u32p, _c_u32p, _c_u32p]),
     "east_hip_debug_child_tables": (ctypes.c_int, [ctypes.c_int, _c_u32p, ctypes.c_int64, _c_i64p, ctypes.c_int32, _c_i32p,
                                                    _c_u32p, _c_u32p, _c_u32p, _c_u32p, _c_u32p, _c_u32p]),
+    "east_hip_debug_radix_sort_ex": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, _c_u32p, ctypes.c_int64,
+                                                    ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_i64p, ctypes.c_int32, _c_u32p]),
+    "east_hip_debug_radix_spine": (ctypes.c_int, [ctypes.c_int, _c_u32p, ctypes.c_int64, _c_u32p, _c_i64p, ctypes.c_int32,
+                                                  _c_u32p, _c_u32p, _c_u32p]),
+    "east_hip_debug_scan_ex": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _c_u32p, ctypes.c_int64, _c_u32p, _c_u32p]),
+    "east_hip_debug_run_heads": (ctypes.c_int, [ctypes.c_int, _c_u64p, ctypes.c_int64, ctypes.c_int, _c_u32p, _c_u32p]),
+    "east_hip_debug_scan_pair_bounded": (ctypes.c_int, [ctypes.c_int, _c_u32p, _c_u32p, ctypes.c_int64, ctypes.c_uint32,
+                                                        ctypes.c_uint32, _c_u32p, _c_u32p]),
+    "east_hip_debug_ascending_offsets": (ctypes.c_int, [ctypes.c_int, _c_u32p, ctypes.c_int64, ctypes.c_int64, _c_u32p]),
     "east_hip_debug_pyramid_level": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _c_u32p, ctypes.c_int64, _c_i64p]),
     "east_hip_debug_set_score_scratch": (ctypes.c_int, [ctypes.c_int64]),
     "east_hip_debug_set_score_path": (ctypes.c_int, [ctypes.c_int]),
@@ -183,7 +192,9 @@ COSINE_TEXTS_CHUNK, COSINE_TEXTS_SEG = 32, 8192      # csrc/cosine_texts.h: the 
 COSINE_TEXTS_INFO_FIELDS = ("n_docs", "units", "postings", "tiles", "segments", "launches", "chunk_units", "segment_units")
 CLUSTERS_INFO_FIELDS = ("members", "merges", "rounds", "launches")      # east_hip_clusters_build_*: out
 RELATED_DIRECTED, RELATED_SYMMETRIC = 0, 1                               # east_hip_related_build: the orientation
-TOP_BY_TEXT, TOP_BY_KEYPHRASE = 0, 1                                        # east_hip_top_build_*: what a segment is
+DEBUG_GUARD = 4096                          # east_hip_debug_radix_sort_ex and its kin: elements behind every output
+SCAN_EXCLUSIVE, SCAN_INCLUSIVE, SCAN_EXCLUSIVE_IN_PLACE, SCAN_INCLUSIVE_IN_PLACE, SCAN_WITH_TOTAL = range(5)    # east_hip_debug_scan_ex
+TOP_BY_TEXT, TOP_BY_KEYPHRASE = 0, 1                                     # east_hip_top_build_*: what a segment is
 TOP_MAX_N = 1024
 
 _lib = None

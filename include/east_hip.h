@@ -751,6 +751,51 @@ int east_hip_debug_annotate(int device, const uint32_t *lcp, int64_t n, const in
 int east_hip_debug_child_tables(int device, const uint32_t *lcp, int64_t n, const int64_t *doc_off, int32_t n_docs,
                                 const int32_t *n_strings, uint32_t *up_out, uint32_t *down_out, uint32_t *next_out,
                                 uint32_t *left_out, uint32_t *geometry_out, uint32_t *listed_out);
+/*
+ * Kernel-level tests of the radix sort, its spine and the scans in every form the library uses them in (csrc/radix_sort.h,
+ * csrc/scan.h).  Every output buffer takes its elements AND a guard of EAST_HIP_DEBUG_GUARD elements behind them: on the
+ * device both are filled with 0xEE before the run and both come back, so that an element the kernels left out and a
+ * write behind the end show.  Arguments are checked before any device work (EAST_HIP_ERR_INVALID; the outputs are then
+ * untouched).  geometry_out[9]: RS_TILE, RS_GROUP, RS_TOTAL_SHARDS, RS_SPINE_DOC_GROUPS, RS_SPINE_PARTS * RS_SPINE_HELD,
+ * SCAN_TILE, SCAN_RAW_TILES as the library was compiled, EAST_HIP_DEBUG_GUARD, RS_SPINE_PARTS.
+ *
+ * radix_sort_ex: radix_sort_pairs<u32 | u64> (key_bytes 4 | 8) with exactly these arguments -- a stable sort on the key
+ * bits [begin_bit, bits), the histogram passes below check_from_bit without the test for a wavefront on one bin.  keys /
+ * vals: n pairs in, n + guard elements out.  n_docs > 0: the segmented sort, every document [doc_off[d], doc_off[d + 1])
+ * sorted in its own range (doc_off: n_docs + 1 strictly increasing offsets from 0 to n, n_docs <= 65 535); the segments'
+ * tables are made by the function the build calls (rs_seg_make).
+ *
+ * radix_spine: the spine step of one pass (radix_spine: radix_spine_kernel, radix_spine_docs_kernel) on the caller's
+ * group sums (n_groups rows of 256) and digit totals (one segment: RS_TOTAL_SHARDS rows of 256; segmented: per document
+ * RS_TOTAL_SHARDS rows below RS_TOTAL_SHARDS documents, one row from there on).  Segmented, doc_off gives the documents'
+ * pairs as above and n_groups must be the number of their groups (ceil(ceil(pairs / RS_TILE) / RS_GROUP) each).
+ * group_prefix_out: n_groups x 256 + guard words; next_total_out (the other totals buffer, which the step clears): as
+ * many words as digit_total + guard.
+ *
+ * scan_ex: device_scan / device_scan_with_total over n words in the form EAST_HIP_SCAN_*; out: n words (n + 1 with the
+ * total) + guard.  run_heads: the heads of the runs of n sorted keys above bit `shift` (RunHeadIn<u64>) -- their
+ * inclusive scan (n + guard words) and their number as device_scan_count returns it.  scan_pair_bounded:
+ * device_scan_pair_bounded of a and b with n_dev_value in a word of the device; out_a / out_b: n + guard words, defined
+ * on [0, min(n, n_dev_value + extra)).  ascending_offsets: ascending_offsets_kernel over n sorted words; off_out:
+ * n_values + 1 + guard words.
+ */
+#define EAST_HIP_DEBUG_GUARD 4096
+#define EAST_HIP_SCAN_EXCLUSIVE 0
+#define EAST_HIP_SCAN_INCLUSIVE 1
+#define EAST_HIP_SCAN_EXCLUSIVE_IN_PLACE 2          /* out aliases the input */
+#define EAST_HIP_SCAN_INCLUSIVE_IN_PLACE 3
+#define EAST_HIP_SCAN_WITH_TOTAL 4                  /* exclusive, n + 1 outputs: out[n] = the sum */
+int east_hip_debug_radix_sort_ex(int device, int key_bytes, void *keys, uint32_t *vals, int64_t n, int bits, int begin_bit,
+                                 int check_from_bit, const int64_t *doc_off, int32_t n_docs, uint32_t *geometry_out);
+int east_hip_debug_radix_spine(int device, const uint32_t *group_sum, int64_t n_groups, const uint32_t *digit_total,
+                               const int64_t *doc_off, int32_t n_docs, uint32_t *group_prefix_out, uint32_t *next_total_out,
+                               uint32_t *geometry_out);
+int east_hip_debug_scan_ex(int device, int form, const uint32_t *in, int64_t n, uint32_t *out, uint32_t *geometry_out);
+int east_hip_debug_run_heads(int device, const uint64_t *keys64, int64_t n, int shift, uint32_t *inclusive_out,
+                             uint32_t *count_out);
+int east_hip_debug_scan_pair_bounded(int device, const uint32_t *a, const uint32_t *b, int64_t n, uint32_t n_dev_value,
+                                     uint32_t extra, uint32_t *out_a, uint32_t *out_b);
+int east_hip_debug_ascending_offsets(int device, const uint32_t *sorted, int64_t n, int64_t n_values, uint32_t *off_out);
 /* One level of a built handle's min pyramid over the LCP table (csrc/tables.h: Pyramid; level 0 is the table itself, level
  * l + 1 holds the minima of level l's aligned groups of 16), padding included.  geometry_out[3]: the number of levels, the
  * level's length and its padded length (0, 0 for a level the pyramid does not have); out (may be null: the geometry alone)
