@@ -144,6 +144,29 @@ static void prepare_ht_code(east_hip_index *h, Ctx &ctx, u32 n, u32 sigma_t, u32
     ctx.ht_mean_len = h->ht_mean_len;
 }
 
+// The direct pass over the LCP table where it did not come with the suffix array (fused_lcp): neighbouring suffixes
+// compared on the byte stream or on the u32 codes, cut entries marked and `capped` raised (tables.h), then 0 at every
+// document's first rank.  (build_impl and the kernel-level test entry east_hip_debug_lcp both call this.)
+static void direct_lcp(east_hip_index *h, Ctx &ctx, u32 n, u32 n_docs, bool fused_lcp, u32 *capped)
+{
+    Arena &ar = *ctx.arena;
+    const size_t mark = ar.mark();
+    u32 *rank = ctx.dry ? ar.alloc<u32>(n) : nullptr;       // only allocated for real when needed
+    if (fused_lcp) {
+        // (the table's padding up to a multiple of 16 is written by ann_stream_kernel)
+    } else if (h->use_s8) {
+        LAUNCH(ctx, lcp8_kernel, ceil_div_u32(pyr_padded(n), BLOCK), (const uint8_t *)h->s8, (const u32 *)h->sa,
+               n, h->lcp, capped, ctx.lcp_budget);
+    } else {
+        LAUNCH(ctx, lcp_kernel, ceil_div_u32(pyr_padded(n), BLOCK), (const u32 *)h->s, (const u32 *)h->sa,
+               n, h->lcp, capped, ctx.lcp_budget);
+    }
+    if (n_docs > 1)
+        LAUNCH(ctx, lcp_doc_starts_kernel, ceil_div_u32(n_docs, BLOCK), (const u32 *)h->doc_off, n_docs, h->lcp);
+    (void)rank;
+    ar.release(mark);
+}
+
 // The build proper.  With ctx.dry it only measures the arena high-water mark
 // (worst case: widest keys, recursion to the bottom).
 static void build_impl(east_hip_index *h, Ctx &ctx, const u32 *d_sym, u32 n, u32 n_docs,
@@ -428,23 +451,7 @@ static void build_impl(east_hip_index *h, Ctx &ctx, const u32 *d_sym, u32 n, u32
                      (const u32 *)h->n_strings, n_docs, status);
 
     // ---- LCP, min pyramid, annotation + child tables ------------------------------
-    {
-        const size_t mark = ar.mark();
-        u32 *rank = ctx.dry ? ar.alloc<u32>(n) : nullptr;       // only allocated for real when needed
-        if (fused_lcp) {
-            // (the table's padding up to a multiple of 16 is written by ann_stream_kernel)
-        } else if (h->use_s8) {
-            LAUNCH(ctx, lcp8_kernel, ceil_div_u32(pyr_padded(n), BLOCK), (const uint8_t *)h->s8, (const u32 *)h->sa,
-                   n, h->lcp, capped, ctx.lcp_budget);
-        } else {
-            LAUNCH(ctx, lcp_kernel, ceil_div_u32(pyr_padded(n), BLOCK), (const u32 *)h->s, (const u32 *)h->sa,
-                   n, h->lcp, capped, ctx.lcp_budget);
-        }
-        if (n_docs > 1)
-            LAUNCH(ctx, lcp_doc_starts_kernel, ceil_div_u32(n_docs, BLOCK), (const u32 *)h->doc_off, n_docs, h->lcp);
-        (void)rank;
-        ar.release(mark);
-    }
+    direct_lcp(h, ctx, n, n_docs, fused_lcp, capped);
     // (comparisons that hit the cap -- a repetitive input -- are found out about at the end of the build,
     // together with the status word: build_common then finishes those ranks and redoes the two steps below)
     annotate(h, ctx);
@@ -454,7 +461,8 @@ static void build_impl(east_hip_index *h, Ctx &ctx, const u32 *d_sym, u32 n, u32
 
 // A repetitive input: the ranks whose direct comparison was capped are finished with the Kasai carry
 // over the text (blocked, O(n + marked work)), then pyramid and annotation are built again.
-static void finish_capped_lcp(east_hip_index *h, Ctx &ctx)
+// (counts_out != nullptr, a test's: two device words that take the numbers of positions listed and handed to the long kernel)
+static void finish_capped_lcp(east_hip_index *h, Ctx &ctx, u32 *counts_out = nullptr)
 {
     Arena &ar = *ctx.arena;
     const u32 n = h->pyr.len[0];
@@ -480,6 +488,7 @@ static void finish_capped_lcp(east_hip_index *h, Ctx &ctx)
         LAUNCH_BLOCK(ctx, (lcp_phi_long_kernel<false>), 512, PHI_LONG_THREADS, sym, (const u32 *)h->sa, (const u32 *)rank, (const u32 *)long_list,
                      (const u32 *)(counters + 1), n, h->lcp);
     }
+    if (counts_out) HIP_CHECK(hipMemcpyAsync(counts_out, counters, 2 * sizeof(u32), hipMemcpyDeviceToDevice, ctx.stream));
     device_scan<U8In, true>(ctx, U8In{anchor}, n, count);
     LAUNCH(ctx, lcp_phi_anchors_kernel, gn, (const uint8_t *)anchor, (const u32 *)count, n, apos);
     LAUNCH(ctx, lcp_phi_fill_kernel, gn, (const uint8_t *)anchor, (const u32 *)count, (const u32 *)apos, (const u32 *)rank, n, h->lcp);

@@ -94,10 +94,11 @@ static void debug_first_pass_hist(int device, const u32 *symbols, i64 n64, const
 }
 
 // what annotate() and the passes behind it read of a handle, in the scope's arena: the caller's table with the levels of
-// its pyramid, the annotation, the document tables
+// its pyramid, the annotation, the document tables (lcp_words of the table go up: n, or the padding as well, or nothing)
 static void debug_table_handle(DebugScope &sc, east_hip_index &h, const u32 *lcp, u32 n, const i64 *doc_off, int32_t n_docs,
-                               const int32_t *n_strings)
+                               const int32_t *n_strings, u32 lcp_words = 0xFFFFFFFFu)
 {
+    if (lcp_words == 0xFFFFFFFFu) lcp_words = n;
     Arena &ar = sc.arena;
     std::vector<u32> off32((size_t)n_docs + 1), m32(n_docs);
     for (int32_t d = 0; d <= n_docs; d++) off32[d] = (u32)doc_off[d];
@@ -120,7 +121,7 @@ static void debug_table_handle(DebugScope &sc, east_hip_index &h, const u32 *lcp
     // (the table's padding and the annotation start out as something no result is: the pass writes both)
     HIP_CHECK(hipMemsetAsync(h.lcp, 0x5A, (size_t)pyr_padded(n) * 4, sc.stream));
     HIP_CHECK(hipMemsetAsync(h.ann, 0xEE, (size_t)n * 4, sc.stream));
-    HIP_CHECK(hipMemcpyAsync(h.lcp, lcp, (size_t)n * 4, hipMemcpyHostToDevice, sc.stream));
+    if (lcp_words) HIP_CHECK(hipMemcpyAsync(h.lcp, lcp, (size_t)lcp_words * 4, hipMemcpyHostToDevice, sc.stream));
     HIP_CHECK(hipMemcpyAsync(h.doc_off, off32.data(), off32.size() * 4, hipMemcpyHostToDevice, sc.stream));
     HIP_CHECK(hipMemcpyAsync(h.n_strings, m32.data(), m32.size() * 4, hipMemcpyHostToDevice, sc.stream));
     HIP_CHECK(hipStreamSynchronize(sc.stream));     // (the two small tables go up out of this frame)
@@ -192,6 +193,117 @@ static void debug_child_tables(int device, const u32 *lcp, i64 n64, const i64 *d
     geometry_out[1] = CH_HALO;
     geometry_out[2] = CH_NEAR;
     geometry_out[3] = CH_LOCAL;
+}
+
+// The two LCP passes on a caller's text and per-document suffix array: the direct pass (build.h: direct_lcp -- lcp8_kernel
+// on the byte stream, width 1, or lcp_kernel on u32 codes, width 4, then lcp_doc_starts_kernel) or, table_in != nullptr,
+// the caller's table in its place; then finish_capped_lcp where `capped` is raised, as build_common decides, else
+// annotate().  The scope is laid out as build_impl lays a handle out: the text with its pad first, the other arrays behind
+// it, so that what the finishing kernels read past a position (8 192 bytes / 1 024 words) lies inside the scope; the
+// whole scope starts out as pad_fill.  Every argument is checked here, before anything is launched.
+static void debug_lcp(int device, int width, const void *text, i64 n64, u32 term_first, const u32 *sa, const i64 *doc_off,
+                      int32_t n_docs, const int32_t *n_strings, int32_t deep_per_slot, const u32 *table_in, int pad_fill,
+                      u32 *direct_out, u32 *capped_out, u32 *final_out, u32 *counters_out, u32 *ann_out, u32 *geometry_out)
+{
+    if ((width != 1 && width != 4) || !text || !sa || !doc_off || !n_strings || !direct_out || !capped_out || !final_out ||
+        !counters_out || !ann_out || !geometry_out || n64 < 1 || n64 >= (i64)0x7FFFFFF0 || n_docs < 1 || deep_per_slot < -1 ||
+        pad_fill < 0 || pad_fill > 255 || doc_off[0] != 0)
+        east_throw(EAST_HIP_ERR_INVALID, "bad LCP arguments");
+    for (int32_t d = 0; d < n_docs; d++)
+        if (doc_off[d + 1] <= doc_off[d] || doc_off[d + 1] > n64) east_throw(EAST_HIP_ERR_INVALID, "document offsets must increase");
+    if (doc_off[n_docs] != n64) east_throw(EAST_HIP_ERR_INVALID, "document offsets end at n");
+    const u32 n = (u32)n64;
+    const uint8_t *t8 = (const uint8_t *)text;
+    const u32 *t32 = (const u32 *)text;
+    if (width == 4 && (term_first < 2 || term_first > 0x7FFFFFEFu - n)) east_throw(EAST_HIP_ERR_INVALID, "term_first out of range");
+    // symbols in range, the terminators of u32 codes numbered apart (ascending, as the build's scan numbers them)
+    u32 last_term = 0;
+    for (u32 i = 0; i < n; i++) {
+        if (width == 1) {
+            if (t8[i] == 0) east_throw(EAST_HIP_ERR_INVALID, "a zero byte: text codes start at 1, the pad is zero");
+        } else {
+            const u32 c = t32[i];
+            if (c == 0 || c >= term_first + n) east_throw(EAST_HIP_ERR_INVALID, "a code outside [1, term_first + n)");
+            if (c >= term_first) {
+                if (last_term && c <= last_term) east_throw(EAST_HIP_ERR_INVALID, "terminator codes must ascend: each is a symbol of its own");
+                last_term = c;
+            }
+        }
+    }
+    std::vector<uint8_t> seen(n, 0);
+    for (int32_t d = 0; d < n_docs; d++) {
+        const u32 lo = (u32)doc_off[d], hi = (u32)doc_off[d + 1];
+        const bool ends = width == 1 ? t8[hi - 1] == 0xFFu : t32[hi - 1] >= term_first;
+        if (!ends) east_throw(EAST_HIP_ERR_INVALID, "a document does not end in a terminator");
+        i64 terms = 0;
+        for (u32 i = lo; i < hi; i++) terms += width == 1 ? t8[i] == 0xFFu : t32[i] >= term_first;
+        if (n_strings[d] < 1 || terms != n_strings[d]) east_throw(EAST_HIP_ERR_INVALID, "n_strings is not the number of a document's terminators");
+        for (u32 r = lo; r < hi; r++) {
+            const u32 p = sa[r];
+            if (p < lo || p >= hi || seen[p]) east_throw(EAST_HIP_ERR_INVALID, "the suffix array is no permutation of a document's range");
+            seen[p] = 1;
+        }
+    }
+    u32 capped_in = 0;
+    if (table_in) {
+        for (int32_t d = 0; d < n_docs; d++)
+            if (table_in[doc_off[d]] & LCP_PARTIAL_BIT) east_throw(EAST_HIP_ERR_INVALID, "an unfinished entry at a document's first rank");
+        for (u32 r = 1; r < n; r++) {
+            if (!(table_in[r] & LCP_PARTIAL_BIT)) continue;
+            capped_in = 1;
+            const u32 k = table_in[r] & ~LCP_PARTIAL_BIT, later = std::max(sa[r], sa[r - 1]);
+            if (k > n - later) east_throw(EAST_HIP_ERR_INVALID, "an unfinished entry claims more than is left behind its suffixes");
+        }
+    }
+    const u32 padded = pyr_padded(n);
+    // text, suffix array, table, annotation, pyramid; rank, count, apos and the two lists of the finishing pass; the
+    // annotation pass's lists; and room behind everything for the look-ahead of a comparison at the stream's end
+    DebugScope sc(device, (size_t)n * 4 * 14 + 2 * (size_t)n_docs * 4 + (4u << 20));
+    Arena &ar = sc.arena;
+    HIP_CHECK(hipMemsetAsync(ar.base, pad_fill, ar.cap, sc.stream));
+    east_hip_index h;                   // (what direct_lcp() and finish_capped_lcp() read of a handle, and no more)
+    h.use_s8 = width == 1;
+    if (h.use_s8) {
+        h.s8 = ar.alloc<uint8_t>((size_t)n + 64);
+        HIP_CHECK(hipMemsetAsync(h.s8 + n, 0, 16, sc.stream));
+        HIP_CHECK(hipMemcpyAsync(h.s8, text, n, hipMemcpyHostToDevice, sc.stream));
+    } else {
+        h.s = ar.alloc<u32>((size_t)n + 3);
+        HIP_CHECK(hipMemsetAsync(h.s + n, 0, 12, sc.stream));
+        HIP_CHECK(hipMemcpyAsync(h.s, text, (size_t)n * 4, hipMemcpyHostToDevice, sc.stream));
+    }
+    h.sa = ar.alloc<u32>(n);
+    HIP_CHECK(hipMemcpyAsync(h.sa, sa, (size_t)n * 4, hipMemcpyHostToDevice, sc.stream));
+    std::vector<u32> start(padded, NONE_U32);          // (mode B: the padding as the direct pass leaves it)
+    if (table_in) memcpy(start.data(), table_in, (size_t)n * 4);
+    debug_table_handle(sc, h, start.data(), n, doc_off, n_docs, n_strings, table_in ? padded : 0u);
+    u32 *words = ar.alloc<u32>(3 + LCP_BUDGET_SLOTS);   // capped, the two counters, the budget's slots
+    u32 *capped = words, *counters = words + 1;
+    HIP_CHECK(hipMemsetAsync(words, 0, (3 + LCP_BUDGET_SLOTS) * 4, sc.stream));
+    if (table_in) {
+        HIP_CHECK(hipMemcpyAsync(capped, &capped_in, 4, hipMemcpyHostToDevice, sc.stream));
+        if (n_docs > 1)
+            LAUNCH(sc.ctx, lcp_doc_starts_kernel, ceil_div_u32(n_docs, BLOCK), (const u32 *)h.doc_off, (u32)n_docs, h.lcp);
+    } else {
+        sc.ctx.lcp_budget.slots = deep_per_slot < 0 ? nullptr : words + 3;
+        sc.ctx.lcp_budget.per_slot = deep_per_slot < 0 ? 0u : (u32)deep_per_slot;
+        direct_lcp(&h, sc.ctx, n, (u32)n_docs, false, capped);
+    }
+    HIP_CHECK(hipMemcpyAsync(direct_out, h.lcp, (size_t)padded * 4, hipMemcpyDeviceToHost, sc.stream));
+    HIP_CHECK(hipMemcpyAsync(capped_out, capped, 4, hipMemcpyDeviceToHost, sc.stream));
+    HIP_CHECK(hipStreamSynchronize(sc.stream));
+    if (*capped_out) finish_capped_lcp(&h, sc.ctx, counters);
+    else annotate(&h, sc.ctx);
+    HIP_CHECK(hipMemcpyAsync(final_out, h.lcp, (size_t)padded * 4, hipMemcpyDeviceToHost, sc.stream));
+    HIP_CHECK(hipMemcpyAsync(counters_out, counters, 8, hipMemcpyDeviceToHost, sc.stream));
+    HIP_CHECK(hipMemcpyAsync(ann_out, h.ann, (size_t)n * 4, hipMemcpyDeviceToHost, sc.stream));
+    HIP_CHECK(hipStreamSynchronize(sc.stream));
+    geometry_out[0] = LCP_SOFT_CAP;
+    geometry_out[1] = LCP_DIRECT_CAP;
+    geometry_out[2] = LCP_BUDGET_SLOTS;
+    geometry_out[3] = PHI_WAVE_STEPS * WAVE;
+    geometry_out[4] = PHI_LONG_THREADS;
+    geometry_out[5] = PYR_FAN;
 }
 
 // ---- radix sort, spine and scans in every form the library uses them in --------------------------------------------------
@@ -583,6 +695,17 @@ int east_hip_debug_child_tables(int device, const uint32_t *lcp, int64_t n, cons
 {
     return guarded([&] {
         debug_child_tables(device, lcp, n, doc_off, n_docs, n_strings, up_out, down_out, next_out, left_out, geometry_out, listed_out);
+    });
+}
+
+int east_hip_debug_lcp(int device, int width, const void *text, int64_t n, uint32_t term_first, const uint32_t *sa,
+                       const int64_t *doc_off, int32_t n_docs, const int32_t *n_strings, int32_t deep_per_slot,
+                       const uint32_t *table_in, int pad_fill, uint32_t *direct_out, uint32_t *capped_out, uint32_t *final_out,
+                       uint32_t *counters_out, uint32_t *ann_out, uint32_t *geometry_out)
+{
+    return guarded([&] {
+        debug_lcp(device, width, text, n, term_first, sa, doc_off, n_docs, n_strings, deep_per_slot, table_in, pad_fill, direct_out,
+                  capped_out, final_out, counters_out, ann_out, geometry_out);
     });
 }
 

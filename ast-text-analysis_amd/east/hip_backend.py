@@ -79,6 +79,9 @@ SIGNATURES = {
                                                _c_u32p, _c_u32p, _c_u32p]),
     "east_hip_debug_child_tables": (ctypes.c_int, [ctypes.c_int, _c_u32p, ctypes.c_int64, _c_i64p, ctypes.c_int32, _c_i32p,
                                                    _c_u32p, _c_u32p, _c_u32p, _c_u32p, _c_u32p, _c_u32p]),
+    "east_hip_debug_lcp": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint32, _c_u32p,
+                                          _c_i64p, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_u32p, ctypes.c_int, _c_u32p,
+                                          _c_u32p, _c_u32p, _c_u32p, _c_u32p, _c_u32p]),
     "east_hip_debug_radix_sort_ex": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, _c_u32p, ctypes.c_int64,
                                                     ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_i64p, ctypes.c_int32, _c_u32p]),
     "east_hip_debug_radix_spine": (ctypes.c_int, [ctypes.c_int, _c_u32p, ctypes.c_int64, _c_u32p, _c_i64p, ctypes.c_int32,

@@ -751,6 +751,26 @@ int east_hip_debug_annotate(int device, const uint32_t *lcp, int64_t n, const in
 int east_hip_debug_child_tables(int device, const uint32_t *lcp, int64_t n, const int64_t *doc_off, int32_t n_docs,
                                 const int32_t *n_strings, uint32_t *up_out, uint32_t *down_out, uint32_t *next_out,
                                 uint32_t *left_out, uint32_t *geometry_out, uint32_t *listed_out);
+/* Kernel-level test of the two passes that make the LCP table (csrc/build.h: direct_lcp -- lcp8_kernel / lcp_kernel,
+ * lcp_doc_starts_kernel --, finish_capped_lcp -- inverse_sa_kernel, lcp_phi_classify / compare / long_kernel, the anchors'
+ * scan, lcp_phi_anchors_kernel, lcp_phi_fill_kernel), on the caller's text and per-document suffix array.  width 1: text
+ * is the byte stream as a build holds it (text codes from 1, 0xFF = a terminator); width 4: dense u32 codes, text below
+ * term_first, the terminators ascending from term_first on.  sa[n]: positions in the shard, every document's ranks a
+ * permutation of its own range; doc_off / n_docs / n_strings as in east_hip_build.  deep_per_slot: the budget of deep
+ * comparisons per slot, -1 = none.  table_in == NULL (mode A): the direct pass runs; else (mode B) table_in[n] stands in
+ * its place, with LCP_PARTIAL_BIT | k (0x80000000 | k, the first k symbols known to agree) at any ranks but a document's
+ * first.  The finishing pass runs where `capped` is raised, as in a build.  pad_fill: the byte that everything behind the
+ * stream's zero pad (16 bytes / 3 words) holds before the run.  Anything wrong with an argument -- a suffix array that
+ * is no permutation, a document without a last terminator, a byte or code out of range, n_strings that is not the number
+ * of terminators, in mode B an unfinished entry at a document's first rank or k > n - max(sa[r - 1], sa[r]) -- is
+ * EAST_HIP_ERR_INVALID before a launch.  direct_out / final_out: ceil(n / 16) * 16 words, the table behind the direct
+ * and behind the finishing pass; capped_out: the flag word; counters_out[2]: positions listed as irreducible, positions
+ * handed to the long kernel; ann_out[n]: the annotation; geometry_out[6]: LCP_SOFT_CAP, LCP_DIRECT_CAP, LCP_BUDGET_SLOTS,
+ * PHI_WAVE_STEPS * WAVE, PHI_LONG_THREADS, PYR_FAN as compiled. */
+int east_hip_debug_lcp(int device, int width, const void *text, int64_t n, uint32_t term_first, const uint32_t *sa,
+                       const int64_t *doc_off, int32_t n_docs, const int32_t *n_strings, int32_t deep_per_slot,
+                       const uint32_t *table_in, int pad_fill, uint32_t *direct_out, uint32_t *capped_out, uint32_t *final_out,
+                       uint32_t *counters_out, uint32_t *ann_out, uint32_t *geometry_out);
 /*
  * Kernel-level tests of the radix sort, its spine and the scans in every form the library uses them in (csrc/radix_sort.h,
  * csrc/scan.h).  Every output buffer takes its elements AND a guard of EAST_HIP_DEBUG_GUARD elements behind them: on the
