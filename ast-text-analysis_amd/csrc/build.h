@@ -100,13 +100,13 @@ static void prepare_ht_code(east_hip_index *h, Ctx &ctx, u32 n, u32 sigma_t, u32
     ctx.ht_max_len = 0;
     if (ctx.dry || !h->use_s8 || !ctx.knobs.window_sort || ctx.knobs.ht_mode == 0) return;
     if (ctx.spec) {
-        if (!h->ht_valid || h->ht_sigma != sigma_t) {
+        if (!h->ht.valid || h->ht.sigma != sigma_t) {
             // (no code from the build before.  Forced -- the tests -- the build starts over with its read-backs in place and makes one)
             if (ctx.knobs.ht_mode == 1 && sigma_t + 1 >= 8 && n >= 64) throw SpecAbort();
             return;
         }
     } else {
-        h->ht_valid = false;
+        h->ht.valid = false;
         // (an alphabet of at most 5 bits -- letters only -- has nothing to gain: at best a fraction of a symbol per key)
         if (sigma_t + 1 < 8 || (ctx.knobs.ht_mode != 1 && (bit_width_u32(sigma_t + 1) < 6 || n < 65536)) || n < 64) return;
         Arena &ar = *ctx.arena;
@@ -124,24 +124,24 @@ static void prepare_ht_code(east_hip_index *h, Ctx &ctx, u32 n, u32 sigma_t, u32
         std::vector<uint16_t> dec;
         double mean_len = 0.0;
         if (!ht_make_tables(counts, sigma_t, m_total, enc, dec, &mean_len)) return;
-        if (!h->ht_tab.try_ensure(256 * 4 + HT_DEC_SIZE * 2)) return;
+        if (!h->ht.tab.try_ensure(256 * 4 + HT_DEC_SIZE * 2)) return;
         // (pageable host buffers: the copies are staged before the calls return)
-        HIP_CHECK(hipMemcpyAsync(h->ht_tab.p, enc.data(), 256 * 4, hipMemcpyHostToDevice, ctx.stream));
-        HIP_CHECK(hipMemcpyAsync(h->ht_tab.p + 256 * 4, dec.data(), HT_DEC_SIZE * 2, hipMemcpyHostToDevice, ctx.stream));
+        HIP_CHECK(hipMemcpyAsync(h->ht.tab.p, enc.data(), 256 * 4, hipMemcpyHostToDevice, ctx.stream));
+        HIP_CHECK(hipMemcpyAsync(h->ht.tab.p + 256 * 4, dec.data(), HT_DEC_SIZE * 2, hipMemcpyHostToDevice, ctx.stream));
         HIP_CHECK(sync_stream(ctx.stream));
         int longest = 0;
         for (u32 c = 0; c < 256; c++) longest = std::max(longest, (int)(enc[c] & 0xFFu));
-        h->ht_valid = true;
-        h->ht_sigma = sigma_t;
-        h->ht_max_len = longest;
-        h->ht_mean_len = mean_len;
+        h->ht.valid = true;
+        h->ht.sigma = sigma_t;
+        h->ht.max_len = longest;
+        h->ht.mean_len = mean_len;
         if (g_trace) fprintf(stderr, "[east_hip] variable-length code: %u symbols, %.2f bits per symbol on average, longest code word %d\n",
                              sigma_t + 1, mean_len, longest);
     }
-    ctx.ht_enc = h->ht_tab.as<const u32>();
-    ctx.ht_dec = (const uint16_t *)(h->ht_tab.p + 256 * 4);
-    ctx.ht_max_len = h->ht_max_len;
-    ctx.ht_mean_len = h->ht_mean_len;
+    ctx.ht_enc = h->ht.tab.as<const u32>();
+    ctx.ht_dec = (const uint16_t *)(h->ht.tab.p + 256 * 4);
+    ctx.ht_max_len = h->ht.max_len;
+    ctx.ht_mean_len = h->ht.mean_len;
 }
 
 // The direct pass over the LCP table where it did not come with the suffix array (fused_lcp): neighbouring suffixes
@@ -191,18 +191,7 @@ static void build_impl(east_hip_index *h, Ctx &ctx, const u32 *d_sym, u32 n, u32
     h->code_map = ar.alloc<u32>(TEXT_SYMBOLS + ZEROED_WORDS + 3 * TOTAL_WORDS);
     h->hi_bits = tagged ? ar.alloc<u32>(HI_WORDS) : nullptr;
     h->hi_rank = tagged ? ar.alloc<u32>(HI_WORDS) : nullptr;
-    Pyramid pyr;
-    pyr.levels = 1;
-    pyr.ptr[0] = h->lcp;
-    pyr.len[0] = n;
-    while (pyr.len[pyr.levels - 1] > PYR_FAN) {
-        if (pyr.levels >= PYR_MAX_LEVELS) east_throw(EAST_HIP_ERR_INTERNAL, "pyramid too deep");
-        const u32 len = ceil_div_u32(pyr.len[pyr.levels - 1], PYR_FAN);
-        pyr.ptr[pyr.levels] = ar.alloc<u32>(pyr_padded(len));
-        pyr.len[pyr.levels] = len;
-        pyr.levels++;
-    }
-    h->pyr = pyr;
+    h->pyr = pyramid_layout(ar, h->lcp, n);
     h->build_docs = n_docs;
 
     // ---- host-side small tables ---------------------------------------------
@@ -228,7 +217,7 @@ static void build_impl(east_hip_index *h, Ctx &ctx, const u32 *d_sym, u32 n, u32
     // block below; the sort takes them if it turns out to run that very pass (radix_sort_pairs), else counts itself.
     RsFirstHist first_hist;
     ctx.first_hist = nullptr;
-    const Ctx::FirstPassPlan fp = ctx.spec && ctx.knobs.first_hist && n_docs == 1 && !tagged ? h->first_plan : Ctx::FirstPassPlan();
+    const FirstPassPlan fp = ctx.spec && ctx.knobs.first_hist && n_docs == 1 && !tagged ? ctx.plan.first : FirstPassPlan();
     if (ctx.dry || fp.valid) {
         first_hist.n = n;
         first_hist.n_tiles = ceil_div_u32(n, RS_TILE);
@@ -364,7 +353,7 @@ static void build_impl(east_hip_index *h, Ctx &ctx, const u32 *d_sym, u32 n, u32
     // partition by document).
     bool window_sorted = false;
     const int doc_bits = n_docs > 1 ? bit_width_u32(n_docs - 1) : 0;
-    h->kg_marked = false;
+    h->kg.marked = false;
     prepare_ht_code(h, ctx, n, sigma_t, m_total);
     if ((h->use_s8 || ctx.dry) && ctx.knobs.window_sort) {       // (the sizing run prices it with 64-bit keys)
         DocKey docs;
@@ -381,15 +370,15 @@ static void build_impl(east_hip_index *h, Ctx &ctx, const u32 *d_sym, u32 n, u32
                 km.k++;
             }
             if (km.k > 0 && kgram_reserve(h, bins, n_docs)) {
-                km.kg = h->kg.as<u32>();
+                km.kg = h->kg.buf.as<u32>();
                 km.doc_off = h->doc_off;
                 km.n_docs = n_docs;
                 // (the pair layout: the level above the last in a table of its own, behind the 8-byte entries)
                 // (... where the score table has many columns: with a handful of long documents the 8-byte marks cost the
                 // build more than the few thousand walks of a score call get back; forced by the test knob)
                 if (ctx.knobs.kg_pairs && (n_docs >= 16 || ctx.knobs.kg_pairs_forced)) km.kg3 = km.kg + 2 * (size_t)(bins + 1) * n_docs;
-                h->kg3 = km.kg3;
-                h->kg_up = km.kg3 ? km.kg3 + (size_t)(bins / km.A + 1) * n_docs : nullptr;
+                h->kg.kg3 = km.kg3;
+                h->kg.up = km.kg3 ? km.kg3 + (size_t)(bins / km.A + 1) * n_docs : nullptr;
             } else {
                 km.k = 0;
             }
@@ -397,11 +386,11 @@ static void build_impl(east_hip_index *h, Ctx &ctx, const u32 *d_sym, u32 n, u32
         window_sorted = window_suffix_sort(ctx, h->s8, n, sigma_t + 1, h->sa, h->lcp, capped, docs, longest_doc,
                                            km.k > 0 ? &km : nullptr);
         if (window_sorted && km.k > 0) {                 // (km.k is 0 if the sort did not mark: small inputs)
-            h->kg_marked = true;
-            h->kg_pairs = km.pairs != 0;
-            h->kg_k = km.k;
-            h->kg_A = km.A;
-            h->kg_bins = km.bins;
+            h->kg.marked = true;
+            h->kg.pairs = km.pairs != 0;
+            h->kg.k = km.k;
+            h->kg.A = km.A;
+            h->kg.bins = km.bins;
         }
     }
     ctx.stats->window_sorted = window_sorted;
@@ -455,7 +444,7 @@ static void build_impl(east_hip_index *h, Ctx &ctx, const u32 *d_sym, u32 n, u32
     // (comparisons that hit the cap -- a repetitive input -- are found out about at the end of the build,
     // together with the status word: build_common then finishes those ranks and redoes the two steps below)
     annotate(h, ctx);
-    h->kg_built = false;
+    h->kg.built = false;
     h->child_built = false;      // childtab_up / down / next_l_index: built on first east_hip_get_tables request
 }
 
@@ -503,17 +492,11 @@ static size_t plan_arena_bytes(u32 n, u32 n_docs, bool lean = false, bool tagged
     size_t high = 0;
     for (int t = 0; t <= (tagged ? 1 : 0); t++) {
         east_hip_index tmp;
-        Arena dry;
-        dry.dry = true;
-        Stats st;
-        Ctx ctx;
-        if (knobs) ctx.knobs = *knobs;
-        ctx.arena = &dry;
-        ctx.dry = true;
-        ctx.lean = lean;
-        ctx.stats = &st;
-        build_impl(&tmp, ctx, nullptr, n, n_docs, nullptr, nullptr, 0, t == 1);
-        high = std::max(high, dry.high + (tagged ? 2 * (size_t)HI_WORDS * 4 + 1024 : 0));
+        SizingRun dry;
+        if (knobs) dry.ctx.knobs = *knobs;
+        dry.ctx.lean = lean;
+        build_impl(&tmp, dry.ctx, nullptr, n, n_docs, nullptr, nullptr, 0, t == 1);
+        high = std::max(high, dry.arena.high + (tagged ? 2 * (size_t)HI_WORDS * 4 + 1024 : 0));
     }
     return high + (1u << 20);
 }
@@ -537,6 +520,23 @@ static void ensure_arena(east_hip_index *h, size_t bytes)
     }
     h->arena.base = (char *)p;
     h->arena.cap = bytes;
+}
+
+// The plan of the next (speculative) build on the handle: what this build's window sort did, where it did well by it
+static SortPlan next_plan(const Stats &stats, const SortPlan &did)
+{
+    if (!stats.window_sorted) return SortPlan();
+    SortPlan plan = did;
+    // (hardly anything tied behind the wide window -- another kind of text on the same handle: back to the estimate)
+    if (did.wide && stats.first_n > 0 && stats.first_kept * 50 < stats.first_n) plan.wide = -1;
+    // (the same for the fused finish: it handed more than a few per cent of the suffixes to the rounds, or the separate
+    // placement pass left next to nothing -- another kind of text than the plan was made for: the next build decides anew)
+    if (stats.first_n > 0 && ((did.fused && stats.first_kept * 20 > stats.first_n) ||
+                              (!did.fused && stats.first_kept * 50 < stats.first_n)))
+        plan.fused = -1;
+    // (the first radix pass as this build ran it, for the next remap pass to count ahead: only while the plan it came from stands)
+    if (plan.wide < 0 || plan.fused < 0) plan.first = FirstPassPlan();
+    return plan;
 }
 
 static void check_build_args(i64 n_total, const i64 *doc_offsets, const int32_t *n_strings, int32_t n_docs)
@@ -577,14 +577,14 @@ static void build_common(east_hip_index *h, const u32 *sym, bool sym_on_host, i6
     const bool narrow = narrow_shape && h->ring != nullptr;
     const size_t narrow_bytes = narrow_shape ? (((size_t)n + 8) * 2 + 255) & ~(size_t)255 : 0;    // (also while the ring is still being pinned: the arena is sized once)
     const size_t staging_bytes = (sym_on_host ? ((size_t)n * 4 + 255) & ~(size_t)255 : 0) + narrow_bytes;
-    if (h->plan_n != n || h->plan_docs != (u32)n_docs || h->plan_epoch != kn.plan_epoch || h->plan_tagged != tagged) {     // (the sizing run costs host time: remembered per shape)
-        h->plan_bytes = plan_arena_bytes(n, (u32)n_docs, false, tagged, &kn);
-        h->plan_tagged = tagged;
-        h->plan_n = n;
-        h->plan_docs = (u32)n_docs;
-        h->plan_epoch = kn.plan_epoch;
+    if (h->sized.n != n || h->sized.docs != (u32)n_docs || h->sized.epoch != kn.plan_epoch || h->sized.tagged != tagged) {     // (the sizing run costs host time: remembered per shape)
+        h->sized.bytes = plan_arena_bytes(n, (u32)n_docs, false, tagged, &kn);
+        h->sized.tagged = tagged;
+        h->sized.n = n;
+        h->sized.docs = (u32)n_docs;
+        h->sized.epoch = kn.plan_epoch;
     }
-    size_t need = h->plan_bytes + staging_bytes;
+    size_t need = h->sized.bytes + staging_bytes;
     bool lean = kn.force_lean;
     if (!lean && need > h->arena.cap) {
         // the tie-refinement rounds are the largest consumer: when they do not fit next to what else
@@ -634,13 +634,10 @@ static void build_common(east_hip_index *h, const u32 *sym, bool sym_on_host, i6
     auto run = [&](bool spec, bool spec_rounds) -> bool {
         ctx.spec = spec;
         ctx.spec_rounds = spec && spec_rounds;
-        ctx.plan_wide = spec ? h->plan_wide : -1;        // (a build that waits for the alphabet plans from its own sample)
-        ctx.plan_fused = spec ? h->plan_fused : -1;
-        ctx.plan_ht = spec ? h->plan_ht : -1;
-        ctx.plan_persist = spec ? h->plan_persist : -1;
-        ctx.did_first = Ctx::FirstPassPlan();
+        ctx.plan = spec ? h->plan : SortPlan();          // (a build that waits for the alphabet plans from its own sample)
+        ctx.did.first = FirstPassPlan();
         try {
-            build_impl(h, ctx, sym, n, (u32)n_docs, doc_offsets, n_strings, h->hint_sigma, tagged);
+            build_impl(h, ctx, sym, n, (u32)n_docs, doc_offsets, n_strings, h->hint.sigma, tagged);
         } catch (const SpecAbort &) {
             HIP_CHECK(hipStreamSynchronize(h->stream));
             return false;
@@ -656,8 +653,8 @@ static void build_common(east_hip_index *h, const u32 *sym, bool sym_on_host, i6
     };
     HIP_CHECK(hipEventRecord(h->ev0, h->stream));
     // (the alphabet is guessed whenever the last build took the window sort; that no tie group is large only if it found none)
-    const bool speculate = kn.speculate && kn.window_sort && h->hint_valid && h->hint_window && h->hint_sigma <= 254 && !tagged;
-    const bool spec_rounds = speculate && h->hint_no_rounds;
+    const bool speculate = kn.speculate && kn.window_sort && h->hint.valid && h->hint.window && h->hint.sigma <= 254 && !tagged;
+    const bool spec_rounds = speculate && h->hint.no_rounds;
     const bool went_through = run(speculate, spec_rounds);
     const bool repeat = speculate && (!went_through || (flags[FLAG_STATUS] & STATUS_SIGMA_GUESS) ||
                                       (spec_rounds && (flags[FLAG_KEEP] || flags[FLAG_FAIL] || flags[FLAG_PLACE_FAIL])));
@@ -681,28 +678,16 @@ static void build_common(east_hip_index *h, const u32 *sym, bool sym_on_host, i6
         east_throw(EAST_HIP_ERR_DOMAIN, tagged ? "n_strings does not match the tagged terminators found in a document"
                                                : "n_strings does not match the terminators found in a document "
                                                  "(text symbols must be < U+0A00 unless the terminators are tagged)");
-    if (flags[FLAG_KG_BAD]) h->kg_marked = false;    // (the score side then builds its k-gram tables itself)
-    h->hint_valid = !tagged || h->sigma_hi == 0;
-    h->hint_sigma = h->sigma_t;
-    h->hint_window = h->stats.window_sorted != 0;
-    h->plan_wide = h->stats.window_sorted ? ctx.did_wide : -1;
-    // (hardly anything tied behind the wide window -- another kind of text on the same handle: back to the estimate)
-    if (ctx.did_wide && h->stats.first_n > 0 && h->stats.first_kept * 50 < h->stats.first_n) h->plan_wide = -1;
-    h->plan_fused = h->stats.window_sorted ? ctx.did_fused : -1;
-    h->plan_ht = h->stats.window_sorted ? ctx.did_ht : -1;
-    h->plan_persist = h->stats.window_sorted ? ctx.did_persist : -1;
-    // (the same for the fused finish: it handed more than a few per cent of the suffixes to the rounds, or the separate
-    // placement pass left next to nothing -- another kind of text than the plan was made for: the next build decides anew)
-    if (h->stats.first_n > 0 && ((ctx.did_fused && h->stats.first_kept * 20 > h->stats.first_n) ||
-                                 (!ctx.did_fused && h->stats.first_kept * 50 < h->stats.first_n)))
-        h->plan_fused = -1;
-    // (the first radix pass as this build ran it, for the next remap pass to count ahead: only while the plan it came from stands)
-    h->first_plan = h->stats.window_sorted && h->plan_wide >= 0 && h->plan_fused >= 0 ? ctx.did_first : Ctx::FirstPassPlan();
-    h->hint_no_rounds = h->stats.window_sorted && h->stats.refine_rounds == 0 && !h->stats.long_repeats;
+    if (flags[FLAG_KG_BAD]) h->kg.marked = false;    // (the score side then builds its k-gram tables itself)
+    h->hint.valid = !tagged || h->sigma_hi == 0;
+    h->hint.sigma = h->sigma_t;
+    h->hint.window = h->stats.window_sorted != 0;
+    h->plan = next_plan(h->stats, ctx.did);
+    h->hint.no_rounds = h->stats.window_sorted && h->stats.refine_rounds == 0 && !h->stats.long_repeats;
     h->prof.collect();
     HIP_CHECK(hipEventElapsedTime(&h->last_build_ms, h->ev0, h->ev1));
     h->n = n;
-    if (h->n_docs != (u32)n_docs) h->n_kp = 0;       // resident keyphrase scratch is sized per n_docs
+    if (h->n_docs != (u32)n_docs) h->kp.n_kp = 0;       // resident keyphrase scratch is sized per n_docs
     h->n_docs = (u32)n_docs;
     h->h_doc_off.assign(doc_offsets, doc_offsets + n_docs + 1);
     h->h_n_strings.assign(n_strings, n_strings + n_docs);

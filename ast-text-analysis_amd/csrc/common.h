@@ -248,6 +248,24 @@ template <class F> static inline void knobs_update(F f)
     f(g_knobs);
 }
 
+// The first radix pass of the window sort's first level, for the next build's remap pass to count ahead (radix_sort.h: RsFirstHist)
+struct FirstPassPlan {
+    bool valid = false;                     // fixed-width keys of text only: no document number, not segmented, all suffixes
+    int key_bytes = 0, w = 0, b = 0, spare = 0, shift = 0;
+    u32 term_first = 0, mask = 0;
+};
+
+// What the all-suffix window sort decides for itself unless it is told.  As a plan (Ctx::plan, the handle's): -1 = decide
+// from the sample / the estimates, 0 / 1 / 2 = do as the build before did.  As a record (Ctx::did): what this build did.
+struct SortPlan {
+    int wide = -1;                          // the wide first window
+    int fused = -1;                         // the fused finish (2: with the small halo)
+    int ht = -1;                            // first-level keys of variable-length code words (ht_code.h; 2: in the wide window)
+    int persist = -1;                       // the first domain went to the persistent rounds at once (repetitive text: persist_rounds.h)
+    FirstPassPlan first;                    // the first radix pass of the first level
+    static SortPlan nothing() { SortPlan p; p.wide = p.fused = p.ht = p.persist = 0; return p; }     // (a record starts here)
+};
+
 struct Ctx {
     Knobs knobs = knobs_snapshot();         // the test knobs as they stood when the call began
     hipStream_t stream = nullptr;
@@ -269,33 +287,42 @@ struct Ctx {
     // Speculative build: the first level's first radix pass as the build before ran it (FirstPassPlan), and -- where the
     // remap pass counted that pass's histogram ahead -- the counts for the sort to take (radix_sort.h: RsFirstHist)
     const struct RsFirstHist *first_hist = nullptr;
-    struct FirstPassPlan {
-        bool valid = false;                 // fixed-width keys of text only: no document number, not segmented, all suffixes
-        int key_bytes = 0, w = 0, b = 0, spare = 0, shift = 0;
-        u32 term_first = 0, mask = 0;
-    } did_first;                            // out: what the all-suffix window sort's first pass was
     u32 *kg_bad = nullptr;      // raised by the fused finish when the k-gram marks it writes are incomplete (a bucket handed to the rounds)
     // What the sample of the build's own text says (sample_prefix_kernel; a handle's first build and every build that
     // waits for the alphabet): of sample_n consecutive suffixes, sample_dup2[l] / sample_dup4[l] share their first
     // l symbols with at least 1 / 3 others of the sample.  sample_n == 0: no sample (speculative build: the plan of
-    // the build before is taken instead -- plan_wide / plan_fused).
+    // the build before is taken instead -- plan.wide / plan.fused).
     u32 sample_n = 0, sample_dup2[9] = {0}, sample_dup4[9] = {0};
     u32 rep_n = 0, rep_dup = 0;             // "is the text repetitive?": of rep_n sample suffixes, rep_dup share 8 symbols with three others (also from samples too small to plan from)
-    int plan_wide = -1, plan_fused = -1;    // -1 = decide from the sample / the estimates; 0 / 1 = as the build before did
-    int did_wide = 0, did_fused = 0;        // out: what the all-suffix window sort did (the next speculative build's plan)
+    SortPlan plan;                          // in: -1 = decide from the sample / the estimates; 0 / 1 / 2 = as the build before did
+    SortPlan did = SortPlan::nothing();     // out: what the all-suffix window sort did (the next speculative build's plan)
     // An order-preserving variable-length code for the text's symbols is at hand (ht_code.h; ht_max_len > 0): the device
     // tables, the longest code word and the mean code word length over the text (bits per symbol)
     const u32 *ht_enc = nullptr;
     const uint16_t *ht_dec = nullptr;
     int ht_max_len = 0;
     double ht_mean_len = 0.0;
-    int plan_ht = -1, did_ht = 0;           // first-level keys of variable-length code words: plan (as plan_wide) / what was done
-    int plan_persist = -1, did_persist = 0; // the first domain went to the persistent rounds at once (repetitive text: persist_rounds.h)
     int did_seg = 0;                        // the first-level sort kept the documents apart by segments, not by key bits
     std::vector<u32> seg_host;              // ... its tables on the host (the uploads are asynchronous)
     LcpBudget lcp_budget;                   // the build's budget of deep LCP comparisons (LCP_SOFT_CAP)
     Stats *stats = nullptr;
     Profiler *prof = nullptr;
+};
+
+// A sizing run: the host orchestration runs on ctx with nothing backed by memory, arena.high is what it would have taken
+// (a build's arena, a test entry point's scope: measured with the very code that then runs in it)
+struct SizingRun {
+    Arena arena;
+    Stats stats;
+    Ctx ctx;
+    SizingRun()
+    {
+        arena.dry = true;
+        ctx.arena = &arena;
+        ctx.dry = true;
+        ctx.stats = &stats;
+    }
+    SizingRun(const SizingRun &) = delete;
 };
 
 // Wait for a stream the way the build's read-backs want it: they sit between kernels a few microseconds long, and a

@@ -140,7 +140,7 @@ static TableRef resolve_table(const east_hip_index *h, int32_t source, const Upl
     TableRef t;
     const char *missing = nullptr;
     if (source == EAST_HIP_GRAPH_SOURCE_AST) {
-        if (h->built && h->table_scored) { t.p = h->table; t.K = h->n_kp; t.D = h->n_docs; }
+        if (h->built && h->table_scored) { t.p = h->kp.table; t.K = h->kp.n_kp; t.D = h->n_docs; }
         missing = ": no score table is resident (score the keyphrases first)";
     } else if (source == EAST_HIP_GRAPH_SOURCE_UPLOADED) {
         if (own) t = own->ref();

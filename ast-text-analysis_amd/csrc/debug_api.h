@@ -108,16 +108,7 @@ static void debug_table_handle(DebugScope &sc, east_hip_index &h, const u32 *lcp
     h.doc_off = ar.alloc<u32>((size_t)n_docs + 1);
     h.n_strings = ar.alloc<u32>(n_docs);
     h.build_docs = (u32)n_docs;
-    Pyramid &pyr = h.pyr;
-    pyr.levels = 1;
-    pyr.ptr[0] = h.lcp;
-    pyr.len[0] = n;
-    while (pyr.len[pyr.levels - 1] > PYR_FAN) {
-        const u32 len = ceil_div_u32(pyr.len[pyr.levels - 1], PYR_FAN);
-        pyr.ptr[pyr.levels] = ar.alloc<u32>(pyr_padded(len));
-        pyr.len[pyr.levels] = len;
-        pyr.levels++;
-    }
+    h.pyr = pyramid_layout(ar, h.lcp, n);
     // (the table's padding and the annotation start out as something no result is: the pass writes both)
     HIP_CHECK(hipMemsetAsync(h.lcp, 0x5A, (size_t)pyr_padded(n) * 4, sc.stream));
     HIP_CHECK(hipMemsetAsync(h.ann, 0xEE, (size_t)n * 4, sc.stream));
@@ -387,15 +378,9 @@ static void debug_sort_ex(int device, K *keys, u32 *vals, i64 n64, int bits, int
         r = radix_sort_pairs<K>(ctx, sb, n, bits, begin_bit, NoGen(), check_from_bit, seg);
     };
     // (the arena is measured with the same code, then the sort runs in it)
-    Arena dry;
-    dry.dry = true;
-    Stats st;
-    Ctx dctx;
-    dctx.arena = &dry;
-    dctx.dry = true;
-    dctx.stats = &st;
-    run(dctx);
-    DebugScope sc(device, dry.high + (8u << 20));
+    SizingRun dry;
+    run(dry.ctx);
+    DebugScope sc(device, dry.arena.high + (8u << 20));
     run(sc.ctx);
     // (a write behind the end of the pair of buffers the result is not in shows in the result's guard as well)
     std::vector<K> gk(DBG_GUARD);
@@ -799,17 +784,11 @@ int east_hip_debug_suffix_array(int device, const uint32_t *symbols, int64_t n, 
         for (i64 i = 0; i < n; i++)
             if (symbols[i] < 1 || symbols[i] > sigma) east_throw(EAST_HIP_ERR_INVALID, "symbol outside [1, sigma]");
         // measure the arena with the same code path, then run it
-        Arena dry;
-        dry.dry = true;
-        Stats st;
-        Ctx dctx;
-        dctx.arena = &dry;
-        dctx.dry = true;
-        dctx.stats = &st;
-        (void)dry.alloc<u32>((size_t)n + 3);
-        (void)dry.alloc<u32>(n);
-        dc3_suffix_array(dctx, nullptr, (u32)n, (u32)std::max<i64>(n, sigma), nullptr);
-        DebugScope sc(device, dry.high + (8u << 20));
+        SizingRun dry;
+        (void)dry.arena.alloc<u32>((size_t)n + 3);
+        (void)dry.arena.alloc<u32>(n);
+        dc3_suffix_array(dry.ctx, nullptr, (u32)n, (u32)std::max<i64>(n, sigma), nullptr);
+        DebugScope sc(device, dry.arena.high + (8u << 20));
         u32 *s = sc.arena.alloc<u32>((size_t)n + 3), *sa = sc.arena.alloc<u32>(n);
         HIP_CHECK(hipMemsetAsync(s + n, 0, 12, sc.stream));
         HIP_CHECK(hipMemcpyAsync(s, symbols, (size_t)n * 4, hipMemcpyHostToDevice, sc.stream));

@@ -225,10 +225,10 @@ int east_hip_score_resident(east_hip_handle_t h, int normalized, double *d_out)
         // A small table goes to the caller's block from the score kernels themselves (every score written twice: a copy's
         // launch costs more than its bytes).  A large one is copied behind the walk: its 8-byte stores are the strided side
         // of the kernel, and doubling them cost 29 us at 10 000 x 256 where the copy takes 13.
-        const bool direct = d_out && h && (u64)h->n_kp * h->n_docs <= SCORE_DIRECT_OUT_MAX;
+        const bool direct = d_out && h && (u64)h->kp.n_kp * h->n_docs <= SCORE_DIRECT_OUT_MAX;
         score_resident(h, normalized, nullptr, nullptr, direct ? d_out : nullptr);
         if (d_out && !direct)
-            HIP_CHECK(hipMemcpyAsync(d_out, h->table, (size_t)h->n_kp * h->n_docs * 8, hipMemcpyDeviceToDevice,
+            HIP_CHECK(hipMemcpyAsync(d_out, h->kp.table, (size_t)h->kp.n_kp * h->n_docs * 8, hipMemcpyDeviceToDevice,
                                      h->stream));
         HIP_CHECK(hipStreamSynchronize(h->stream));
         HIP_CHECK(hipEventElapsedTime(&h->last_score_ms, h->ev0, h->ev1));
@@ -239,9 +239,9 @@ int east_hip_score_probes(east_hip_handle_t h, int normalized, int64_t *probes)
 {
     return guarded([&] {
         if (!h || !probes) east_throw(EAST_HIP_ERR_INVALID, "null handle or output");
-        if (!h->n_kp) east_throw(EAST_HIP_ERR_INVALID, "no keyphrases set");
+        if (!h->kp.n_kp) east_throw(EAST_HIP_ERR_INVALID, "no keyphrases set");
         use_device(h);
-        unsigned long long *d_count = h->q_buf.as<unsigned long long>();
+        unsigned long long *d_count = h->kp.buf.as<unsigned long long>();
         HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(unsigned long long), h->stream));
         score_resident(h, normalized, d_count);
         unsigned long long c = 0;
@@ -263,7 +263,7 @@ int east_hip_score_table(east_hip_handle_t h, const uint32_t *q_symbols, const i
         if (!out) east_throw(EAST_HIP_ERR_INVALID, "null output table");
         set_keyphrases(h, q_symbols, q_offsets, n_keyphrases);
         score_resident(h, normalized, nullptr, suffix_out);
-        HIP_CHECK(hipMemcpyAsync(out, h->table, (size_t)h->n_kp * h->n_docs * 8, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipMemcpyAsync(out, h->kp.table, (size_t)h->kp.n_kp * h->n_docs * 8, hipMemcpyDeviceToHost, h->stream));
         HIP_CHECK(hipStreamSynchronize(h->stream));
         HIP_CHECK(hipEventElapsedTime(&h->last_score_ms, h->ev0, h->ev1));
     });
@@ -282,13 +282,13 @@ int east_hip_score_table_grouped(east_hip_handle_t h, const uint32_t *q_symbols,
         set_keyphrases(h, q_symbols, q_offsets, n_queries);
         std::vector<u32> goff((size_t)n_groups + 1);
         for (int32_t g = 0; g <= n_groups; g++) goff[g] = (u32)group_offsets[g];
-        HIP_CHECK(hipMemcpyAsync(h->group_off, goff.data(), goff.size() * 4, hipMemcpyHostToDevice, h->stream));
+        HIP_CHECK(hipMemcpyAsync(h->kp.group_off, goff.data(), goff.size() * 4, hipMemcpyHostToDevice, h->stream));
         score_resident(h, normalized);
         Ctx ctx = handle_ctx(h);
-        LAUNCH(ctx, score_group_max_kernel, ceil_div_u32((u64)n_groups * h->n_docs, BLOCK), (const double *)h->table,
-               (const u32 *)h->group_off, (u32)n_groups, h->n_docs, h->table_g);
+        LAUNCH(ctx, score_group_max_kernel, ceil_div_u32((u64)n_groups * h->n_docs, BLOCK), (const double *)h->kp.table,
+               (const u32 *)h->kp.group_off, (u32)n_groups, h->n_docs, h->kp.table_g);
         HIP_CHECK(hipEventRecord(h->ev1, h->stream));
-        HIP_CHECK(hipMemcpyAsync(out, h->table_g, (size_t)n_groups * h->n_docs * 8, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipMemcpyAsync(out, h->kp.table_g, (size_t)n_groups * h->n_docs * 8, hipMemcpyDeviceToHost, h->stream));
         HIP_CHECK(hipStreamSynchronize(h->stream));       // (also covers goff)
         HIP_CHECK(hipEventElapsedTime(&h->last_score_ms, h->ev0, h->ev1));
     });
@@ -319,27 +319,25 @@ int east_hip_reset(east_hip_handle_t h)
         if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
         use_device(h);
         HIP_CHECK(hipStreamSynchronize(h->stream));
-        h->built = false;
-        h->table_scored = false;
-        h->n = 0;
-        h->n_docs = 0;
-        h->n_kp = 0;
-        h->n_q = 0;
-        h->q_code_epoch = 0;
-        h->kg_built = false;
-        h->child_built = false;
+        // the index and the prepared texts are gone, the handle takes the reference encoding and does not profile
+        h->built = h->child_built = h->table_scored = false;
+        h->n = h->n_docs = h->sigma_hi = 0;
         h->prep_n = 0;
         h->prep_doc_off.clear();
         h->prep_n_strings.clear();
-        h->prep_tagged = false;
-        h->tagged_input = false;
-        h->sigma_hi = 0;
+        h->prep_tagged = h->tagged_input = false;
         h->prof.enabled = false;
         h->prof.only.clear();
-        h->plan_wide = h->plan_fused = h->plan_ht = h->plan_persist = -1;
-        h->first_plan = Ctx::FirstPassPlan();
-        h->ht_valid = false;
         h->stats = Stats();
+        // Every group forgets what it holds and keeps its allocation (handle.h).  The plan goes, the hints stay: the next
+        // owner's first build speculates on this one's alphabet as a second build on one handle would (hip_backend.py's
+        // handle pool counts on it), but decides its sort anew.  What else stays costs time to make and says nothing about
+        // an index -- the sizing cache, the upload ring with bytes_refused, the Unicode tables, the alphabet guess --, only
+        // ever advances (map_epoch) or reports the last call (last_*_ms, narrow_upload)
+        h->plan = SortPlan();
+        h->kp.forget();
+        h->kg.forget();
+        h->ht.forget();
         // a recycled handle keeps its stream and a small arena, not gigabytes of side allocations
         const size_t keep = (size_t)64 << 20;
         for (DevBuf *b : h->bufs)

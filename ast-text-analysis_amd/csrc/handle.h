@@ -30,44 +30,62 @@ struct east_hip_index {
     u32 *s = nullptr, *sa = nullptr, *lcp = nullptr, *ann = nullptr, *up = nullptr, *down = nullptr,
         *next = nullptr, *doc_off = nullptr, *n_strings = nullptr, *code_map = nullptr;
     Pyramid pyr;
+    // what the last successful build found, the guesses of the next (speculative) one.  The hints say whether and how far
+    // to speculate; east_hip_reset KEEPS them -- a recycled handle's first build speculates on its previous owner's text
+    // as a second build on one handle would (the device checks the guess, a wrong one costs a second build)
+    struct Hints {
+        bool valid = false;
+        u32 sigma = 0;                     // the size of the text alphabet
+        bool window = false;               // the window sort took it
+        bool no_rounds = false;            // ... and left no suffix in a large tie group
+    } hint;
+    // ... and what that build's window sort did, first radix pass included: a speculative build does the same (build.h:
+    // next_plan).  east_hip_reset forgets it: a plan is worth following only on the kind of text it was made on
+    SortPlan plan;
     u32 build_docs = 0;          // documents of the build in progress (h->n_docs is set when it has succeeded)
-    // what the last successful build found, the guesses of the next (speculative) one
-    bool hint_valid = false, hint_no_rounds = false, hint_window = false;
-    int plan_wide = -1, plan_fused = -1;   // what the last build's window sort did (wide first window, fused finish): a speculative build does the same
-    int plan_ht = -1;                      // ... (first-level keys of variable-length code words)
-    int plan_persist = -1;                 // ... (the first domain went straight to the persistent rounds)
-    Ctx::FirstPassPlan first_plan;         // ... (the first radix pass of its first level: what the next remap pass counts ahead)
     // the order-preserving variable-length code of the last build that made one (ht_code.h): device tables (own
-    // allocation: 256 x u32 enc, 4096 x u16 dec), valid for text with ht_sigma text symbols
-    DevBuf ht_tab;
-    bool ht_valid = false;
-    u32 ht_sigma = 0;
-    int ht_max_len = 0;
-    double ht_mean_len = 0.0;
-    u32 hint_sigma = 0;
-    u32 plan_n = 0, plan_docs = 0, plan_epoch = 0;
-    bool plan_tagged = false;   // shape of the last sizing run (and test-knob epoch), its result
-    size_t plan_bytes = 0;
-    // keyphrases + score scratch (own allocation, grown on demand)
-    DevBuf q_buf;
-    u32 n_kp = 0, n_q = 0, score_chunk = 0;     // score_chunk: documents per stretch the scratch was sized for
-    u32 *q_raw = nullptr, *q_code = nullptr, *q_end = nullptr, *q_off = nullptr, *group_off = nullptr;
+    // allocation: 256 x u32 enc, 4096 x u16 dec), valid for text with `sigma` text symbols
+    struct HtCode {
+        DevBuf tab;
+        bool valid = false;
+        u32 sigma = 0;
+        int max_len = 0;
+        double mean_len = 0.0;
+        void forget() { const DevBuf keep = tab; *this = HtCode(); tab = keep; }
+    } ht;
+    // the last sizing run (build.h: plan_arena_bytes): its shape and test-knob epoch, its result.  Kept by east_hip_reset
+    struct Sized {
+        u32 n = 0, docs = 0, epoch = 0;
+        bool tagged = false;
+        size_t bytes = 0;
+    } sized;
+    // the resident keyphrases + score scratch (own allocation, grown on demand; laid out by set_keyphrases_device)
+    struct Keyphrases {
+        DevBuf buf;
+        u32 n_kp = 0, n_q = 0, score_chunk = 0;     // score_chunk: documents per stretch the scratch was sized for
+        u32 *q_raw = nullptr, *q_code = nullptr, *q_end = nullptr, *q_off = nullptr, *group_off = nullptr;
+        u64 q_code_epoch = 0;        // the map_epoch (below) q_code was made under (0: not made -- new keyphrases)
+        u32 *q_blk = nullptr;        // whole keyphrases per workgroup of the score walk: [q_blk[i], q_blk[i + 1]), n_blk of them
+        u32 n_blk = 0;               // (0: a keyphrase is longer than a workgroup -- the walk writes per-suffix results, a second kernel sums)
+        double *suffix = nullptr, *table = nullptr, *table_g = nullptr;
+        void forget() { const DevBuf keep = buf; *this = Keyphrases(); buf = keep; }
+    } kp;
     // q_code is a function of the resident keyphrases and the code map: map_epoch advances with every build that may have
-    // changed the map (all but a speculative build whose alphabet guess was confirmed: same presence bitmap, same map),
-    // q_code_epoch is the epoch q_code was made under (0: not made -- new keyphrases)
-    u64 map_epoch = 1, q_code_epoch = 0;
-    u32 *q_blk = nullptr;        // whole keyphrases per workgroup of the score walk: [q_blk[i], q_blk[i + 1]), n_blk of them
-    u32 n_blk = 0;               // (0: a keyphrase is longer than a workgroup -- the walk writes per-suffix results, a second kernel sums)
-    double *suffix = nullptr, *table = nullptr, *table_g = nullptr;
+    // changed the map (all but a speculative build whose alphabet guess was confirmed: same presence bitmap, same map).
+    // It only ever advances: no reset puts it back
+    u64 map_epoch = 1;
     // k-gram bucket tables for the score walk (own allocation, rebuilt after every build)
-    DevBuf kg;
-    int kg_k = 0;
-    u32 kg_A = 0, kg_bins = 0;
-    bool kg_built = false;
-    bool kg_marked = false;      // the bucket starts were written by the build (off the window keys): only the fill is due
-    bool kg_pairs = false;       // ... in the pair layout (score.h: KgTables); kg3 = the table of the levels above the last,
-    u32 *kg3 = nullptr, *kg_up = nullptr;        // kg_up = the small tables of the levels above kg3's own
-    u32 kg_up_stride = 0;
+    struct Kgram {
+        DevBuf buf;
+        int k = 0;
+        u32 A = 0, bins = 0;
+        bool built = false;
+        bool marked = false;         // the bucket starts were written by the build (off the window keys): only the fill is due
+        bool pairs = false;          // ... in the pair layout (score.h: KgTables); kg3 = the table of the levels above the last,
+        u32 *kg3 = nullptr, *up = nullptr;           // up = the small tables of the levels above kg3's own
+        u32 up_stride = 0;
+        void forget() { const DevBuf keep = buf; *this = Kgram(); buf = keep; }
+    } kg;
     float last_build_ms = -1.f, last_score_ms = -1.f, last_prep_ms = -1.f;
     // the caller's Unicode tables of the device text preparation (own allocation, re-uploaded when their hash changes)
     DevBuf tp_tables;
@@ -101,7 +119,8 @@ struct east_hip_index {
     enum { SLOT_COS, SLOT_GRAPH, SLOT_SYN, SLOT_TOP, SLOT_SIM, SLOT_REL, SLOT_COSTEXT, SLOT_CLU, N_CONSUMERS };
     Consumer *consumers[N_CONSUMERS] = {};
     // the handle's own device allocations besides the arena: east_hip_destroy frees them, east_hip_reset the large ones
-    DevBuf *bufs[6] = {&guess, &ht_tab, &q_buf, &kg, &tp_tables, &prep_sym};
+    // (a DevBuf has no destructor: the groups' forget() carries theirs over)
+    DevBuf *bufs[6] = {&guess, &ht.tab, &kp.buf, &kg.buf, &tp_tables, &prep_sym};
 };
 
 struct SpecAbort {};             // a speculative build cannot go on: build_common starts over with the read-backs in place

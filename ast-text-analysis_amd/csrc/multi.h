@@ -221,7 +221,7 @@ static void group_allgather(east_hip_group *g, u32 K)
         const u32 Ds = (u32)(g->first_doc[s + 1] - g->first_doc[s]);
         if (Ds) {
             hipLaunchKernelGGL(group_pad_kernel, dim3(ceil_div_u32((u64)K * width, BLOCK)), dim3(BLOCK), 0, h->stream,
-                               (const double *)h->table, K, Ds, width, g->buf[s].send.as<double>());
+                               (const double *)h->kp.table, K, Ds, width, g->buf[s].send.as<double>());
             HIP_CHECK(hipGetLastError());
         } else {
             HIP_CHECK(hipMemsetAsync(g->buf[s].send.p, 0, block, h->stream));

@@ -203,8 +203,8 @@ static void rel_build(east_hip_index *h, int normalized, int32_t orientation, i6
     RelState &g = consumer_begin<RelState>(h);
     // the handle's resident keyphrases are replaced, its score table withdrawn -- whatever becomes of this call
     h->table_scored = false;
-    h->q_code_epoch = 0;
-    h->n_kp = h->n_q = 0;
+    h->kp.q_code_epoch = 0;
+    h->kp.n_kp = h->kp.n_q = 0;
     const u32 D = h->n_docs, n = h->n, m = h->m_total;
     u64 m_sum = 0;
     for (u32 d = 0; d < D; d++) m_sum += h->h_n_strings[d];
@@ -316,7 +316,7 @@ static void rel_build(east_hip_index *h, int normalized, int32_t orientation, i6
     }
     const u32 most_tiles = std::min(chunk_tiles, NT);
     if (!g.partial.try_ensure((size_t)most_tiles * D * 8 + 256, h->stream)) rel_oom("a chunk's partial sums", (double)most_tiles * D * 8.0);
-    if (!h->q_buf.try_ensure(q_bytes, h->stream)) rel_oom("a chunk's score table", (double)q_bytes);
+    if (!h->kp.buf.try_ensure(q_bytes, h->stream)) rel_oom("a chunk's score table", (double)q_bytes);
     u32 *d_tile_row = da.alloc<u32>(tile_row.size()), *d_doc_tile = da.alloc<u32>(doc_tile.size()),
         *d_blk = da.alloc<u32>(std::max<size_t>(blk_all.size(), 1));
     HIP_CHECK(hipMemcpyAsync(d_tile_row, tile_row.data(), tile_row.size() * 4, hipMemcpyHostToDevice, h->stream));
@@ -330,24 +330,24 @@ static void rel_build(east_hip_index *h, int normalized, int32_t orientation, i6
     for (const Chunk &c : chunks) {
         set_keyphrases_device(h, c.K, c.n_q, c.n_blk, kn, [&] {
             if (c.n_blk)
-                HIP_CHECK(hipMemcpyAsync(h->q_blk, d_blk + c.blk0, ((size_t)c.n_blk + 1) * 4, hipMemcpyDeviceToDevice, h->stream));
+                HIP_CHECK(hipMemcpyAsync(h->kp.q_blk, d_blk + c.blk0, ((size_t)c.n_blk + 1) * 4, hipMemcpyDeviceToDevice, h->stream));
             const u32 grid = ceil_div_u32(std::max(c.j1 - c.j0, 1u), BLOCK);
             if (h->use_s8)
                 LAUNCH_NAMED(ctx, "rel_feed_kernel", rel_feed_kernel<uint8_t>, grid, (const uint8_t *)h->s8, (const u32 *)d_end, (const u32 *)d_len,
-                             (const u32 *)d_q, (const u32 *)d_rank, c.j0, c.j1, c.g0, c.Q0, c.K, c.n_q, space, h->q_code, h->q_end, h->q_off);
+                             (const u32 *)d_q, (const u32 *)d_rank, c.j0, c.j1, c.g0, c.Q0, c.K, c.n_q, space, h->kp.q_code, h->kp.q_end, h->kp.q_off);
             else
                 LAUNCH_NAMED(ctx, "rel_feed_kernel", rel_feed_kernel<u32>, grid, (const u32 *)h->s, (const u32 *)d_end, (const u32 *)d_len,
-                             (const u32 *)d_q, (const u32 *)d_rank, c.j0, c.j1, c.g0, c.Q0, c.K, c.n_q, space, h->q_code, h->q_end, h->q_off);
-            h->q_code_epoch = h->map_epoch;                   // (q_code holds dense codes already: no query_map_kernel)
+                             (const u32 *)d_q, (const u32 *)d_rank, c.j0, c.j1, c.g0, c.Q0, c.K, c.n_q, space, h->kp.q_code, h->kp.q_end, h->kp.q_off);
+            h->kp.q_code_epoch = h->map_epoch;                   // (q_code holds dense codes already: no query_map_kernel)
         });
         score_resident(h, normalized);
-        LAUNCH(ctx, rel_reduce_kernel, (c.t1 - c.t0) * strips, (const double *)h->table, D, (const u32 *)d_tile_row, c.t0, c.g0, strips, partial);
+        LAUNCH(ctx, rel_reduce_kernel, (c.t1 - c.t0) * strips, (const double *)h->kp.table, D, (const u32 *)d_tile_row, c.t0, c.g0, strips, partial);
         const u32 n_d = c.d_hi - c.d_lo + 1u;
         LAUNCH(ctx, rel_fold_kernel, (u32)std::min<u64>(((u64)n_d * D + BLOCK - 1) / BLOCK, REL_MAX_GRID), (const double *)partial, D, (const u32 *)d_doc_tile, c.t0, c.t1, c.d_lo,
                n_d, g.matrix);
         h->table_scored = false;
-        h->q_code_epoch = 0;
-        h->n_kp = h->n_q = 0;
+        h->kp.q_code_epoch = 0;
+        h->kp.n_kp = h->kp.n_q = 0;
     }
     LAUNCH(ctx, rel_finish_kernel, (u32)std::min<u64>(((u64)D * D + BLOCK - 1) / BLOCK, REL_MAX_GRID), g.matrix, D, (const int32_t *)g.count, (int)(orientation == EAST_HIP_RELATED_SYMMETRIC),
            g.per_member);

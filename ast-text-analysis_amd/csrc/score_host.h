@@ -27,25 +27,25 @@ template <class Fill>
 static void set_keyphrases_device(east_hip_index *h, u32 n_kp, u32 n_q, u32 n_blk, const Knobs &kn, Fill fill)
 {
     h->table_scored = false;
-    h->q_code_epoch = 0;
-    h->n_kp = h->n_q = 0;                                  // (until the arrays are queued: a refused call leaves no keyphrases)
+    h->kp.q_code_epoch = 0;
+    h->kp.n_kp = h->kp.n_q = 0;                                  // (until the arrays are queued: a refused call leaves no keyphrases)
     const u32 chunk = score_doc_chunk(n_q, h->n_docs, kn.score_scratch_bytes);
-    h->q_buf.ensure(keyphrase_scratch_bytes(n_kp, n_q, h->n_docs, chunk), "the score scratch", h->stream);
-    char *p = h->q_buf.p + 256;                            // (the first bytes hold the probe counter of east_hip_score_probes)
-    h->q_raw = (u32 *)p;  p += align256((size_t)n_q * 4);
-    h->q_code = (u32 *)p; p += align256((size_t)n_q * 4);
-    h->q_end = (u32 *)p;  p += align256((size_t)n_q * 4);
-    h->q_off = (u32 *)p;  p += align256(((size_t)n_kp + 1) * 4);
-    h->group_off = (u32 *)p; p += align256(((size_t)n_kp + 1) * 4);      // synonym-expanded scoring: variants per keyphrase
-    h->q_blk = (u32 *)p;  p += align256(((size_t)n_kp + 1) * 4);
-    h->suffix = (double *)p; p += align256((size_t)n_q * chunk * 8);
-    h->table = (double *)p; p += align256((size_t)n_kp * h->n_docs * 8);
-    h->table_g = (double *)p;
-    h->n_blk = n_blk;
+    h->kp.buf.ensure(keyphrase_scratch_bytes(n_kp, n_q, h->n_docs, chunk), "the score scratch", h->stream);
+    char *p = h->kp.buf.p + 256;                            // (the first bytes hold the probe counter of east_hip_score_probes)
+    h->kp.q_raw = (u32 *)p;  p += align256((size_t)n_q * 4);
+    h->kp.q_code = (u32 *)p; p += align256((size_t)n_q * 4);
+    h->kp.q_end = (u32 *)p;  p += align256((size_t)n_q * 4);
+    h->kp.q_off = (u32 *)p;  p += align256(((size_t)n_kp + 1) * 4);
+    h->kp.group_off = (u32 *)p; p += align256(((size_t)n_kp + 1) * 4);      // synonym-expanded scoring: variants per keyphrase
+    h->kp.q_blk = (u32 *)p;  p += align256(((size_t)n_kp + 1) * 4);
+    h->kp.suffix = (double *)p; p += align256((size_t)n_q * chunk * 8);
+    h->kp.table = (double *)p; p += align256((size_t)n_kp * h->n_docs * 8);
+    h->kp.table_g = (double *)p;
+    h->kp.n_blk = n_blk;
     fill();
-    h->n_kp = n_kp;
-    h->n_q = n_q;
-    h->score_chunk = chunk;
+    h->kp.n_kp = n_kp;
+    h->kp.n_q = n_q;
+    h->kp.score_chunk = chunk;
 }
 
 // The score walk's workgroups take whole keyphrases (score.h: score_walk_kernel, blk): consecutive keyphrases packed into
@@ -90,10 +90,10 @@ static void set_keyphrases(east_hip_index *h, const u32 *q_symbols, const i64 *q
     std::vector<u32> blk;
     pack_keyphrase_blocks((u32)n_kp, kn.score_fused, [&](u32 k) { return (u64)(q_offsets[k + 1] - q_offsets[k]); }, blk);
     set_keyphrases_device(h, (u32)n_kp, n_q, blk.empty() ? 0u : (u32)blk.size() - 1, kn, [&] {
-        if (!blk.empty()) HIP_CHECK(hipMemcpyAsync(h->q_blk, blk.data(), blk.size() * 4, hipMemcpyHostToDevice, h->stream));
-        HIP_CHECK(hipMemcpyAsync(h->q_raw, q_symbols, (size_t)n_q * 4, hipMemcpyHostToDevice, h->stream));
-        HIP_CHECK(hipMemcpyAsync(h->q_end, end.data(), (size_t)n_q * 4, hipMemcpyHostToDevice, h->stream));
-        HIP_CHECK(hipMemcpyAsync(h->q_off, off.data(), off.size() * 4, hipMemcpyHostToDevice, h->stream));
+        if (!blk.empty()) HIP_CHECK(hipMemcpyAsync(h->kp.q_blk, blk.data(), blk.size() * 4, hipMemcpyHostToDevice, h->stream));
+        HIP_CHECK(hipMemcpyAsync(h->kp.q_raw, q_symbols, (size_t)n_q * 4, hipMemcpyHostToDevice, h->stream));
+        HIP_CHECK(hipMemcpyAsync(h->kp.q_end, end.data(), (size_t)n_q * 4, hipMemcpyHostToDevice, h->stream));
+        HIP_CHECK(hipMemcpyAsync(h->kp.q_off, off.data(), off.size() * 4, hipMemcpyHostToDevice, h->stream));
         HIP_CHECK(hipStreamSynchronize(h->stream));
     });
 }
@@ -105,41 +105,41 @@ static bool kgram_reserve(east_hip_index *h, u64 bins, u32 n_docs)
     // layout with its chunk scratch is smaller)
     const size_t chunks = (size_t)((bins + KGF_CHUNK - 1) / KGF_CHUNK);
     const size_t bytes = (2 * (size_t)(bins + 1) + (size_t)(bins / 2 + 2) + (size_t)(bins / 4 + 8) + 2 * chunks) * n_docs * 4 + 256;
-    return h->kg.try_ensure(bytes, h->stream);
+    return h->kg.buf.try_ensure(bytes, h->stream);
 }
 
 // k-gram bucket tables of the current index (score.h); k = 0 when the alphabet is too wide
 static void ensure_kgram(east_hip_index *h, Ctx &ctx)
 {
-    if (h->kg_built) return;
-    if (h->kg_marked && h->kg_pairs) {
+    if (h->kg.built) return;
+    if (h->kg.marked && h->kg.pairs) {
         // the pair layout: the last level stays as the build marked it (+ its end entries), the small table above it is filled
-        const u32 bins3 = h->kg_bins / h->kg_A;
-        LAUNCH(ctx, kgram_pairs_end_kernel, ceil_div_u32(h->n_docs, BLOCK), (const u32 *)h->doc_off, h->n_docs, h->kg_bins, h->kg.as<u32>());
-        LAUNCH(ctx, kgram_fill_kernel, h->n_docs, (const u32 *)h->doc_off, bins3, h->kg3);
+        const u32 bins3 = h->kg.bins / h->kg.A;
+        LAUNCH(ctx, kgram_pairs_end_kernel, ceil_div_u32(h->n_docs, BLOCK), (const u32 *)h->doc_off, h->n_docs, h->kg.bins, h->kg.buf.as<u32>());
+        LAUNCH(ctx, kgram_fill_kernel, h->n_docs, (const u32 *)h->doc_off, bins3, h->kg.kg3);
         // (levels 1 .. k - 2 as tables of their own: A + 1, A^2 + 1, ... entries per document)
-        h->kg_up_stride = 0;
-        u32 len = h->kg_A;
-        for (int l = 1; l < h->kg_k - 1; l++) { h->kg_up_stride += len + 1; len *= h->kg_A; }
-        if (h->kg_up_stride && h->kg_up)
-            LAUNCH(ctx, kgram_upper_kernel, h->n_docs, (const u32 *)h->kg3, bins3, h->kg_A, h->kg_k - 1, h->kg_up_stride, h->kg_up);
-        h->kg_built = true;
+        h->kg.up_stride = 0;
+        u32 len = h->kg.A;
+        for (int l = 1; l < h->kg.k - 1; l++) { h->kg.up_stride += len + 1; len *= h->kg.A; }
+        if (h->kg.up_stride && h->kg.up)
+            LAUNCH(ctx, kgram_upper_kernel, h->n_docs, (const u32 *)h->kg.kg3, bins3, h->kg.A, h->kg.k - 1, h->kg.up_stride, h->kg.up);
+        h->kg.built = true;
         return;
     }
-    if (h->kg_marked) {
+    if (h->kg.marked) {
         // the build left the bucket starts in the table: suffix minimum per document, in chunks
-        const u32 bins = h->kg_bins, n_chunks = ceil_div_u32(bins, KGF_CHUNK);
-        u32 *cmin = h->kg.as<u32>() + (size_t)(bins + 1) * h->n_docs, *csuf = cmin + (size_t)n_chunks * h->n_docs;
-        LAUNCH(ctx, kgram_chunk_min_kernel, dim3(n_chunks, h->n_docs), h->kg.as<const u32>(), bins, n_chunks, cmin);
+        const u32 bins = h->kg.bins, n_chunks = ceil_div_u32(bins, KGF_CHUNK);
+        u32 *cmin = h->kg.buf.as<u32>() + (size_t)(bins + 1) * h->n_docs, *csuf = cmin + (size_t)n_chunks * h->n_docs;
+        LAUNCH(ctx, kgram_chunk_min_kernel, dim3(n_chunks, h->n_docs), h->kg.buf.as<const u32>(), bins, n_chunks, cmin);
         LAUNCH(ctx, kgram_chunk_suffix_kernel, h->n_docs, (const u32 *)cmin, (const u32 *)h->doc_off, n_chunks, csuf);
         LAUNCH(ctx, kgram_chunk_fill_kernel, dim3(n_chunks, h->n_docs), (const u32 *)csuf, (const u32 *)h->doc_off, bins,
-               n_chunks, h->kg.as<u32>());
-        h->kg_built = true;
+               n_chunks, h->kg.buf.as<u32>());
+        h->kg.built = true;
         return;
     }
-    h->kg_k = 0;
-    h->kg_pairs = false;
-    h->kg_built = true;
+    h->kg.k = 0;
+    h->kg.pairs = false;
+    h->kg.built = true;
     if (!h->use_s8 || h->n_docs > 65535) return;
     const u32 A = h->sigma_t + 2;
     int k = 0;
@@ -155,91 +155,91 @@ static void ensure_kgram(east_hip_index *h, Ctx &ctx)
     if ((u64)h->n / h->n_docs >= 256 * bins) {
         // long documents: every table entry by binary search on the suffix array
         LAUNCH(ctx, kgram_search_kernel, dim3(ceil_div_u32(bins + 1, BLOCK), h->n_docs), (const u32 *)h->sa,
-               (const uint8_t *)h->s8, (const u32 *)h->doc_off, k, A, (u32)bins, h->kg.as<u32>());
+               (const uint8_t *)h->s8, (const u32 *)h->doc_off, k, A, (u32)bins, h->kg.buf.as<u32>());
     } else {
-        HIP_CHECK(hipMemsetAsync(h->kg.p, 0xFF, bytes, h->stream));
+        HIP_CHECK(hipMemsetAsync(h->kg.buf.p, 0xFF, bytes, h->stream));
         i64 longest = 0;
         for (u32 d = 0; d < h->n_docs; d++) longest = std::max(longest, h->h_doc_off[d + 1] - h->h_doc_off[d]);
         if (h->n_docs > 1)
             LAUNCH_NAMED(ctx, "kgram_mark_kernel", kgram_mark_tiled_kernel,
                          dim3(ceil_div_u32((u64)longest + 3, BLOCK * 4), h->n_docs), (const u32 *)h->lcp, (const u32 *)h->sa,
-                         (const uint8_t *)h->s8, (const u32 *)h->doc_off, h->n_docs, h->n, k, A, (u32)bins, h->kg.as<u32>());
+                         (const uint8_t *)h->s8, (const u32 *)h->doc_off, h->n_docs, h->n, k, A, (u32)bins, h->kg.buf.as<u32>());
         else
             LAUNCH(ctx, kgram_mark_kernel, dim3(ceil_div_u32((u64)longest, BLOCK), h->n_docs), (const u32 *)h->lcp,
                    (const u32 *)h->sa, (const uint8_t *)h->s8, (const u32 *)h->doc_off, h->n_docs, h->n, k, A, (u32)bins,
-                   h->kg.as<u32>());
-        LAUNCH(ctx, kgram_fill_kernel, h->n_docs, (const u32 *)h->doc_off, (u32)bins, h->kg.as<u32>());
+                   h->kg.buf.as<u32>());
+        LAUNCH(ctx, kgram_fill_kernel, h->n_docs, (const u32 *)h->doc_off, (u32)bins, h->kg.buf.as<u32>());
     }
-    h->kg_k = k;
-    h->kg_A = A;
-    h->kg_bins = (u32)bins;
+    h->kg.k = k;
+    h->kg.A = A;
+    h->kg.bins = (u32)bins;
 }
 
 #define SCORE_DIRECT_OUT_MAX ((u64)1 << 18)     // scores (2 MiB): up to here east_hip_score_resident's block is written by the kernels
 
-// queues the score kernels; result in h->table (K x D) / h->suffix (D x S), and -- table_out != nullptr, device memory --
+// queues the score kernels; result in h->kp.table (K x D) / h->kp.suffix (D x S), and -- table_out != nullptr, device memory --
 // in the caller's block as well: the kernels write every score to both
 static void score_resident(east_hip_index *h, int normalized, unsigned long long *probe_count = nullptr,
                            double *suffix_host = nullptr, double *table_out = nullptr)
 {
     if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
     if (!h->built) east_throw(EAST_HIP_ERR_NOT_BUILT, "no index has been built on this handle");
-    if (!h->n_kp) east_throw(EAST_HIP_ERR_INVALID, "no keyphrases set");
+    if (!h->kp.n_kp) east_throw(EAST_HIP_ERR_INVALID, "no keyphrases set");
     use_device(h);
     Ctx ctx = handle_ctx(h);
     HIP_CHECK(hipEventRecord(h->ev0, h->stream));
     ensure_kgram(h, ctx);
-    if (h->q_code_epoch != h->map_epoch) {               // (the same keyphrases under the same code map: q_code stands)
-        LAUNCH(ctx, query_map_kernel, ceil_div_u32(h->n_q, BLOCK), (const u32 *)h->q_raw, h->n_q,
+    if (h->kp.q_code_epoch != h->map_epoch) {               // (the same keyphrases under the same code map: q_code stands)
+        LAUNCH(ctx, query_map_kernel, ceil_div_u32(h->kp.n_q, BLOCK), (const u32 *)h->kp.q_raw, h->kp.n_q,
                (const u32 *)h->code_map, (const u32 *)h->hi_bits, (const u32 *)h->hi_rank,
-               h->sigma_hi ? h->sigma_t - h->sigma_hi + 1u : 0u, h->q_code);
-        h->q_code_epoch = h->map_epoch;
+               h->sigma_hi ? h->sigma_t - h->sigma_hi + 1u : 0u, h->kp.q_code);
+        h->kp.q_code_epoch = h->map_epoch;
     }
     KgTables kt;
-    kt.kg = h->kg.as<u32>(); kt.kg3 = h->kg3; kt.k = h->kg_k; kt.pairs = h->kg_k > 0 && h->kg_pairs; kt.A = h->kg_A; kt.bins = h->kg_bins;
-    if (kt.pairs && h->kg_up_stride && h->kg_up) {
-        kt.up = h->kg_up;
-        kt.up_stride = h->kg_up_stride;
+    kt.kg = h->kg.buf.as<u32>(); kt.kg3 = h->kg.kg3; kt.k = h->kg.k; kt.pairs = h->kg.k > 0 && h->kg.pairs; kt.A = h->kg.A; kt.bins = h->kg.bins;
+    if (kt.pairs && h->kg.up_stride && h->kg.up) {
+        kt.up = h->kg.up;
+        kt.up_stride = h->kg.up_stride;
         static const bool up_lds_off = getenv("EAST_HIP_SCORE_UP_LDS") && atoi(getenv("EAST_HIP_SCORE_UP_LDS")) == 0;   // (A/B timing)
-        kt.up_lds = !up_lds_off && h->kg_up_stride <= KG_UP_LDS_WORDS;
+        kt.up_lds = !up_lds_off && h->kg.up_stride <= KG_UP_LDS_WORDS;
     }
     if (kt.k > 0) kt.finish();
     kt.endgame = ctx.knobs.score_endgame;
     // whole keyphrases per workgroup, summed in the walk (no per-suffix results unless the caller wants them: then the
     // documents go a stretch at a time, as far as the scratch reaches); otherwise per-suffix results + the reduction kernel
-    const bool fused = h->n_blk > 0;
-    u32 chunk = h->score_chunk;
+    const bool fused = h->kp.n_blk > 0;
+    u32 chunk = h->kp.score_chunk;
     if (fused && !suffix_host) {
         // (no scratch to bound the stretch -- the grid does: a launch of at most Knobs::score_grid_blocks workgroups, far below
         // HIP's limit of 2^32 threads per grid dimension; many short documents times thousands of keyphrases go a stretch
         // of documents at a time, a multiple of 8 for the XCD-aware order)
-        const u64 fit = ctx.knobs.score_grid_blocks / h->n_blk;
+        const u64 fit = ctx.knobs.score_grid_blocks / h->kp.n_blk;
         chunk = (u32)std::min<u64>(h->n_docs, fit >= 8 ? fit & ~(u64)7 : std::max<u64>(fit, 1));
     }
     for (u32 first = 0; first < h->n_docs; first += chunk) {
         const u32 count = std::min(chunk, h->n_docs - first);
         const int xcd_order = count >= 64;                // see score_walk_kernel
-        const u32 per_doc = fused ? h->n_blk : ceil_div_u32(h->n_q, BLOCK);
+        const u32 per_doc = fused ? h->kp.n_blk : ceil_div_u32(h->kp.n_q, BLOCK);
         const u64 walk_grid64 = (u64)(xcd_order ? 8u * ceil_div_u32(count, 8) : count) * per_doc;
         if (walk_grid64 >= ((u64)1 << 24)) east_throw(EAST_HIP_ERR_INVALID, "keyphrase set too large for one score launch");
         const u32 walk_grid = (u32)walk_grid64;
-        double *suffix = fused && !suffix_host ? (double *)nullptr : h->suffix;
-        const u32 *blk = fused ? (const u32 *)h->q_blk : (const u32 *)nullptr;
+        double *suffix = fused && !suffix_host ? (double *)nullptr : h->kp.suffix;
+        const u32 *blk = fused ? (const u32 *)h->kp.q_blk : (const u32 *)nullptr;
         if (h->use_s8)
             LAUNCH_NAMED(ctx, "score_walk_kernel", (score_walk_kernel<uint8_t>), walk_grid, (const uint8_t *)h->s8,
                          (const u32 *)h->sa, (const u32 *)h->doc_off, (const u32 *)h->n_strings, h->n_docs,
-                         (const u32 *)h->q_code, (const u32 *)h->q_end, h->n_q, normalized, kt, xcd_order, first, count, suffix,
-                         probe_count, blk, h->n_blk, (const u32 *)h->q_off, h->table, fused ? table_out : (double *)nullptr);
+                         (const u32 *)h->kp.q_code, (const u32 *)h->kp.q_end, h->kp.n_q, normalized, kt, xcd_order, first, count, suffix,
+                         probe_count, blk, h->kp.n_blk, (const u32 *)h->kp.q_off, h->kp.table, fused ? table_out : (double *)nullptr);
         else
             LAUNCH_NAMED(ctx, "score_walk_kernel", (score_walk_kernel<u32>), walk_grid, (const u32 *)h->s,
                          (const u32 *)h->sa, (const u32 *)h->doc_off, (const u32 *)h->n_strings, h->n_docs,
-                         (const u32 *)h->q_code, (const u32 *)h->q_end, h->n_q, normalized, kt, xcd_order, first, count, suffix,
-                         probe_count, blk, h->n_blk, (const u32 *)h->q_off, h->table, fused ? table_out : (double *)nullptr);
+                         (const u32 *)h->kp.q_code, (const u32 *)h->kp.q_end, h->kp.n_q, normalized, kt, xcd_order, first, count, suffix,
+                         probe_count, blk, h->kp.n_blk, (const u32 *)h->kp.q_off, h->kp.table, fused ? table_out : (double *)nullptr);
         if (!fused)
-            LAUNCH(ctx, score_reduce_kernel, ceil_div_u32((u64)h->n_kp * count, BLOCK), (const double *)h->suffix,
-                   (const u32 *)h->q_off, h->n_kp, h->n_docs, h->n_q, first, count, h->table, table_out);
+            LAUNCH(ctx, score_reduce_kernel, ceil_div_u32((u64)h->kp.n_kp * count, BLOCK), (const double *)h->kp.suffix,
+                   (const u32 *)h->kp.q_off, h->kp.n_kp, h->n_docs, h->kp.n_q, first, count, h->kp.table, table_out);
         if (suffix_host)                                  // the per-suffix results of this stretch of documents (D x S, row-major)
-            HIP_CHECK(hipMemcpyAsync(suffix_host + (size_t)first * h->n_q, h->suffix, (size_t)count * h->n_q * 8,
+            HIP_CHECK(hipMemcpyAsync(suffix_host + (size_t)first * h->kp.n_q, h->kp.suffix, (size_t)count * h->kp.n_q * 8,
                                      hipMemcpyDeviceToHost, h->stream));
     }
     HIP_CHECK(hipEventRecord(h->ev1, h->stream));

@@ -34,6 +34,24 @@ struct Pyramid {
 static inline u32 pyr_padded(u32 len) { return (len + PYR_FAN - 1u) & ~(PYR_FAN - 1u); }
 __device__ __forceinline__ u32 pyr_padded_dev(u32 len) { return (len + PYR_FAN - 1u) & ~(PYR_FAN - 1u); }
 
+// The pyramid over the table of n entries at lcp (padded by its owner): the upper levels, each a sixteenth of the one
+// below, laid out in the arena
+static Pyramid pyramid_layout(Arena &ar, const u32 *lcp, u32 n)
+{
+    Pyramid pyr = {};
+    pyr.levels = 1;
+    pyr.ptr[0] = lcp;
+    pyr.len[0] = n;
+    while (pyr.len[pyr.levels - 1] > PYR_FAN) {
+        if (pyr.levels >= PYR_MAX_LEVELS) east_throw(EAST_HIP_ERR_INTERNAL, "pyramid too deep");
+        const u32 len = ceil_div_u32(pyr.len[pyr.levels - 1], PYR_FAN);
+        pyr.ptr[pyr.levels] = ar.alloc<u32>(pyr_padded(len));
+        pyr.len[pyr.levels] = len;
+        pyr.levels++;
+    }
+    return pyr;
+}
+
 // document of a rank / position: last d with doc_off[d] <= x
 __device__ __forceinline__ u32 doc_of(const u32 *__restrict__ doc_off, u32 n_docs, u32 x)
 {

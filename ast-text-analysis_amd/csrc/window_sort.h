@@ -2012,9 +2012,9 @@ static bool dc3_level0_bytes(Ctx &ctx, const uint8_t *s8, u32 n0, u32 n02, int w
     if (fused && !ctx.dry) {
         if (ctx.knobs.force_fused) {
             // (test knob: buckets of any size -- the large ones go to the rounds)
-        } else if (ctx.plan_fused >= 0) {
-            fused = ctx.plan_fused != 0;                 // (speculative build: as the build before)
-            fin_small_halo = ctx.plan_fused == 2 && !ht;
+        } else if (ctx.plan.fused >= 0) {
+            fused = ctx.plan.fused != 0;                 // (speculative build: as the build before)
+            fin_small_halo = ctx.plan.fused == 2 && !ht;
         } else if (ht) {
             // (variable-length keys come with a wide window: few suffixes per bucket of the top part)
         } else {
@@ -2038,7 +2038,7 @@ static bool dc3_level0_bytes(Ctx &ctx, const uint8_t *s8, u32 n0, u32 n02, int w
                         "top part holds %d symbols, segmented by document %d\n", (int)sizeof(K) * 8, w, bt, spare, ht ? " (variable-length)" : "",
                 total_bits, low_bits, (int)fused, fin_small_halo ? " (halo 32)" : "", depth0, (int)(docs.seg.n_docs != 0));
     if (ht) w = fused ? depth0 : ht_sb / ht->max_len;     // the depth the rounds start from: what every key (its top part) holds at least
-    if (n0 == 0) ctx.did_fused = fused ? (fin_small_halo ? 2 : 1) : 0;
+    if (n0 == 0) ctx.did.fused = fused ? (fin_small_halo ? 2 : 1) : 0;
     if (ctx.stats && n0 == 0) ctx.stats->fused_finish = fused;
     SortBufs<K> sb;
     // (one spare element each: the idle half serves as scratch after the sort)
@@ -2063,7 +2063,7 @@ static bool dc3_level0_bytes(Ctx &ctx, const uint8_t *s8, u32 n0, u32 n02, int w
                                                              ctx.first_hist);
     if (n0 == 0 && !ctx.dry) {
         // what the next speculative build's remap pass may count ahead (build.h): the first pass of fixed-width text keys
-        Ctx::FirstPassPlan &fp = ctx.did_first;
+        FirstPassPlan &fp = ctx.did.first;
         fp.valid = !ht && !docs.bits && !docs.seg.n_docs && total_bits > low_bits;
         fp.key_bytes = (int)sizeof(K); fp.w = w; fp.b = bt; fp.spare = spare; fp.term_first = term_first;
         fp.shift = low_bits; fp.mask = (1u << std::min(RS_DB, total_bits - low_bits)) - 1u;
@@ -2094,7 +2094,7 @@ static bool dc3_level0_bytes(Ctx &ctx, const uint8_t *s8, u32 n0, u32 n02, int w
     // groups agree for hundreds of symbols, and every member would compare itself with every other to the end; the
     // persistent rounds take it, persist_rounds.h)
     const bool repetitive_text = n0 == 0 && !ctx.dry && ctx.knobs.lds_rounds && ctx.knobs.persist && n02 >= 4u * PR_CTL_WORDS &&
-                                 (ctx.rep_n ? ctx.rep_dup * 2u > ctx.rep_n : ctx.plan_persist == 1);
+                                 (ctx.rep_n ? ctx.rep_dup * 2u > ctx.rep_n : ctx.plan.persist == 1);
     const bool small_input = n02 <= REFINE_SMALL_INPUT && !repetitive_text;
     if (kg_mark) kg_mark->k = kg_mark->kg && n0 == 0 && !ctx.dry && !small_input && !ht ? kg_mark->k : 0;   // (variable-length keys: the score side builds its tables itself)
     if (kg_mark && kg_mark->k > 0) {
@@ -2399,7 +2399,7 @@ static bool dc3_level0_bytes(Ctx &ctx, const uint8_t *s8, u32 n0, u32 n02, int w
                         lcp_from_rounds = false;
                         redo_hinted = true;
                     }
-                    if (round == 0 && n0 == 0) ctx.did_persist = 1;
+                    if (round == 0 && n0 == 0) ctx.did.persist = 1;
                     m_next = 0;
                     done = true;
                     break;
@@ -2640,7 +2640,7 @@ static bool window_suffix_sort(Ctx &ctx, const uint8_t *s8, u32 n, u32 term_firs
     // consecutive suffixes --, most of the corpus is tied behind it.  (A speculative build does as the build before.)
     const int w_wide = std::min(12, (64 - docs.bits) / bt);
     bool wide = false;
-    if (ctx.plan_wide >= 0) wide = ctx.plan_wide != 0;
+    if (ctx.plan.wide >= 0) wide = ctx.plan.wide != 0;
     else if (ctx.sample_n && w < w_wide && w * bt + docs.bits <= 32)
         wide = (u64)ctx.sample_dup2[std::min(w, 8)] * 2u > ctx.sample_n;
     if (getenv("EAST_HIP_WIDE")) wide = atoi(getenv("EAST_HIP_WIDE")) != 0;      // (experiments)
@@ -2656,7 +2656,7 @@ static bool window_suffix_sort(Ctx &ctx, const uint8_t *s8, u32 n, u32 term_firs
     bool use_ht = false, ht_wide = false;
     if (ctx.ht_max_len > 0 && !ctx.dry && ctx.knobs.ht_mode != 0) {
         if (ctx.knobs.ht_mode == 1) { use_ht = true; ht_wide = wide || ctx.knobs.force_wide_keys || w * bt + docs.bits > 32; }
-        else if (ctx.plan_ht >= 0) { use_ht = ctx.plan_ht != 0; ht_wide = ctx.plan_ht == 2; }
+        else if (ctx.plan.ht >= 0) { use_ht = ctx.plan.ht != 0; ht_wide = ctx.plan.ht == 2; }
         else if (docs.seg.n_docs) {
             // (segmented sort: all 32 bits of a narrow key are text -- six and a half symbols of prose, sorted in four passes
             // of 8-byte pairs; measured on 64 x 1 MiB of prose: 5.29 ms, against 5.35 with 48 stream bits in 64-bit keys,
@@ -2674,10 +2674,10 @@ static bool window_suffix_sort(Ctx &ctx, const uint8_t *s8, u32 n, u32 term_firs
     if (use_ht && ht_wide) ht_sb -= (ht_sb + docs.bits) % RS_DB;
     // (experiments: EAST_HIP_HT_SB=<bits> overrides the stream bits of a wide key -- 42 next to 6 document bits is a pass less than 48)
     if (use_ht && ht_wide && getenv("EAST_HIP_HT_SB")) ht_sb = std::max(20, std::min(ht_sb, atoi(getenv("EAST_HIP_HT_SB"))));
-    ctx.did_ht = use_ht ? (ht_wide ? 2 : 1) : 0;
-    if (ctx.stats) ctx.stats->ht_keys = ctx.did_ht;
+    ctx.did.ht = use_ht ? (ht_wide ? 2 : 1) : 0;
+    if (ctx.stats) ctx.stats->ht_keys = ctx.did.ht;
     if (wide) w = std::max(w, w_wide);
-    ctx.did_wide = wide;
+    ctx.did.wide = wide;
     // (experiments, DESIGN.md 5.2: EAST_HIP_WINDOW=<symbols> overrides the width of the first window)
     if (getenv("EAST_HIP_WINDOW")) w = std::max(3, std::min(atoi(getenv("EAST_HIP_WINDOW")), std::min(12, (64 - docs.bits) / bt)));
     u32 n_names = 0;
