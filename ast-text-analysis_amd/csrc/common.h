@@ -328,6 +328,7 @@ struct SizingRun {
 // Wait for a stream the way the build's read-backs want it: they sit between kernels a few microseconds long, and a
 // blocking hipStreamSynchronize comes back tens of microseconds after the stream has drained (the waiter sleeps on an
 // interrupt).  The stream is polled for a short while first; what is still running after that is waited for asleep.
+static const bool g_trace = getenv("EAST_HIP_TRACE") != nullptr;   // per-round progress on stderr
 static bool g_spin_sync = getenv("EAST_HIP_NO_SPIN_SYNC") == nullptr;
 static inline hipError_t sync_stream(hipStream_t stream)
 {

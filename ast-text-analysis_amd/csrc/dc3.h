@@ -5,7 +5,7 @@
 // result is bit-identical to the reference's suftab although none of its sequential
 // dict-counting / list-merging code is reproduced.
 //
-// A. window_suffix_sort (window_sort.h; text on the byte stream, the path ordinary inputs take):
+// A. window_suffix_sort (level0.h, kernels in window_sort.h; text on the byte stream, the path ordinary inputs take):
 //      ALL suffixes are keyed by their first w symbols (w*bits <= 32 or 64), generated inside the
 //      first pass of one stable LSD radix sort; one classify pass then places every suffix whose
 //      key is unique and orders small groups of equal keys directly on the text; members of
@@ -16,7 +16,8 @@
 //
 // B. dc3_suffix_array, data-parallel DC3 / skew (Karkkainen & Sanders 2003), takes over:
 //   1. sample positions i mod 3 != 0 become packed keys -- at level 0 on the byte stream the same
-//      w-symbol windows and the same classify / refinement as in A, otherwise (s[i],s[i+1],s[i+2])
+//      w-symbol windows and the same classify / refinement as in A (level0.h: dc3_level0_bytes with
+//      n0 > 0), otherwise (s[i],s[i+1],s[i+2])
 //      read coalesced from the symbol stream -- sorted by the LDS-staged wave64 radix sort
 //      (radix_sort.h)                                           [easa.py:163-167]
 //   2. naming = inclusive scan of "key differs from predecessor"  [easa.py:169-182]
@@ -32,7 +33,7 @@
 #include "common.h"
 #include "radix_sort.h"
 #include "scan.h"
-#include "window_sort.h"
+#include "level0.h"
 #include <math.h>
 #include <algorithm>
 

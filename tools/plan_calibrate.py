@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What the planning sample (csrc/alphabet.h: sample_prefix_kernel) says about different kinds of text, next to
 what the build then finds: first builds on fresh handles with EAST_HIP_TRACE=1 (the sample's counts go to stderr),
-for every combination of the window / fused-finish knobs.  Used to set the thresholds in window_sort.h.
+for every combination of the window / fused-finish knobs.  Used to set the thresholds in level0.h.
 
     python tools/plan_calibrate.py [--quick]
 """
