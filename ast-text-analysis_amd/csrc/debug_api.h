@@ -507,6 +507,109 @@ static void debug_ascending_offsets(int device, const u32 *sorted, i64 n64, i64 
     HIP_CHECK(hipStreamSynchronize(sc.stream));
 }
 
+// dc3_suffix_array exactly as build_impl calls it, on a caller's text in one of the three forms a build uses: (0) plain u32
+// symbols -- every recursion level --, (1) u32 codes with term_first > 0 -- level 0 of wide-alphabet text --, (2) the byte
+// stream -- level 0 in sample mode, the 16-byte records, the merge that also writes the LCP table.  The scope is laid out
+// as a handle is: the u32 stream with its three zero words, the byte stream with 16 zero bytes of a 64-byte tail, the two
+// outputs behind them, each with its guard; the whole scope starts out as pad_fill.  In form 2 the u32 stream is there and
+// holds pad_fill: dc3_suffix_array does not read it, and a read would show as a wrong answer.  Every argument is checked
+// here, before anything is launched.
+static void debug_suffix_array_ex(int device, int form, const void *text, i64 n64, u32 sigma, u32 term_first, i64 rank_bucket_bytes,
+                                  int lean, int want_lcp, int32_t deep_per_slot, int pad_fill, u32 *sa_out, u32 *lcp_out,
+                                  u32 *capped_out, i64 *info_out, u32 *geometry_out)
+{
+    if (form < 0 || form > 2 || !text || !sa_out || !capped_out || !info_out || !geometry_out || n64 < 1 || n64 >= (i64)0x7FFFFFF0 ||
+        sigma < 1 || rank_bucket_bytes < -1 || (lean != 0 && lean != 1) || (want_lcp != 0 && want_lcp != 1) || deep_per_slot < -1 ||
+        pad_fill < 0 || pad_fill > 255)
+        east_throw(EAST_HIP_ERR_INVALID, "bad suffix array arguments");
+    if (want_lcp && form != 2) east_throw(EAST_HIP_ERR_INVALID, "the LCP table comes out of the byte form's merge only");
+    if (want_lcp && !lcp_out) east_throw(EAST_HIP_ERR_INVALID, "bad suffix array arguments");
+    const u32 n = (u32)n64;
+    const uint8_t *t8 = (const uint8_t *)text;
+    const u32 *t32 = (const u32 *)text;
+    if (form == 0 && term_first != 0) east_throw(EAST_HIP_ERR_INVALID, "term_first belongs to forms 1 and 2");
+    // (form 1: the level-0 keys hold three symbols of bit_width(term_first) bits in 64: at most 21 bits each)
+    if (form == 1 && (term_first < 2 || term_first >= (1u << 21))) east_throw(EAST_HIP_ERR_INVALID, "term_first out of range");
+    if (form == 2 && (term_first < 2 || term_first > 255)) east_throw(EAST_HIP_ERR_INVALID, "term_first out of range");
+    u32 last_term = 0;
+    u64 terms = 0;
+    for (u32 i = 0; i < n; i++) {
+        if (form == 0) {
+            if (t32[i] < 1 || t32[i] > sigma) east_throw(EAST_HIP_ERR_INVALID, "symbol outside [1, sigma]");
+        } else if (form == 1) {
+            const u32 c = t32[i];
+            if (c == 0 || c >= term_first + n) east_throw(EAST_HIP_ERR_INVALID, "a code outside [1, term_first + n)");
+            if (c >= term_first) {
+                if (last_term && c <= last_term) east_throw(EAST_HIP_ERR_INVALID, "terminator codes must ascend: each is a symbol of its own");
+                last_term = c;
+                terms++;
+            }
+        } else {
+            if (t8[i] == 0) east_throw(EAST_HIP_ERR_INVALID, "a zero byte: text codes start at 1, the pad is zero");
+            if (t8[i] >= term_first && t8[i] != 0xFFu) east_throw(EAST_HIP_ERR_INVALID, "a byte that is neither a text code nor 0xFF");
+            terms += t8[i] == 0xFFu;
+        }
+    }
+    if (form != 0) {
+        if (!(form == 1 ? t32[n - 1] >= term_first : t8[n - 1] == 0xFFu)) east_throw(EAST_HIP_ERR_INVALID, "the text does not end in a terminator");
+        if ((u64)sigma != (u64)term_first - 1 + terms) east_throw(EAST_HIP_ERR_INVALID, "sigma is not term_first - 1 + the number of terminators");
+    }
+    const size_t guard = DBG_GUARD;
+    u32 *s = nullptr, *sa = nullptr, *lcp = nullptr, *words = nullptr;
+    uint8_t *s8 = nullptr;
+    int levels = 0;
+    auto run = [&](Ctx &ctx) {
+        Arena &ar = *ctx.arena;
+        s = ar.alloc<u32>((size_t)n + 3);
+        s8 = ar.alloc<uint8_t>((size_t)n + 64);
+        sa = ar.alloc<u32>(n + guard);
+        lcp = ar.alloc<u32>(n + guard);
+        words = ar.alloc<u32>(1 + LCP_BUDGET_SLOTS);        // capped, the budget's slots
+        ctx.lean = lean != 0;
+        if (rank_bucket_bytes >= 0) ctx.knobs.rank_bucket_bytes = (size_t)rank_bucket_bytes;
+        if (ctx.dry) {                                      // (priced as build_impl's sizing run prices it: no byte stream yet)
+            dc3_suffix_array(ctx, nullptr, n, std::max(n, sigma), nullptr, 0, term_first);
+            return;
+        }
+        HIP_CHECK(hipMemsetAsync(ar.base, pad_fill, ar.cap, ctx.stream));
+        HIP_CHECK(hipMemsetAsync(sa, 0xEE, (n + guard) * 4, ctx.stream));
+        HIP_CHECK(hipMemsetAsync(lcp, 0xEE, (n + guard) * 4, ctx.stream));
+        HIP_CHECK(hipMemsetAsync(words, 0, (1 + LCP_BUDGET_SLOTS) * 4, ctx.stream));
+        if (form == 2) {
+            HIP_CHECK(hipMemsetAsync(s8 + n, 0, 16, ctx.stream));
+            HIP_CHECK(hipMemcpyAsync(s8, text, n, hipMemcpyHostToDevice, ctx.stream));
+        } else {
+            HIP_CHECK(hipMemsetAsync(s + n, 0, 12, ctx.stream));
+            HIP_CHECK(hipMemcpyAsync(s, text, (size_t)n * 4, hipMemcpyHostToDevice, ctx.stream));
+        }
+        ctx.lcp_budget.slots = deep_per_slot < 0 ? nullptr : words + 1;
+        ctx.lcp_budget.per_slot = deep_per_slot < 0 ? 0u : (u32)deep_per_slot;
+        levels = dc3_suffix_array(ctx, s, n, sigma, sa, 0, term_first, form == 2 ? s8 : nullptr, want_lcp ? lcp : nullptr, words);
+    };
+    // (the arena is measured with the same code, then the sort runs in it)
+    SizingRun dry;
+    run(dry.ctx);
+    DebugScope sc(device, dry.arena.high + (8u << 20));
+    run(sc.ctx);
+    HIP_CHECK(hipMemcpyAsync(sa_out, sa, (n + guard) * 4, hipMemcpyDeviceToHost, sc.stream));
+    if (lcp_out) HIP_CHECK(hipMemcpyAsync(lcp_out, lcp, (n + guard) * 4, hipMemcpyDeviceToHost, sc.stream));
+    HIP_CHECK(hipMemcpyAsync(capped_out, words, 4, hipMemcpyDeviceToHost, sc.stream));
+    HIP_CHECK(hipStreamSynchronize(sc.stream));
+    info_out[0] = levels;
+    info_out[1] = sc.stats.levels_resolved;
+    info_out[2] = sc.stats.refine_rounds;
+    info_out[3] = sc.stats.radix_passes_u32;
+    info_out[4] = sc.stats.radix_passes_u64;
+    info_out[5] = sc.stats.merge_elems;
+    geometry_out[0] = MERGE_TILE;
+    geometry_out[1] = RESOLVE_MAX_GROUP;
+    geometry_out[2] = RESOLVE_MAX_LEN;
+    geometry_out[3] = LCP_SOFT_CAP;
+    geometry_out[4] = LCP_DIRECT_CAP;
+    geometry_out[5] = LCP_BUDGET_SLOTS;
+    geometry_out[6] = DBG_GUARD;
+}
+
 extern "C" {
 
 int east_hip_debug_set_rank_bucket_bytes(int64_t bytes)
@@ -796,6 +899,17 @@ int east_hip_debug_suffix_array(int device, const uint32_t *symbols, int64_t n, 
         HIP_CHECK(hipMemcpyAsync(sa_out, sa, (size_t)n * 4, hipMemcpyDeviceToHost, sc.stream));
         HIP_CHECK(hipStreamSynchronize(sc.stream));
         if (levels_out) *levels_out = levels;
+    });
+}
+
+int east_hip_debug_suffix_array_ex(int device, int form, const void *text, int64_t n, uint32_t sigma, uint32_t term_first,
+                                   int64_t rank_bucket_bytes, int lean, int want_lcp, int32_t deep_per_slot, int pad_fill,
+                                   uint32_t *sa_out, uint32_t *lcp_out, uint32_t *capped_out, int64_t *info_out,
+                                   uint32_t *geometry_out)
+{
+    return guarded([&] {
+        debug_suffix_array_ex(device, form, text, n, sigma, term_first, rank_bucket_bytes, lean, want_lcp, deep_per_slot, pad_fill,
+                              sa_out, lcp_out, capped_out, info_out, geometry_out);
     });
 }
 

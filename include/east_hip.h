@@ -697,6 +697,28 @@ int east_hip_debug_radix_sort_u32(int device, uint32_t *keys, uint32_t *vals, in
 int east_hip_debug_exclusive_scan(int device, const uint32_t *in, uint32_t *out, int64_t n);
 int east_hip_debug_suffix_array(int device, const uint32_t *symbols, int64_t n, uint32_t sigma,
                                 int32_t *sa_out, int32_t *levels_out);
+/* Kernel-level test of the DC3 suffix sort (csrc/dc3.h: dc3_suffix_array) in the three forms a build calls it in.
+ * form 0: text is n u32 symbols in [1, sigma], term_first 0 -- every recursion level.  form 1: n u32 codes, text in
+ * [1, term_first), the terminators ascending from term_first on (as east_hip_debug_lcp takes them), 2 <= term_first < 2^21
+ * -- level 0 of wide-alphabet text.  form 2: n bytes, text codes 1 .. term_first - 1 <= 254, 0xFF for every terminator --
+ * level 0 on the byte stream (the window keys in sample mode, the 16-byte records, the merge that also writes the LCP
+ * table).  Forms 1 and 2 end in a terminator and take sigma = term_first - 1 + the number of terminators, as a build does.
+ * rank_bucket_bytes: the threshold of the bucketed rank scatter for this call alone (-1: the process-wide knob's value);
+ * lean 1: as a build short of memory (no refinement rounds at level 0 of form 2); want_lcp 1 (form 2 only): the merge also
+ * writes the LCP table, under the budget deep_per_slot of deep comparisons per slot (-1 = none); pad_fill: the byte the
+ * whole scope holds before the run, behind the text's zero pad (3 words / 16 bytes) and, in form 2, in the u32 stream that
+ * is not read.  Anything else -- a symbol, code or byte out of range, a zero byte, terminators that do not ascend, a text
+ * of form 1 or 2 that does not end in one, a sigma that is not the sum above, want_lcp with another form -- is
+ * EAST_HIP_ERR_INVALID before a launch; the outputs are then untouched.  sa_out (and lcp_out, which may be NULL without
+ * want_lcp): n words + EAST_HIP_DEBUG_GUARD words, which the device held as 0xEE before the run; lcp_out holds the table as
+ * the merge leaves it (LCP_PARTIAL_BIT | k where a comparison was cut, no padding behind n).  capped_out: the flag word.
+ * info_out[6]: the levels run (the return value), then levels_resolved, refine_rounds, radix_passes_u32, radix_passes_u64
+ * and merge_elems of the call's statistics.  geometry_out[7]: MERGE_TILE, RESOLVE_MAX_GROUP, RESOLVE_MAX_LEN, LCP_SOFT_CAP,
+ * LCP_DIRECT_CAP, LCP_BUDGET_SLOTS as compiled, EAST_HIP_DEBUG_GUARD. */
+int east_hip_debug_suffix_array_ex(int device, int form, const void *text, int64_t n, uint32_t sigma, uint32_t term_first,
+                                   int64_t rank_bucket_bytes, int lean, int want_lcp, int32_t deep_per_slot, int pad_fill,
+                                   uint32_t *sa_out, uint32_t *lcp_out, uint32_t *capped_out, int64_t *info_out,
+                                   uint32_t *geometry_out);
 /* Test knob: rank arrays larger than this many bytes are filled through the bucketed scatter
  * (default 192 MiB, the Infinity Cache); 0 forces the bucketed path on every input. */
 int east_hip_debug_set_rank_bucket_bytes(int64_t bytes);

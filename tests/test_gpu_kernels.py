@@ -101,7 +101,8 @@ def test_suffix_array_adversarial(hip, case):
         while len(b) < n:
             a, b = b, b + a
         s = np.array(b[:n], dtype=np.uint32)
-    else:   # distinct symbols beyond 2^21: the two-stage (3b > 64) key path
+    else:   # symbols beyond 2^21: the two-stage (3b > 64) sort, but every triple is unique -- no tie reaches its naming
+            # (KeyNeq2In); the ties of that path are in tests/test_gpu_dc3.py
         rng = np.random.default_rng(3)
         s = rng.integers(1, 1 << 23, size=n, dtype=np.uint32)
     sigma = int(s.max())
