@@ -335,6 +335,18 @@ __global__ __launch_bounds__(BLOCK) void cos_doc_lengths_kernel(const u32 *__res
     n_d[d] = nsx[ascending_lower_bound(kdoc, n_kept, d + 1u)] - nsx[ascending_lower_bound(kdoc, n_kept, d)];
 }
 
+// ---- the token sequence (phrases.h) ---------------------------------------------------------------------------------
+// what stays of the kept tokens themselves: the term of kept token j (COS_NONE: a stopword) and its document
+__global__ __launch_bounds__(BLOCK) void cos_tok_terms_kernel(const u32 *__restrict__ run_of_tok, const u32 *__restrict__ run_term,
+                                                              const u32 *__restrict__ kdoc, u32 n_kept, u32 *__restrict__ tok_term,
+                                                              u32 *__restrict__ tok_doc)
+{
+    const u32 j = blockIdx.x * BLOCK + threadIdx.x;
+    if (j >= n_kept) return;
+    tok_term[j] = run_term[run_of_tok[j]];
+    tok_doc[j] = kdoc[j];
+}
+
 // ---- the terms' text (east_hip_cosine_get_terms, query look-ups) ----------------------------------------------------
 __global__ __launch_bounds__(BLOCK) void cos_term_len_kernel(const u32 *__restrict__ term_run, const u32 *__restrict__ run_hlen, u32 V,
                                                              u32 *__restrict__ tlen)
@@ -519,6 +531,7 @@ struct CosState : Consumer {
     DevBuf score;            // the last score call's queries and table
     u64 *run_key = nullptr;
     u32 *run_term = nullptr, *term_off = nullptr, *term_len = nullptr, *tcp = nullptr, *n_d = nullptr;
+    u32 *tok_term = nullptr, *tok_doc = nullptr;          // per kept token, in text order: its term (COS_NONE: a stopword), its document
     CosUnits terms, cls;
     float build_ms = -1.f, score_ms = -1.f;               // the timer's ms of the last build and of the last score call
     double *table = nullptr;                              // the last score call's K x D table, where it lies in `score` (offers(): the graph, the ranking and the similarity read it there)
@@ -548,6 +561,12 @@ struct CosState : Consumer {
 static void cos_withdraw_texts_matrix(east_hip_index *h)
 {
     if (Consumer *t = h->consumers[east_hip_index::SLOT_COSTEXT]) t->withdraw();
+}
+
+// the extracted phrases (phrases.h) are a function of the index's token sequence: every build withdraws them
+static void cos_withdraw_phrases(east_hip_index *h)
+{
+    if (Consumer *p = h->consumers[east_hip_index::SLOT_PHR]) p->withdraw();
 }
 
 static CosState &cos_built(east_hip_index *h) { return consumer_built<CosState>(h, "no cosine index has been built on this handle"); }
@@ -597,6 +616,7 @@ static void cos_build(east_hip_index *h, HostTexts in, const UnicodeTablesHost &
     CosState &c = consumer_begin<CosState>(h);
     c.clear();
     cos_withdraw_texts_matrix(h);
+    cos_withdraw_phrases(h);
     const u32 N = (u32)in.n_bytes, D = (u32)in.D;
     Stats stats;
 
@@ -620,7 +640,8 @@ static void cos_build(east_hip_index *h, HostTexts in, const UnicodeTablesHost &
 
     // ---- what stays (runs, terms and postings are at most as many as the kept tokens)
     const size_t K1 = (size_t)n_kept + 2;
-    c.index.ensure(K1 * 48 + (size_t)D * 12 + ((size_t)1 << 16), "the cosine index");
+    // (... and the token sequence: 8 bytes a kept token)
+    c.index.ensure(K1 * 56 + (size_t)D * 12 + ((size_t)1 << 16), "the cosine index");
     Arena ai = c.index.arena();
     c.run_key = ai.alloc<u64>(K1);
     c.run_term = ai.alloc<u32>(K1);
@@ -634,6 +655,8 @@ static void cos_build(east_hip_index *h, HostTexts in, const UnicodeTablesHost &
     T.post_cnt = ai.alloc<u32>(K1);
     T.inv_perm = ai.alloc<u32>(K1);
     T.doc_off = ai.alloc<u32>((size_t)D + 1);
+    c.tok_term = ai.alloc<u32>(K1);
+    c.tok_doc = ai.alloc<u32>(K1);
 
     // ---- the kept tokens and their pieces
     const size_t n_pc_max = (size_t)n_kept + n_cp / COS_PIECE + 2;
@@ -715,6 +738,9 @@ static void cos_build(east_hip_index *h, HostTexts in, const UnicodeTablesHost &
     if (n_runs)
         LAUNCH(ctx, cos_run_terms_kernel, ceil_div_u32(n_runs, BLOCK), (const u32 *)run_start, svals, (const u32 *)is_stop,
                (const u32 *)th_ex, n_runs, c.run_term, term_run);
+    if (n_kept)
+        LAUNCH(ctx, cos_tok_terms_kernel, ceil_div_u32(n_kept, BLOCK), (const u32 *)run_of_tok, (const u32 *)c.run_term,
+               (const u32 *)kdoc, n_kept, c.tok_term, c.tok_doc);
 
     // ---- postings (term, document, count) in (term, document) order
     u32 *pflag = a2.alloc<u32>(K1), *px = a2.alloc<u32>(K1), *post_beg = a2.alloc<u32>(K1), *post_end = a2.alloc<u32>(K1);

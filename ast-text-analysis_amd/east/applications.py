@@ -1,7 +1,9 @@
 # -*- coding: utf-8 -*-
-"""keyphrases_table / keyphrases_graph (reference east/applications.py:11-149), keyphrases_top and keyphrases_similar."""
+"""keyphrases_table / keyphrases_graph (reference east/applications.py:11-149), keyphrases_top and keyphrases_similar;
+texts_related, texts_similar, the clusters and keyphrases_extract."""
 
 import os
+from collections import namedtuple
 from collections.abc import Mapping
 
 import numpy as np
@@ -823,3 +825,121 @@ def keyphrases_clusters(keyphrases, texts, by="text", threshold=None, k=None, si
         return _clustering_of_index(titles if axis == 0 else wanted, index, threshold, k)
     scores, titles = _score_array(keyphrases_table(wanted, texts, measure, synonimizer, language), wanted, titles)
     return _clustering_of_matrix(titles if axis == 0 else wanted, _similarity_matrix(scores, axis), threshold, k)
+
+
+# ---- phrase extraction -----------------------------------------------------------------------------------------------------
+Phrase = namedtuple("Phrase", ("text", "words", "count", "texts", "score"))
+EXTRACT_MAX_WORDS = 8
+
+
+def _extract_arguments(n, max_words, min_words, min_count, min_texts):
+    """The arguments of keyphrases_extract as integers, or ValueError with the line that names the one that is wrong."""
+    values = []
+    for name, value in (("n", n), ("max_words", max_words), ("min_words", min_words), ("min_count", min_count),
+                        ("min_texts", min_texts)):
+        if isinstance(value, bool) or int(value) != value:
+            raise ValueError("keyphrases_extract: %s must be an integer, not %r" % (name, value))
+        values.append(int(value))
+    n, max_words, min_words, min_count, min_texts = values
+    if n < 0:
+        raise ValueError("keyphrases_extract: n must not be negative (0 keeps every candidate), not %d" % n)
+    if not 1 <= max_words <= EXTRACT_MAX_WORDS:
+        raise ValueError("keyphrases_extract: max_words must lie in 1 .. %d, not %d" % (EXTRACT_MAX_WORDS, max_words))
+    if not 1 <= min_words <= max_words:
+        raise ValueError("keyphrases_extract: min_words must lie in 1 .. max_words, not %d" % min_words)
+    if min_count < 1:
+        raise ValueError("keyphrases_extract: min_count must be at least 1, not %d" % min_count)
+    if min_texts < 1:
+        raise ValueError("keyphrases_extract: min_texts must be at least 1, not %d" % min_texts)
+    return values
+
+
+def _phrases_on_host(texts, stopwords, n, max_words, min_words, min_count, min_texts):
+    """The contract of include/east_hip.h ("Phrase extraction") in plain Python, without a device: the tokens of
+    utils.tokenize(utils.prepare_text(text)) with at least 3 code points, the stopwords as breaks; the n-grams named level
+    by level through dicts.  -> ([(text, words, count, texts, first, first_text, term ids)], best first and cut by n; the
+    candidates before the cut)."""
+    term, doc, words, number = [], [], [], {}
+    for d, text in enumerate(texts):
+        for token in utils.tokenize(utils.prepare_text(text)):
+            if len(token) < 3:
+                continue
+            term.append(-1 if token in stopwords else number.setdefault(token, len(number)))
+            doc.append(d)
+            words.append(token)
+    T = len(term)
+    candidates = []
+    below = None                                        # (ids per position, count per id, open per id, the level's survivors)
+    for level in range(1, max_words + 1):
+        groups = {}
+        if level == 1:
+            for j in range(T):
+                if term[j] >= 0:
+                    groups.setdefault(term[j], []).append(j)
+        else:
+            ids = below[0]
+            for j in range(T - level + 1):
+                e = j + level - 1
+                if ids[j] >= 0 and doc[e] == doc[j] and term[e] >= 0:
+                    groups.setdefault((ids[j], term[e]), []).append(j)
+        ids, count, is_open, found = [-1] * T, [], [], []
+        for positions in groups.values():
+            if len(positions) < min_count:
+                continue
+            for j in positions:
+                ids[j] = len(count)
+            n_texts = 1 + sum(1 for a, b in zip(positions, positions[1:]) if doc[a] != doc[b])
+            found.append((level, len(positions), n_texts, positions[0]))
+            count.append(len(positions))
+            is_open.append(False)
+            if below is not None:
+                for j in (positions[0], positions[0] + 1):
+                    if below[1][below[0][j]] == len(positions):
+                        below[2][below[0][j]] = True
+        if below is not None:
+            candidates += [c for c, o in zip(below[3], below[2]) if not o]
+        below = (ids, count, is_open, found)
+        if not found:
+            break
+    candidates += [c for c, o in zip(below[3], below[2]) if not o]
+    candidates = sorted((c for c in candidates if c[0] >= min_words and c[2] >= min_texts), key=lambda c: (c[0], c[3]))
+    candidates.sort(key=lambda c: -c[0] * c[1])         # (stable: words, then first, among equal scores)
+    kept = candidates[:n] if n else candidates
+    return [(" ".join(words[first:first + w]), w, c, t, first, doc[first], term[first:first + w])
+            for w, c, t, first in kept], len(candidates)
+
+
+def keyphrases_extract(texts, n=100, max_words=3, min_words=1, min_count=2, min_texts=1, similarity_measure=None,
+                       language=consts.Language.ENGLISH):
+    """Keyphrase candidates out of the texts themselves: the repeated phrases of min_words to max_words words, counted
+    exactly, without those that only ever occur inside one longer phrase of the same count, best first (the contract:
+    include/east_hip.h, "Phrase extraction").
+
+    :param texts: {text name: text} or a sequence of texts (bytes or str), in the order that numbers the positions
+    :param n: phrases at most; 0 = every candidate
+    :param max_words: the longest phrase, 1 .. 8; min_words: the shortest, 1 .. max_words
+    :param min_count: occurrences a phrase needs; min_texts: texts it must occur in
+    :param similarity_measure: a relevance.CosineRelevanceMeasure in the `words` space, whose stopwords are the breaks
+                               (None: CosineRelevanceMeasure("words") with the default stopwords); any other raises ValueError
+    :returns: [Phrase(text, words, count, texts, score)], score = count * words, by score descending, then words
+              ascending, then first occurrence; `text` is the upper-cased words joined by one space -- a line of a keyphrase
+              file
+
+    The phrases are extracted on the device from the measure's term index (csrc/phrases.h) unless EAST_HIP_EXTRACT is
+    `host`; then plain Python computes the same contract from the same tokens and touches no device.  Nothing in it is
+    floating point: the two give the same bytes.
+    """
+    n, max_words, min_words, min_count, min_texts = _extract_arguments(n, max_words, min_words, min_count, min_texts)
+    measure = relevance.CosineRelevanceMeasure(consts.VectorSpace.WORDS) if similarity_measure is None else similarity_measure
+    if not isinstance(measure, relevance.CosineRelevanceMeasure) or measure.vector_space != consts.VectorSpace.WORDS:
+        raise ValueError("keyphrases_extract: phrases are extracted from the term index of a CosineRelevanceMeasure in the "
+                         "'words' space, not %s" % (type(measure).__name__ if not isinstance(measure, relevance.CosineRelevanceMeasure)
+                                                    else "the '%s' space" % measure.vector_space))
+    texts = list(texts.values()) if isinstance(texts, Mapping) else list(texts)
+    if os.environ.get("EAST_HIP_EXTRACT", "device") == "host":
+        rows = _phrases_on_host(texts, measure.stopwords, n, max_words, min_words, min_count, min_texts)[0]
+        return [Phrase(text, w, c, t, c * w) for text, w, c, t, _, _, _ in rows]
+    measure.set_text_collection(texts, language)
+    found = measure.extract_phrases(n, max_words, min_words, min_count, min_texts)
+    return [Phrase(text, w, c, t, c * w) for text, w, c, t in
+            zip(found.strings(), found.words.tolist(), found.count.tolist(), found.texts.tolist())]

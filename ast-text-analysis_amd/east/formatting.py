@@ -202,6 +202,33 @@ def clusters2merges(clustering):
     return "".join("%s,%s,%s\n" % (_csv_quote(a), _csv_quote(b), _SCORE % similarity) for a, b, similarity in clustering.merges)
 
 
+def format_phrases(result, format="txt"):
+    """Extracted phrases (applications.keyphrases_extract: [Phrase(text, words, count, texts, score)], best first).  txt:
+    one phrase a line and nothing else -- exactly a keyphrase file."""
+    renderers = {"txt": phrases2txt, "csv": phrases2csv, "xml": phrases2xml}
+    if format not in renderers:
+        raise Exception("Unknown phrases format: '%s'. Please use one of: 'txt', 'csv', 'xml'." % format)
+    return renderers[format](result)
+
+
+def phrases2txt(result):
+    return "".join("%s\n" % phrase.text for phrase in result)
+
+
+def phrases2csv(result):
+    """One line per phrase, best first: "phrase",words,count,texts,score."""
+    return "".join("%s,%d,%d,%d,%d\n" % (_csv_quote(p.text), p.words, p.count, p.texts, p.score) for p in result)
+
+
+def phrases2xml(result):
+    """<phrases count=..> / <phrase rank=.. words=.. count=.. texts=.. score=..>text</phrase>, best first."""
+    lines = ['<phrases count="%d">' % len(result)]
+    lines.extend('  <phrase rank="%d" words="%d" count="%d" texts="%d" score="%d">%s</phrase>'
+                 % (rank, p.words, p.count, p.texts, p.score, p.text) for rank, p in enumerate(result, 1))
+    lines.append("</phrases>")
+    return "\n".join(lines) + "\n"
+
+
 def format_graph(graph, format):
     renderers = {"gml": graph2gml, "edges": graph2edges}
     if format not in renderers:

@@ -179,6 +179,12 @@ SIGNATURES = {
     "east_hip_clusters_cut_threshold": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, _c_i32p, _c_i64p]),
     "east_hip_clusters_cut_count": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _c_i32p, _c_i64p]),
     "east_hip_last_clusters_ms": (ctypes.c_double, [ctypes.c_void_p]),
+    "east_hip_phrases_build": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                              ctypes.c_int64, _c_i64p]),
+    "east_hip_phrases_fetch": (ctypes.c_int, [ctypes.c_void_p, _c_i32p, _c_i32p, _c_i32p, _c_i32p, _c_i32p, _c_i32p, _c_i64p,
+                                              _c_u32p]),
+    "east_hip_phrases_levels": (ctypes.c_int, [ctypes.c_void_p, _c_i64p, _c_i64p]),
+    "east_hip_last_phrases_ms": (ctypes.c_double, [ctypes.c_void_p]),
 }
 
 BUILD_INFO_FIELDS = ("n_total", "n_docs", "n_strings", "sigma_text", "bits_level0", "dc3_levels", "arena_bytes",
@@ -420,6 +426,44 @@ def _matrix_fetch(fetch, h, M, count=True):
     return found
 
 
+PHRASES_MAX_WORDS = 8                       # csrc/phrases.h: PHR_MAX_WORDS
+
+
+class PhraseArrays(object):
+    """Extracted phrases as the device left them (include/east_hip.h, "Phrase extraction"), best first: per phrase `words`,
+    `count`, `texts`, `first`, `first_text` (int32[returned]); `term_ids` (int32, ragged by the prefix sum of words);
+    `text_off` (int64[returned + 1]) and `text` (uint32 code points, the words joined by one space); `candidates` = the
+    candidates before the cut by N; `levels`, `domain[8]`, `survivors[8]` = what the levels did."""
+    __slots__ = ("words", "count", "texts", "first", "first_text", "term_ids", "text_off", "text", "candidates", "levels",
+                 "domain", "survivors")
+
+    def strings(self):
+        """The phrases' text as a list of str."""
+        whole = self.text.astype("<u4").tobytes().decode("utf-32-le", errors="surrogatepass")
+        return [whole[a:e] for a, e in zip(self.text_off[:-1].tolist(), self.text_off[1:].tolist())]
+
+
+def _phrases(lib, h, n, max_words, min_words, min_count, min_texts):
+    out = np.zeros(4, dtype=np.int64)
+    _check(lib.east_hip_phrases_build(h, int(min_words), int(max_words), int(min_count), int(min_texts), int(n),
+                                      _ptr(out, _c_i64p)))
+    R = int(out[0])
+    found = PhraseArrays()
+    rows = [np.zeros(R, dtype=np.int32) for _ in range(5)]
+    found.words, found.count, found.texts, found.first, found.first_text = rows
+    found.text_off = np.zeros(R + 1, dtype=np.int64)
+    found.text = np.zeros(int(out[2]), dtype=np.uint32)
+    found.domain, found.survivors = np.zeros(PHRASES_MAX_WORDS, dtype=np.int64), np.zeros(PHRASES_MAX_WORDS, dtype=np.int64)
+    # (the ids are as many as the words of the returned phrases: the rows first)
+    _check(lib.east_hip_phrases_fetch(h, *([_ptr(r, _c_i32p) for r in rows] + [None, _ptr(found.text_off, _c_i64p),
+                                                                                _ptr(found.text, _c_u32p)])))
+    found.term_ids = np.zeros(int(found.words.sum()), dtype=np.int32)
+    _check(lib.east_hip_phrases_fetch(h, None, None, None, None, None, _ptr(found.term_ids, _c_i32p), None, None))
+    _check(lib.east_hip_phrases_levels(h, _ptr(found.domain, _c_i64p), _ptr(found.survivors, _c_i64p)))
+    found.candidates, found.levels = int(out[1]), int(out[3])
+    return found
+
+
 class _ResidentTableConsumers(object):
     """The graph, the ranking and the similarity of the score table that lies on the device of a handle (self._lib,
     self._h): the table `_table_source` names -- the AST table of a HipIndex, the cosine table of a HipCosineIndex."""
@@ -431,6 +475,16 @@ class _ResidentTableConsumers(object):
     def _sim_holder(self):
         """The HipIndex that remembers the size of the handle's last similarity matrix."""
         return self
+
+    # -- phrase extraction -----------------------------------------------------
+    def phrases(self, n=0, max_words=3, min_words=1, min_count=2, min_texts=1):
+        """The repeated phrases of the texts the handle's cosine term index holds (include/east_hip.h, "Phrase
+        extraction"), best first; n = 0: every candidate -> PhraseArrays."""
+        return _phrases(self._lib, self._h, n, max_words, min_words, min_count, min_texts)
+
+    @property
+    def last_phrases_ms(self):
+        return float(self._lib.east_hip_last_phrases_ms(self._h))
 
     # -- keyphrase graph -------------------------------------------------------
     def graph(self, rows, relevance_threshold, support_threshold, referral_confidence):

@@ -26,6 +26,12 @@ README.rst:27-63; the shipped reference main crashes with a NameError, SURVEY.md
         that reach it, -k: that many clusters, one of the two -- or neither with -f merges, the dendrogram a merge a line
     east [-s ast|cosine] [-b text|keyphrase] [-r threshold | -k clusters] [-f xml|csv|merges] keyphrases clusters <keyphrases file> <texts>
         the same of the texts (-b text) or the keyphrases (-b keyphrase) by the profile cosines of `keyphrases similar`
+    east [-n N] [-x max words] [-m min count] [-u min texts] [-l language] [-f txt|csv|xml] keyphrases extract <texts>
+        keyphrase candidates out of the texts themselves (no keyphrase file): the repeated phrases of one to -x (default 3, at
+        most 8) words that occur -m (default 2) times or more in -u (default 1) texts or more, without those that only ever
+        occur inside one longer phrase, by count x words, best first; -n: that many (default 100, 0 = all); the words are
+        the cosine measure's (at least 3 code points, its stopwords break a phrase), counted on the device (csrc/phrases.h);
+        -f txt (the default) is a keyphrase file: east keyphrases extract texts > kp.txt; east keyphrases top kp.txt texts
     east -s cosine [-w tf|tf-idf] [-v stems|words] keyphrases table|graph|top|similar|clusters ...
         the cosine measure (relevance.CosineRelevanceMeasure) on one device; `-v stems` (the default) needs nltk's
         Snowball stemmer, and without nltk's stopword list no stopwords are removed (said on stderr)
@@ -56,7 +62,7 @@ def _read(path):
         return f.read()
 
 
-_OPTIONS = "s:a:w:v:l:f:c:r:p:g:t:n:b:o:k:dy"
+_OPTIONS = "s:a:w:v:l:f:c:r:p:g:t:n:b:o:k:x:m:u:dy"
 _VALUE_OPTIONS = frozenset(c for c, nxt in zip(_OPTIONS, _OPTIONS[1:] + " ") if nxt == ":")
 
 
@@ -100,6 +106,8 @@ def main(argv=None, measure_factory=None):
         return _texts_main(opts, args, world, rank)
     if args[:2] == ["keyphrases", "clusters"]:
         return _clusters_main(opts, args, world, rank)
+    if args[:2] == ["keyphrases", "extract"]:
+        return _extract_main(opts, args, world, rank)
     cosine = opts.get("-s", "").lower() == consts.RelevanceMeasure.COSINE
     if world > 1 and cosine:
         if rank == 0:
@@ -157,7 +165,7 @@ def _main(opts, args, world, measure_factory):
         print("Invalid syntax: EAST should be called as:\n\n"
               "    east [options] <command> <subcommand> args\n\n"
               "Commands available: keyphrases, texts.\n"
-              "Subcommands available: table/graph/top/similar/clusters.")
+              "Subcommands available: table/graph/top/similar/clusters/extract.")
         return 1
 
     command, subcommand = args[0], args[1]
@@ -474,6 +482,80 @@ def _clusters_main(opts, args, world, rank):
     return 0
 
 
+def _extract_options(opts):
+    """(n, max_words, min_count, min_texts, format, None) of `keyphrases extract`, or five times None and the one line that
+    says what is wrong."""
+    numbers = []
+    for key, default, least, most, what in (("-n", "100", 0, None, "number of phrases"), ("-x", "3", 1, applications.EXTRACT_MAX_WORDS, "number of words"),
+                                            ("-m", "2", 1, None, "number of occurrences"), ("-u", "1", 1, None, "number of texts")):
+        try:
+            value = int(opts.get(key, default))
+        except ValueError:
+            value = None
+        if value is None or value < least or (most is not None and value > most) or value >= 2 ** 31:
+            return (None,) * 5 + ("Invalid %s: '%s'. Please use an integer %s." % (
+                what, opts[key], "from %d to %d" % (least, most) if most is not None else "of at least %d" % least),)
+        numbers.append(value)
+    fmt = opts.get("-f", "txt").lower()
+    if fmt not in ("txt", "csv", "xml"):
+        return (None,) * 5 + ("Unknown phrases format: '%s'. Please use one of: 'txt', 'csv', 'xml'." % opts["-f"],)
+    return tuple(numbers) + (fmt, None)
+
+
+def _extract_main(opts, args, world, rank):
+    """`east keyphrases extract <texts>`.  Everything that cannot be done is refused with one line before a file is read or
+    anything touches a device."""
+    def refuse(line):
+        if rank == 0:
+            print(line)
+        return 1
+
+    if len(args) < 3:
+        return refuse('Invalid syntax. For phrase extraction, EAST should be called as:\n\n'
+                      '    east [options] keyphrases extract "path/to/texts/dir"')
+    n, max_words, min_count, min_texts, fmt, refusal = _extract_options(opts)
+    if refusal:
+        return refuse(refusal)
+    if "-s" in opts:
+        return refuse("Phrases are counted, not scored: -s %s is not supported (score the extracted phrases with `keyphrases table` or `top`)." % opts["-s"])
+    if "-w" in opts:
+        return refuse("Phrases are counted, not weighted: -w %s is not supported." % opts["-w"])
+    if opts.get("-v", consts.VectorSpace.WORDS).lower() != consts.VectorSpace.WORDS:
+        return refuse("Phrases are made of words: -v %s is not supported." % opts["-v"])
+    for key, line in (("-y", "Phrase extraction takes no synonyms: -y is not supported."),
+                      ("-o", "Phrases have no orientation: -o %s is not supported."),
+                      ("-b", "Phrases are extracted from the whole collection: -b %s is not supported."),
+                      ("-r", "Phrases have no relevance threshold: -r %s is not supported (use -m for occurrences, -u for texts)."),
+                      ("-k", "Phrases are not clustered: -k %s is not supported (use -n for their number)."),
+                      ("-c", "Phrase extraction builds no graph: -c %s is not supported."),
+                      ("-p", "Phrase extraction builds no graph: -p %s is not supported.")):
+        if key in opts:
+            return refuse(line % opts[key] if "%s" in line else line)
+    if world > 1:
+        return refuse("Phrase extraction runs on one device: a launcher with WORLD_SIZE=%d is not supported." % world)
+    if os.environ.get("EAST_HIP_FORCE_DIST") == "1":
+        return refuse("Phrase extraction runs on one device: the collective path is not supported.")
+    devices = opts.get("-g", os.environ.get("EAST_HIP_DEVICES", "1"))
+    try:
+        n_ranks = int(devices)
+    except ValueError:
+        return refuse("Invalid number of GPUs: '%s'." % devices)
+    if n_ranks > 1:
+        return refuse("Phrase extraction runs on one device: -g %d is not supported." % n_ranks)
+    try:
+        measure = relevance.CosineRelevanceMeasure(consts.VectorSpace.WORDS)
+        if measure.stopwords_source == "none":
+            sys.stderr.write("nltk's English stopword list is not available: no stopwords are removed.\n")
+        texts = _read_texts(args[2])
+        found = applications.keyphrases_extract(texts, n, max_words, 1, min_count, min_texts, measure,
+                                                opts.get("-l", consts.Language.ENGLISH))
+        sys.stdout.write(formatting.format_phrases(found, fmt))       # (txt: a keyphrase file, no line added)
+    except exceptions.EastException as e:       # (no device, a failed build ...): a message, not a traceback
+        print(e)
+        return 1
+    return 0
+
+
 def _run_cosine(subcommand, keyphrases, texts, opts, synonimizer=None):
     """-s cosine with its -w / -v options (reference main.py:95-98, relevance.py:58-62); bad values, -v lemmata and a
     missing stemmer end here with one line, before anything touches the device."""
@@ -554,7 +636,7 @@ def _run(subcommand, keyphrases, texts, similarity_measure, opts, synonimizer=No
             print(e)
             return 1
         return 0
-    print("Invalid subcommand: '%s'. Please use one of: 'table', 'graph', 'top', 'similar', 'clusters'." % subcommand)
+    print("Invalid subcommand: '%s'. Please use one of: 'table', 'graph', 'top', 'similar', 'clusters', 'extract'." % subcommand)
     return 1
 
 

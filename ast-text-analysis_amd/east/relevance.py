@@ -473,6 +473,14 @@ class CosineRelevanceMeasure(RelevanceMeasure):
             self.index.clusters_build(hip_backend.GRAPH_SOURCE_SIMILARITY)
         return self.index
 
+    def extract_phrases(self, n=0, max_words=3, min_words=1, min_count=2, min_texts=1):
+        """The repeated phrases of the indexed collection as keyphrase candidates, best first (include/east_hip.h, "Phrase
+        extraction"; csrc/phrases.h); after set_text_collection, in the `words` space: a phrase is made of words, not of
+        stems.  n = 0: every candidate.  -> hip_backend.PhraseArrays."""
+        if self.vector_space != consts.VectorSpace.WORDS:
+            raise ValueError("extract_phrases: phrases are made of words, not of %s (use vector_space='words')" % self.vector_space)
+        return self.index.phrases(n, max_words, min_words, min_count, min_texts)
+
     def _score(self, prepared_keyphrases, fetch):
         per_query = [self._query_terms(q) for q in prepared_keyphrases]
         offsets = np.zeros(len(per_query) + 1, dtype=np.int64)

@@ -588,6 +588,61 @@ int east_hip_clusters_cut_count(east_hip_handle_t h, int32_t k, int32_t *labels,
 double east_hip_last_clusters_ms(east_hip_handle_t h);
 
 /*
+ * Phrase extraction (`east keyphrases extract`): the repeated phrases of one to eight words of the texts the cosine term
+ * index holds, counted exactly, the redundant ones removed, the rest ranked -- keyphrase candidates out of the texts
+ * themselves.  Integers only: two builds, the host path of the Python package and any other exact count give the same
+ * bytes.  (How: csrc/phrases.h)
+ *
+ * Tokens: the index's kept tokens in text order as the cosine build sees them -- the [\w']+ tokens of the prepared text
+ * (1:1 upper case) with at least 3 code points; shorter tokens are invisible.  A kept token that is a stopword of the
+ * index is a BREAK.  A token's POSITION is its index among the collection's kept tokens, stopwords counted, the texts in
+ * the order given.
+ * Phrase: n kept tokens that are no stopwords at consecutive positions of one text -- no phrase contains a break, none
+ * crosses from one text into the next.  Two phrases are the same when their words are, code point for code point.
+ * count(g) = the positions at which g starts (overlapping occurrences all count: AAA AAA AAA AAA AAA holds AAA AAA four
+ * times); texts(g) = the texts with at least one occurrence; first(g) = the smallest starting position.
+ * Candidates: with min_words <= n <= max_words (1 .. 8), min_count >= 1 and min_texts >= 1, g is a candidate when
+ * count(g) >= min_count, texts(g) >= min_texts and g is CLOSED: n = max_words, or no phrase of n + 1 words that starts
+ * with g or ends with g has the count of g.  (A phrase that only ever occurs inside one longer phrase is dropped in favour
+ * of the longer one; extensions beyond max_words are not looked at; an extension of the same count has the same
+ * occurrences shifted by at most a word, hence the same texts: it passes the same filters.)
+ * Order: by score = count * n descending, then n ascending, then first ascending -- strict, the list is unique.  N > 0
+ * keeps the first N, N = 0 all.
+ *
+ * Example.  One text `abc bcd cde abc bcd cde abc bcd cde abc bcd`, no stopwords, min_words 1, max_words 3, min_count 2,
+ * min_texts 1 gives, in this order:
+ *   ABC BCD CDE  (3 words, count 3, score 9, first 0)
+ *   BCD CDE ABC  (3 words, count 3, score 9, first 1)
+ *   CDE ABC BCD  (3 words, count 3, score 9, first 2)
+ *   ABC BCD      (2 words, count 4, score 8, first 0)
+ * Every single word and every other pair has an extension of its own count.
+ *
+ * east_hip_phrases_build: out[4] = the phrases returned, the candidates before the cut by N, the code points of the
+ * returned phrases' text, the levels run (level n names the n-grams; a level without a surviving n-gram is the last).
+ * EAST_HIP_ERR_NOT_BUILT "phrases: no cosine index has been built on this handle" without an index; EAST_HIP_ERR_INVALID
+ * with a line that names the argument for max_words outside 1 .. 8, min_words outside 1 .. max_words, min_count < 1,
+ * min_texts < 1, N < 0 and a null out.  Every refusal comes before anything is withdrawn: an earlier result stays
+ * fetchable.  Zero candidates is a result.  A cosine build on the handle withdraws the result, east_hip_reset drops it;
+ * score calls and east_hip_cosine_set_classes leave it alone (phrases are made of words, not of classes).
+ * east_hip_phrases_fetch: per returned phrase words[r], count[r], texts[r], first[r], first_text[r] (the text of
+ * first); term_ids: the phrases' words as east_hip_cosine_get_terms numbers them, ragged by the prefix sum of words;
+ * text_off[returned + 1] and text: the phrases' code points, the words joined by one U+0020.  Null outputs are skipped.
+ * EAST_HIP_ERR_NOT_BUILT "no phrases have been extracted on this handle" before a build.
+ * east_hip_phrases_levels: domain[8] and survivors[8] -- per level the positions whose n-gram was named and the distinct
+ * n-grams with count >= min_count; 0 for the levels that were not run.
+ * Limits: fewer than 2^31 - 16 candidates; the returned phrases' text has fewer than 2^32 code points.  Memory: 8 bytes a
+ * kept token in the index; during a build 112 bytes a kept token and 16 a candidate, buffers of the phrases' own.
+ * Device time of the last build in milliseconds (the read-backs between the levels included), -1 before a build and
+ * after a failed one.
+ */
+int east_hip_phrases_build(east_hip_handle_t h, int32_t min_words, int32_t max_words, int32_t min_count, int32_t min_texts,
+                           int64_t N, int64_t *out);
+int east_hip_phrases_fetch(east_hip_handle_t h, int32_t *words, int32_t *count, int32_t *texts, int32_t *first,
+                           int32_t *first_text, int32_t *term_ids, int64_t *text_off, uint32_t *text);
+int east_hip_phrases_levels(east_hip_handle_t h, int64_t *domain, int64_t *survivors);
+double east_hip_last_phrases_ms(east_hip_handle_t h);
+
+/*
  * Several devices in one process ("single-process/8-device fits the one-process CLI best").
  * Every document is an independent AST (east/relevance.py:41-46) and every (keyphrase, document) score is independent
  * (east/applications.py:43-52): a GROUP shards a collection at document granularity -- contiguous blocks of documents
