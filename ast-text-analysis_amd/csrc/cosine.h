@@ -516,6 +516,9 @@ struct CosUnits {
     u32 *inv_perm = nullptr, *doc_off = nullptr;        // a posting's place in document order; per document its range there
     DevBuf weights;                                       // per weighting (0 tf, 1 tf-idf): P weights and D norms, made on first use
     bool w_valid[2] = {false, false};
+    DevBuf bm_weights;                                    // the BM25 weights (bm25.h): P doubles, made for (bm_k1, bm_b)
+    double bm_k1 = 0.0, bm_b = 0.0;
+    bool bm_valid = false;
 };
 
 struct CosState : Consumer {
@@ -537,15 +540,20 @@ struct CosState : Consumer {
     double *table = nullptr;                              // the last score call's K x D table, where it lies in `score` (offers(): the graph, the ranking and the similarity read it there)
     u32 table_K = 0;
     bool table_valid = false;
+    u32 bm_N = 0, bm_made = 0;                            // bm25.h: the sum of n_d; how often BM25 weights were computed on this index
+    double bm_avgdl = 0.0;                                // ... (double)bm_N / (double)n_docs
+    bool bm_total_valid = false;
     CosState()
     {
-        bufs = {&text, &work, &index, &term_text, &classes, &score, &terms.weights, &cls.weights};
+        bufs = {&text, &work, &index, &term_text, &classes, &score, &terms.weights, &cls.weights, &terms.bm_weights, &cls.bm_weights};
         keep_bytes = (size_t)64 << 20;                      // (a recycled handle keeps small buffers only, as east_hip_reset does)
     }
     void clear() override
     {
         use_classes = table_valid = false;
         terms.w_valid[0] = terms.w_valid[1] = cls.w_valid[0] = cls.w_valid[1] = false;
+        terms.bm_valid = cls.bm_valid = bm_total_valid = false;
+        bm_made = 0;
         build_ms = score_ms = -1.f;
     }
     TableRef offers() const override
@@ -790,6 +798,7 @@ static void cos_set_classes(east_hip_index *h, const int32_t *term_class, int32_
 {
     CosState &c = cos_built(h);
     cos_withdraw_texts_matrix(h);
+    c.terms.bm_valid = c.cls.bm_valid = false;              // (bm25.h: its cached weights are those of one vector space)
     if (n_classes == 0) {                                   // back to the terms
         c.use_classes = false;
         return;

@@ -439,6 +439,7 @@ double east_hip_last_score_ms(east_hip_handle_t h) { return h ? (double)h->last_
 #include "format.h"
 // ---- the consumers (consumer.h), each with its kernels, its state and its entry points -------------------
 #include "cosine.h"         // the cosine relevance measure
+#include "bm25.h"           // the BM25 relevance measure on the cosine index
 #include "graph.h"          // the keyphrase graph
 #include "synonyms.h"       // synonym extraction from dependency triples
 #include "similarity.h"     // similar texts and keyphrases

@@ -561,26 +561,19 @@ def _texts_cosine_matrix(doc_units, n_units, tfidf):
     return matrix, own, postings
 
 
+def _refuse_bm25(who, measure):
+    """BM25 scores keyphrases against texts: the questions asked of the texts alone are the cosine measure's (the isinstance
+    checks below would let its subclass through)."""
+    if isinstance(measure, relevance.BM25RelevanceMeasure):
+        raise ValueError("%s: BM25 scores keyphrases against texts; the texts alone are compared by the cosine measure "
+                         "(use a CosineRelevanceMeasure), not by %s" % (who, type(measure).__name__))
+
+
 def _texts_similar_on_host(texts, measure, language):
     """texts_similar's matrix on the host, without a device: the tokens of utils.tokenize(utils.prepare_text(text)) through
     the measure's own filter (at least 3 code points, not a stopword) and, in the stems space, its stemmer; the units
     numbered by first occurrence."""
-    stems = measure.vector_space == consts.VectorSpace.STEMS
-    stemmer = None
-    if stems:
-        stemmer = measure.stemmer if measure._snowball is None else measure._snowball.SnowballStemmer(language)
-    number, stem_of, doc_units = {}, {}, []
-    for text in texts.values():
-        ids = []
-        for token in utils.tokenize(utils.prepare_text(text)):
-            if len(token) < 3 or token in measure.stopwords:
-                continue
-            if stems:
-                if token not in stem_of:
-                    stem_of[token] = stemmer.stem(token)
-                token = stem_of[token]
-            ids.append(number.setdefault(token, len(number)))
-        doc_units.append(ids)
+    doc_units, number, _ = relevance.host_doc_units(texts.values(), measure, language)
     return _texts_cosine_matrix(doc_units, len(number), measure.term_weighting == consts.TermWeighting.TF_IDF)
 
 
@@ -610,6 +603,7 @@ def texts_similar(texts, n=10, similarity_threshold=None, similarity_measure=Non
     if not isinstance(measure, relevance.CosineRelevanceMeasure):
         raise ValueError("texts_similar: the cosine of term vectors needs a CosineRelevanceMeasure, not %s (texts_related "
                          "answers with the AST measure)" % type(measure).__name__)
+    _refuse_bm25("texts_similar", measure)
     titles = list(texts.keys())
     if not titles:
         return {}
@@ -782,6 +776,7 @@ def texts_clusters(texts, threshold=None, k=None, similarity_measure=None, langu
     """
     threshold, k = _cut_arguments("texts_clusters", threshold, k)
     measure = similarity_measure or relevance.ASTRelevanceMeasure()
+    _refuse_bm25("texts_clusters", measure)
     titles = list(texts.keys())
     if not titles:
         return Clustering([], [], [], [], None if threshold is None and k is None else [])
@@ -935,6 +930,7 @@ def keyphrases_extract(texts, n=100, max_words=3, min_words=1, min_count=2, min_
         raise ValueError("keyphrases_extract: phrases are extracted from the term index of a CosineRelevanceMeasure in the "
                          "'words' space, not %s" % (type(measure).__name__ if not isinstance(measure, relevance.CosineRelevanceMeasure)
                                                     else "the '%s' space" % measure.vector_space))
+    _refuse_bm25("keyphrases_extract", measure)
     texts = list(texts.values()) if isinstance(texts, Mapping) else list(texts)
     if os.environ.get("EAST_HIP_EXTRACT", "device") == "host":
         rows = _phrases_on_host(texts, measure.stopwords, n, max_words, min_words, min_count, min_texts)[0]

@@ -30,7 +30,7 @@ TraversalOrder = _Group(DEPTH_FIRST_PRE_ORDER="depth-first|pre-order",
 String = _Group(UNICODE_SPECIAL_SYMBOLS_START=0x0A00)
 
 # -s option of the CLI
-RelevanceMeasure = _Group(AST="AST", COSINE="cosine")
+RelevanceMeasure = _Group(AST="AST", COSINE="cosine", BM25="bm25")
 
 # -a option of the CLI / second argument of AST.get_ast; "easa_hip" names the MI355X backend explicitly
 ASTAlgorithm = _Group(EASA="easa", AST_LINEAR="ast_linear", AST_NAIVE="ast_naive", EASA_HIP="easa_hip")

@@ -138,6 +138,10 @@ SIGNATURES = {
     "east_hip_cosine_score_table": (ctypes.c_int, [ctypes.c_void_p, _c_i32p, _c_i64p, ctypes.c_int64, ctypes.c_int32,
                                                    ctypes.c_int32, _c_dblp]),
     "east_hip_debug_set_term_hash_bits": (ctypes.c_int, [ctypes.c_int]),
+    "east_hip_bm25_score_table": (ctypes.c_int, [ctypes.c_void_p, _c_i32p, _c_i64p, ctypes.c_int64, ctypes.c_int32,
+                                                 ctypes.c_double, ctypes.c_double, _c_dblp]),
+    "east_hip_bm25_info": (ctypes.c_int, [ctypes.c_void_p, _c_dblp, ctypes.c_int32]),
+    "east_hip_debug_set_bm25_strip": (ctypes.c_int, [ctypes.c_int32]),
     "east_hip_graph_build_resident": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _c_i32p, ctypes.c_int64, ctypes.c_double,
                                                      ctypes.c_double, ctypes.c_double, _c_i64p]),
     "east_hip_graph_build_host": (ctypes.c_int, [ctypes.c_void_p, _c_dblp, ctypes.c_int32, ctypes.c_int32, _c_i32p,
@@ -195,6 +199,7 @@ BUILD_INFO_FIELDS = ("n_total", "n_docs", "n_strings", "sigma_text", "bits_level
                      "first_hist_fused")
 COSINE_INFO_FIELDS = ("built", "n_docs", "kept_tokens", "words", "terms", "classes", "postings", "hash_attempts", "build_us",
                       "score_us")
+BM25_INFO_FIELDS = ("N", "avgdl", "k1", "b", "weights_computed")        # east_hip_bm25_info (k1, b: NaN while no weights are cached)
 
 GRAPH_SOURCE_AST, GRAPH_SOURCE_COSINE, GRAPH_SOURCE_UPLOADED = 0, 1, 2      # east_hip_graph_build_resident: which resident table
 GRAPH_SOURCE_SIMILARITY = 3                 # east_hip_top_build_resident only: the matrix the last similarity build left
@@ -948,6 +953,26 @@ class HipCosineIndex(_ResidentTableConsumers):
         _check(self._lib.east_hip_cosine_score_table(self._h, _ptr(q_ids, _c_i32p), _ptr(q_offsets, _c_i64p), q_ids.size, K,
                                                      1 if tfidf else 0, _ptr(out, _c_dblp) if fetch else None))
         return out
+
+    # -- BM25: a second score call of the same index ------------------------------
+    def bm25_table(self, q_ids, q_offsets, k1=1.2, b=0.75, fetch=True):
+        """K x D BM25 scores (include/east_hip.h, "BM25") of the queries score_table takes; the table replaces the last
+        score call's on the device.  fetch=False: it stays there, nothing is returned."""
+        q_ids = np.ascontiguousarray(q_ids, dtype=np.int32)
+        q_offsets = np.ascontiguousarray(q_offsets, dtype=np.int64)
+        K = q_offsets.size - 1
+        out = np.empty((K, self.n_docs), dtype=np.float64) if fetch else None
+        _check(self._lib.east_hip_bm25_score_table(self._h, _ptr(q_ids, _c_i32p), _ptr(q_offsets, _c_i64p), q_ids.size, K,
+                                                   float(k1), float(b), _ptr(out, _c_dblp) if fetch else None))
+        return out
+
+    def bm25_info(self):
+        """{BM25_INFO_FIELDS: value}: N and weights_computed as int, the rest float."""
+        buf = np.zeros(len(BM25_INFO_FIELDS), dtype=np.float64)
+        _check(self._lib.east_hip_bm25_info(self._h, _ptr(buf, _c_dblp), buf.size))
+        info = dict(zip(BM25_INFO_FIELDS, (float(x) for x in buf)))
+        info["N"], info["weights_computed"] = int(info["N"]), int(info["weights_computed"])
+        return info
 
     # -- text-to-text cosine similarity ------------------------------------------
     def texts_build(self, tfidf=True):

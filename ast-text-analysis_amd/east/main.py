@@ -24,7 +24,7 @@ README.rst:27-63; the shipped reference main crashes with a NameError, SURVEY.md
         the groups the texts fall into: single-linkage clusters of the symmetric relatedness (-s ast, the default) or of the
         term-vector cosine (-s cosine), built where the matrix lies (csrc/clusters.h); -r: the texts joined by similarities
         that reach it, -k: that many clusters, one of the two -- or neither with -f merges, the dendrogram a merge a line
-    east [-s ast|cosine] [-b text|keyphrase] [-r threshold | -k clusters] [-f xml|csv|merges] keyphrases clusters <keyphrases file> <texts>
+    east [-s ast|cosine|bm25] [-b text|keyphrase] [-r threshold | -k clusters] [-f xml|csv|merges] keyphrases clusters <keyphrases file> <texts>
         the same of the texts (-b text) or the keyphrases (-b keyphrase) by the profile cosines of `keyphrases similar`
     east [-n N] [-x max words] [-m min count] [-u min texts] [-l language] [-f txt|csv|xml] keyphrases extract <texts>
         keyphrase candidates out of the texts themselves (no keyphrase file): the repeated phrases of one to -x (default 3, at
@@ -35,6 +35,9 @@ README.rst:27-63; the shipped reference main crashes with a NameError, SURVEY.md
     east -s cosine [-w tf|tf-idf] [-v stems|words] keyphrases table|graph|top|similar|clusters ...
         the cosine measure (relevance.CosineRelevanceMeasure) on one device; `-v stems` (the default) needs nltk's
         Snowball stemmer, and without nltk's stopword list no stopwords are removed (said on stderr)
+    east -s bm25 [-v stems|words] [-z k1,b] keyphrases table|graph|top|similar|clusters ...
+        Okapi BM25 (relevance.BM25RelevanceMeasure) as a second score call of the cosine measure's term index, on one
+        device: its tokens, stopwords and stemmer; -z: k1 >= 0 and 0 <= b <= 1 (default 1.2,0.75); -w belongs to cosine
     east -y -t <triples file> keyphrases table|graph ...
         synonym extraction (synonyms.SynonymExtractor, reference main.py:104-133) from dependency triples made elsewhere:
         Tomita's XML output, or lines of w1<TAB>relation<TAB>w2; one device; -y without -t is refused (no parser here)
@@ -62,7 +65,7 @@ def _read(path):
         return f.read()
 
 
-_OPTIONS = "s:a:w:v:l:f:c:r:p:g:t:n:b:o:k:x:m:u:dy"
+_OPTIONS = "s:a:w:v:l:f:c:r:p:g:t:n:b:o:k:x:m:u:z:dy"
 _VALUE_OPTIONS = frozenset(c for c, nxt in zip(_OPTIONS, _OPTIONS[1:] + " ") if nxt == ":")
 
 
@@ -95,6 +98,11 @@ def main(argv=None, measure_factory=None):
     opt_list = opts                                         # (as given: repeated options, empty values)
     opts = dict(opts)
     world, rank = _world()
+    refusal = _bm25_refusal(opts, args, world)             # (before a rank is started, a file is read or anything touches the device)
+    if refusal:
+        if rank == 0:
+            print(refusal)
+        return 1
     if args[:2] in (["keyphrases", "top"], ["keyphrases", "similar"]):
         # (-n, -b, -r: refused here, before a rank is started, a file is read or anything touches the device)
         refusal = _top_options(opts)[3]
@@ -203,8 +211,9 @@ def _main(opts, args, world, measure_factory):
 
     measure_name = opts["-s"]
     cosine = measure_name.lower() == consts.RelevanceMeasure.COSINE
-    if measure_name.lower() != "ast" and not cosine:
-        print("Relevance measure '%s' is not available (use 'ast' or 'cosine')." % measure_name)
+    bm25 = measure_name.lower() == consts.RelevanceMeasure.BM25
+    if measure_name.lower() != "ast" and not cosine and not bm25:
+        print("Relevance measure '%s' is not available (use 'ast', 'cosine' or 'bm25')." % measure_name)
         return 1
     if "-y" in opts and "-t" not in opts:
         print("Synonym extraction (-y) needs the external Tomita parser and is not available.")
@@ -228,6 +237,8 @@ def _main(opts, args, world, measure_factory):
             print("Relevance measure 'cosine' runs on one device: the collective path is not supported.")
             return 1
         return _run_cosine(subcommand, keyphrases, texts, opts, synonimizer)
+    if bm25:                                                # (the collective path was refused in main)
+        return _run_bm25(subcommand, keyphrases, texts, opts, synonimizer)
 
     group_up = False
     try:
@@ -436,8 +447,9 @@ def _clusters_main(opts, args, world, rank):
         return refuse(refusal)
     measure_name = opts.get("-s", consts.RelevanceMeasure.AST).lower()
     cosine = measure_name == consts.RelevanceMeasure.COSINE
-    if measure_name != consts.RelevanceMeasure.AST.lower() and not cosine:
-        return refuse("Relevance measure '%s' is not available (use 'ast' or 'cosine')." % opts["-s"])
+    bm25 = measure_name == consts.RelevanceMeasure.BM25      # (keyphrases clusters: `texts clusters` was refused in main)
+    if measure_name != consts.RelevanceMeasure.AST.lower() and not cosine and not bm25:
+        return refuse("Relevance measure '%s' is not available (use 'ast', 'cosine' or 'bm25')." % opts["-s"])
     by = opts.get("-b", "text").lower()
     if by not in ("text", "keyphrase"):
         return refuse("Invalid clustering direction: '%s'. Please use one of: 'text', 'keyphrase'." % opts["-b"])
@@ -464,8 +476,11 @@ def _clusters_main(opts, args, world, rank):
         return refuse("Clusters run on one device: -g %d is not supported." % n_ranks)
     language = opts.get("-l", consts.Language.ENGLISH)
     try:
-        if cosine:
-            measure = relevance.CosineRelevanceMeasure(opts.get("-v", consts.VectorSpace.STEMS), opts.get("-w", consts.TermWeighting.TF_IDF))
+        if cosine or bm25:
+            if bm25:
+                measure = relevance.BM25RelevanceMeasure(opts.get("-v", consts.VectorSpace.STEMS), *_bm25_parameters(opts))
+            else:
+                measure = relevance.CosineRelevanceMeasure(opts.get("-v", consts.VectorSpace.STEMS), opts.get("-w", consts.TermWeighting.TF_IDF))
             if measure.stopwords_source == "none":
                 sys.stderr.write("nltk's English stopword list is not available: no stopwords are removed.\n")
         else:
@@ -562,6 +577,63 @@ def _run_cosine(subcommand, keyphrases, texts, opts, synonimizer=None):
     try:
         measure = relevance.CosineRelevanceMeasure(opts.get("-v", consts.VectorSpace.STEMS),
                                                    opts.get("-w", consts.TermWeighting.TF_IDF))
+        if measure.stopwords_source == "none":
+            sys.stderr.write("nltk's English stopword list is not available: no stopwords are removed.\n")
+        return _run(subcommand, keyphrases, texts, measure, opts, synonimizer)
+    except exceptions.EastException as e:
+        print(e)
+        return 1
+
+
+def _bm25_parameters(opts):
+    """(k1, b) of -z k1,b (default 1.2,0.75); ValueError for anything else than two numbers with k1 finite and >= 0 and
+    0 <= b <= 1."""
+    if "-z" not in opts:
+        return relevance.BM25_K1, relevance.BM25_B
+    parts = opts["-z"].split(",")
+    if len(parts) != 2:
+        raise ValueError("two numbers")
+    return relevance.bm25_parameters(float(parts[0]), float(parts[1]))
+
+
+def _bm25_refusal(opts, args, world):
+    """The one line that says why a command line with `-s bm25` or `-z` cannot run, or None.  Nothing is read and no device
+    is touched."""
+    bm25 = opts.get("-s", "").lower() == consts.RelevanceMeasure.BM25
+    if "-z" in opts and not bm25:
+        return "Option -z gives the k1,b of the BM25 measure: use it with -s bm25."
+    if not bm25:
+        return None
+    if args[:1] == ["texts"] or args[:2] == ["keyphrases", "extract"]:
+        return ("Relevance measure 'bm25' scores keyphrases against texts: `%s` is not supported (the texts alone are the "
+                "cosine measure's: -s cosine)." % " ".join(args[:2]))
+    if "-w" in opts:
+        return "Relevance measure 'bm25' has no term weighting: -w %s is not supported (it belongs to -s cosine; see -z k1,b)." % opts["-w"]
+    try:
+        _bm25_parameters(opts)
+    except ValueError:
+        return "Invalid BM25 parameters: '%s'. Please use -z k1,b with k1 >= 0 and 0 <= b <= 1 (default 1.2,0.75)." % opts["-z"]
+    if opts.get("-v", consts.VectorSpace.STEMS).lower() == consts.VectorSpace.LEMMATA:
+        return "Relevance measure 'bm25' has no lemmatizer: -v %s is not supported (use 'stems' or 'words')." % opts["-v"]
+    if world > 1:
+        return "Relevance measure 'bm25' runs on one device: a launcher with WORLD_SIZE=%d is not supported." % world
+    if os.environ.get("EAST_HIP_FORCE_DIST") == "1":
+        return "Relevance measure 'bm25' runs on one device: the collective path is not supported."
+    devices = opts.get("-g", os.environ.get("EAST_HIP_DEVICES", "1"))
+    try:
+        n_ranks = int(devices)
+    except ValueError:
+        return "Invalid number of GPUs: '%s'." % devices
+    if n_ranks > 1:
+        return "Relevance measure 'bm25' runs on one device: -g %d is not supported." % n_ranks
+    return None
+
+
+def _run_bm25(subcommand, keyphrases, texts, opts, synonimizer=None):
+    """-s bm25 with its -v / -z options; what _bm25_refusal lets through and the measure still refuses (an unknown -v, a
+    missing stemmer) ends here with one line, before anything touches the device."""
+    try:
+        measure = relevance.BM25RelevanceMeasure(opts.get("-v", consts.VectorSpace.STEMS), *_bm25_parameters(opts))
         if measure.stopwords_source == "none":
             sys.stderr.write("nltk's English stopword list is not available: no stopwords are removed.\n")
         return _run(subcommand, keyphrases, texts, measure, opts, synonimizer)

@@ -6,6 +6,7 @@ call for the whole text collection and `relevance_table`, ONE score call for all
 ASTRelevanceMeasure: the documents become one device-resident shard of annotated suffix arrays.
 CosineRelevanceMeasure (`-s cosine`): the documents become one device-resident term index -- postings (term, document,
 count) -- and a keyphrase is scored against every document by walking the posting lists of its terms.
+BM25RelevanceMeasure (`-s bm25`): Okapi BM25 as a second score call of that term index.
 """
 import itertools
 import os
@@ -481,7 +482,9 @@ class CosineRelevanceMeasure(RelevanceMeasure):
             raise ValueError("extract_phrases: phrases are made of words, not of %s (use vector_space='words')" % self.vector_space)
         return self.index.phrases(n, max_words, min_words, min_count, min_texts)
 
-    def _score(self, prepared_keyphrases, fetch):
+    def _query_ids(self, prepared_keyphrases):
+        """(ids int32, offsets int64) of a score call: the kept tokens of every keyphrase as units of the index's vector
+        space, -1 outside it."""
         per_query = [self._query_terms(q) for q in prepared_keyphrases]
         offsets = np.zeros(len(per_query) + 1, dtype=np.int64)
         np.cumsum([len(q) for q in per_query], out=offsets[1:])
@@ -492,11 +495,147 @@ class CosineRelevanceMeasure(RelevanceMeasure):
             distinct = list(dict.fromkeys(flat))
             where = dict(zip(distinct, self.index.lookup(distinct).tolist()))
             ids = [where[t] for t in flat]
-        return self.index.score_table(np.array(ids, dtype=np.int32), offsets,
-                                      self.term_weighting == consts.TermWeighting.TF_IDF, fetch)
+        return np.array(ids, dtype=np.int32), offsets
+
+    def _score(self, prepared_keyphrases, fetch):
+        ids, offsets = self._query_ids(prepared_keyphrases)
+        return self.index.score_table(ids, offsets, self.term_weighting == consts.TermWeighting.TF_IDF, fetch)
 
     def relevance(self, keyphrase, text, synonimizer=None):
         """relevance.py:150-168: the score of a prepared keyphrase in text number `text` (one row is cached)."""
         if self._row[0] != keyphrase:
             self._row = (keyphrase, self.relevance_table([keyphrase])[0])
         return float(self._row[1][text])
+
+
+def host_doc_units(texts, measure, language):
+    """The token loop of the host paths, without a device: per text the units of its kept tokens -- utils.tokenize(
+    utils.prepare_text(text)) through the measure's own filter (at least 3 code points, not a stopword) and, in the stems
+    space, its stemmer -- one entry a token, the units numbered by first occurrence.
+    -> (doc_units, {unit's word or stem: its number}, the stemmer or None)."""
+    stems = measure.vector_space == consts.VectorSpace.STEMS
+    stemmer = None
+    if stems:
+        stemmer = measure.stemmer if measure._snowball is None else measure._snowball.SnowballStemmer(language)
+    number, stem_of, doc_units = {}, {}, []
+    for text in texts:
+        ids = []
+        for token in utils.tokenize(utils.prepare_text(text)):
+            if len(token) < 3 or token in measure.stopwords:
+                continue
+            if stems:
+                if token not in stem_of:
+                    stem_of[token] = stemmer.stem(token)
+                token = stem_of[token]
+            ids.append(number.setdefault(token, len(number)))
+        doc_units.append(ids)
+    return doc_units, number, stemmer
+
+
+BM25_K1, BM25_B = 1.2, 0.75
+
+
+def bm25_parameters(k1, b):
+    """(k1, b) as floats; ValueError unless k1 is finite and >= 0 and 0 <= b <= 1 (NaN is neither)."""
+    try:
+        k1, b = float(k1), float(b)
+    except (TypeError, ValueError):
+        raise ValueError("BM25: k1 and b must be numbers, not %r and %r" % (k1, b))
+    if not (0.0 <= k1 < float("inf")) or not (0.0 <= b <= 1.0):
+        raise ValueError("BM25: k1 must be finite and >= 0 and b between 0 and 1, not k1 = %r, b = %r" % (k1, b))
+    return k1, b
+
+
+def bm25_host_table(doc_units, n_units, q_ids, k1, b):
+    """The contract of include/east_hip.h ("BM25") in numpy: doc_units[d] = the units of text d's kept tokens, one entry a
+    token; q_ids[k] = the units of keyphrase k's kept tokens, -1 outside the vector space.  Every operation in the order
+    the device takes it.  -> K x D float64."""
+    D = len(doc_units)
+    out = np.zeros((len(q_ids), D), dtype=np.float64)
+    if not D:
+        return out
+    n_d = np.array([len(ids) for ids in doc_units], dtype=np.float64)
+    avgdl = float(sum(len(ids) for ids in doc_units)) / float(D)
+    doc, unit, count = [], [], []
+    for d, ids in enumerate(doc_units):
+        u, c = np.unique(np.asarray(ids, dtype=np.int64), return_counts=True)
+        doc.append(np.full(u.size, d, dtype=np.int64))
+        unit.append(u)
+        count.append(c.astype(np.float64))
+    doc, unit, count = np.concatenate(doc), np.concatenate(unit), np.concatenate(count)
+    order = np.argsort(unit, kind="stable")                  # (unit, document) order: the documents ascend inside a unit
+    doc, unit, count = doc[order], unit[order], count[order]
+    unit_off = np.searchsorted(unit, np.arange(n_units + 1))
+    w = np.zeros(0, dtype=np.float64)
+    if unit.size:
+        df = (unit_off[1:] - unit_off[:-1]).astype(np.float64)[unit]
+        idf = np.log1p((float(D) - df + 0.5) / (df + 0.5))
+        w = idf * (count * (k1 + 1.0)) / (count + k1 * ((1.0 - b) + b * (n_d[doc] / avgdl)))
+    for k, ids in enumerate(q_ids):
+        qtf = {}
+        for u in ids:
+            if 0 <= u < n_units:
+                qtf[u] = qtf.get(u, 0) + 1
+        for u, c in qtf.items():                             # (a dict keeps the order of the first occurrences)
+            a, e = unit_off[u], unit_off[u + 1]
+            out[k, doc[a:e]] += float(c) * w[a:e]
+    return out
+
+
+class BM25RelevanceMeasure(CosineRelevanceMeasure):
+    """Okapi BM25 (`-s bm25`; include/east_hip.h, "BM25") over the cosine measure's term index: the same tokens, stopwords,
+    stemmer, set_text_collection and query preparation; the score call is the index's second one (csrc/bm25.h), whose table
+    the graph, the ranking, the similarity and the clusters read as they read a cosine table.
+
+    score(k, d) = the sum over the keyphrase's distinct units u with a posting in d of
+                  qtf_ku * log1p((D - df_u + 0.5) / (df_u + 0.5)) * c_ud (k1 + 1) / (c_ud + k1 (1 - b + b n_d / avgdl)).
+
+    k1 finite and >= 0, 0 <= b <= 1: anything else raises ValueError here, before any device work.  BM25 scores keyphrases
+    against texts: the text-to-text questions and the phrase extraction are the cosine measure's and raise ValueError.
+
+    EAST_HIP_BM25=host (read here): the measure touches no device -- relevance_table computes the formula in numpy from
+    the tokens of host_doc_units, and relevance_graph / relevance_top / relevance_similar / relevance_clusters are None, so
+    the applications take their host loops.  Device and host agree to (t + 24) * 2^-53 relative each of the exact value
+    (t = the contributing units of a score); they are not promised to be the same bytes (log1p is two libraries' code)."""
+
+    def __init__(self, vector_space=consts.VectorSpace.STEMS, k1=BM25_K1, b=BM25_B, device=None, stopwords=None, stemmer=None):
+        self.k1, self.b = bm25_parameters(k1, b)
+        super(BM25RelevanceMeasure, self).__init__(vector_space, consts.TermWeighting.TF_IDF, device, stopwords, stemmer)
+        self.on_host = os.environ.get("EAST_HIP_BM25", "device") == "host"
+        if self.on_host:
+            self.relevance_graph = self.relevance_top = self.relevance_similar = self.relevance_clusters = None
+            self._doc_units, self._number = [], {}
+
+    def set_text_collection(self, texts, language=consts.Language.ENGLISH):
+        if not self.on_host:
+            return super(BM25RelevanceMeasure, self).set_text_collection(texts, language)
+        self.texts = list(texts)
+        self.language = language
+        self._doc_units, self._number, stemmer = host_doc_units(self.texts, self, language)
+        if stemmer is not None:
+            self.stemmer = stemmer
+        self._row = (None, None)
+
+    def _score(self, prepared_keyphrases, fetch):
+        if self.on_host:
+            q_ids = [[self._number.get(t, -1) for t in self._query_terms(q)] for q in prepared_keyphrases]
+            return bm25_host_table(self._doc_units, len(self._number), q_ids, self.k1, self.b)
+        ids, offsets = self._query_ids(prepared_keyphrases)
+        return self.index.bm25_table(ids, offsets, self.k1, self.b, fetch)
+
+    def _cosine_only(self, what):
+        raise ValueError("%s: BM25 scores keyphrases against texts; this is the cosine measure's (use a CosineRelevanceMeasure)" % what)
+
+    def relevance_texts_similar(self, n, threshold=-np.inf):
+        self._cosine_only("relevance_texts_similar")
+
+    def text_similarity_matrix(self):
+        self._cosine_only("text_similarity_matrix")
+
+    def extract_phrases(self, n=0, max_words=3, min_words=1, min_count=2, min_texts=1):
+        self._cosine_only("extract_phrases")
+
+    def relevance_clusters(self, prepared_keyphrases=None, axis=None):
+        if prepared_keyphrases is None:
+            self._cosine_only("relevance_clusters without keyphrases")
+        return super(BM25RelevanceMeasure, self).relevance_clusters(prepared_keyphrases, axis)

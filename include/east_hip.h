@@ -277,6 +277,37 @@ int east_hip_cosine_score_table(east_hip_handle_t h, const int32_t *q_ids, const
                                 int32_t n_keyphrases, int32_t weighting, double *out);
 
 /*
+ * BM25 (`east -s bm25`): Okapi BM25 as a second score call of the cosine term index -- the same postings, document
+ * lengths, classes and query look-up; nothing else is built.  (How: csrc/bm25.h)
+ *
+ * In the current vector space (the terms, or the classes after east_hip_cosine_set_classes): D = the documents, df_u = the
+ * postings of unit u, c_ud = the count of a posting, n_d = the index's own document length (the one tf divides by),
+ * N = the sum of n_d (an exact integer) and avgdl = (double)N / (double)D, one double that every path shares.
+ *     idf_u = log1p((D - df_u + 0.5) / (df_u + 0.5))                      (the non-negative form; log1p, not log(1 + x))
+ *     w_ud  = idf_u * (c_ud * (k1 + 1)) / (c_ud + k1 * ((1 - b) + b * (n_d / avgdl)))
+ *     score(k, d) = the sum of qtf_ku * w_ud over the distinct units u of keyphrase k that have a posting in d, taken in
+ *                   the order of their first occurrence in the keyphrase; qtf = how often the unit occurs among the
+ *                   keyphrase's kept tokens.  A token outside the vector space (id -1) contributes nothing and changes
+ *                   nothing.  A (k, d) without a common unit is exactly +0.0; every score is >= 0.
+ * Every operation is one IEEE double rounding in the order written.  k1 finite and >= 0, 0 <= b <= 1; anything else, NaN
+ * included, is EAST_HIP_ERR_INVALID (the usual values: 1.2 and 0.75).  Not in it: BM25+ / BM25F / a query-side k3, a
+ * text-to-text BM25, several devices, the AST side.
+ *
+ * east_hip_bm25_score_table  q_ids / q_offsets / q_len / n_keyphrases / out as east_hip_cosine_score_table takes them,
+ *     with the same checks, made before anything is invalidated: a refused call leaves the previous table offered.  out
+ *     may be null.  The K x D table is left where a cosine score call leaves its own: EAST_HIP_GRAPH_SOURCE_COSINE names
+ *     the table of the last score call of either kind, and east_hip_cosine_info out[9] is that call's time.  The P
+ *     weights are cached per vector space with the (k1, b) they were made for; a build and east_hip_cosine_set_classes
+ *     drop them, other parameters replace them.  The cosine weights are never touched.  Two calls give the same bytes.
+ * east_hip_bm25_info  out[0..4]: N, avgdl, the cached k1 and b of the current vector space (NaN: none), and how many
+ *     times the weights have been computed on this index since its build.
+ * Both: EAST_HIP_ERR_NOT_BUILT before a cosine build.
+ */
+int east_hip_bm25_score_table(east_hip_handle_t h, const int32_t *q_ids, const int64_t *q_offsets, int64_t q_len,
+                              int32_t n_keyphrases, double k1, double b, double *out);
+int east_hip_bm25_info(east_hip_handle_t h, double *out, int32_t cap);
+
+/*
  * The keyphrase graph (`east keyphrases graph`): the main loop of keyphrases_graph (east/applications.py:59-149) on the
  * device, from a K x D score table that is already there.  A keyphrase occurs in a text when score >= relevance_threshold
  * (a NaN score never does, -0.0 >= 0.0 does); its support is the number of such texts; the nodes are the positions p of
@@ -920,6 +951,10 @@ int east_hip_debug_set_text_ring(int mode, int64_t slot_bytes);
  * all 61, the default), so that different words collide, the verification finds it and the build starts over with the
  * next seed (east_hip_cosine_info: hash attempts).  The index does not depend on it. */
 int east_hip_debug_set_term_hash_bits(int bits);
+/* Test knob: the documents of a strip of the BM25 score kernel (more than its accumulators hold -- 2 048, or 512 for
+ * collections of up to 512 documents -- is taken as that; 0 or less = the default, all they hold), so that a collection of
+ * 65 documents has strip boundaries inside.  Process-wide, read when a score call starts.  The scores do not depend on it. */
+int east_hip_debug_set_bm25_strip(int32_t documents);
 /* Test knob: the number of entries of a source row the synonyms' pair kernel stages in LDS at a time (1 .. 128; 0 or less =
  * the default, 128), so that rows of a few dozen entries go through the chunk-to-chunk path.  Process-wide, read when a
  * pairs call starts.  The pairs do not depend on it. */
