@@ -33,6 +33,8 @@
 //
 // The merges are fetched ONCE, at the end of the build, into the state: the cuts are a union-find over at most M - 1 merges
 // on the host, and the matrix is not needed again.
+//
+// Complete and average linkage share the state, the symmetry check, the fetch and the cuts; their rounds are linkage.h.
 #pragma once
 #include "consumer.h"
 
@@ -269,9 +271,10 @@ struct ClustersState : Consumer {
     i64 rounds = 0, launches = 0;
     UploadedTable table;                    // a host matrix's copy (east_hip_clusters_build_host)
     DevBuf work;
+    DevBuf wcopy;                           // the working copy of a complete or average linkage build, released after it (linkage.h)
     std::vector<int32_t> merge_a, merge_b;  // the forest, strongest first
     std::vector<double> merge_w;
-    ClustersState() { bufs = {&table.buf, &work}; }
+    ClustersState() { bufs = {&table.buf, &work, &wcopy}; }
     void clear() override
     {
         M = 0;

@@ -447,4 +447,5 @@ double east_hip_last_score_ms(east_hip_handle_t h) { return h ? (double)h->last_
 #include "related.h"        // text-to-text relatedness
 #include "cosine_texts.h"   // text-to-text cosine similarity
 #include "clusters.h"       // single-linkage clusters of a square matrix
+#include "linkage.h"        // complete and average linkage on a working copy of it
 #include "phrases.h"        // repeated phrases of the indexed texts as keyphrase candidates

@@ -2,6 +2,7 @@
 """keyphrases_table / keyphrases_graph (reference east/applications.py:11-149), keyphrases_top and keyphrases_similar;
 texts_related, texts_similar, the clusters and keyphrases_extract."""
 
+import inspect
 import os
 from collections import namedtuple
 from collections.abc import Mapping
@@ -674,18 +675,112 @@ def _single_linkage(matrix):
     return a[took].astype(np.int32), b[took].astype(np.int32), w[took]
 
 
+LINKAGES = ("single", "complete", "average")
+
+
+class RefusedSimilarity(ValueError):
+    """A matrix holds a similarity that complete or average linkage does not take (the host path's EAST_HIP_ERR_INVALID)."""
+
+
+def _linkage_argument(who, linkage):
+    if linkage not in LINKAGES:
+        raise ValueError("%s: linkage must be 'single', 'complete' or 'average', not %r" % (who, linkage))
+    return linkage
+
+
+def _lance_williams(average, x, y, n, n2):
+    """LW of include/east_hip.h ("Clusters"), elementwise: x the representative's values, y its partner's, n and n2 their
+    sizes before the round as doubles."""
+    lo = np.where(y < x, y, x)
+    if not average:
+        return lo
+    hi = np.where(y < x, x, y)
+    r = (n * x + n2 * y) / (n + n2)
+    return np.where(r < lo, lo, np.where(r > hi, hi, r))
+
+
+def _linkage_rounds(matrix, linkage, floor=None):
+    """Complete or average linkage by the contract of include/east_hip.h ("Clusters"): rounds of reciprocal strongest
+    pairs on a working copy, the contract's operations in the contract's order, whole arrays at a time.
+    -> (merge_a, merge_b, merge_w, rounds); ValueError for a similarity the linkage does not take."""
+    average = _linkage_argument("_linkage_rounds", linkage) == "average"
+    if linkage == "single":
+        raise ValueError("_linkage_rounds: single linkage is _single_linkage's")
+    S = np.asarray(matrix, dtype=np.float64)
+    M = S.shape[0]
+    floor = -np.inf if floor is None or floor != floor else float(floor)
+    rows, cols = np.triu_indices(M, 1)
+    upper = S[rows, cols]
+    refused = ~np.isfinite(upper) if average else np.isnan(upper)
+    if refused.any():
+        at = int(np.flatnonzero(refused)[0])
+        raise RefusedSimilarity("clusters: S[%d][%d] is %s: %s linkage takes no such similarity"
+                         % (rows[at], cols[at], "not finite" if average else "a NaN", linkage))
+    W = np.zeros((M, M), dtype=np.float64)
+    W[rows, cols] = upper
+    W[cols, rows] = upper
+    alive = np.arange(M)                                    # the representatives, ascending
+    size = np.ones(M, dtype=np.float64)
+    found, rounds = [], 0
+    with np.errstate(all="ignore"):
+        while alive.size > 1:
+            A = alive.size
+            sub = W[np.ix_(alive, alive)]
+            own = np.arange(A)
+            masked = sub.copy()
+            masked[own, own] = -np.inf
+            pick = np.argmax(masked, axis=1)                # (the first of equal weights: the smallest other end; -0.0 == +0.0)
+            alone = pick == own                             # (every weight is minus infinity: the diagonal came first)
+            pick[alone] = np.where(own[alone] == 0, 1, 0)
+            reciprocal = (pick[pick] == own) & (own < pick)
+            weight = sub[own, pick]
+            merged = reciprocal & (weight >= floor)
+            if not merged.any():
+                break
+            u, v = own[merged], pick[merged]                # positions in alive: the ends that stay, the ends that die
+            found.extend(zip(weight[merged].tolist(), [rounds] * u.size, alive[u].tolist(), alive[v].tolist()))
+            partner = own.copy()
+            partner[u] = v
+            has = partner != own
+            stay = np.ones(A, dtype=bool)
+            stay[v] = False
+            keep = own[stay]
+            kp, kh = partner[keep], has[keep]
+            n, n2 = size[alive[keep]], size[alive[kp]]
+            # rows u (and u') against columns v (and v'), every value in the orientation of the pair with u < v
+            a, b = sub[np.ix_(keep, keep)], sub[np.ix_(keep, kp)]
+            c, d = sub[np.ix_(kp, keep)], sub[np.ix_(kp, kp)]
+            cu = np.where(kh[None, :], _lance_williams(average, a, b, n[None, :], n2[None, :]), a)
+            cu2 = np.where(kh[None, :], _lance_williams(average, c, d, n[None, :], n2[None, :]), c)
+            new = np.where(kh[:, None], _lance_williams(average, cu, cu2, n[:, None], n2[:, None]), cu)
+            K = keep.size
+            is_upper = np.arange(K)[:, None] < np.arange(K)[None, :]
+            new = np.where(is_upper, new, new.T)
+            changed = kh[:, None] | kh[None, :]
+            block = W[np.ix_(alive[keep], alive[keep])]
+            W[np.ix_(alive[keep], alive[keep])] = np.where(changed, new, block)
+            size[alive[u]] += size[alive[v]]
+            alive = alive[keep]
+            rounds += 1
+    found.sort(key=lambda m: (-(m[0] + 0.0), m[1], m[2]))
+    return (np.asarray([m[2] for m in found], dtype=np.int32), np.asarray([m[3] for m in found], dtype=np.int32),
+            np.asarray([m[0] for m in found], dtype=np.float64), rounds)
+
+
 class Clustering(object):
-    """Single-linkage clusters of named members.
+    """Clusters of named members (single linkage unless `linkage` says otherwise).
 
     names     the members, in index order
+    linkage   "single", "complete" or "average"
     merges    the dendrogram, [(name_a, name_b, similarity)], strongest merge first (index of a < index of b);
               merge_a, merge_b (int32), merge_w (float64) hold the same as arrays of member indexes
     labels    per member the smallest member index of its cluster -- None when neither a threshold nor k was given
     clusters  lists of names: the clusters ordered by their smallest member, the members in index order -- or None
     """
 
-    def __init__(self, names, merge_a, merge_b, merge_w, labels=None):
+    def __init__(self, names, merge_a, merge_b, merge_w, labels=None, linkage="single"):
         self.names = list(names)
+        self.linkage = linkage
         self.merge_a = np.asarray(merge_a, dtype=np.int32)
         self.merge_b = np.asarray(merge_b, dtype=np.int32)
         self.merge_w = np.asarray(merge_w, dtype=np.float64)
@@ -732,18 +827,21 @@ def _cut_arguments(who, threshold, k):
     return threshold, k
 
 
-def _clustering_of_index(names, index, threshold, k):
+def _clustering_of_index(names, index, threshold, k, linkage="single"):
     """The Clustering of the clusters `index` (a hip_backend index) has just built."""
     merge_a, merge_b, merge_w = index.clusters_merges()
     labels = None
     if threshold is not None or k is not None:
         labels = index.clusters_cut(threshold, k)[0]
-    return Clustering(names, merge_a, merge_b, merge_w, labels)
+    return Clustering(names, merge_a, merge_b, merge_w, labels, linkage)
 
 
-def _clustering_of_matrix(names, matrix, threshold, k):
+def _clustering_of_matrix(names, matrix, threshold, k, linkage="single"):
     """The same on the host, from an M x M array."""
-    merge_a, merge_b, merge_w = _single_linkage(matrix)
+    if linkage == "single":
+        merge_a, merge_b, merge_w = _single_linkage(matrix)
+    else:
+        merge_a, merge_b, merge_w = _linkage_rounds(matrix, linkage, threshold)[:3]
     M, F = len(names), len(merge_a)
     labels = None
     if threshold is not None:
@@ -753,13 +851,29 @@ def _clustering_of_matrix(names, matrix, threshold, k):
         labels = _roots(M, merge_a, merge_b, n)
     elif k is not None:
         labels = _roots(M, merge_a, merge_b, max(0, min(F, M - k)))
-    return Clustering(names, merge_a, merge_b, merge_w, labels)
+    return Clustering(names, merge_a, merge_b, merge_w, labels, linkage)
 
 
-def texts_clusters(texts, threshold=None, k=None, similarity_measure=None, language=consts.Language.ENGLISH):
-    """The groups the texts fall into, from the texts alone: single-linkage agglomerative clustering of the matrix
-    texts_related (an AST measure: the symmetric relatedness) or texts_similar (a CosineRelevanceMeasure: the cosine of
-    the term vectors) ranks.
+def _clusters_on_device(measure, linkage, threshold, *arguments):
+    """measure.relevance_clusters: as ever for single linkage; complete and average take the threshold as their floor."""
+    if linkage == "single":
+        return measure.relevance_clusters(*arguments)
+    try:
+        parameters = inspect.signature(measure.relevance_clusters).parameters
+    except (TypeError, ValueError):                         # (no signature to read: the call itself will tell)
+        parameters = None
+    if parameters is not None and not any(p.kind == p.VAR_KEYWORD for p in parameters.values()) \
+            and not ("linkage" in parameters and "floor" in parameters):
+        raise ValueError("%s.relevance_clusters takes no linkage and floor: it serves single linkage only, not linkage=%r"
+                         % (type(measure).__name__, linkage))
+    return measure.relevance_clusters(*arguments, linkage=linkage, floor=threshold)
+
+
+def texts_clusters(texts, threshold=None, k=None, similarity_measure=None, language=consts.Language.ENGLISH, linkage="single"):
+    """The groups the texts fall into, from the texts alone: agglomerative clustering -- single linkage, or with
+    linkage="complete" / "average" those linkages (include/east_hip.h, "Clusters"; a threshold is then also the floor
+    below which no merge is made, so the dendrogram ends there) -- of the matrix texts_related (an AST measure: the
+    symmetric relatedness) or texts_similar (a CosineRelevanceMeasure: the cosine of the term vectors) ranks.
 
     :param texts: {text name: text}
     :param threshold: flat clusters = the connected components of "similarity >= threshold"
@@ -775,25 +889,27 @@ def texts_clusters(texts, threshold=None, k=None, similarity_measure=None, langu
     own contracts, so a near-tie may merge differently; on ONE matrix both give the same bytes.
     """
     threshold, k = _cut_arguments("texts_clusters", threshold, k)
+    linkage = _linkage_argument("texts_clusters", linkage)
     measure = similarity_measure or relevance.ASTRelevanceMeasure()
     _refuse_bm25("texts_clusters", measure)
     titles = list(texts.keys())
     if not titles:
-        return Clustering([], [], [], [], None if threshold is None and k is None else [])
+        return Clustering([], [], [], [], None if threshold is None and k is None else [], linkage)
     if _device_applies(measure, texts, None, "relevance_clusters", "EAST_HIP_CLUSTERS"):
         measure.set_text_collection(list(texts.values()), language)
-        return _clustering_of_index(titles, measure.relevance_clusters(), threshold, k)
+        return _clustering_of_index(titles, _clusters_on_device(measure, linkage, threshold), threshold, k, linkage)
     if isinstance(measure, relevance.CosineRelevanceMeasure):
         matrix = _texts_similar_on_host(texts, measure, language)[0]
     else:
         matrix = _related_on_host(texts, 1, measure, language)[0]
-    return _clustering_of_matrix(titles, matrix, threshold, k)
+    return _clustering_of_matrix(titles, matrix, threshold, k, linkage)
 
 
 def keyphrases_clusters(keyphrases, texts, by="text", threshold=None, k=None, similarity_measure=None, synonimizer=None,
-                        language=consts.Language.ENGLISH):
+                        language=consts.Language.ENGLISH, linkage="single"):
     """The groups the texts (by="text") or the keyphrases (by="keyphrase") fall into by their profiles in the keyphrase x
-    text score table: single-linkage agglomerative clustering of the cosine matrix keyphrases_similar ranks.
+    text score table: agglomerative clustering (single linkage, or linkage="complete" / "average" as texts_clusters takes
+    it) of the cosine matrix keyphrases_similar ranks.
 
     :param keyphrases: raw keyphrase strings, taken as keyphrases_table takes them (empty ones are skipped, duplicates
                        collapse)
@@ -809,17 +925,18 @@ def keyphrases_clusters(keyphrases, texts, by="text", threshold=None, k=None, si
         raise ValueError("keyphrases_clusters: by must be 'text' or 'keyphrase', not %r" % (by,))
     axis = _TOP_AXES.index(by)
     threshold, k = _cut_arguments("keyphrases_clusters", threshold, k)
+    linkage = _linkage_argument("keyphrases_clusters", linkage)
     measure = similarity_measure or relevance.ASTRelevanceMeasure()
     titles = list(texts.keys())
     wanted = [kp for kp in dict.fromkeys(keyphrases) if kp]              # applications.py:44-45
     if not wanted or not titles:
-        return Clustering([], [], [], [], None if threshold is None and k is None else [])
+        return Clustering([], [], [], [], None if threshold is None and k is None else [], linkage)
     if _device_applies(measure, texts, synonimizer, "relevance_clusters", "EAST_HIP_CLUSTERS"):
         measure.set_text_collection(list(texts.values()), language)
-        index = measure.relevance_clusters([utils.prepare_text(kp) for kp in wanted], axis)
-        return _clustering_of_index(titles if axis == 0 else wanted, index, threshold, k)
+        index = _clusters_on_device(measure, linkage, threshold, [utils.prepare_text(kp) for kp in wanted], axis)
+        return _clustering_of_index(titles if axis == 0 else wanted, index, threshold, k, linkage)
     scores, titles = _score_array(keyphrases_table(wanted, texts, measure, synonimizer, language), wanted, titles)
-    return _clustering_of_matrix(titles if axis == 0 else wanted, _similarity_matrix(scores, axis), threshold, k)
+    return _clustering_of_matrix(titles if axis == 0 else wanted, _similarity_matrix(scores, axis), threshold, k, linkage)
 
 
 # ---- phrase extraction -----------------------------------------------------------------------------------------------------

@@ -179,6 +179,9 @@ SIGNATURES = {
     "east_hip_debug_set_text_similarity_batch": (ctypes.c_int, [ctypes.c_int64]),
     "east_hip_clusters_build_resident": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _c_i64p]),
     "east_hip_clusters_build_host": (ctypes.c_int, [ctypes.c_void_p, _c_dblp, ctypes.c_int32, _c_i64p]),
+    "east_hip_clusters_build_resident_linkage": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, _c_i64p]),
+    "east_hip_clusters_build_host_linkage": (ctypes.c_int, [ctypes.c_void_p, _c_dblp, ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
+                                             _c_i64p]),
     "east_hip_clusters_fetch": (ctypes.c_int, [ctypes.c_void_p, _c_i32p, _c_i32p, _c_dblp]),
     "east_hip_clusters_cut_threshold": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, _c_i32p, _c_i64p]),
     "east_hip_clusters_cut_count": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _c_i32p, _c_i64p]),
@@ -208,6 +211,8 @@ GRAPH_SOURCE_COSINE_TEXTS = 5               # east_hip_top_build_resident only: 
 COSINE_TEXTS_CHUNK, COSINE_TEXTS_SEG = 32, 8192      # csrc/cosine_texts.h: the units of a staged chunk and of a segment (texts_build reports them)
 COSINE_TEXTS_INFO_FIELDS = ("n_docs", "units", "postings", "tiles", "segments", "launches", "chunk_units", "segment_units")
 CLUSTERS_INFO_FIELDS = ("members", "merges", "rounds", "launches")      # east_hip_clusters_build_*: out
+LINKAGE_SINGLE, LINKAGE_COMPLETE, LINKAGE_AVERAGE = 0, 1, 2            # EAST_HIP_LINKAGE_*
+LINKAGES = {"single": LINKAGE_SINGLE, "complete": LINKAGE_COMPLETE, "average": LINKAGE_AVERAGE}
 RELATED_DIRECTED, RELATED_SYMMETRIC = 0, 1                               # east_hip_related_build: the orientation
 DEBUG_GUARD = 4096                          # east_hip_debug_radix_sort_ex and its kin: elements behind every output
 SCAN_EXCLUSIVE, SCAN_INCLUSIVE, SCAN_EXCLUSIVE_IN_PLACE, SCAN_INCLUSIVE_IN_PLACE, SCAN_WITH_TOTAL = range(5)    # east_hip_debug_scan_ex
@@ -235,6 +240,15 @@ def load():
             fn.argtypes = args
         _lib = lib
     return _lib
+
+
+def _linkage_arguments(linkage, floor):
+    """(the EAST_HIP_LINKAGE_* value of a name or of a value, the floor as a double: NaN = none)"""
+    if isinstance(linkage, str):
+        if linkage not in LINKAGES:
+            raise exceptions.HipBackendError(reason="unknown linkage %r: one of 'single', 'complete', 'average'" % (linkage,))
+        linkage = LINKAGES[linkage]
+    return int(linkage), float("nan") if floor is None else float(floor)
 
 
 def _check(rc):
@@ -546,22 +560,31 @@ class _ResidentTableConsumers(object):
         self._sim_holder._clu_info = info
         return info
 
-    def clusters_build(self, source):
-        """Single-linkage clusters (include/east_hip.h, "Clusters") of a square matrix that lies on the device of this
-        handle: GRAPH_SOURCE_SIMILARITY, GRAPH_SOURCE_RELATED (symmetric), GRAPH_SOURCE_COSINE_TEXTS, or
-        GRAPH_SOURCE_UPLOADED = the copy the last clusters_build_host left -> {CLUSTERS_INFO_FIELDS: value}."""
+    def clusters_build(self, source, linkage="single", floor=None):
+        """Clusters (include/east_hip.h, "Clusters") of a square matrix that lies on the device of this handle:
+        GRAPH_SOURCE_SIMILARITY, GRAPH_SOURCE_RELATED (symmetric), GRAPH_SOURCE_COSINE_TEXTS, or GRAPH_SOURCE_UPLOADED = the
+        copy the last clusters_build_host left.  linkage: "single", "complete", "average" or an EAST_HIP_LINKAGE_* value;
+        floor: only merges of at least this similarity are made (None: all) -> {CLUSTERS_INFO_FIELDS: value}."""
         out = np.zeros(len(CLUSTERS_INFO_FIELDS), dtype=np.int64)
-        _check(self._lib.east_hip_clusters_build_resident(self._h, int(source), _ptr(out, _c_i64p)))
+        linkage, floor = _linkage_arguments(linkage, floor)
+        if linkage == LINKAGE_SINGLE and floor != floor:
+            _check(self._lib.east_hip_clusters_build_resident(self._h, int(source), _ptr(out, _c_i64p)))
+        else:
+            _check(self._lib.east_hip_clusters_build_resident_linkage(self._h, int(source), linkage, floor, _ptr(out, _c_i64p)))
         return self._clusters_built(out)
 
-    def clusters_build_host(self, matrix):
+    def clusters_build_host(self, matrix, linkage="single", floor=None):
         """The same of an M x M host array, which is uploaded and checked for symmetry first."""
         matrix = np.ascontiguousarray(matrix, dtype=np.float64)
         if matrix.ndim != 2 or matrix.shape[0] != matrix.shape[1]:
             raise exceptions.HipBackendError(reason="the matrix of clusters is an M x M array")
         out = np.zeros(len(CLUSTERS_INFO_FIELDS), dtype=np.int64)
-        _check(self._lib.east_hip_clusters_build_host(self._h, _ptr(matrix, _c_dblp) if matrix.size else None, matrix.shape[0],
-                                                      _ptr(out, _c_i64p)))
+        linkage, floor = _linkage_arguments(linkage, floor)
+        pointer = _ptr(matrix, _c_dblp) if matrix.size else None
+        if linkage == LINKAGE_SINGLE and floor != floor:
+            _check(self._lib.east_hip_clusters_build_host(self._h, pointer, matrix.shape[0], _ptr(out, _c_i64p)))
+        else:
+            _check(self._lib.east_hip_clusters_build_host_linkage(self._h, pointer, matrix.shape[0], linkage, floor, _ptr(out, _c_i64p)))
         return self._clusters_built(out)
 
     def clusters_merges(self):

@@ -20,11 +20,14 @@ README.rst:27-63; the shipped reference main crashes with a NameError, SURVEY.md
         the N texts most like every text, from the texts alone: the cosine of their tf or tf-idf term vectors (the cosine
         measure's own index, stopwords and stemmer), best first, matrix and ranking on the device (csrc/cosine_texts.h); one
         device; `-s ast` is refused (that question is `texts related`)
-    east [-s ast|cosine] [-r threshold | -k clusters] [-w tf|tf-idf] [-v stems|words] [-d] [-f xml|csv|merges] texts clusters <texts>
+    east [-s ast|cosine] [-j single|complete|average] [-r threshold | -k clusters] [-w tf|tf-idf] [-v stems|words] [-d]
+         [-f xml|csv|merges] texts clusters <texts>
         the groups the texts fall into: single-linkage clusters of the symmetric relatedness (-s ast, the default) or of the
         term-vector cosine (-s cosine), built where the matrix lies (csrc/clusters.h); -r: the texts joined by similarities
-        that reach it, -k: that many clusters, one of the two -- or neither with -f merges, the dendrogram a merge a line
-    east [-s ast|cosine|bm25] [-b text|keyphrase] [-r threshold | -k clusters] [-f xml|csv|merges] keyphrases clusters <keyphrases file> <texts>
+        that reach it, -k: that many clusters, one of the two -- or neither with -f merges, the dendrogram a merge a line;
+        -j complete / -j average: those linkages, in rounds of reciprocal strongest pairs on a working copy of the matrix
+        (csrc/linkage.h) -- -r is then also the floor below which no merge is made: -f merges ends there
+    east [-s ast|cosine|bm25] [-j linkage] [-b text|keyphrase] [-r threshold | -k clusters] [-f xml|csv|merges] keyphrases clusters <keyphrases file> <texts>
         the same of the texts (-b text) or the keyphrases (-b keyphrase) by the profile cosines of `keyphrases similar`
     east [-n N] [-x max words] [-m min count] [-u min texts] [-l language] [-f txt|csv|xml] keyphrases extract <texts>
         keyphrase candidates out of the texts themselves (no keyphrase file): the repeated phrases of one to -x (default 3, at
@@ -65,7 +68,7 @@ def _read(path):
         return f.read()
 
 
-_OPTIONS = "s:a:w:v:l:f:c:r:p:g:t:n:b:o:k:x:m:u:z:dy"
+_OPTIONS = "s:a:w:v:l:f:c:r:p:g:t:n:b:o:k:x:m:u:z:j:dy"
 _VALUE_OPTIONS = frozenset(c for c, nxt in zip(_OPTIONS, _OPTIONS[1:] + " ") if nxt == ":")
 
 
@@ -98,7 +101,7 @@ def main(argv=None, measure_factory=None):
     opt_list = opts                                         # (as given: repeated options, empty values)
     opts = dict(opts)
     world, rank = _world()
-    refusal = _bm25_refusal(opts, args, world)             # (before a rank is started, a file is read or anything touches the device)
+    refusal = _linkage_refusal(opts, args) or _bm25_refusal(opts, args, world)     # (before a rank is started, a file is read or anything touches the device)
     if refusal:
         if rank == 0:
             print(refusal)
@@ -401,6 +404,18 @@ def _texts_similar_main(opts, args, world, refuse):
     return 0
 
 
+def _linkage_refusal(opts, args):
+    """The one line that refuses -j, or None: a linkage belongs to `texts clusters` and `keyphrases clusters` and is one of
+    applications.LINKAGES."""
+    if "-j" not in opts:
+        return None
+    if args[:2] not in (["texts", "clusters"], ["keyphrases", "clusters"]):
+        return "A linkage belongs to clusters: -j %s is supported by `texts clusters` and `keyphrases clusters` only." % opts["-j"]
+    if opts["-j"] not in applications.LINKAGES:
+        return "Unknown linkage: '%s'. Please use one of: 'single', 'complete', 'average'." % opts["-j"]
+    return None
+
+
 def _clusters_options(opts):
     """(threshold, k, format, None) of `texts clusters` and `keyphrases clusters`, or (None, None, None, the one line that
     says what is wrong)."""
@@ -475,6 +490,7 @@ def _clusters_main(opts, args, world, rank):
     if n_ranks > 1:
         return refuse("Clusters run on one device: -g %d is not supported." % n_ranks)
     language = opts.get("-l", consts.Language.ENGLISH)
+    linkage = {"linkage": opts["-j"]} if "-j" in opts else {}      # (checked in main, before anything else)
     try:
         if cosine or bm25:
             if bm25:
@@ -486,12 +502,13 @@ def _clusters_main(opts, args, world, rank):
         else:
             measure = relevance.ASTRelevanceMeasure(opts.get("-a", consts.ASTAlgorithm.EASA), "-d" not in opts)
         if of_texts:
-            found = applications.texts_clusters(_read_texts(args[2]), threshold, k, measure, language)
+            found = applications.texts_clusters(_read_texts(args[2]), threshold, k, measure, language, **linkage)
         else:
             keyphrases = _read(os.path.abspath(args[2])).decode("utf-8", errors="replace").splitlines()
-            found = applications.keyphrases_clusters(keyphrases, _read_texts(args[3]), by, threshold, k, measure, None, language)
+            found = applications.keyphrases_clusters(keyphrases, _read_texts(args[3]), by, threshold, k, measure, None, language,
+                                                     **linkage)
         print(formatting.format_clusters(found, fmt))
-    except exceptions.EastException as e:       # (a missing stemmer, no device, a failed build ...): a message, not a traceback
+    except (exceptions.EastException, applications.RefusedSimilarity) as e:     # (a missing stemmer, no device, a failed build ...): a message, not a traceback
         print(e)
         return 1
     return 0

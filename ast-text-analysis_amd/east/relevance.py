@@ -255,19 +255,20 @@ class ASTRelevanceMeasure(RelevanceMeasure):
         self.index.related_build(self.normalized, orientation)
         return self.index.related_matrix()
 
-    def relevance_clusters(self, prepared_keyphrases=None, axis=None):
-        """Single-linkage clusters of a matrix of this measure, built and clustered where it lies (csrc/clusters.h).
+    def relevance_clusters(self, prepared_keyphrases=None, axis=None, linkage="single", floor=None):
+        """Clusters of a matrix of this measure, built and clustered where it lies (csrc/clusters.h, csrc/linkage.h).
         Without keyphrases: the texts, by their symmetric relatedness (relatedness_matrix).  With keyphrases: the texts
         (axis hip_backend.TOP_BY_TEXT) or the keyphrases (TOP_BY_KEYPHRASE) by the cosine of their score profiles, the
-        matrix relevance_similar ranks.  -> the index: its clusters_merges(), clusters_cut(), similarity_matrix() /
+        matrix relevance_similar ranks.  linkage: "single", "complete" or "average"; floor: only merges of at least this
+        similarity are made (None: all).  -> the index: its clusters_merges(), clusters_cut(), similarity_matrix() /
         related_matrix() speak of what was built."""
         if prepared_keyphrases is None:
             self.index.related_build(self.normalized, hip_backend.RELATED_SYMMETRIC)
-            self.index.clusters_build(hip_backend.GRAPH_SOURCE_RELATED)
+            self.index.clusters_build(hip_backend.GRAPH_SOURCE_RELATED, linkage, floor)
         else:
             self._score_resident(prepared_keyphrases)
             self.index.similarity(axis)
-            self.index.clusters_build(hip_backend.GRAPH_SOURCE_SIMILARITY)
+            self.index.clusters_build(hip_backend.GRAPH_SOURCE_SIMILARITY, linkage, floor)
         return self.index
 
 
@@ -460,18 +461,18 @@ class CosineRelevanceMeasure(RelevanceMeasure):
         self.index.texts_build(self.term_weighting == consts.TermWeighting.TF_IDF)
         return self.index.texts_matrix()
 
-    def relevance_clusters(self, prepared_keyphrases=None, axis=None):
-        """Single-linkage clusters of a matrix of this measure, built and clustered where it lies
+    def relevance_clusters(self, prepared_keyphrases=None, axis=None, linkage="single", floor=None):
+        """Clusters of a matrix of this measure, built and clustered where it lies
         (ASTRelevanceMeasure.relevance_clusters).  Without keyphrases: the texts, by the cosine of their term vectors
         (text_similarity_matrix).  With keyphrases: the texts or the keyphrases by the cosine of their score profiles.
         -> the index."""
         if prepared_keyphrases is None:
             self.index.texts_build(self.term_weighting == consts.TermWeighting.TF_IDF)
-            self.index.clusters_build(hip_backend.GRAPH_SOURCE_COSINE_TEXTS)
+            self.index.clusters_build(hip_backend.GRAPH_SOURCE_COSINE_TEXTS, linkage, floor)
         else:
             self._score(prepared_keyphrases, False)
             self.index.similarity(axis)
-            self.index.clusters_build(hip_backend.GRAPH_SOURCE_SIMILARITY)
+            self.index.clusters_build(hip_backend.GRAPH_SOURCE_SIMILARITY, linkage, floor)
         return self.index
 
     def extract_phrases(self, n=0, max_words=3, min_words=1, min_count=2, min_texts=1):
@@ -635,7 +636,7 @@ class BM25RelevanceMeasure(CosineRelevanceMeasure):
     def extract_phrases(self, n=0, max_words=3, min_words=1, min_count=2, min_texts=1):
         self._cosine_only("extract_phrases")
 
-    def relevance_clusters(self, prepared_keyphrases=None, axis=None):
+    def relevance_clusters(self, prepared_keyphrases=None, axis=None, linkage="single", floor=None):
         if prepared_keyphrases is None:
             self._cosine_only("relevance_clusters without keyphrases")
-        return super(BM25RelevanceMeasure, self).relevance_clusters(prepared_keyphrases, axis)
+        return super(BM25RelevanceMeasure, self).relevance_clusters(prepared_keyphrases, axis, linkage, floor)

@@ -610,7 +610,49 @@ int east_hip_debug_set_text_similarity_batch(int64_t segments);
  * EAST_HIP_ERR_INVALID.  The work arrays (64 bytes a member) and the uploaded copy are buffers of the clusters' own.
  * Device time of the last build in milliseconds (events on the handle's stream around all launches and the read-backs
  * between the rounds), -1 before a build and after a failed one.
+ *
+ * COMPLETE and AVERAGE linkage (`-j complete|average`; csrc/linkage.h): east_hip_clusters_build_resident_linkage and
+ * east_hip_clusters_build_host_linkage take the linkage and a floor (a NaN: none).  EAST_HIP_LINKAGE_SINGLE gives the bytes
+ * of the two calls above, and a floor keeps the prefix w >= floor of their merges.  The sources, the refusals, the lifetime,
+ * out, the fetch, the cuts and the time are as above; any other linkage value is EAST_HIP_ERR_INVALID and leaves no result.
+ * Input: S as above (symmetric, the diagonal never read; only the upper triangle's bytes are read at all).  In addition an
+ * off-diagonal NaN is EAST_HIP_ERR_INVALID for `complete`, and any off-diagonal value that is not finite for `average`;
+ * the message names the first offending pair in row-major order as "S[a][b]", and neither a result nor an uploaded copy
+ * is left.
+ * State: a working copy W, which starts as the upper triangle of S mirrored (W[a][b] = W[b][a] = S[a][b]'s bytes, a < b),
+ * and the set of alive clusters.  A cluster is named by its smallest member, its representative; it has a size n, 1 at the
+ * start.  The source matrix is never written and stays valid byte for byte.
+ * Order: the pair (a, b), a < b, of alive representatives is STRONGER than (c, d) when W[a][b] > W[c][d] (-0.0 and +0.0 are
+ * equal), or the weights are equal and a < c, or the weights and a are equal and b < d -- the order above.
+ * One round: every alive cluster picks its strongest pair; a pair whose two ends picked each other is RECIPROCAL; every
+ * reciprocal pair (u, u'), u < u', with W[u][u'] >= floor is merged in this round and recorded as merge_a = u, merge_b = u',
+ * merge_w = W[u][u'] (its bytes) and the number of the round; u stays alive with size n_u + n_u', u' dies.  The rounds end
+ * when one cluster is left or when no pair of alive clusters reaches the floor (then a round merges nothing; it is not
+ * counted).  A reciprocal pair below the floor stays unmerged; every pair touching its ends is below the floor as well.
+ * Update: for alive representatives u < v after the round, with u' and v' their partners if they merged,
+ *     c(x) = LW_v(W[x][v], W[x][v']) if v merged, else W[x][v],     for x in {u, u'}
+ *     W[u][v] = W[v][u] = LW_u(c(u), c(u')) if u merged, else c(u)
+ * complete: LW(x, y) = (y < x) ? y : x.
+ * average:  LW_z(x, y) = clamp((n * x + n' * y) / (n + n')), n and n' the sizes of z and its partner BEFORE the round as
+ * doubles, x the representative's value and y its partner's: two products, one sum, one quotient of doubles, no FMA; then
+ * with lo = (y < x) ? y : x and hi = (y < x) ? x : y the result is lo if r < lo, hi if r > hi, else r.  The clamp is exact;
+ * it keeps a merged cluster's similarity to anything at most the weight of the merge that made it, so later merges on a
+ * branch are never stronger than earlier ones and the list by weight is a valid order of the tree.
+ * Result: the F merges by weight descending (-0.0 and +0.0 equal), then round ascending, then merge_a ascending.  Without
+ * a floor F = M - 1.  A floor yields exactly the prefix w >= floor of the list without one.  merge_a and merge_b are
+ * members, so the cuts, the labels and the fetch are as above.
+ * Guaranteed: no atomic is used; two builds give the same bytes; the result does not depend on the grid or on timing.  For
+ * `average` every merge_w joining the clusters A and B lies within 4 * (|A| + |B|) * 2^-53 * max|S| of the exact mean of
+ * S[a][b] over a in A and b in B.
+ * out = M, F, the rounds that merged, the kernel launches: 3 a round, and at most 5 more (the symmetry check of an upload,
+ * the copy, the two launches of a round that finds no pair at the floor -- it launches no update --, the ranking).  The working copy (M * M * 8 bytes, EAST_HIP_ERR_OOM where it does
+ * not fit) is a buffer of the clusters' own and is released when the build ends.
  */
+#define EAST_HIP_LINKAGE_SINGLE 0
+#define EAST_HIP_LINKAGE_COMPLETE 1
+#define EAST_HIP_LINKAGE_AVERAGE 2
+int east_hip_clusters_build_resident_linkage(east_hip_handle_t h, int32_t source, int32_t linkage, double floor, int64_t *out);
+int east_hip_clusters_build_host_linkage(east_hip_handle_t h, const double *matrix, int32_t m, int32_t linkage, double floor, int64_t *out);
 int east_hip_clusters_build_resident(east_hip_handle_t h, int32_t source, int64_t *out);
 int east_hip_clusters_build_host(east_hip_handle_t h, const double *matrix, int32_t m, int64_t *out);
 int east_hip_clusters_fetch(east_hip_handle_t h, int32_t *merge_a, int32_t *merge_b, double *merge_w);
