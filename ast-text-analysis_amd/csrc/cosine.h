@@ -577,6 +577,12 @@ static void cos_withdraw_phrases(east_hip_index *h)
     if (Consumer *p = h->consumers[east_hip_index::SLOT_PHR]) p->withdraw();
 }
 
+// the characteristic terms (terms.h) are a function of the index and of its vector space, as the texts' matrix is
+static void cos_withdraw_terms(east_hip_index *h)
+{
+    if (Consumer *t = h->consumers[east_hip_index::SLOT_TERMS]) t->withdraw();
+}
+
 static CosState &cos_built(east_hip_index *h) { return consumer_built<CosState>(h, "no cosine index has been built on this handle"); }
 
 // A ragged host array: n + 1 offsets into a payload of offsets[n] words, narrowed to 32 bits for the device.  bad: the
@@ -625,6 +631,7 @@ static void cos_build(east_hip_index *h, HostTexts in, const UnicodeTablesHost &
     c.clear();
     cos_withdraw_texts_matrix(h);
     cos_withdraw_phrases(h);
+    cos_withdraw_terms(h);
     const u32 N = (u32)in.n_bytes, D = (u32)in.D;
     Stats stats;
 
@@ -798,6 +805,7 @@ static void cos_set_classes(east_hip_index *h, const int32_t *term_class, int32_
 {
     CosState &c = cos_built(h);
     cos_withdraw_texts_matrix(h);
+    cos_withdraw_terms(h);
     c.terms.bm_valid = c.cls.bm_valid = false;              // (bm25.h: its cached weights are those of one vector space)
     if (n_classes == 0) {                                   // back to the terms
         c.use_classes = false;

@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
 """keyphrases_table / keyphrases_graph (reference east/applications.py:11-149), keyphrases_top and keyphrases_similar;
-texts_related, texts_similar, the clusters and keyphrases_extract."""
+texts_related, texts_similar, the clusters, keyphrases_extract and texts_terms."""
 
 import inspect
 import os
@@ -1056,3 +1056,141 @@ def keyphrases_extract(texts, n=100, max_words=3, min_words=1, min_count=2, min_
     found = measure.extract_phrases(n, max_words, min_words, min_count, min_texts)
     return [Phrase(text, w, c, t, c * w) for text, w, c, t in
             zip(found.strings(), found.words.tolist(), found.count.tolist(), found.texts.tolist())]
+
+
+# ---- characteristic terms --------------------------------------------------------------------------------------------------
+Term = namedtuple("Term", ("text", "value", "texts", "df"))
+TermGroup = namedtuple("TermGroup", ("names", "terms"))
+
+
+def _terms_arguments(n, min_texts):
+    for name, value in (("n", n), ("min_texts", min_texts)):
+        if isinstance(value, bool) or int(value) != value:
+            raise ValueError("texts_terms: %s must be an integer, not %r" % (name, value))
+    if not 1 <= n <= TOP_MAX_N:
+        raise ValueError("texts_terms: n must lie in 1 .. %d, not %d" % (TOP_MAX_N, n))
+    if min_texts < 1:
+        raise ValueError("texts_terms: min_texts must be at least 1, not %d" % min_texts)
+    return int(n), int(min_texts)
+
+
+def _terms_vectors(doc_units, n_units, tfidf, group, n_groups):
+    """The contract of include/east_hip.h ("Characteristic terms") in numpy: doc_units[d] = the units of text d's kept
+    tokens, one entry a token; group[d] in 0 .. n_groups - 1.  x = count / max(n_d, 1), times 1 + ln(D / df) under tf-idf;
+    norm = the root of the sum of the squares, 1.0 for a text without a posting; q = x / norm; per (group, unit) the sum of
+    q over the group's texts in ascending order, divided by the group's members.
+    -> (members[G], offsets[G + 1], unit, value, texts per entry in (group, unit) order, df[n_units])."""
+    D = len(doc_units)
+    group = np.asarray(group, dtype=np.int64)
+    members = np.bincount(group, minlength=n_groups).astype(np.int32)
+    df = np.zeros(n_units, dtype=np.int64)
+    doc, unit, q = [], [], []
+    for d, ids in enumerate(doc_units):
+        u, count = np.unique(np.asarray(ids, dtype=np.int64), return_counts=True)
+        df[u] += 1
+        doc.append(np.full(u.size, d, dtype=np.int64))
+        unit.append(u)
+        q.append(count.astype(np.float64) / float(max(len(ids), 1)))
+    if tfidf:
+        q = [x * (1.0 + np.log(float(D) / df[u].astype(np.float64))) for x, u in zip(q, unit)]
+    q = [x / (np.sqrt(np.sum(x * x)) if x.size else 1.0) for x in q]
+    doc = np.concatenate(doc) if doc else np.zeros(0, np.int64)
+    unit = np.concatenate(unit) if unit else np.zeros(0, np.int64)
+    q = np.concatenate(q) if q else np.zeros(0, np.float64)
+    key = group[doc] * max(n_units, 1) + unit
+    order = np.argsort(key, kind="stable")                  # (the texts ascend inside a (group, unit) run)
+    key, q = key[order], q[order]
+    heads = np.flatnonzero(np.concatenate(([True], key[1:] != key[:-1]))) if key.size else np.zeros(0, np.int64)
+    e_group, e_unit = key[heads] // max(n_units, 1), key[heads] % max(n_units, 1)
+    texts = np.diff(np.concatenate((heads, [key.size]))).astype(np.int32)
+    value = np.add.reduceat(q, heads) / members[e_group].astype(np.float64) if key.size else np.zeros(0, np.float64)
+    offsets = np.searchsorted(e_group, np.arange(n_groups + 1)).astype(np.int64)
+    return members, offsets, e_unit.astype(np.int32), value, texts, df.astype(np.int32)
+
+
+def _terms_ranked(unit, value, texts, min_texts, n):
+    """The contract's order of one group's entries: those with texts >= min_texts by value descending, then unit ascending;
+    the first n -> indexes into the arrays."""
+    keep = np.flatnonzero(texts >= min_texts)
+    return keep[np.lexsort((unit[keep], -value[keep]))][:n]
+
+
+def _terms_on_host(doc_units, n_units, tfidf, group, n_groups, n, min_texts):
+    """-> (members[G], per group [(unit, value, texts, df)], best first)."""
+    members, offsets, unit, value, texts, df = _terms_vectors(doc_units, n_units, tfidf, group, n_groups)
+    lists = []
+    for g in range(n_groups):
+        a, e = offsets[g], offsets[g + 1]
+        best = a + _terms_ranked(unit[a:e], value[a:e], texts[a:e], min_texts, n)
+        lists.append([(int(unit[i]), float(value[i]), int(texts[i]), int(df[unit[i]])) for i in best])
+    return members, lists
+
+
+def _groups_of_labels(labels):
+    """Clustering.labels (per member the smallest member of its cluster) -> (group[d], the groups ordered by their smallest member)."""
+    roots = sorted(set(labels))
+    number = {root: g for g, root in enumerate(roots)}
+    return [number[root] for root in labels], len(roots)
+
+
+def texts_terms(texts, n=10, min_texts=1, similarity_measure=None, language=consts.Language.ENGLISH, threshold=None, k=None,
+                linkage="single"):
+    """What every text -- or, with a threshold or k, every cluster of texts -- is about: its characteristic terms, the units
+    of the cosine measure's vector space (words or stems) with the largest mean normalised tf or tf-idf weight (the
+    contract: include/east_hip.h, "Characteristic terms").
+
+    :param texts: {text name: text}
+    :param n: terms per group at most, 1 .. 1024
+    :param min_texts: a term is listed when that many texts of its group hold it
+    :param similarity_measure: a relevance.CosineRelevanceMeasure (None: CosineRelevanceMeasure()); any other raises ValueError
+    :param threshold, k, linkage: with one of threshold and k the texts are clustered exactly as texts_clusters clusters them
+                                  with the same measure, linkage and cut, on the same index, and the groups are the clusters,
+                                  ordered by their smallest member; with neither, every text is a group of its own
+    :returns: [TermGroup(names=[text names], terms=[Term(text, value, texts, df), ...])]: value = the mean over the group's
+              texts of weight / norm, texts = the group's texts that hold the term, df = the collection's; by value
+              descending, then in the order the terms first occur in the collection
+
+    The sums and the ranking are made on the device (csrc/terms.h) when the text titles are distinct and EAST_HIP_TERMS is not
+    `host`; in every other case on the host, which then touches no device at all: the same tokens, the contract in numpy, the
+    clusters through the host clustering.  The two paths agree to (texts + max ceil(p_d / 64) / 2 + 48) * 2^-53 relative each of the exact value and name
+    the same terms in the same order wherever neighbouring values lie further apart than twice that -- they are NOT promised
+    to be the same bytes.
+    """
+    n, min_texts = _terms_arguments(n, min_texts)
+    threshold, k = _cut_arguments("texts_terms", threshold, k)
+    linkage = _linkage_argument("texts_terms", linkage)
+    measure = relevance.CosineRelevanceMeasure() if similarity_measure is None else similarity_measure
+    if not isinstance(measure, relevance.CosineRelevanceMeasure):
+        raise ValueError("texts_terms: characteristic terms are read off the term index of a CosineRelevanceMeasure, not %s"
+                         % type(measure).__name__)
+    _refuse_bm25("texts_terms", measure)
+    titles = list(texts.keys())
+    if not titles:
+        return []
+    clustered = threshold is not None or k is not None
+    tfidf = measure.term_weighting == consts.TermWeighting.TF_IDF
+    if _device_applies(measure, texts, None, "relevance_terms", "EAST_HIP_TERMS"):
+        measure.set_text_collection(list(texts.values()), language)
+        group, n_groups = None, len(titles)
+        if clustered:
+            found = _clustering_of_index(titles, _clusters_on_device(measure, linkage, threshold), threshold, k, linkage)
+            group, n_groups = _groups_of_labels(found.labels)
+        arrays = measure.relevance_terms(n, min_texts, group)
+        names = measure.unit_names()
+        lists = [[(names[u], v, t, f) for u, v, t, f in zip(arrays.unit[g, :c].tolist(), arrays.value[g, :c].tolist(),
+                                                           arrays.texts[g, :c].tolist(), arrays.df[g, :c].tolist())]
+                 for g, c in enumerate(arrays.count.tolist())]
+    else:
+        doc_units, number, _ = relevance.host_doc_units(texts.values(), measure, language)
+        group, n_groups = list(range(len(titles))), len(titles)
+        if clustered:
+            matrix = _texts_cosine_matrix(doc_units, len(number), tfidf)[0]
+            group, n_groups = _groups_of_labels(_clustering_of_matrix(titles, matrix, threshold, k, linkage).labels)
+        names = list(number)                                # (numbered by first occurrence: the dict's own order)
+        lists = [[(names[u], v, t, f) for u, v, t, f in found]
+                 for found in _terms_on_host(doc_units, len(number), tfidf, group, n_groups, n, min_texts)[1]]
+    group = list(range(len(titles))) if group is None else group
+    members = [[] for _ in range(n_groups)]
+    for d, g in enumerate(group):
+        members[g].append(titles[d])
+    return [TermGroup(members[g], [Term(*t) for t in lists[g]]) for g in range(n_groups)]

@@ -229,6 +229,34 @@ def phrases2xml(result):
     return "\n".join(lines) + "\n"
 
 
+def format_terms(result, format):
+    """Characteristic terms (applications.texts_terms: [TermGroup(names, [Term(text, value, texts, df)])])."""
+    renderers = {"xml": terms2xml, "csv": terms2csv}
+    if format not in renderers:
+        raise Exception("Unknown terms format: '%s'. Please use one of: 'xml', 'csv'." % format)
+    return renderers[format](result)
+
+
+def terms2xml(result):
+    """<terms groups=..> / <group id=.. size=..> / <member name=../> ... <term rank=.. texts=.. df=.. value=..>text</term>; the
+    groups in the order given, numbered from 1, the terms best first."""
+    lines = ['<terms groups="%d">' % len(result)]
+    for number, group in enumerate(result, 1):
+        lines.append('  <group id="%d" size="%d">' % (number, len(group.names)))
+        lines.extend('    <member name="%s"/>' % name for name in group.names)
+        lines.extend('    <term rank="%d" texts="%d" df="%d" value="%s">%s</term>' % (rank, t.texts, t.df, _SCORE % t.value, t.text)
+                     for rank, t in enumerate(group.terms, 1))
+        lines.append("  </group>")
+    lines.append("</terms>")
+    return "\n".join(lines) + "\n"
+
+
+def terms2csv(result):
+    """One line per (group, term): "the group's members joined by |","term",value,texts,df; groups in the order given, terms best first."""
+    return "".join("%s,%s,%s,%d,%d\n" % (_csv_quote("|".join(group.names)), _csv_quote(t.text), _SCORE % t.value, t.texts, t.df)
+                   for group in result for t in group.terms)
+
+
 def format_graph(graph, format):
     renderers = {"gml": graph2gml, "edges": graph2edges}
     if format not in renderers:

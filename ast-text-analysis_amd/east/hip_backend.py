@@ -192,6 +192,12 @@ SIGNATURES = {
                                               _c_u32p]),
     "east_hip_phrases_levels": (ctypes.c_int, [ctypes.c_void_p, _c_i64p, _c_i64p]),
     "east_hip_last_phrases_ms": (ctypes.c_double, [ctypes.c_void_p]),
+    "east_hip_terms_build": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _c_i32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                            _c_i64p]),
+    "east_hip_terms_fetch": (ctypes.c_int, [ctypes.c_void_p, _c_i32p, _c_i32p, _c_i32p, _c_dblp, _c_i32p, _c_i32p]),
+    "east_hip_terms_fetch_vectors": (ctypes.c_int, [ctypes.c_void_p, _c_i64p, _c_i32p, _c_dblp, _c_i32p]),
+    "east_hip_last_terms_ms": (ctypes.c_double, [ctypes.c_void_p]),
+    "east_hip_debug_set_terms_select": (ctypes.c_int, [ctypes.c_int]),
 }
 
 BUILD_INFO_FIELDS = ("n_total", "n_docs", "n_strings", "sigma_text", "bits_level0", "dc3_levels", "arena_bytes",
@@ -210,6 +216,8 @@ GRAPH_SOURCE_RELATED = 4                    # east_hip_top_build_resident only: 
 GRAPH_SOURCE_COSINE_TEXTS = 5               # east_hip_top_build_resident only: the matrix the last cosine texts build left
 COSINE_TEXTS_CHUNK, COSINE_TEXTS_SEG = 32, 8192      # csrc/cosine_texts.h: the units of a staged chunk and of a segment (texts_build reports them)
 COSINE_TEXTS_INFO_FIELDS = ("n_docs", "units", "postings", "tiles", "segments", "launches", "chunk_units", "segment_units")
+TERMS_INFO_FIELDS = ("n_docs", "groups", "units", "postings", "entries", "passing", "sorted", "radix_passes", "launches",
+                     "grouping_sort_skipped")                           # east_hip_terms_build: out
 CLUSTERS_INFO_FIELDS = ("members", "merges", "rounds", "launches")      # east_hip_clusters_build_*: out
 LINKAGE_SINGLE, LINKAGE_COMPLETE, LINKAGE_AVERAGE = 0, 1, 2            # EAST_HIP_LINKAGE_*
 LINKAGES = {"single": LINKAGE_SINGLE, "complete": LINKAGE_COMPLETE, "average": LINKAGE_AVERAGE}
@@ -446,6 +454,18 @@ def _matrix_fetch(fetch, h, M, count=True):
 
 
 PHRASES_MAX_WORDS = 8                       # csrc/phrases.h: PHR_MAX_WORDS
+
+
+class TermArrays(object):
+    """Characteristic terms as arrays (include/east_hip.h, "Characteristic terms"): members[G] the texts of every group,
+    count[G] its listed terms, and per place [G, n] the unit (a term or a class of the vector space), its value, the group's
+    texts that hold it and its texts in the whole collection; places behind count[g] hold -1 and NaN.  info: the build's
+    out as {TERMS_INFO_FIELDS: value}."""
+
+    __slots__ = ("members", "count", "unit", "value", "texts", "df", "info")
+
+    def __init__(self, members, count, unit, value, texts, df, info=None):
+        self.members, self.count, self.unit, self.value, self.texts, self.df, self.info = members, count, unit, value, texts, df, info
 
 
 class PhraseArrays(object):
@@ -941,8 +961,13 @@ class HipCosineIndex(_ResidentTableConsumers):
         _check(self._lib.east_hip_cosine_info(self._h, _ptr(buf, _c_i64p), buf.size))
         return dict(zip(COSINE_INFO_FIELDS, (int(x) for x in buf)))
 
-    def terms(self):
-        """The terms in id order (first occurrence in the collection)."""
+    def terms(self, tfidf=None, n=None, min_texts=1, groups=None, n_groups=None):
+        """Without arguments: the terms in id order (first occurrence in the collection).
+        terms(tfidf, n, min_texts, groups=None): the characteristic terms of every text (groups None) or of every group of
+        texts (groups[d] = the group of text d in 0 .. n_groups - 1, n_groups None: max(groups) + 1; include/east_hip.h,
+        "Characteristic terms") -> TermArrays."""
+        if n is not None:
+            return self._characteristic_terms(tfidf, n, min_texts, groups, n_groups)
         n = ctypes.c_int64(0)
         _check(self._lib.east_hip_cosine_get_terms(self._h, None, None, ctypes.byref(n)))
         offsets = np.zeros(self.n_terms + 1, dtype=np.int64)
@@ -1023,6 +1048,36 @@ class HipCosineIndex(_ResidentTableConsumers):
 
     def last_texts_ms(self):
         return float(self._lib.east_hip_last_text_similarity_ms(self._h))
+
+    # -- characteristic terms ------------------------------------------------------
+    def _characteristic_terms(self, tfidf, n, min_texts, groups, n_groups=None):
+        group = None if groups is None else np.ascontiguousarray(groups, dtype=np.int32)
+        if n_groups is None:
+            n_groups = self.n_docs if group is None else (int(group.max()) + 1 if group.size else 0)
+        out = np.zeros(len(TERMS_INFO_FIELDS), dtype=np.int64)
+        _check(self._lib.east_hip_terms_build(self._h, 1 if tfidf else 0, None if group is None else _ptr(group, _c_i32p),
+                                              int(n_groups), int(n), int(min_texts), _ptr(out, _c_i64p)))
+        G, n = int(out[1]), int(n)
+        self._terms_info = dict(zip(TERMS_INFO_FIELDS, (int(x) for x in out)))
+        found = TermArrays(np.empty(G, np.int32), np.empty(G, np.int32), np.empty((G, n), np.int32), np.empty((G, n), np.float64),
+                           np.empty((G, n), np.int32), np.empty((G, n), np.int32), self._terms_info)
+        _check(self._lib.east_hip_terms_fetch(self._h, _ptr(found.members, _c_i32p), _ptr(found.count, _c_i32p),
+                                              _ptr(found.unit, _c_i32p), _ptr(found.value, _c_dblp), _ptr(found.texts, _c_i32p),
+                                              _ptr(found.df, _c_i32p)))
+        return found
+
+    def terms_vectors(self):
+        """Every entry of the last terms() build before min_texts and the cut, in (group, unit) order
+        -> (offsets[G + 1] int64, unit int32, value float64, texts int32)."""
+        G, E = self._terms_info["groups"], self._terms_info["entries"]
+        offsets, unit = np.zeros(G + 1, np.int64), np.empty(E, np.int32)
+        value, texts = np.empty(E, np.float64), np.empty(E, np.int32)
+        _check(self._lib.east_hip_terms_fetch_vectors(self._h, _ptr(offsets, _c_i64p), _ptr(unit, _c_i32p), _ptr(value, _c_dblp),
+                                                      _ptr(texts, _c_i32p)))
+        return offsets, unit, value, texts
+
+    def last_terms_ms(self):
+        return float(self._lib.east_hip_last_terms_ms(self._h))
 
 
 SYNONYMS_INFO_FIELDS = ("raw_triples", "distinct_triples", "words", "relations", "features", "longest_row")

@@ -27,6 +27,12 @@ README.rst:27-63; the shipped reference main crashes with a NameError, SURVEY.md
         that reach it, -k: that many clusters, one of the two -- or neither with -f merges, the dendrogram a merge a line;
         -j complete / -j average: those linkages, in rounds of reciprocal strongest pairs on a working copy of the matrix
         (csrc/linkage.h) -- -r is then also the floor below which no merge is made: -f merges ends there
+    east [-w tf|tf-idf] [-v stems|words] [-n N] [-u min texts] [-l language] [-f xml|csv] texts terms <texts>
+        what every text is about: its N (default 10, at most 1024) characteristic terms, the words or stems with the largest
+        tf or tf-idf weight over the text's norm, best first, summed and ranked on the device (csrc/terms.h)
+    east [-j linkage] (-r threshold | -k clusters) [-w ..] [-v ..] [-n N] [-u min texts] [-f xml|csv] texts terms <texts>
+        the same of every cluster `texts clusters -s cosine` finds with that linkage and cut, on the same index: the terms
+        with the largest mean over the cluster's texts among those that -u (default 1) of them hold
     east [-s ast|cosine|bm25] [-j linkage] [-b text|keyphrase] [-r threshold | -k clusters] [-f xml|csv|merges] keyphrases clusters <keyphrases file> <texts>
         the same of the texts (-b text) or the keyphrases (-b keyphrase) by the profile cosines of `keyphrases similar`
     east [-n N] [-x max words] [-m min count] [-u min texts] [-l language] [-f txt|csv|xml] keyphrases extract <texts>
@@ -176,7 +182,7 @@ def _main(opts, args, world, measure_factory):
         print("Invalid syntax: EAST should be called as:\n\n"
               "    east [options] <command> <subcommand> args\n\n"
               "Commands available: keyphrases, texts.\n"
-              "Subcommands available: table/graph/top/similar/clusters/extract.")
+              "Subcommands available: table/graph/top/similar/clusters/extract; related/similar/clusters/terms.")
         return 1
 
     command, subcommand = args[0], args[1]
@@ -309,17 +315,20 @@ def _related_options(opts):
 
 
 def _texts_main(opts, args, world, rank):
-    """`east texts related <texts>` (and `east texts similar <texts>`: _texts_similar_main).  Everything that cannot be done is refused with one line before a file is read or
+    """`east texts related <texts>` (and `east texts similar <texts>`: _texts_similar_main; `east texts terms <texts>`:
+    _texts_terms_main).  Everything that cannot be done is refused with one line before a file is read or
     anything touches a device."""
     def refuse(line):
         if rank == 0:
             print(line)
         return 1
 
-    if len(args) < 2 or args[1] not in ("related", "similar", "clusters"):
-        return refuse("Invalid subcommand: '%s'. Please use one of: 'related', 'similar', 'clusters'." % (args[1] if len(args) > 1 else ""))
+    if len(args) < 2 or args[1] not in ("related", "similar", "clusters", "terms"):
+        return refuse("Invalid subcommand: '%s'. Please use one of: 'related', 'similar', 'clusters', 'terms'." % (args[1] if len(args) > 1 else ""))
     if args[1] == "similar":
         return _texts_similar_main(opts, args, world, refuse)
+    if args[1] == "terms":
+        return _texts_terms_main(opts, args, world, refuse)
     if args[1] == "clusters":
         return _clusters_main(opts, args, world, rank)
     if len(args) < 3:
@@ -404,12 +413,86 @@ def _texts_similar_main(opts, args, world, refuse):
     return 0
 
 
+def _texts_terms_main(opts, args, world, refuse):
+    """`east texts terms <texts>`: the characteristic terms of every text, or with -r / -k of every cluster.  Everything that
+    cannot be done is refused with one line (refuse) before a file is read or a measure is made."""
+    if len(args) < 3:
+        return refuse('Invalid syntax. For text analysis, EAST should be called as:\n\n'
+                      '    east [options] texts terms "path/to/texts/dir"')
+    numbers = {}
+    for key, default, most, what in (("-n", "10", applications.TOP_MAX_N, "number of terms"), ("-u", "1", 2 ** 31 - 1, "number of texts")):
+        try:
+            numbers[key] = int(opts.get(key, default))
+        except ValueError:
+            numbers[key] = 0
+        if not 1 <= numbers[key] <= most:
+            return refuse("Invalid %s: '%s'. Please use an integer %s." % (
+                what, opts[key], "from 1 to %d" % most if key == "-n" else "of at least 1"))
+    fmt = opts.get("-f", "xml").lower()
+    if fmt not in ("xml", "csv"):
+        return refuse("Unknown terms format: '%s'. Please use one of: 'xml', 'csv'." % opts["-f"])
+    if "-r" in opts and "-k" in opts:
+        return refuse("Clusters are cut by a threshold (-r) or by their number (-k): please give one of the two.")
+    if "-j" in opts and "-r" not in opts and "-k" not in opts:
+        return refuse("A linkage belongs to clusters: -j %s needs a threshold (-r) or a number of clusters (-k)." % opts["-j"])
+    threshold = k = None
+    if "-r" in opts:
+        try:
+            threshold = float(opts["-r"])
+        except ValueError:
+            threshold = float("nan")
+        if threshold != threshold:
+            return refuse("Invalid similarity threshold: '%s'." % opts["-r"])
+    if "-k" in opts:
+        try:
+            k = int(opts["-k"])
+        except ValueError:
+            k = 0
+        if k < 1:
+            return refuse("Invalid number of clusters: '%s'. Please use an integer of at least 1." % opts["-k"])
+    if opts.get("-s", consts.RelevanceMeasure.COSINE).lower() != consts.RelevanceMeasure.COSINE:
+        return refuse("Characteristic terms are read off the cosine measure's term index: -s %s is not supported." % opts["-s"])
+    if opts.get("-v", consts.VectorSpace.STEMS).lower() == consts.VectorSpace.LEMMATA:
+        return refuse("Characteristic terms have no lemmatizer: -v %s is not supported (use 'stems' or 'words')." % opts["-v"])
+    for key, line in (("-y", "Characteristic terms take no synonyms: -y is not supported."),
+                      ("-o", "Characteristic terms have no orientation: -o %s is not supported."),
+                      ("-b", "Characteristic terms are listed per text or per cluster of texts: -b %s is not supported."),
+                      ("-c", "Characteristic terms build no graph: -c %s is not supported."),
+                      ("-p", "Characteristic terms build no graph: -p %s is not supported.")):
+        if key in opts:
+            return refuse(line % opts[key] if "%s" in line else line)
+    if world > 1:
+        return refuse("Characteristic terms run on one device: a launcher with WORLD_SIZE=%d is not supported." % world)
+    if os.environ.get("EAST_HIP_FORCE_DIST") == "1":
+        return refuse("Characteristic terms run on one device: the collective path is not supported.")
+    devices = opts.get("-g", os.environ.get("EAST_HIP_DEVICES", "1"))
+    try:
+        n_ranks = int(devices)
+    except ValueError:
+        return refuse("Invalid number of GPUs: '%s'." % devices)
+    if n_ranks > 1:
+        return refuse("Characteristic terms run on one device: -g %d is not supported." % n_ranks)
+    linkage = {"linkage": opts["-j"]} if "-j" in opts else {}      # (checked in main, before anything else)
+    try:
+        measure = relevance.CosineRelevanceMeasure(opts.get("-v", consts.VectorSpace.STEMS), opts.get("-w", consts.TermWeighting.TF_IDF))
+        if measure.stopwords_source == "none":
+            sys.stderr.write("nltk's English stopword list is not available: no stopwords are removed.\n")
+        texts = _read_texts(args[2])
+        found = applications.texts_terms(texts, numbers["-n"], numbers["-u"], measure, opts.get("-l", consts.Language.ENGLISH),
+                                         threshold, k, **linkage)
+        print(formatting.format_terms(found, fmt))
+    except (exceptions.EastException, applications.RefusedSimilarity) as e:     # (a missing stemmer, no device, a failed build ...): a message, not a traceback
+        print(e)
+        return 1
+    return 0
+
+
 def _linkage_refusal(opts, args):
-    """The one line that refuses -j, or None: a linkage belongs to `texts clusters` and `keyphrases clusters` and is one of
-    applications.LINKAGES."""
+    """The one line that refuses -j, or None: a linkage belongs to `texts clusters` and `keyphrases clusters` -- and to the
+    clusters `texts terms` labels -- and is one of applications.LINKAGES."""
     if "-j" not in opts:
         return None
-    if args[:2] not in (["texts", "clusters"], ["keyphrases", "clusters"]):
+    if args[:2] not in (["texts", "clusters"], ["keyphrases", "clusters"], ["texts", "terms"]):
         return "A linkage belongs to clusters: -j %s is supported by `texts clusters` and `keyphrases clusters` only." % opts["-j"]
     if opts["-j"] not in applications.LINKAGES:
         return "Unknown linkage: '%s'. Please use one of: 'single', 'complete', 'average'." % opts["-j"]

@@ -483,6 +483,22 @@ class CosineRelevanceMeasure(RelevanceMeasure):
             raise ValueError("extract_phrases: phrases are made of words, not of %s (use vector_space='words')" % self.vector_space)
         return self.index.phrases(n, max_words, min_words, min_count, min_texts)
 
+    def relevance_terms(self, n, min_texts=1, groups=None):
+        """The characteristic terms of every text of the collection (groups None) or of every group of texts (groups[d] =
+        the group of text d): per group the n units of this measure's vector space with the largest mean normalised
+        weight among those that min_texts of its texts hold (include/east_hip.h, "Characteristic terms"; csrc/terms.h);
+        after set_text_collection.  -> hip_backend.TermArrays; unit_names() names the units."""
+        return self.index.terms(self.term_weighting == consts.TermWeighting.TF_IDF, n, min_texts, groups)
+
+    def unit_names(self):
+        """The units of the vector space in id order: the words, or in the stems space the stem of every class."""
+        if self._stem_class is None:
+            return self.index.terms()
+        names = [None] * len(self._stem_class)
+        for stem, number in self._stem_class.items():
+            names[number] = stem
+        return names
+
     def _query_ids(self, prepared_keyphrases):
         """(ids int32, offsets int64) of a score call: the kept tokens of every keyphrase as units of the index's vector
         space, -1 outside it."""
@@ -635,6 +651,12 @@ class BM25RelevanceMeasure(CosineRelevanceMeasure):
 
     def extract_phrases(self, n=0, max_words=3, min_words=1, min_count=2, min_texts=1):
         self._cosine_only("extract_phrases")
+
+    def relevance_terms(self, n, min_texts=1, groups=None):
+        self._cosine_only("relevance_terms")
+
+    def unit_names(self):
+        self._cosine_only("unit_names")
 
     def relevance_clusters(self, prepared_keyphrases=None, axis=None, linkage="single", floor=None):
         if prepared_keyphrases is None:

@@ -716,6 +716,64 @@ int east_hip_phrases_levels(east_hip_handle_t h, int64_t *domain, int64_t *survi
 double east_hip_last_phrases_ms(east_hip_handle_t h);
 
 /*
+ * Characteristic terms (`east texts terms`): what a text, or a group of texts such as a cluster, is about -- per group the
+ * units of the vector space with the largest mean normalised weight, the keyword list by tf or tf-idf weight that any
+ * keyphrase method is compared with.  (How: csrc/terms.h)
+ *
+ * A cosine index has been built.  The vector space is the one the score call uses: the terms, or the classes after
+ * east_hip_cosine_set_classes.
+ * Weight and norm: x_d[u] and norm_d are exactly the doubles of "Text-to-text cosine similarity" -- the weight of posting
+ * (u, d) is the double the score call uses, the norm is summed in 64 slices and is 1.0 for a document without postings.
+ * Grouping: group[d] in [0, G) for d < D; a null `group` means G = D and group[d] = d (the per-text question).  A group may
+ * be empty.  members[g] = the number of its texts.
+ * Value of a unit in a group: for a unit u with a posting in at least one text of g, q_d = x_d[u] / norm_d (one quotient);
+ * s_gu = the sum of q_d over the texts of g that hold u, in ascending d, in one accumulator that starts from the first
+ * addend; value_gu = s_gu / (double)members[g] (one quotient: exact for a group of one).  texts_gu = the number of addends,
+ * df_u = the unit's postings in the whole collection.
+ * Entries and order: the entries of g are its units with texts_gu >= min_texts (min_texts >= 1), ordered by value
+ * descending, then u ascending -- strict, there is one answer.  The first n are the result, 1 <= n <= 1024 (the ranking's
+ * own limit).
+ * Guarantees: no floating-point atomic; the order of every sum is fixed by the collection and the grouping alone.  Two
+ * builds give the same bytes, as do builds under either value of east_hip_debug_set_terms_select; a null `group` and the
+ * explicit identity array give the same bytes.  Every value is > 0 (and at most 1).
+ * Accuracy: all addends are positive, nothing cancels.  With p_d the postings of text d,
+ *   |value_gu - exact| <= (texts_gu + (max over d in g of ceil(p_d / 64)) / 2 + 48) * 2^-53 * exact
+ * (DESIGN.md 19 derives it: texts_gu roundings of the sum and its quotient; the ceil(p_d / 64) + 62 roundings of a norm's
+ * radicand, halved by the root; 6 for the weight, ln at one ulp included, 13 for a square -- 47 in all beside the two
+ * variable terms.  It is less than half of what section 15's accounting, a whole ulp a rounding, would give.)
+ * Lifetime (the text-similarity matrix's rule): the result is withdrawn by east_hip_reset, by every
+ * east_hip_cosine_build_texts* call and by every east_hip_cosine_set_classes call; score calls, rankings, matrices and
+ * clusters leave it alone.  Every argument and index check comes before anything is withdrawn: a refused call leaves the
+ * earlier result fetchable.  The result lives in buffers of its own.
+ *
+ * east_hip_terms_build: weighting 0 tf, 1 tf-idf.  out (nullable, at least 10 entries): D; G; the units; the postings; the
+ * entries, that is, the distinct (group, unit) pairs; the entries that pass min_texts; the entries that reach the final
+ * sort; the radix passes run; the kernel launches; 1 when the grouping sort was skipped (a null `group`: the postings are
+ * in key order as they lie).
+ * east_hip_terms_fetch: members[G], count[G] = min(n, the group's entries), and unit, value, texts, df as [G * n], each
+ * nullable; places behind count[g] hold -1 and NaN.
+ * east_hip_terms_fetch_vectors: every entry before min_texts and the cut, in (group, unit) order: offsets[G + 1], then
+ * unit, value and texts_gu per entry (out[4] of the build sizes them); each nullable.
+ * east_hip_debug_set_terms_select: 0 (the default) a pre-selection in front of the final sort -- per group only the
+ * entries at or above the 12-bit digest of the value below which the n-th cannot lie are sorted; 1 none, every entry is
+ * sorted.  The result does not depend on it.
+ * Errors: EAST_HIP_ERR_NOT_BUILT "no cosine index has been built on this handle" without an index, "no characteristic terms
+ * have been built on this handle" for the fetches without a result; EAST_HIP_ERR_INVALID for a null handle, an unknown
+ * weighting, n outside 1 .. 1024, min_texts < 1, n_groups < 1 -- or not D with a null `group` -- and a group[d] outside
+ * [0, G), with the text's index and the value in the message, checked on the host before anything is queued;
+ * EAST_HIP_ERR_OOM "characteristic terms: ... of D texts in G groups needs N bytes, which the device does not have".
+ * Memory: during a build 96 bytes a posting; 20 bytes an entry and 20 bytes a place of the result stay.
+ * Device time of the last build in milliseconds (its read-backs included), -1 before a build and after a failed one.
+ */
+int east_hip_terms_build(east_hip_handle_t h, int32_t weighting, const int32_t *group, int32_t n_groups, int32_t n,
+                         int32_t min_texts, int64_t *out);
+int east_hip_terms_fetch(east_hip_handle_t h, int32_t *members, int32_t *count, int32_t *unit, double *value,
+                         int32_t *texts, int32_t *df);
+int east_hip_terms_fetch_vectors(east_hip_handle_t h, int64_t *offsets, int32_t *unit, double *value, int32_t *texts);
+double east_hip_last_terms_ms(east_hip_handle_t h);
+int east_hip_debug_set_terms_select(int mode);
+
+/*
  * Several devices in one process ("single-process/8-device fits the one-process CLI best").
  * Every document is an independent AST (east/relevance.py:41-46) and every (keyphrase, document) score is independent
  * (east/applications.py:43-52): a GROUP shards a collection at document granularity -- contiguous blocks of documents
