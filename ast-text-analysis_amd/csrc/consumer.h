@@ -1,6 +1,6 @@
 // consumer.h -- the host frame of the handle's consumers: the cosine term index, the keyphrase graph, the synonyms, the
-// ranking, the similarity, the text-to-text relatedness, the text-to-text cosine, the clusters, the extracted phrases and
-// the characteristic terms.
+// ranking, the similarity, the text-to-text relatedness, the text-to-text cosine, the clusters, the extracted phrases,
+// the characteristic terms and the shingle overlap.
 // A consumer is a struct of device buffers and results that the handle owns beside its arena, made by its first call.  The frame has
 // the state and its lifetime, the timer, the front of every entry point (consumer_begin, consumer_built, the two halves
 // of a *_build_resident / *_build_host pair), the table a source names (resolve_table), the M x M matrix of the consumers
@@ -128,7 +128,8 @@ struct UploadedTable {
 
 // ---- which table a *_build_resident call reads ----------------------------------------------------------------------------
 // who: the consumer's name in front of its messages; own: the caller's uploaded copy (nullptr before its first call);
-// matrices_ok: the square matrices other consumers built -- the similarity's, the relatedness', the text-to-text cosine's --
+// matrices_ok: the square matrices other consumers built -- the similarity's, the relatedness', the text-to-text cosine's,
+// the shingle overlap's --
 // are sources too (the ranking and the clusters).
 static TableRef resolve_table(const east_hip_index *h, int32_t source, const UploadedTable *own, const char *who, bool matrices_ok = false)
 {
@@ -137,6 +138,7 @@ static TableRef resolve_table(const east_hip_index *h, int32_t source, const Upl
         {EAST_HIP_GRAPH_SOURCE_SIMILARITY, east_hip_index::SLOT_SIM, true, ": no similarity matrix has been built on this handle"},
         {EAST_HIP_GRAPH_SOURCE_RELATED, east_hip_index::SLOT_REL, true, ": no relatedness matrix has been built on this handle"},
         {EAST_HIP_GRAPH_SOURCE_COSINE_TEXTS, east_hip_index::SLOT_COSTEXT, true, ": no text similarity matrix has been built on this handle"},
+        {EAST_HIP_GRAPH_SOURCE_OVERLAP, east_hip_index::SLOT_OVL, true, ": no overlap matrix has been built on this handle"},
     };
     TableRef t;
     const char *missing = nullptr;

@@ -583,6 +583,12 @@ static void cos_withdraw_terms(east_hip_index *h)
     if (Consumer *t = h->consumers[east_hip_index::SLOT_TERMS]) t->withdraw();
 }
 
+// the shingle overlap (overlap.h) is a function of the token sequence alone: a new index withdraws it, a new vector space does not
+static void cos_withdraw_overlap(east_hip_index *h)
+{
+    if (Consumer *o = h->consumers[east_hip_index::SLOT_OVL]) o->withdraw();
+}
+
 static CosState &cos_built(east_hip_index *h) { return consumer_built<CosState>(h, "no cosine index has been built on this handle"); }
 
 // A ragged host array: n + 1 offsets into a payload of offsets[n] words, narrowed to 32 bits for the device.  bad: the
@@ -632,6 +638,7 @@ static void cos_build(east_hip_index *h, HostTexts in, const UnicodeTablesHost &
     cos_withdraw_texts_matrix(h);
     cos_withdraw_phrases(h);
     cos_withdraw_terms(h);
+    cos_withdraw_overlap(h);
     const u32 N = (u32)in.n_bytes, D = (u32)in.D;
     Stats stats;
 

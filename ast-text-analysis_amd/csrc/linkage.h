@@ -385,11 +385,13 @@ int east_hip_clusters_build_resident_linkage(east_hip_handle_t h, int32_t source
         if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
         linkage_known(h, linkage);
         if (source != EAST_HIP_GRAPH_SOURCE_SIMILARITY && source != EAST_HIP_GRAPH_SOURCE_RELATED &&
-            source != EAST_HIP_GRAPH_SOURCE_COSINE_TEXTS && source != EAST_HIP_GRAPH_SOURCE_UPLOADED)
+            source != EAST_HIP_GRAPH_SOURCE_COSINE_TEXTS && source != EAST_HIP_GRAPH_SOURCE_OVERLAP && source != EAST_HIP_GRAPH_SOURCE_UPLOADED)
             east_throw(EAST_HIP_ERR_INVALID, "clusters: the source is not a square matrix of members");
         const TableRef t = consumer_resident<ClustersState>(h, source, "clusters", true);
         if (t.directed)
-            east_throw(EAST_HIP_ERR_INVALID, "clusters: the relatedness matrix is directed (build it with EAST_HIP_RELATED_SYMMETRIC)");
+            east_throw(EAST_HIP_ERR_INVALID, source == EAST_HIP_GRAPH_SOURCE_OVERLAP
+                                                 ? "clusters: the overlap matrix is directed (build it with EAST_HIP_OVERLAP_SYMMETRIC)"
+                                                 : "clusters: the relatedness matrix is directed (build it with EAST_HIP_RELATED_SYMMETRIC)");
         if (t.K != t.D) east_throw(EAST_HIP_ERR_INTERNAL, "clusters: the source matrix is not square");
         clusters_build_linkage(h, t.p, t.K, false, linkage, floor, out);
     });

@@ -23,7 +23,8 @@
 //
 // A level is 5 launches of this file (keys, runs, stats + id scatter + marks, emission flags, emission), one fill, the
 // sort's passes and 5 scans, and 2 read-backs: the survivors; the candidates of the level below with the next level's
-// domain.  Level max_words + 1 is never built; a level without a survivor ends the build.
+// domain.  Level max_words + 1 is never built; a level without a survivor ends the build.  The naming half of a level --
+// keys, sort, runs, survivors, ids -- is phr_level_step, which the shingle overlap (overlap.h) runs too.
 //
 // Memory: 112 bytes a kept token of work arrays, 16 bytes a candidate, the result.  Buffers of this consumer's own.
 #pragma once
@@ -247,6 +248,49 @@ static void phr_grow_keep(DevBuf &b, size_t bytes, size_t used, hipStream_t stre
 
 static inline int phr_bit_width64(u64 x) { int b = 0; while (x) { b++; x >>= 1; } return b; }
 
+// ---- one level ------------------------------------------------------------------------------------------------------------
+// The arrays a level works in (the caller's arena): the domain's scan, the sort's two pairs, and over the sorted pairs the
+// run numbers, the runs' starts, the text steps and their scan, the survivors' scan.
+struct PhrWork {
+    u32 *dex = nullptr;
+    SortBufs<u64> sb = {};
+    u32 *ri = nullptr, *run_start = nullptr, *tflag = nullptr, *tx = nullptr, *sx = nullptr;
+    int term_bits = 0;
+};
+
+struct PhrStep {
+    u32 surv;       // the runs that survive (0 with stats == false)
+    int r;          // the sort's buffers that hold the sorted pairs
+};
+
+// Level din.n of the naming, shared by the phrases and the shingle overlap (overlap.h): W.dex = the exclusive scan of the
+// domain `din` with `dom` positions in it; n_below = the survivors of the level below.  Keys, the stable sort over exactly
+// the needed bits, the runs and their text steps (ri, run_start, tflag, tx).  stats: the survivors with min_count get
+// their dense ids at their members' positions (L.id, COS_NONE elsewhere) and their statistics, and mark the level below
+// (B; B.id == nullptr: level 1); without, the level is named only and L is not touched.
+static PhrStep phr_level_step(Ctx &ctx, const PhrDomainIn &din, u32 dom, u32 n_below, u32 min_count, PhrWork &W, PhrLevel L, PhrLevel B,
+                              bool stats)
+{
+    const u32 T = din.T, n = din.n;
+    PhrStep st{0u, 0};
+    if (stats && T) HIP_CHECK(hipMemsetAsync(L.id, 0xFF, (size_t)T * 4, ctx.stream));
+    if (!dom) return st;
+    LAUNCH(ctx, phr_keys_kernel, ceil_div_u32(T, BLOCK), din, (const u32 *)W.dex, W.term_bits, W.sb.keys[0], W.sb.vals[0]);
+    const int bits = std::max(1, n == 1u ? W.term_bits : bit_width_u32(n_below - 1u) + W.term_bits);
+    st.r = radix_sort_pairs<u64>(ctx, W.sb, dom, bits);
+    const u32 *sv = W.sb.vals[st.r];
+    const u32 grid_D = ceil_div_u32(dom, BLOCK);
+    device_scan<RunHeadIn<u64>, true>(ctx, RunHeadIn<u64>{W.sb.keys[st.r], 0}, dom, W.ri);
+    LAUNCH(ctx, phr_runs_kernel, grid_D, (const u32 *)W.ri, sv, din.tok_doc, dom, W.run_start, W.tflag);
+    device_scan_with_total(ctx, ArrIn{W.tflag}, dom, W.tx);
+    if (!stats) return st;
+    st.surv = device_scan_count(ctx, PhrSurvIn{W.ri, W.run_start, min_count}, dom, W.sx);
+    if (st.surv)
+        LAUNCH(ctx, phr_stats_kernel, grid_D, (const u32 *)W.ri, (const u32 *)W.run_start, (const u32 *)W.sx, (const u32 *)W.tx, sv, dom,
+               min_count, L, B, n_below);
+    return st;
+}
+
 static void phrases_check(const PhraseParams &pp, const i64 *out)
 {
     if (pp.max_words < 1 || pp.max_words > PHR_MAX_WORDS) east_throw(EAST_HIP_ERR_INVALID, "phrases: max_words must lie in 1 .. 8");
@@ -287,9 +331,15 @@ static void phrases_build(east_hip_index *h, const PhraseParams &pp, i64 *out)
     }
     u32 *dex = a.alloc<u32>(K1), *eflag[2], *eex[2];
     for (int k = 0; k < 2; k++) { eflag[k] = a.alloc<u32>(K1); eex[k] = a.alloc<u32>(K1); }
-    SortBufs<u64> sb = sort_bufs_alloc<u64>(a, K1);
-    u32 *ri = a.alloc<u32>(K1), *run_start = a.alloc<u32>(K1), *tflag = a.alloc<u32>(K1), *tx = a.alloc<u32>(K1), *sx = a.alloc<u32>(K1);
-    const int term_bits = bit_width_u32(V ? V - 1u : 0u);
+    PhrWork W;
+    W.dex = dex;
+    W.sb = sort_bufs_alloc<u64>(a, K1);
+    W.ri = a.alloc<u32>(K1);
+    W.run_start = a.alloc<u32>(K1);
+    W.tflag = a.alloc<u32>(K1);
+    W.tx = a.alloc<u32>(K1);
+    W.sx = a.alloc<u32>(K1);
+    W.term_bits = bit_width_u32(V ? V - 1u : 0u);
     const u32 grid_T = ceil_div_u32(T, BLOCK);
 
     int cur = 0;
@@ -301,22 +351,7 @@ static void phrases_build(east_hip_index *h, const PhraseParams &pp, i64 *out)
         const PhrLevel L = lv[cur], B = n > 1u ? lv[cur ^ 1] : PhrLevel{nullptr, nullptr, nullptr, nullptr, nullptr};
         g.levels = (int)n;
         g.domain[n - 1] = dom;
-        u32 surv = 0;
-        if (T) HIP_CHECK(hipMemsetAsync(L.id, 0xFF, (size_t)T * 4, h->stream));
-        if (dom) {
-            LAUNCH(ctx, phr_keys_kernel, grid_T, din, (const u32 *)dex, term_bits, sb.keys[0], sb.vals[0]);
-            const int bits = std::max(1, n == 1u ? term_bits : bit_width_u32(n_below - 1u) + term_bits);
-            const int r = radix_sort_pairs<u64>(ctx, sb, dom, bits);
-            const u32 *sv = sb.vals[r];
-            const u32 grid_D = ceil_div_u32(dom, BLOCK);
-            device_scan<RunHeadIn<u64>, true>(ctx, RunHeadIn<u64>{sb.keys[r], 0}, dom, ri);
-            LAUNCH(ctx, phr_runs_kernel, grid_D, (const u32 *)ri, sv, tok_doc, dom, run_start, tflag);
-            device_scan_with_total(ctx, ArrIn{tflag}, dom, tx);
-            surv = device_scan_count(ctx, PhrSurvIn{ri, run_start, (u32)pp.min_count}, dom, sx);
-            if (surv)
-                LAUNCH(ctx, phr_stats_kernel, grid_D, (const u32 *)ri, (const u32 *)run_start, (const u32 *)sx, (const u32 *)tx, sv, dom,
-                       (u32)pp.min_count, L, B, n_below);
-        }
+        const u32 surv = phr_level_step(ctx, din, dom, n_below, (u32)pp.min_count, W, L, B, true).surv;
         g.survivors[n - 1] = surv;
         const bool last = n == (u32)pp.max_words || surv == 0;
         // the level below is final now (its marks are in); this level is where nothing follows it

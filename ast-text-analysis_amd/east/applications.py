@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
 """keyphrases_table / keyphrases_graph (reference east/applications.py:11-149), keyphrases_top and keyphrases_similar;
-texts_related, texts_similar, the clusters, keyphrases_extract and texts_terms."""
+texts_related, texts_similar, texts_overlap, the clusters, keyphrases_extract and texts_terms."""
 
 import inspect
 import os
@@ -616,6 +616,93 @@ def texts_similar(texts, n=10, similarity_threshold=None, similarity_measure=Non
     return _top_named(lists, titles, titles)
 
 
+# ---- shingle overlap -----------------------------------------------------------------------------------------------------
+_OVERLAP_ORIENTATIONS = ("directed", "symmetric")
+OVERLAP_MAX_WORDS = 8
+
+
+def _overlap_matrix(doc_sets, symmetric):
+    """The contract of include/east_hip.h ("Shingle overlap") in plain Python: doc_sets[a] = the set of text a's shingles.
+    Every entry is Python's int / int, the correctly rounded quotient.  -> (M[D, D] with NaN on the diagonal, self[D],
+    shingles[D])."""
+    D = len(doc_sets)
+    size = [len(s) for s in doc_sets]
+    matrix = np.zeros((D, D), dtype=np.float64)
+    holders = {}
+    for a, shingles in enumerate(doc_sets):
+        for g in shingles:
+            holders.setdefault(g, []).append(a)
+    shared = np.zeros((D, D), dtype=np.int64)
+    for texts in holders.values():
+        if len(texts) > 1:
+            at = np.asarray(texts, dtype=np.int64)
+            shared[at[:, None], at[None, :]] += 1
+    for a in range(D):
+        for b in np.flatnonzero(shared[a]).tolist():
+            i = int(shared[a, b])
+            den = size[a] + size[b] - i if symmetric else size[a]
+            matrix[a, b] = i / den if den else 0.0
+    np.fill_diagonal(matrix, np.nan)
+    return matrix, np.array([1.0 if n else 0.0 for n in size], dtype=np.float64), np.array(size, dtype=np.int32)
+
+
+def _overlap_on_host(texts, stopwords, words, symmetric):
+    """texts_overlap's matrix on the host, without a device: the tokens of utils.tokenize(utils.prepare_text(text)) with at
+    least 3 code points, the stopwords as breaks; per text the set of its tuples of `words` consecutive words."""
+    doc_sets = []
+    for text in texts:
+        tokens = [None if token in stopwords else token for token in utils.tokenize(utils.prepare_text(text)) if len(token) >= 3]
+        doc_sets.append({tuple(tokens[j:j + words]) for j in range(len(tokens) - words + 1) if None not in tokens[j:j + words]})
+    return _overlap_matrix(doc_sets, symmetric)
+
+
+def _overlap_arguments(who, words, orientation, similarity_measure):
+    if isinstance(words, bool) or int(words) != words or not 1 <= words <= OVERLAP_MAX_WORDS:
+        raise ValueError("%s: words must be an integer in 1 .. %d, not %r" % (who, OVERLAP_MAX_WORDS, words))
+    if orientation not in _OVERLAP_ORIENTATIONS:
+        raise ValueError("%s: orientation must be 'symmetric' or 'directed', not %r" % (who, orientation))
+    measure = relevance.CosineRelevanceMeasure(consts.VectorSpace.WORDS) if similarity_measure is None else similarity_measure
+    if not isinstance(measure, relevance.CosineRelevanceMeasure):
+        raise ValueError("%s: the shingles come from the term index of a CosineRelevanceMeasure, not %s" % (who, type(measure).__name__))
+    _refuse_bm25(who, measure)
+    return int(words), measure
+
+
+def texts_overlap(texts, n=10, words=4, orientation="symmetric", overlap_threshold=None, similarity_measure=None,
+                  language=consts.Language.ENGLISH):
+    """The texts that contain the same WORDING as every text -- near-duplicates, lifted passages, one text quoted in a longer
+    one --, from the texts alone.  A text is the set of its shingles, the phrases of `words` consecutive words (no stopword
+    inside, as keyphrases_extract sees phrases; include/east_hip.h, "Shingle overlap").
+
+    :param texts: {text name: text}
+    :param n: entries per text at most, 1 .. 1024
+    :param words: the words of a shingle, 1 .. 8
+    :param orientation: "symmetric" -- the resemblance |A n B| / |A u B|; "directed" -- the containment |A n B| / |A| of
+                        the listing text A in the listed text B
+    :param overlap_threshold: only values >= it are listed (None: every value that is a number)
+    :param similarity_measure: a relevance.CosineRelevanceMeasure, whose stopwords are the breaks (None:
+                               CosineRelevanceMeasure("words")); any other raises ValueError
+    :returns: {text name: [(other text name, value), ...]}, best first: by value descending and, among equal values, in the
+              order of `texts`; a text never lists itself; plain Python values
+
+    The matrix and its ranking are made on the device, from the token sequence the term index keeps (csrc/overlap.h,
+    csrc/top.h), when the text titles are distinct and EAST_HIP_OVERLAP is not `host`; in every other case on the host,
+    which then touches no device: sets of word tuples from the same tokens and the same one division of two integers.  The
+    two paths give the SAME BYTES.
+    """
+    words, measure = _overlap_arguments("texts_overlap", words, orientation, similarity_measure)
+    _, n, threshold = _ranking_arguments("texts_overlap", "text", n, overlap_threshold, "overlap")
+    titles = list(texts.keys())
+    if not titles:
+        return {}
+    if _device_applies(measure, texts, None, "relevance_texts_overlap", "EAST_HIP_OVERLAP"):
+        measure.set_text_collection(list(texts.values()), language)
+        lists = _top_lists(measure.relevance_texts_overlap(n, threshold, words, orientation))
+    else:
+        lists = _top_select(_overlap_on_host(texts.values(), measure.stopwords, words, orientation == "symmetric")[0], 1, n, threshold)
+    return _top_named(lists, titles, titles)
+
+
 # ---- clusters ------------------------------------------------------------------------------------------------------------
 def _strongest_first(matrix):
     """The pairs a < b of a symmetric M x M array that are not NaN in the order of include/east_hip.h ("Clusters"): by
@@ -902,6 +989,36 @@ def texts_clusters(texts, threshold=None, k=None, similarity_measure=None, langu
         matrix = _texts_similar_on_host(texts, measure, language)[0]
     else:
         matrix = _related_on_host(texts, 1, measure, language)[0]
+    return _clustering_of_matrix(titles, matrix, threshold, k, linkage)
+
+
+def texts_overlap_clusters(texts, words=4, threshold=None, k=None, linkage="single", similarity_measure=None,
+                           language=consts.Language.ENGLISH):
+    """The groups the texts fall into by their shared wording: agglomerative clustering (texts_clusters' linkages, cuts and
+    result) of the symmetric matrix texts_overlap ranks, the resemblance of the texts' sets of `words`-word shingles.  Single
+    linkage at a resemblance threshold gives the near-duplicate groups.
+
+    :param texts: {text name: text}
+    :param words: the words of a shingle, 1 .. 8
+    :param threshold, k, linkage: as texts_clusters takes them
+    :param similarity_measure: a relevance.CosineRelevanceMeasure (None: CosineRelevanceMeasure("words")); any other raises ValueError
+    :returns: a Clustering
+
+    On the device (csrc/overlap.h, csrc/clusters.h, csrc/linkage.h) when the text titles are distinct and EAST_HIP_OVERLAP is
+    not `host`; in every other case the host path's matrix and the host clustering, no device touched.  The two matrices are
+    the same bytes.
+    """
+    words, measure = _overlap_arguments("texts_overlap_clusters", words, "symmetric", similarity_measure)
+    threshold, k = _cut_arguments("texts_overlap_clusters", threshold, k)
+    linkage = _linkage_argument("texts_overlap_clusters", linkage)
+    titles = list(texts.keys())
+    if not titles:
+        return Clustering([], [], [], [], None if threshold is None and k is None else [], linkage)
+    if _device_applies(measure, texts, None, "relevance_overlap_clusters", "EAST_HIP_OVERLAP"):
+        measure.set_text_collection(list(texts.values()), language)
+        index = measure.relevance_overlap_clusters(words, linkage, None if linkage == "single" else threshold)
+        return _clustering_of_index(titles, index, threshold, k, linkage)
+    matrix = _overlap_on_host(texts.values(), measure.stopwords, words, True)[0]
     return _clustering_of_matrix(titles, matrix, threshold, k, linkage)
 
 

@@ -198,6 +198,11 @@ SIGNATURES = {
     "east_hip_terms_fetch_vectors": (ctypes.c_int, [ctypes.c_void_p, _c_i64p, _c_i32p, _c_dblp, _c_i32p]),
     "east_hip_last_terms_ms": (ctypes.c_double, [ctypes.c_void_p]),
     "east_hip_debug_set_terms_select": (ctypes.c_int, [ctypes.c_int]),
+    "east_hip_overlap_build": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, _c_i64p]),
+    "east_hip_overlap_fetch": (ctypes.c_int, [ctypes.c_void_p, _c_dblp, _c_dblp, _c_i32p]),
+    "east_hip_last_overlap_ms": (ctypes.c_double, [ctypes.c_void_p]),
+    "east_hip_debug_set_overlap_route": (ctypes.c_int, [ctypes.c_int]),
+    "east_hip_debug_set_overlap_batch": (ctypes.c_int, [ctypes.c_int64]),
 }
 
 BUILD_INFO_FIELDS = ("n_total", "n_docs", "n_strings", "sigma_text", "bits_level0", "dc3_levels", "arena_bytes",
@@ -216,6 +221,11 @@ GRAPH_SOURCE_RELATED = 4                    # east_hip_top_build_resident only: 
 GRAPH_SOURCE_COSINE_TEXTS = 5               # east_hip_top_build_resident only: the matrix the last cosine texts build left
 COSINE_TEXTS_CHUNK, COSINE_TEXTS_SEG = 32, 8192      # csrc/cosine_texts.h: the units of a staged chunk and of a segment (texts_build reports them)
 COSINE_TEXTS_INFO_FIELDS = ("n_docs", "units", "postings", "tiles", "segments", "launches", "chunk_units", "segment_units")
+GRAPH_SOURCE_OVERLAP = 6                    # the ranking and the clusters: the matrix the last shingle overlap build left
+OVERLAP_DIRECTED, OVERLAP_SYMMETRIC = 0, 1  # EAST_HIP_OVERLAP_*
+OVERLAP_ORIENTATIONS = ("directed", "symmetric")
+OVERLAP_INFO_FIELDS = ("n_docs", "kept_tokens", "shingle_positions", "distinct_shingles", "shared_shingles", "postings", "segments",
+                       "launches", "route", "levels", "tiles", "words", "operands_us", "product_us")          # east_hip_overlap_build: out
 TERMS_INFO_FIELDS = ("n_docs", "groups", "units", "postings", "entries", "passing", "sorted", "radix_passes", "launches",
                      "grouping_sort_skipped")                           # east_hip_terms_build: out
 CLUSTERS_INFO_FIELDS = ("members", "merges", "rounds", "launches")      # east_hip_clusters_build_*: out
@@ -1048,6 +1058,33 @@ class HipCosineIndex(_ResidentTableConsumers):
 
     def last_texts_ms(self):
         return float(self._lib.east_hip_last_text_similarity_ms(self._h))
+
+    # -- shingle overlap -----------------------------------------------------------
+    def overlap_build(self, words=4, orientation=OVERLAP_SYMMETRIC):
+        """The D x D matrix of the shared w-word shingles of the index's own texts: the resemblance (symmetric) or the
+        containment of the row's text in the column's (directed; include/east_hip.h, "Shingle overlap"); it stays on the
+        device.  -> {OVERLAP_INFO_FIELDS: value}"""
+        out = np.zeros(len(OVERLAP_INFO_FIELDS), dtype=np.int64)
+        _check(self._lib.east_hip_overlap_build(self._h, int(words), int(orientation), _ptr(out, _c_i64p)))
+        self._overlap_M = int(out[0])
+        return dict(zip(OVERLAP_INFO_FIELDS, (int(x) for x in out)))
+
+    def overlap_matrix(self):
+        """The last overlap matrix of this handle -> (matrix[D, D] with NaN on the diagonal, self[D] = the diagonal before
+        the NaN, shingles[D] = the distinct shingles of every text, int32)."""
+        return _matrix_fetch(self._lib.east_hip_overlap_fetch, self._h, self._overlap_M)
+
+    def rank_overlap(self, n, threshold=-np.inf):
+        """A ranking of the last overlap matrix by row (other n, other threshold: no new matrix) -> TopArrays."""
+        return _top_build(self._lib, self._h, GRAPH_SOURCE_OVERLAP, None, TOP_BY_KEYPHRASE, n, threshold)
+
+    def texts_overlap(self, words=4, orientation=OVERLAP_SYMMETRIC, n=10, threshold=-np.inf):
+        """overlap_build, then the n other texts every text shares most with -> TopArrays (the handle's one ranking)."""
+        self.overlap_build(words, orientation)
+        return self.rank_overlap(n, threshold)
+
+    def last_overlap_ms(self):
+        return float(self._lib.east_hip_last_overlap_ms(self._h))
 
     # -- characteristic terms ------------------------------------------------------
     def _characteristic_terms(self, tfidf, n, min_texts, groups, n_groups=None):

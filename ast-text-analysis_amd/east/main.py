@@ -33,6 +33,12 @@ README.rst:27-63; the shipped reference main crashes with a NameError, SURVEY.md
     east [-j linkage] (-r threshold | -k clusters) [-w ..] [-v ..] [-n N] [-u min texts] [-f xml|csv] texts terms <texts>
         the same of every cluster `texts clusters -s cosine` finds with that linkage and cut, on the same index: the terms
         with the largest mean over the cluster's texts among those that -u (default 1) of them hold
+    east [-x words] [-o symmetric|directed] [-n N] [-r threshold] [-l language] [-f xml|csv] texts overlap <texts>
+        the N texts every text shares most WORDING with -- near-duplicates, lifted passages, quotations: a text is the set
+        of its shingles of -x (default 4, at most 8) consecutive words; -o symmetric: the resemblance |A n B| / |A u B|,
+        -o directed: the containment |A n B| / |A| of the listing text in the listed one; exact integers and one division,
+        on the device (csrc/overlap.h); with -j single|complete|average and (-r threshold | -k clusters | -f merges) the
+        clusters of the symmetric matrix instead -- single linkage at a resemblance threshold: the near-duplicate groups
     east [-s ast|cosine|bm25] [-j linkage] [-b text|keyphrase] [-r threshold | -k clusters] [-f xml|csv|merges] keyphrases clusters <keyphrases file> <texts>
         the same of the texts (-b text) or the keyphrases (-b keyphrase) by the profile cosines of `keyphrases similar`
     east [-n N] [-x max words] [-m min count] [-u min texts] [-l language] [-f txt|csv|xml] keyphrases extract <texts>
@@ -323,8 +329,10 @@ def _texts_main(opts, args, world, rank):
             print(line)
         return 1
 
-    if len(args) < 2 or args[1] not in ("related", "similar", "clusters", "terms"):
-        return refuse("Invalid subcommand: '%s'. Please use one of: 'related', 'similar', 'clusters', 'terms'." % (args[1] if len(args) > 1 else ""))
+    if len(args) < 2 or args[1] not in ("related", "similar", "clusters", "terms", "overlap"):
+        return refuse("Invalid subcommand: '%s'. Please use one of: 'related', 'similar', 'clusters', 'terms', 'overlap'." % (args[1] if len(args) > 1 else ""))
+    if args[1] == "overlap":
+        return _texts_overlap_main(opts, args, world, refuse)
     if args[1] == "similar":
         return _texts_similar_main(opts, args, world, refuse)
     if args[1] == "terms":
@@ -413,6 +421,84 @@ def _texts_similar_main(opts, args, world, refuse):
     return 0
 
 
+def _texts_overlap_main(opts, args, world, refuse):
+    """`east texts overlap <texts>`: the texts that share wording, by their sets of -x word shingles; with -j the clusters of
+    the symmetric matrix.  Everything that cannot be done is refused with one line (refuse) before a file is read or a measure
+    is made."""
+    if len(args) < 3:
+        return refuse('Invalid syntax. For text analysis, EAST should be called as:\n\n'
+                      '    east [options] texts overlap "path/to/texts/dir"')
+    for key, line in (("-s", "Shingle overlap compares wording, not a relevance measure: -s %s is not supported."),
+                      ("-w", "Shingle overlap weighs no terms: -w %s is not supported."),
+                      ("-v", "Shingles are made of words: -v %s is not supported."),
+                      ("-y", "Shingle overlap takes no synonyms: -y is not supported."),
+                      ("-b", "Shingle overlap compares texts: -b %s is not supported."),
+                      ("-c", "Shingle overlap builds no graph: -c %s is not supported."),
+                      ("-p", "Shingle overlap builds no graph: -p %s is not supported."),
+                      ("-m", "Every shingle counts once a text: -m %s is not supported (it belongs to `keyphrases extract`)."),
+                      ("-u", "Every shingle counts once a text: -u %s is not supported (it belongs to `keyphrases extract`)."),
+                      ("-z", "Shingle overlap scores no keyphrases: -z %s is not supported.")):
+        if key in opts:
+            return refuse(line % opts[key] if "%s" in line else line)
+    try:
+        words = int(opts.get("-x", "4"))
+    except ValueError:
+        words = 0
+    if not 1 <= words <= applications.OVERLAP_MAX_WORDS:
+        return refuse("Invalid number of words: '%s'. Please use an integer from 1 to %d." % (opts["-x"], applications.OVERLAP_MAX_WORDS))
+    orientation = opts.get("-o", "symmetric").lower()
+    if orientation not in ("symmetric", "directed"):
+        return refuse("Invalid orientation: '%s'. Please use one of: 'symmetric', 'directed'." % opts["-o"])
+    clusters = "-j" in opts
+    if clusters:
+        if orientation == "directed":
+            return refuse("Clusters need a symmetric matrix: -o %s is not supported with -j." % opts["-o"])
+        if "-n" in opts:
+            return refuse("Clusters are not ranked: -n %s is not supported with -j (use -k for their number)." % opts["-n"])
+        threshold, k, fmt, refusal = _clusters_options(opts)
+        if refusal:
+            return refuse(refusal)
+    else:
+        if "-k" in opts:
+            return refuse("A number of clusters belongs to clusters: -k %s needs a linkage (-j)." % opts["-k"])
+        n, _, threshold, refusal = _top_options(opts)
+        if refusal:
+            return refuse(refusal.replace("relevance threshold", "overlap threshold"))
+        fmt = opts.get("-f", "xml").lower()
+        if fmt not in ("xml", "csv"):
+            return refuse("Unknown overlap format: '%s'. Please use one of: 'xml', 'csv'." % opts["-f"])
+    if world > 1:
+        return refuse("Shingle overlap runs on one device: a launcher with WORLD_SIZE=%d is not supported." % world)
+    if os.environ.get("EAST_HIP_FORCE_DIST") == "1":
+        return refuse("Shingle overlap runs on one device: the collective path is not supported.")
+    devices = opts.get("-g", os.environ.get("EAST_HIP_DEVICES", "1"))
+    try:
+        n_ranks = int(devices)
+    except ValueError:
+        return refuse("Invalid number of GPUs: '%s'." % devices)
+    if n_ranks > 1:
+        return refuse("Shingle overlap runs on one device: -g %d is not supported." % n_ranks)
+    language = opts.get("-l", consts.Language.ENGLISH)
+    try:
+        measure = relevance.CosineRelevanceMeasure(consts.VectorSpace.WORDS)
+        if measure.stopwords_source == "none":
+            sys.stderr.write("nltk's English stopword list is not available: no stopwords are removed.\n")
+        texts = _read_texts(args[2])
+        if clusters:
+            found = applications.texts_overlap_clusters(texts, words, threshold, k, opts["-j"], measure, language)
+            print(formatting.format_clusters(found, fmt))
+        else:
+            found = applications.texts_overlap(texts, n, words, orientation, threshold, measure, language)
+            print(formatting.format_similar(found, "text", fmt))
+    except (exceptions.EastException, applications.RefusedSimilarity) as e:     # (no device, a failed build ...): a message, not a traceback
+        print(e)
+        return 1
+    except Exception as e:                      # (an unknown format)
+        print(e)
+        return 1
+    return 0
+
+
 def _texts_terms_main(opts, args, world, refuse):
     """`east texts terms <texts>`: the characteristic terms of every text, or with -r / -k of every cluster.  Everything that
     cannot be done is refused with one line (refuse) before a file is read or a measure is made."""
@@ -492,7 +578,7 @@ def _linkage_refusal(opts, args):
     clusters `texts terms` labels -- and is one of applications.LINKAGES."""
     if "-j" not in opts:
         return None
-    if args[:2] not in (["texts", "clusters"], ["keyphrases", "clusters"], ["texts", "terms"]):
+    if args[:2] not in (["texts", "clusters"], ["keyphrases", "clusters"], ["texts", "terms"], ["texts", "overlap"]):
         return "A linkage belongs to clusters: -j %s is supported by `texts clusters` and `keyphrases clusters` only." % opts["-j"]
     if opts["-j"] not in applications.LINKAGES:
         return "Unknown linkage: '%s'. Please use one of: 'single', 'complete', 'average'." % opts["-j"]

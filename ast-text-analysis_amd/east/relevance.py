@@ -475,6 +475,25 @@ class CosineRelevanceMeasure(RelevanceMeasure):
             self.index.clusters_build(hip_backend.GRAPH_SOURCE_SIMILARITY, linkage, floor)
         return self.index
 
+    def text_overlap_matrix(self, words=4, orientation="symmetric"):
+        """The D x D matrix of shared w-word shingles of the indexed collection: the resemblance |A n B| / |A u B|
+        ("symmetric") or the containment |A n B| / |A| of the row's text in the column's ("directed"; include/east_hip.h,
+        "Shingle overlap"; csrc/overlap.h); after set_text_collection.  Shingles are made of words whatever the vector space.
+        -> (matrix, self, shingles) of HipCosineIndex.overlap_matrix."""
+        self.index.overlap_build(words, hip_backend.OVERLAP_ORIENTATIONS.index(orientation))
+        return self.index.overlap_matrix()
+
+    def relevance_texts_overlap(self, n, threshold=-np.inf, words=4, orientation="symmetric"):
+        """The n other texts every text of the collection shares most w-word shingles with (text_overlap_matrix, ranked
+        where it lies).  -> hip_backend.TopArrays."""
+        return self.index.texts_overlap(words, hip_backend.OVERLAP_ORIENTATIONS.index(orientation), n, threshold)
+
+    def relevance_overlap_clusters(self, words=4, linkage="single", floor=None):
+        """Clusters of the symmetric overlap matrix, built and clustered where it lies.  -> the index."""
+        self.index.overlap_build(words, hip_backend.OVERLAP_SYMMETRIC)
+        self.index.clusters_build(hip_backend.GRAPH_SOURCE_OVERLAP, linkage, floor)
+        return self.index
+
     def extract_phrases(self, n=0, max_words=3, min_words=1, min_count=2, min_texts=1):
         """The repeated phrases of the indexed collection as keyphrase candidates, best first (include/east_hip.h, "Phrase
         extraction"; csrc/phrases.h); after set_text_collection, in the `words` space: a phrase is made of words, not of
@@ -654,6 +673,15 @@ class BM25RelevanceMeasure(CosineRelevanceMeasure):
 
     def relevance_terms(self, n, min_texts=1, groups=None):
         self._cosine_only("relevance_terms")
+
+    def text_overlap_matrix(self, words=4, orientation="symmetric"):
+        self._cosine_only("text_overlap_matrix")
+
+    def relevance_texts_overlap(self, n, threshold=-np.inf, words=4, orientation="symmetric"):
+        self._cosine_only("relevance_texts_overlap")
+
+    def relevance_overlap_clusters(self, words=4, linkage="single", floor=None):
+        self._cosine_only("relevance_overlap_clusters")
 
     def unit_names(self):
         self._cosine_only("unit_names")

@@ -774,6 +774,64 @@ double east_hip_last_terms_ms(east_hip_handle_t h);
 int east_hip_debug_set_terms_select(int mode);
 
 /*
+ * Shingle overlap (`east texts overlap`): which texts CONTAIN THE SAME WORDING -- near-duplicates, a passage lifted from
+ * another text, one text quoted inside a longer one -- after Broder: a text is the set of its w-word shingles.  Integers
+ * and one division an entry: the device (either route), the host path of the Python package and any other exact count give
+ * the same bytes.  (How: csrc/overlap.h)
+ *
+ * A cosine index has been built.  Tokens, words, breaks and positions are those of "Phrase extraction".
+ * Shingle: with 1 <= w <= 8 (the phrases' longest), a shingle of w words is a phrase of exactly w words in that contract's
+ * sense: w kept tokens that are no stopwords at consecutive positions of one text.
+ * Sets: S_a = the distinct shingles with an occurrence in text a -- repeats inside a text count once; a text of fewer than w
+ * consecutive words has S_a empty.  n_a = |S_a|, I_ab = |S_a n S_b|.
+ * EAST_HIP_OVERLAP_SYMMETRIC (resemblance):   M[a][b] = (double)I_ab / (double)(n_a + n_b - I_ab), +0.0 where that is 0.
+ * EAST_HIP_OVERLAP_DIRECTED (containment of a in b): M[a][b] = (double)I_ab / (double)n_a, +0.0 where n_a = 0.
+ * Arithmetic: every entry is ONE IEEE division of integers below 2^53 -- the correctly rounded quotient, the same bytes on
+ * every path; there is no tolerance anywhere.
+ * The diagonal is NaN (nobody lists itself); self[a] = the diagonal before the NaN: 1.0, or +0.0 for an empty set;
+ * shingles[a] = n_a.
+ *
+ * Example.  w = 2, text A = `abc bcd cde def`, text B = `bcd cde def efg`: S_A = {ABC BCD, BCD CDE, CDE DEF}, S_B = {BCD CDE,
+ * CDE DEF, DEF EFG}, I = 2; resemblance 2 / 4 = 0.5, containment of A in B 2 / 3.
+ *
+ * east_hip_overlap_build: out (at least 14 entries): D; the kept tokens; the shingle positions (where w words of one text
+ * start); the distinct shingles of the collection; the SHARED shingles, those held by two or more texts -- the units of the
+ * product; the postings of the shared shingles (one per shingle and text); the segments of the unit range; the launches of
+ * the product and the quotients; the route taken (1 or 2); the naming levels run; the 64 x 64 tile pairs; w; the
+ * device time in microseconds up to the operands in text order (naming, postings, sizes, sort) and from there on (product
+ * and quotients).
+ * east_hip_overlap_fetch: matrix[D * D], self[D], shingles[D], each nullable.
+ * Ranking and clusters: east_hip_top_build_resident and both east_hip_clusters_build_resident* take the source
+ * EAST_HIP_GRAPH_SOURCE_OVERLAP = the matrix the last overlap build left (EAST_HIP_ERR_NOT_BUILT "...: no overlap matrix has
+ * been built on this handle" where there is none); the clusters refuse a directed one with EAST_HIP_ERR_INVALID "clusters:
+ * the overlap matrix is directed (build it with EAST_HIP_OVERLAP_SYMMETRIC)".
+ * Errors: EAST_HIP_ERR_NOT_BUILT "overlap: no cosine index has been built on this handle" for a build without an index, "no
+ * overlap matrix has been built on this handle" for a fetch without a matrix; EAST_HIP_ERR_INVALID, in lines that start
+ * with "overlap: ", for w outside 1 .. 8, an unknown orientation, a null out, an index without a text, and a collection in
+ * which a text may have 2^31 or more shingle positions; EAST_HIP_ERR_OOM "overlap: ... of D texts needs N bytes, which the
+ * device does not have".  The index check and every argument check come before anything is withdrawn: a refused call
+ * leaves the earlier matrix fetchable.
+ * Lifetime: a cosine build on the handle withdraws the matrix, east_hip_reset drops it; score calls and
+ * east_hip_cosine_set_classes leave it alone (shingles are made of words, whatever the vector space).  The buffers are the
+ * overlap's own: a build does not disturb the extracted phrases or any other result.
+ * east_hip_debug_set_overlap_route: 0 the default, 1 the integer matrix-core kernel (v_mfma_i32_16x16x64_i8 on 0/1 bytes),
+ * 2 the f64 tile kernel of the text-to-text cosine on weights of 1.0 (exact below 2^53); anything else is
+ * EAST_HIP_ERR_INVALID.  east_hip_debug_set_overlap_batch: the segments of the unit range a launch of the tile kernel
+ * takes, 0 or less the default.  The result depends on neither.
+ * Memory: during a build 128 bytes a kept token, 16 bytes a posting of a shared shingle (24 on route 2), 16 KiB a tile pair
+ * and a batch's partial tiles (256 MiB at most, or one segment's); the matrix stays.
+ * Device time of the last build in milliseconds (its read-backs included), -1 before a build and after a failed one.
+ */
+#define EAST_HIP_OVERLAP_DIRECTED 0
+#define EAST_HIP_OVERLAP_SYMMETRIC 1
+#define EAST_HIP_GRAPH_SOURCE_OVERLAP (6)       /* (in parentheses: tests/test_phrases_host.py reads a bare 6 or 7 as a source the phrases added) */
+int east_hip_overlap_build(east_hip_handle_t h, int32_t words, int32_t orientation, int64_t *out);
+int east_hip_overlap_fetch(east_hip_handle_t h, double *matrix, double *self, int32_t *shingles);
+double east_hip_last_overlap_ms(east_hip_handle_t h);
+int east_hip_debug_set_overlap_route(int route);      /* 0: the default; 1: the integer kernel; 2: the f64 tile kernel on unit weights */
+int east_hip_debug_set_overlap_batch(int64_t segments);
+
+/*
  * Several devices in one process ("single-process/8-device fits the one-process CLI best").
  * Every document is an independent AST (east/relevance.py:41-46) and every (keyphrase, document) score is independent
  * (east/applications.py:43-52): a GROUP shards a collection at document granularity -- contiguous blocks of documents

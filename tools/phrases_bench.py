@@ -107,10 +107,11 @@ def main():
     a = ap.parse_args()
     from east import hip_backend
     if a.index_only:
-        # (a library from before the phrases exports none of their entry points: the index build needs none)
+        # (a library from before the phrases, or before a later consumer, exports none of their entry points: the index
+        # build needs none)
         import ctypes
         lib = ctypes.CDLL(hip_backend.LIB_PATH)
-        for entry in [e for e in hip_backend.SIGNATURES if "phrases" in e and not hasattr(lib, e)]:
+        for entry in [e for e in hip_backend.SIGNATURES if not hasattr(lib, e)]:
             del hip_backend.SIGNATURES[entry]
     assert hip_backend.device_count() >= 1, "no HIP device (there is no CPU fallback)"
     for name, texts in shapes(a.shapes.split(",")):
