@@ -24,8 +24,8 @@
 //     converges --, comp[v] = the root of comp[v],
 //     and the roots and the roots not done are counted--> 8 bytes read back; the rounds end when at most one root is not done
 //   --clu_rank_kernel: the slot of an edge in the result IS the number of edges stronger than it, counted against tiles of
-//     256 slots in LDS (key = the order-preserving image of the double with the zeros folded, then (a, b)); the weight
-//     that comes back is S[a][b] read again, the upper triangle's own bytes.
+//     256 slots in LDS (key = the order-preserving image of the double with the zeros folded, then (a, b));
+//     the weight that comes back is S[a][b] read again, the upper triangle's own bytes.
 //
 // No atomic anywhere, only comparisons: two builds give the same bytes whatever the grid, the timing or the number of
 // rounds.  Three launches a round and one at the end; an uploaded matrix is checked for symmetry in one tiled pass first
@@ -34,7 +34,11 @@
 // The merges are fetched ONCE, at the end of the build, into the state: the cuts are a union-find over at most M - 1 merges
 // on the host, and the matrix is not needed again.
 //
-// Complete and average linkage share the state, the symmetry check, the fetch and the cuts; their rounds are linkage.h.
+// Complete and average linkage have their rounds in linkage.h, and the build entry points, which take any linkage, come
+// behind them there.  What the three share is in here once: the row maximum (clu_row_best) and the tile minimum
+// (clu_tile_min) under their kernels, the state, the frame of a build (ClustersBuild), clusters_first_bad and the cuts.
+// lnk_rank_kernel is clu_rank_kernel's counting with another tie word, written out a second time: as one template over the
+// slot the two compiled to other code, and clu_rank_kernel measured about 1 % slower in three forms of it.
 #pragma once
 #include "consumer.h"
 
@@ -44,7 +48,54 @@
 #define CLU_SYM_STRIDE 65u                 // doubles from one row of the turned tile to the next (top.h: TOP_LDS_STRIDE)
 #define CLU_MAX_M 0x7FFFFFF0u
 
+// ---- the strongest entry of a row ------------------------------------------------------------------------------------------
+struct CluBest {
+    double w;
+    u32 j;                                 // CLU_NONE: no column of the row may win
+};
+
+// A wavefront a row of M doubles, read once in whole 512-byte pieces with the members' words beside them, CLU_UNROLL of both
+// requested before the first comparison.  In: word(j), member j's word; no_w() and no_word(), what a lane past the row's end
+// holds; in(j, w, word): may column j win.  A lane meets its columns in ascending order, so it keeps what it has unless
+// w > best; the lanes are reduced by (w, j), the smaller column of two equal weights.  Every lane returns the row's result.
+template <class In> __device__ __forceinline__ CluBest clu_row_best(const double *__restrict__ row, u32 M, u32 lane, const In in)
+{
+    double best = 0.0;
+    u32 best_j = CLU_NONE;
+    for (u32 j0 = 0; j0 < M; j0 += 64u * CLU_UNROLL) {
+        double w[CLU_UNROLL];
+        u32 c[CLU_UNROLL];
+#pragma unroll
+        for (u32 i = 0; i < CLU_UNROLL; i++) {                    // (all loads requested before the first is used)
+            const u32 j = j0 + i * 64u + lane;
+            w[i] = j < M ? row[j] : in.no_w();
+            c[i] = j < M ? in.word(j) : in.no_word();
+        }
+#pragma unroll
+        for (u32 i = 0; i < CLU_UNROLL; i++) {
+            const u32 j = j0 + i * 64u + lane;
+            if (in(j, w[i], c[i]) && (best_j == CLU_NONE || w[i] > best)) { best = w[i]; best_j = j; }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double ow = __shfl_xor(best, off, WAVE);
+        const u32 oj = __shfl_xor(best_j, off, WAVE);
+        if (oj != CLU_NONE && (best_j == CLU_NONE || ow > best || (ow == best && oj < best_j))) { best = ow; best_j = oj; }
+    }
+    return CluBest{best, best_j};
+}
+
 // ---- the strongest edge of every member ----------------------------------------------------------------------------------
+struct CluEdgeIn {              // column j is an edge of a member of component cv: another component, and the weight no NaN
+    const u32 *__restrict__ comp;
+    u32 cv;
+    __device__ __forceinline__ u32 word(u32 j) const { return comp[j]; }
+    __device__ __forceinline__ double no_w() const { return __builtin_nan(""); }
+    __device__ __forceinline__ u32 no_word() const { return cv; }
+    __device__ __forceinline__ bool operator()(u32, double w, u32 c) const { return w == w && c != cv; }
+};
+
 __global__ __launch_bounds__(BLOCK) void clu_best_kernel(const double *__restrict__ S, u32 M, const u32 *__restrict__ comp,
                                                          const u32 *__restrict__ done, double *__restrict__ bw, u32 *__restrict__ bj)
 {
@@ -56,31 +107,8 @@ __global__ __launch_bounds__(BLOCK) void clu_best_kernel(const double *__restric
         if (lane == 0u) bj[v] = CLU_NONE;
         return;
     }
-    const double *row = S + (size_t)v * M;
-    double best = 0.0;
-    u32 best_j = CLU_NONE;
-    for (u32 j0 = 0; j0 < M; j0 += 64u * CLU_UNROLL) {
-        double w[CLU_UNROLL];
-        u32 c[CLU_UNROLL];
-#pragma unroll
-        for (u32 i = 0; i < CLU_UNROLL; i++) {                    // (all loads requested before the first is used)
-            const u32 j = j0 + i * 64u + lane;
-            w[i] = j < M ? row[j] : __builtin_nan("");
-            c[i] = j < M ? comp[j] : cv;
-        }
-#pragma unroll
-        for (u32 i = 0; i < CLU_UNROLL; i++) {
-            const bool edge = w[i] == w[i] && c[i] != cv;
-            if (edge && (best_j == CLU_NONE || w[i] > best)) { best = w[i]; best_j = j0 + i * 64u + lane; }
-        }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const double ow = __shfl_xor(best, off, WAVE);
-        const u32 oj = __shfl_xor(best_j, off, WAVE);
-        if (oj != CLU_NONE && (best_j == CLU_NONE || ow > best || (ow == best && oj < best_j))) { best = ow; best_j = oj; }
-    }
-    if (lane == 0u) { bw[v] = best; bj[v] = best_j; }
+    const CluBest best = clu_row_best(S + (size_t)v * M, M, lane, CluEdgeIn{comp, cv});
+    if (lane == 0u) { bw[v] = best.w; bj[v] = best.j; }
 }
 
 // ---- the strongest edge of every component ---------------------------------------------------------------------------------
@@ -219,14 +247,32 @@ __global__ __launch_bounds__(BLOCK) void clu_rank_kernel(const double *__restric
     }
 }
 
+// ---- the end of a pass over the NT x NT tiles of 64 x 64, a workgroup a tile ------------------------------------------------
+// bad[workgroup] = the smallest `worst` of its threads: a * M + b of the tile's first pair that is refused, or ~0
+__device__ __forceinline__ void clu_tile_min(u64 worst, u32 lane, u32 wv, u64 *__restrict__ bad)
+{
+    __shared__ u64 lds8[WAVES_PER_BLOCK];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const u64 o = __shfl_xor(worst, off, WAVE);
+        worst = o < worst ? o : worst;
+    }
+    if (lane == 0u) lds8[wv] = worst;
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        u64 m = lds8[0];
+        for (u32 k = 1; k < WAVES_PER_BLOCK; k++) m = lds8[k] < m ? lds8[k] : m;
+        bad[blockIdx.x] = m;
+    }
+}
+
 // ---- is an uploaded matrix symmetric? --------------------------------------------------------------------------------------
-// Workgroup (ti, tj) of the NT x NT tiles of 64 x 64, ti <= tj (the others leave at once): tile (ti, tj) against tile
-// (tj, ti), both read row-wise, the second turned in LDS.  bad[workgroup] = the smallest a * M + b, a < b, of the tile with
-// S[a][b] != S[b][a] and not both NaN, or ~0; the host takes the smallest over the tiles.
+// Workgroup (ti, tj) of the NT x NT tiles, ti <= tj (the others leave at once): tile (ti, tj) against tile (tj, ti), both
+// read row-wise, the second turned in LDS.  bad[workgroup] = the smallest a * M + b, a < b, of the tile with
+// S[a][b] != S[b][a] and not both NaN, or ~0 (clu_tile_min); the host takes the smallest over the tiles.
 __global__ __launch_bounds__(BLOCK) void clu_symmetry_kernel(const double *__restrict__ S, u32 M, u32 NT, u64 *__restrict__ bad)
 {
     __shared__ double turned[CLU_SYM_TILE * CLU_SYM_STRIDE];
-    __shared__ u64 lds8[WAVES_PER_BLOCK];
     const u32 ti = blockIdx.x / NT, tj = blockIdx.x % NT;
     if (ti > tj) {                                                // (the same for the whole workgroup: its mirror image does the work)
         if (threadIdx.x == 0u) bad[blockIdx.x] = ~0ull;
@@ -249,18 +295,7 @@ __global__ __launch_bounds__(BLOCK) void clu_symmetry_kernel(const double *__res
             if (!same && at < worst) worst = at;
         }
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const u64 o = __shfl_xor(worst, off, WAVE);
-        worst = o < worst ? o : worst;
-    }
-    if (lane == 0u) lds8[wv] = worst;
-    __syncthreads();
-    if (threadIdx.x == 0u) {
-        u64 m = lds8[0];
-        for (u32 k = 1; k < WAVES_PER_BLOCK; k++) m = lds8[k] < m ? lds8[k] : m;
-        bad[blockIdx.x] = m;
-    }
+    clu_tile_min(worst, lane, wv, bad);
 }
 
 // ============================================================================================================ host ==
@@ -272,36 +307,73 @@ struct ClustersState : Consumer {
     UploadedTable table;                    // a host matrix's copy (east_hip_clusters_build_host)
     DevBuf work;
     DevBuf wcopy;                           // the working copy of a complete or average linkage build, released after it (linkage.h)
-    std::vector<int32_t> merge_a, merge_b;  // the forest, strongest first
+    std::vector<int32_t> merge_a, merge_b;  // the merges, strongest first
     std::vector<double> merge_w;
     ClustersState() { bufs = {&table.buf, &work, &wcopy}; }
-    void clear() override
+    ClustersState &clear_result()           // what a build leaves; the uploaded matrix, which it may be reading, stays
     {
         M = 0;
         rounds = launches = 0;
-        table.withdraw();
         merge_a.clear();
         merge_b.clear();
         merge_w.clear();
+        return *this;
+    }
+    void clear() override { clear_result().table.withdraw(); }
+};
+
+// The frame of a build, whatever the linkage.  The opening: the last result withdrawn and cleared, the timer started.
+struct ClustersBuild {
+    east_hip_index *h;
+    ClustersState &g;
+    ConsumerTimer timer;
+    explicit ClustersBuild(east_hip_index *h_) : h(h_), g(consumer_begin<ClustersState>(h_).clear_result()), timer(h_, g) {}
+    void fetch_merges(u32 F, const int32_t *ma, const int32_t *mb, const double *mw)
+    {
+        g.merge_a.resize(F);
+        g.merge_b.resize(F);
+        g.merge_w.resize(F);
+        HIP_CHECK(hipMemcpyAsync(g.merge_a.data(), ma, (size_t)F * 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipMemcpyAsync(g.merge_b.data(), mb, (size_t)F * 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipMemcpyAsync(g.merge_w.data(), mw, (size_t)F * 8, hipMemcpyDeviceToHost, h->stream));
+    }
+    // The closing: the stream drained and timed, the result valid.
+    void close(u32 M, u32 F, i64 *out)
+    {
+        timer.finish();
+        g.M = M;
+        g.valid = true;
+        if (out) { out[0] = (i64)M; out[1] = (i64)F; out[2] = g.rounds; out[3] = g.launches; }
     }
 };
+
+// NT of a pass over the NT x NT tiles of M members, a workgroup a tile.
+static u32 clusters_tiles(u32 M)
+{
+    const u32 NT = ceil_div_u32(M, CLU_SYM_TILE);
+    if ((u64)NT * NT >= (u64)0x7FFFFFF0u) east_throw(EAST_HIP_ERR_INVALID, "clusters: more tiles than one launch takes");
+    return NT;
+}
+
+// What such a pass found: the smallest of bad[tiles], a * M + b of the first refused pair in row-major order, or ~0.
+static u64 clusters_first_bad(east_hip_index *h, const u64 *bad, u32 tiles)
+{
+    std::vector<u64> host(tiles);
+    HIP_CHECK(hipMemcpyAsync(host.data(), bad, (size_t)tiles * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    return *std::min_element(host.begin(), host.end());
+}
 
 // An uploaded matrix: EAST_HIP_ERR_INVALID naming the first pair (in row-major order) that is not symmetric.
 static void clusters_check_symmetry(east_hip_index *h, ClustersState &g, const double *S, u32 M)
 {
-    const u32 NT = ceil_div_u32(M, CLU_SYM_TILE);
-    const u64 tiles = (u64)NT * NT;
-    if (tiles >= (u64)0x7FFFFFF0u) east_throw(EAST_HIP_ERR_INVALID, "clusters: more tiles than one launch takes");
+    const u32 NT = clusters_tiles(M), tiles = NT * NT;
     g.work.ensure((size_t)tiles * 8 + 256, "the clusters' symmetry check", h->stream);
     u64 *bad = g.work.as<u64>();
     Ctx ctx = handle_ctx(h);
-    LAUNCH(ctx, clu_symmetry_kernel, (u32)tiles, S, M, NT, bad);
+    LAUNCH(ctx, clu_symmetry_kernel, tiles, S, M, NT, bad);
     g.launches++;
-    std::vector<u64> host((size_t)tiles);
-    HIP_CHECK(hipMemcpyAsync(host.data(), bad, (size_t)tiles * 8, hipMemcpyDeviceToHost, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
-    u64 worst = ~0ull;
-    for (u64 x : host) worst = std::min(worst, x);
+    const u64 worst = clusters_first_bad(h, bad, tiles);
     if (worst != ~0ull) {
         char msg[200];
         snprintf(msg, sizeof(msg), "clusters: the matrix is not symmetric: S[%llu][%llu] differs from S[%llu][%llu]", (unsigned long long)(worst / M),
@@ -313,67 +385,52 @@ static void clusters_check_symmetry(east_hip_index *h, ClustersState &g, const d
 // S: M x M doubles on the handle's device, symmetric (checked first when it is the caller's).
 static void clusters_build(east_hip_index *h, const double *S, u32 M, bool check, i64 *out)
 {
-    ClustersState &g = consumer_begin<ClustersState>(h);
-    g.M = 0;
-    g.rounds = g.launches = 0;
-    g.merge_a.clear();
-    g.merge_b.clear();
-    g.merge_w.clear();
-    u32 F = 0;
-    ConsumerTimer timer(h, g);
-    if (M >= 2) {
-        if (check) clusters_check_symmetry(h, g, S, M);
-        // 12 arrays of 4 bytes a member, 4 of 8, the read-back words
-        const size_t bytes = 12 * align256((size_t)M * 4) + 4 * align256((size_t)M * 8) + 2 * 256;
-        if (!g.work.try_ensure(bytes, h->stream)) {
-            char msg[200];
-            snprintf(msg, sizeof(msg), "clusters: the work arrays of %u members need %zu bytes, which the device does not have", M, bytes);
-            east_throw(EAST_HIP_ERR_OOM, msg);
-        }
-        Arena a = g.work.arena();
-        u32 *comp = a.alloc<u32>(M), *done = a.alloc<u32>(M), *bj = a.alloc<u32>(M), *clo = a.alloc<u32>(M), *chi = a.alloc<u32>(M),
-            *tgt = a.alloc<u32>(M), *p0 = a.alloc<u32>(M), *p1 = a.alloc<u32>(M), *ea = a.alloc<u32>(M), *eb = a.alloc<u32>(M);
-        int32_t *ma = a.alloc<int32_t>(M), *mb = a.alloc<int32_t>(M);
-        double *bw = a.alloc<double>(M), *cw = a.alloc<double>(M), *mw = a.alloc<double>(M);
-        u64 *ekey = a.alloc<u64>(M);
-        u32 *info = a.alloc<u32>(2);
-        std::vector<u32> ident(M);
-        for (u32 v = 0; v < M; v++) ident[v] = v;
-        HIP_CHECK(hipMemcpyAsync(comp, ident.data(), (size_t)M * 4, hipMemcpyHostToDevice, h->stream));
-        HIP_CHECK(hipMemsetAsync(done, 0, (size_t)M * 4, h->stream));
-        HIP_CHECK(hipMemsetAsync(ea, 0xFF, (size_t)M * 4, h->stream));
-        Ctx ctx = handle_ctx(h);
-        const u32 wave_grid = ceil_div_u32(M, WAVES_PER_BLOCK);
-        u32 host_info[2] = {M, M};
-        // (a round at least halves the roots that are not done, and one more may find that those left have no edge)
-        const i64 most = bit_width_u32(M) + 2;
-        while (host_info[1] > 1u) {
-            if (g.rounds >= most) east_throw(EAST_HIP_ERR_INTERNAL, "clusters: the rounds do not end");
-            LAUNCH(ctx, clu_best_kernel, wave_grid, S, M, (const u32 *)comp, (const u32 *)done, bw, bj);
-            LAUNCH(ctx, clu_pick_kernel, wave_grid, M, (const u32 *)comp, (const double *)bw, (const u32 *)bj, done, cw, clo, chi, tgt);
-            LAUNCH(ctx, clu_merge_kernel, 1, M, comp, (const u32 *)done, (const double *)cw, (const u32 *)clo, (const u32 *)chi,
-                   (const u32 *)tgt, p0, p1, ekey, ea, eb, info);
-            HIP_CHECK(hipMemcpyAsync(host_info, info, 8, hipMemcpyDeviceToHost, h->stream));
-            HIP_CHECK(hipStreamSynchronize(h->stream));
-            g.rounds++;
-            g.launches += 3;
-        }
-        F = M - host_info[0];
-        if (F) {
-            LAUNCH(ctx, clu_rank_kernel, ceil_div_u32(M, 64), S, M, (const u64 *)ekey, (const u32 *)ea, (const u32 *)eb, ma, mb, mw);
-            g.launches++;
-            g.merge_a.resize(F);
-            g.merge_b.resize(F);
-            g.merge_w.resize(F);
-            HIP_CHECK(hipMemcpyAsync(g.merge_a.data(), ma, (size_t)F * 4, hipMemcpyDeviceToHost, h->stream));
-            HIP_CHECK(hipMemcpyAsync(g.merge_b.data(), mb, (size_t)F * 4, hipMemcpyDeviceToHost, h->stream));
-            HIP_CHECK(hipMemcpyAsync(g.merge_w.data(), mw, (size_t)F * 8, hipMemcpyDeviceToHost, h->stream));
-        }
+    ClustersBuild b(h);
+    ClustersState &g = b.g;
+    if (M < 2) return b.close(M, 0, out);
+    if (check) clusters_check_symmetry(h, g, S, M);
+    // 12 arrays of 4 bytes a member, 4 of 8, the read-back words
+    const size_t bytes = 12 * align256((size_t)M * 4) + 4 * align256((size_t)M * 8) + 2 * 256;
+    if (!g.work.try_ensure(bytes, h->stream)) {
+        char msg[200];
+        snprintf(msg, sizeof(msg), "clusters: the work arrays of %u members need %zu bytes, which the device does not have", M, bytes);
+        east_throw(EAST_HIP_ERR_OOM, msg);
     }
-    timer.finish();
-    g.M = M;
-    g.valid = true;
-    if (out) { out[0] = (i64)M; out[1] = (i64)F; out[2] = g.rounds; out[3] = g.launches; }
+    Arena a = g.work.arena();
+    u32 *comp = a.alloc<u32>(M), *done = a.alloc<u32>(M), *bj = a.alloc<u32>(M), *clo = a.alloc<u32>(M), *chi = a.alloc<u32>(M),
+        *tgt = a.alloc<u32>(M), *p0 = a.alloc<u32>(M), *p1 = a.alloc<u32>(M), *ea = a.alloc<u32>(M), *eb = a.alloc<u32>(M);
+    int32_t *ma = a.alloc<int32_t>(M), *mb = a.alloc<int32_t>(M);
+    double *bw = a.alloc<double>(M), *cw = a.alloc<double>(M), *mw = a.alloc<double>(M);
+    u64 *ekey = a.alloc<u64>(M);
+    u32 *info = a.alloc<u32>(2);
+    std::vector<u32> ident(M);
+    for (u32 v = 0; v < M; v++) ident[v] = v;
+    HIP_CHECK(hipMemcpyAsync(comp, ident.data(), (size_t)M * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(hipMemsetAsync(done, 0, (size_t)M * 4, h->stream));
+    HIP_CHECK(hipMemsetAsync(ea, 0xFF, (size_t)M * 4, h->stream));
+    Ctx ctx = handle_ctx(h);
+    const u32 wave_grid = ceil_div_u32(M, WAVES_PER_BLOCK);
+    u32 host_info[2] = {M, M};
+    // (a round at least halves the roots that are not done, and one more may find that those left have no edge)
+    const i64 most = bit_width_u32(M) + 2;
+    while (host_info[1] > 1u) {
+        if (g.rounds >= most) east_throw(EAST_HIP_ERR_INTERNAL, "clusters: the rounds do not end");
+        LAUNCH(ctx, clu_best_kernel, wave_grid, S, M, (const u32 *)comp, (const u32 *)done, bw, bj);
+        LAUNCH(ctx, clu_pick_kernel, wave_grid, M, (const u32 *)comp, (const double *)bw, (const u32 *)bj, done, cw, clo, chi, tgt);
+        LAUNCH(ctx, clu_merge_kernel, 1, M, comp, (const u32 *)done, (const double *)cw, (const u32 *)clo, (const u32 *)chi,
+               (const u32 *)tgt, p0, p1, ekey, ea, eb, info);
+        HIP_CHECK(hipMemcpyAsync(host_info, info, 8, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+        g.rounds++;
+        g.launches += 3;
+    }
+    const u32 F = M - host_info[0];
+    if (F) {
+        LAUNCH(ctx, clu_rank_kernel, ceil_div_u32(M, 64), S, M, (const u64 *)ekey, (const u32 *)ea, (const u32 *)eb, ma, mb, mw);
+        g.launches++;
+        b.fetch_merges(F, ma, mb, mw);
+    }
+    b.close(M, F, out);
 }
 
 // labels[v] = the smallest member of v's cluster after the first n_merges merges
@@ -400,44 +457,6 @@ static const ClustersState &clusters_built(east_hip_index *h)
 }
 
 extern "C" {
-
-int east_hip_clusters_build_resident(east_hip_handle_t h, int32_t source, int64_t *out)
-{
-    return guarded([&] {
-        if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
-        if (source != EAST_HIP_GRAPH_SOURCE_SIMILARITY && source != EAST_HIP_GRAPH_SOURCE_RELATED &&
-            source != EAST_HIP_GRAPH_SOURCE_COSINE_TEXTS && source != EAST_HIP_GRAPH_SOURCE_OVERLAP && source != EAST_HIP_GRAPH_SOURCE_UPLOADED)
-            east_throw(EAST_HIP_ERR_INVALID, "clusters: the source is not a square matrix of members");
-        const TableRef t = consumer_resident<ClustersState>(h, source, "clusters", true);
-        if (t.directed)
-            east_throw(EAST_HIP_ERR_INVALID, source == EAST_HIP_GRAPH_SOURCE_OVERLAP
-                                                 ? "clusters: the overlap matrix is directed (build it with EAST_HIP_OVERLAP_SYMMETRIC)"
-                                                 : "clusters: the relatedness matrix is directed (build it with EAST_HIP_RELATED_SYMMETRIC)");
-        if (t.K != t.D) east_throw(EAST_HIP_ERR_INTERNAL, "clusters: the source matrix is not square");
-        clusters_build(h, t.p, t.K, false, out);
-    });
-}
-
-int east_hip_clusters_build_host(east_hip_handle_t h, const double *matrix, int32_t m, int64_t *out)
-{
-    return guarded([&] {
-        if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
-        if (m < 0 || (u32)m >= CLU_MAX_M || (m > 0 && !matrix)) east_throw(EAST_HIP_ERR_INVALID, "clusters: null matrix or bad size");
-        if (m == 0) {                                             // (no members: nothing to upload, and no uploaded matrix left)
-            use_device(h);
-            consumer_begin<ClustersState>(h).table.withdraw();
-            clusters_build(h, nullptr, 0, false, out);
-            return;
-        }
-        const TableRef t = consumer_upload<ClustersState>(h, matrix, m, m, "clusters: null matrix or bad size", "the clusters' matrix", [] {});
-        try {
-            clusters_build(h, t.p, t.K, true, out);
-        } catch (...) {
-            consumer_peek<ClustersState>(h)->table.withdraw();   // (a matrix that was refused is no source either)
-            throw;
-        }
-    });
-}
 
 int east_hip_clusters_fetch(east_hip_handle_t h, int32_t *merge_a, int32_t *merge_b, double *merge_w)
 {

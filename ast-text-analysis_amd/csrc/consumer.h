@@ -5,7 +5,8 @@
 // the state and its lifetime, the timer, the front of every entry point (consumer_begin, consumer_built, the two halves
 // of a *_build_resident / *_build_host pair), the table a source names (resolve_table), the M x M matrix of the consumers
 // that produce one (MatrixConsumer) and the count-scan-fill of a list of unknown length.  Nothing in here knows one
-// consumer from another but the table of sources in resolve_table ("The consumer frame").
+// consumer from another but OFFERED, the table of sources behind resolve_table and consumer_resident_square ("The
+// consumer frame").
 #pragma once
 #include "handle.h"
 #include "scan.h"
@@ -127,19 +128,22 @@ struct UploadedTable {
 };
 
 // ---- which table a *_build_resident call reads ----------------------------------------------------------------------------
+// What a consumer offers(), a row a source.  matrix: a square matrix of members (the similarity's, the relatedness', the
+// text-to-text cosine's, the shingle overlap's); directed: what a consumer of symmetric matrices says of its directed form.
+static const struct Offered { int32_t source; int slot; bool matrix; const char *missing, *directed; } OFFERED[] = {
+    {EAST_HIP_GRAPH_SOURCE_COSINE, east_hip_index::SLOT_COS, false, ": no cosine score table is resident (score the keyphrases first)", nullptr},
+    {EAST_HIP_GRAPH_SOURCE_SIMILARITY, east_hip_index::SLOT_SIM, true, ": no similarity matrix has been built on this handle", nullptr},
+    {EAST_HIP_GRAPH_SOURCE_RELATED, east_hip_index::SLOT_REL, true, ": no relatedness matrix has been built on this handle",
+     ": the relatedness matrix is directed (build it with EAST_HIP_RELATED_SYMMETRIC)"},
+    {EAST_HIP_GRAPH_SOURCE_COSINE_TEXTS, east_hip_index::SLOT_COSTEXT, true, ": no text similarity matrix has been built on this handle", nullptr},
+    {EAST_HIP_GRAPH_SOURCE_OVERLAP, east_hip_index::SLOT_OVL, true, ": no overlap matrix has been built on this handle",
+     ": the overlap matrix is directed (build it with EAST_HIP_OVERLAP_SYMMETRIC)"},
+};
+
 // who: the consumer's name in front of its messages; own: the caller's uploaded copy (nullptr before its first call);
-// matrices_ok: the square matrices other consumers built -- the similarity's, the relatedness', the text-to-text cosine's,
-// the shingle overlap's --
-// are sources too (the ranking and the clusters).
+// matrices_ok: the square matrices other consumers built are sources too (the ranking and the clusters).
 static TableRef resolve_table(const east_hip_index *h, int32_t source, const UploadedTable *own, const char *who, bool matrices_ok = false)
 {
-    static const struct { int32_t source; int slot; bool matrix; const char *missing; } OFFERED[] = {       // what a consumer offers()
-        {EAST_HIP_GRAPH_SOURCE_COSINE, east_hip_index::SLOT_COS, false, ": no cosine score table is resident (score the keyphrases first)"},
-        {EAST_HIP_GRAPH_SOURCE_SIMILARITY, east_hip_index::SLOT_SIM, true, ": no similarity matrix has been built on this handle"},
-        {EAST_HIP_GRAPH_SOURCE_RELATED, east_hip_index::SLOT_REL, true, ": no relatedness matrix has been built on this handle"},
-        {EAST_HIP_GRAPH_SOURCE_COSINE_TEXTS, east_hip_index::SLOT_COSTEXT, true, ": no text similarity matrix has been built on this handle"},
-        {EAST_HIP_GRAPH_SOURCE_OVERLAP, east_hip_index::SLOT_OVL, true, ": no overlap matrix has been built on this handle"},
-    };
     TableRef t;
     const char *missing = nullptr;
     if (source == EAST_HIP_GRAPH_SOURCE_AST) {
@@ -149,7 +153,7 @@ static TableRef resolve_table(const east_hip_index *h, int32_t source, const Upl
         if (own) t = own->ref();
         missing = ": no host table has been uploaded to this handle";
     }
-    for (const auto &o : OFFERED)
+    for (const Offered &o : OFFERED)
         if (o.source == source && (matrices_ok || !o.matrix)) {
             if (h->consumers[o.slot]) t = h->consumers[o.slot]->offers();
             missing = o.missing;
@@ -167,6 +171,22 @@ template <class T> static TableRef consumer_resident(east_hip_index *h, int32_t 
     use_device(h);
     const T *g = consumer_peek<T>(h);
     return resolve_table(h, source, g ? &g->table : nullptr, who, matrices_ok);
+}
+
+// The resident half of a consumer that takes only symmetric square matrices of members (the clusters): any other source is
+// refused before anything is resolved, a directed matrix in its row's own words.
+template <class T> static TableRef consumer_resident_square(east_hip_index *h, int32_t source, const char *who)
+{
+    const Offered *row = nullptr;
+    for (const Offered &o : OFFERED)
+        if (o.source == source && o.matrix) row = &o;
+    if (!row && source != EAST_HIP_GRAPH_SOURCE_UPLOADED)
+        east_throw(EAST_HIP_ERR_INVALID, std::string(who) + ": the source is not a square matrix of members");
+    const TableRef t = consumer_resident<T>(h, source, who, true);
+    if (t.directed && !(row && row->directed)) east_throw(EAST_HIP_ERR_INTERNAL, std::string(who) + ": OFFERED[] has no words for this directed matrix");
+    if (t.directed) east_throw(EAST_HIP_ERR_INVALID, std::string(who) + row->directed);
+    if (t.K != t.D) east_throw(EAST_HIP_ERR_INTERNAL, std::string(who) + ": the source matrix is not square");
+    return t;
 }
 
 // The host half: the host table's copy on the device, T's last result withdrawn.  empty: the message for no table; check()

@@ -11,8 +11,8 @@
 //   clu_symmetry_kernel reports its pair).  W is symmetric BYTE FOR BYTE from then on, so a kernel may read W[x][y] from
 //   whichever row is convenient.  alive[v] = 1, size[v] = 1.
 //   a round:
-//   --lnk_best_kernel: clu_best_kernel's loop (a wavefront a row, whole 512-byte pieces, CLU_UNROLL of them in flight)
-//     over the alive rows, alive[] read beside the row; dead rows and dead columns are skipped--> nw[u], nn[u]
+//   --lnk_best_kernel: clu_row_best (a wavefront a row, whole 512-byte pieces, CLU_UNROLL of them in flight) over the alive
+//     rows, alive[] read beside the row; dead rows and dead columns are skipped--> nw[u], nn[u]
 //   --lnk_pair_kernel, ONE workgroup, a thread a cluster: x and y = nn[x] are a pair when nn[y] == x and the weight reaches
 //     the floor; every thread writes its OWN entries only (partner[x], alive[x], the new size[x]), and the larger end
 //     records the merge in ITS slot of an M-slot list -- a representative dies once: no counter, no scan (clu_merge_kernel's
@@ -27,6 +27,8 @@
 // LW is computed in ONE orientation, that of the pair (u, v) with u < v: first over v's columns, then over u's rows,
 // whichever of the two rows the lane works for.  Comparisons, two products, a sum and a quotient of doubles (the build has
 // -ffp-contract=off; the pragma below says so again): no atomic, the same bytes whatever the grid or the timing.
+// The state and the frame of a build are clusters.h's; the build entry points, which take any linkage, are at the end of
+// this file, behind linkage_build.
 #pragma once
 #include "clusters.h"
 
@@ -46,12 +48,11 @@ __device__ __forceinline__ double lnk_lw(bool average, double x, double y, doubl
 
 // ---- the working copy, and the values the linkage does not take ------------------------------------------------------------
 // Workgroup (ti, tj) of the NT x NT tiles of 64 x 64, ti <= tj (the others leave at once).  bad[workgroup] = the smallest
-// a * M + b, a < b, of the tile whose S[a][b] is refused, or ~0.  The diagonal gets S's own diagonal: nobody reads it.
+// a * M + b, a < b, of the tile whose S[a][b] is refused, or ~0 (clu_tile_min).  The diagonal gets S's own diagonal: nobody reads it.
 __global__ __launch_bounds__(BLOCK) void lnk_copy_kernel(const double *__restrict__ S, double *__restrict__ W, u32 M, u32 NT, u32 average,
                                                          u64 *__restrict__ bad)
 {
     __shared__ double turned[CLU_SYM_TILE * CLU_SYM_STRIDE];
-    __shared__ u64 lds8[WAVES_PER_BLOCK];
     const u32 ti = blockIdx.x / NT, tj = blockIdx.x % NT;
     if (ti > tj) {                                                // (the same for the whole workgroup)
         if (threadIdx.x == 0u) bad[blockIdx.x] = ~0ull;
@@ -79,23 +80,19 @@ __global__ __launch_bounds__(BLOCK) void lnk_copy_kernel(const double *__restric
         const u32 ma = c0 + r, mb = r0 + lane;                    // the mirror tile: rows c0 .., columns r0 ..
         if (ti < tj && ma < M && mb < M) W[(size_t)ma * M + mb] = down;
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const u64 o = __shfl_xor(worst, off, WAVE);
-        worst = o < worst ? o : worst;
-    }
-    if (lane == 0u) lds8[wv] = worst;
-    __syncthreads();
-    if (threadIdx.x == 0u) {
-        u64 m = lds8[0];
-        for (u32 k = 1; k < WAVES_PER_BLOCK; k++) m = lds8[k] < m ? lds8[k] : m;
-        bad[blockIdx.x] = m;
-    }
+    clu_tile_min(worst, lane, wv, bad);
 }
 
 // ---- the strongest neighbour of every alive cluster -----------------------------------------------------------------------
-// Among the pairs of ONE cluster the stronger of two equal weights is the one with the smaller other end, whichever side of
-// u it is on (clu_best_kernel): a lane that meets its columns in ascending order keeps what it has unless w > best.
+struct LnkPairIn {              // column j is a neighbour of cluster u: alive, and not u itself
+    const u32 *__restrict__ alive;
+    u32 u;
+    __device__ __forceinline__ u32 word(u32 j) const { return alive[j]; }
+    __device__ __forceinline__ double no_w() const { return 0.0; }
+    __device__ __forceinline__ u32 no_word() const { return 0u; }
+    __device__ __forceinline__ bool operator()(u32 j, double, u32 a) const { return a != 0u && j != u; }
+};
+
 __global__ __launch_bounds__(BLOCK) void lnk_best_kernel(const double *__restrict__ W, u32 M, const u32 *__restrict__ alive,
                                                          double *__restrict__ nw, u32 *__restrict__ nn)
 {
@@ -106,32 +103,8 @@ __global__ __launch_bounds__(BLOCK) void lnk_best_kernel(const double *__restric
         if (lane == 0u) nn[u] = CLU_NONE;
         return;
     }
-    const double *row = W + (size_t)u * M;
-    double best = 0.0;
-    u32 best_j = CLU_NONE;
-    for (u32 j0 = 0; j0 < M; j0 += 64u * CLU_UNROLL) {
-        double w[CLU_UNROLL];
-        u32 c[CLU_UNROLL];
-#pragma unroll
-        for (u32 i = 0; i < CLU_UNROLL; i++) {                    // (all loads requested before the first is used)
-            const u32 j = j0 + i * 64u + lane;
-            w[i] = j < M ? row[j] : 0.0;
-            c[i] = j < M ? alive[j] : 0u;
-        }
-#pragma unroll
-        for (u32 i = 0; i < CLU_UNROLL; i++) {
-            const u32 j = j0 + i * 64u + lane;
-            const bool pair = c[i] != 0u && j != u;
-            if (pair && (best_j == CLU_NONE || w[i] > best)) { best = w[i]; best_j = j; }
-        }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const double ow = __shfl_xor(best, off, WAVE);
-        const u32 oj = __shfl_xor(best_j, off, WAVE);
-        if (oj != CLU_NONE && (best_j == CLU_NONE || ow > best || (ow == best && oj < best_j))) { best = ow; best_j = oj; }
-    }
-    if (lane == 0u) { nw[u] = best; nn[u] = best_j; }
+    const CluBest best = clu_row_best(W + (size_t)u * M, M, lane, LnkPairIn{alive, u});
+    if (lane == 0u) { nw[u] = best.w; nn[u] = best.j; }
 }
 
 // ---- the reciprocal pairs: one workgroup ------------------------------------------------------------------------------------
@@ -262,100 +235,76 @@ struct LinkageCopyGuard {                   // the working copy goes when the bu
 // S: M x M doubles on the handle's device, symmetric (checked first when it is the caller's); complete or average.
 static void linkage_build(east_hip_index *h, const double *S, u32 M, bool check, int32_t linkage, double floor, i64 *out)
 {
-    ClustersState &g = consumer_begin<ClustersState>(h);
-    g.M = 0;
-    g.rounds = g.launches = 0;
-    g.merge_a.clear();
-    g.merge_b.clear();
-    g.merge_w.clear();
+    ClustersBuild b(h);
+    ClustersState &g = b.g;
+    if (M < 2) return b.close(M, 0, out);
     const bool average = linkage == EAST_HIP_LINKAGE_AVERAGE;
-    u32 F = 0;
-    ConsumerTimer timer(h, g);
-    if (M >= 2) {
-        if (check) clusters_check_symmetry(h, g, S, M);
-        const u32 NT = ceil_div_u32(M, CLU_SYM_TILE);
-        const u64 tiles = (u64)NT * NT;
-        if (tiles >= (u64)0x7FFFFFF0u) east_throw(EAST_HIP_ERR_INVALID, "clusters: more tiles than one launch takes");
-        LinkageCopyGuard guard{g.wcopy};
-        const size_t copy_bytes = align256((size_t)M * M * 8) + align256((size_t)tiles * 8) + 256;
-        // 10 arrays of 4 bytes a member, 3 of 8, the read-back words
-        const size_t bytes = 10 * align256((size_t)M * 4) + 3 * align256((size_t)M * 8) + 2 * 256;
-        if (!g.wcopy.try_ensure(copy_bytes, h->stream) || !g.work.try_ensure(bytes, h->stream)) {
-            char msg[200];
-            snprintf(msg, sizeof(msg), "clusters: the working copy of %u members needs %zu bytes, which the device does not have", M,
-                     copy_bytes + bytes);
-            east_throw(EAST_HIP_ERR_OOM, msg);
-        }
-        Arena wa = g.wcopy.arena();
-        double *W = wa.alloc<double>((size_t)M * M);
-        u64 *bad = wa.alloc<u64>((size_t)tiles);
-        Ctx ctx = handle_ctx(h);
-        LAUNCH(ctx, lnk_copy_kernel, (u32)tiles, S, W, M, NT, average ? 1u : 0u, bad);
-        g.launches++;
-        {
-            std::vector<u64> host((size_t)tiles);
-            HIP_CHECK(hipMemcpyAsync(host.data(), bad, (size_t)tiles * 8, hipMemcpyDeviceToHost, h->stream));
-            HIP_CHECK(hipStreamSynchronize(h->stream));
-            u64 worst = ~0ull;
-            for (u64 x : host) worst = std::min(worst, x);
-            if (worst != ~0ull) {
-                char msg[200];
-                snprintf(msg, sizeof(msg), "clusters: S[%llu][%llu] is %s: %s linkage takes no such similarity", (unsigned long long)(worst / M),
-                         (unsigned long long)(worst % M), average ? "not finite" : "a NaN", average ? "average" : "complete");
-                east_throw(EAST_HIP_ERR_INVALID, msg);
-            }
-        }
-        Arena a = g.work.arena();
-        u32 *alive = a.alloc<u32>(M), *nn = a.alloc<u32>(M), *partner = a.alloc<u32>(M), *size0 = a.alloc<u32>(M), *size1 = a.alloc<u32>(M),
-            *ea = a.alloc<u32>(M), *eb = a.alloc<u32>(M), *ernd = a.alloc<u32>(M);
-        int32_t *ma = a.alloc<int32_t>(M), *mb = a.alloc<int32_t>(M);
-        double *nw = a.alloc<double>(M), *ew = a.alloc<double>(M), *mw = a.alloc<double>(M);
-        u32 *info = a.alloc<u32>(2);
-        std::vector<u32> ones(M, 1u);
-        HIP_CHECK(hipMemcpyAsync(alive, ones.data(), (size_t)M * 4, hipMemcpyHostToDevice, h->stream));
-        HIP_CHECK(hipMemcpyAsync(size0, ones.data(), (size_t)M * 4, hipMemcpyHostToDevice, h->stream));
-        HIP_CHECK(hipMemsetAsync(ea, 0xFF, (size_t)M * 4, h->stream));
-        const u32 wave_grid = ceil_div_u32(M, WAVES_PER_BLOCK);
-        const double fl = floor != floor ? LNK_NO_FLOOR : floor;
-        u32 host_info[2] = {0u, M};
-        u32 *size_in = size0, *size_out = size1;
-        // Three launches and one read-back a round.  The read-back stands between the pairing and the update, so a round that
-        // finds no pair at the floor launches no update; the next round's pick queues behind the update without a wait.
-        while (host_info[1] > 1u) {
-            if (g.rounds >= (i64)M) east_throw(EAST_HIP_ERR_INTERNAL, "clusters: the rounds do not end");
-            LAUNCH(ctx, lnk_best_kernel, wave_grid, (const double *)W, M, (const u32 *)alive, nw, nn);
-            LAUNCH(ctx, lnk_pair_kernel, 1, M, (u32)g.rounds, fl, alive, (const u32 *)nn, (const double *)nw, (const u32 *)size_in, size_out,
-                   partner, ea, eb, ew, ernd, info);
-            HIP_CHECK(hipMemcpyAsync(host_info, info, 8, hipMemcpyDeviceToHost, h->stream));
-            HIP_CHECK(hipStreamSynchronize(h->stream));
-            g.launches += 2;
-            if (!host_info[0]) break;                             // no pair reaches the floor: that round merged nothing and is not counted
-            LAUNCH(ctx, lnk_update_kernel, wave_grid, W, M, average ? 1u : 0u, (const u32 *)alive, (const u32 *)partner, (const u32 *)size_in);
-            g.launches++;
-            g.rounds++;
-            std::swap(size_in, size_out);
-        }
-        F = M - host_info[1];
-        if (F) {
-            LAUNCH(ctx, lnk_rank_kernel, ceil_div_u32(M, 64), M, (const u32 *)ea, (const u32 *)eb, (const double *)ew, (const u32 *)ernd, ma, mb, mw);
-            g.launches++;
-            g.merge_a.resize(F);
-            g.merge_b.resize(F);
-            g.merge_w.resize(F);
-            HIP_CHECK(hipMemcpyAsync(g.merge_a.data(), ma, (size_t)F * 4, hipMemcpyDeviceToHost, h->stream));
-            HIP_CHECK(hipMemcpyAsync(g.merge_b.data(), mb, (size_t)F * 4, hipMemcpyDeviceToHost, h->stream));
-            HIP_CHECK(hipMemcpyAsync(g.merge_w.data(), mw, (size_t)F * 8, hipMemcpyDeviceToHost, h->stream));
-        }
-        timer.finish();                                           // (before the guard frees the copy the launches read)
-    } else {
-        timer.finish();
+    if (check) clusters_check_symmetry(h, g, S, M);
+    const u32 NT = clusters_tiles(M), tiles = NT * NT;
+    LinkageCopyGuard guard{g.wcopy};
+    const size_t copy_bytes = align256((size_t)M * M * 8) + align256((size_t)tiles * 8) + 256;
+    // 10 arrays of 4 bytes a member, 3 of 8, the read-back words
+    const size_t bytes = 10 * align256((size_t)M * 4) + 3 * align256((size_t)M * 8) + 2 * 256;
+    if (!g.wcopy.try_ensure(copy_bytes, h->stream) || !g.work.try_ensure(bytes, h->stream)) {
+        char msg[200];
+        snprintf(msg, sizeof(msg), "clusters: the working copy of %u members needs %zu bytes, which the device does not have", M,
+                 copy_bytes + bytes);
+        east_throw(EAST_HIP_ERR_OOM, msg);
     }
-    g.M = M;
-    g.valid = true;
-    if (out) { out[0] = (i64)M; out[1] = (i64)F; out[2] = g.rounds; out[3] = g.launches; }
+    Arena wa = g.wcopy.arena();
+    double *W = wa.alloc<double>((size_t)M * M);
+    u64 *bad = wa.alloc<u64>(tiles);
+    Ctx ctx = handle_ctx(h);
+    LAUNCH(ctx, lnk_copy_kernel, tiles, S, W, M, NT, average ? 1u : 0u, bad);
+    g.launches++;
+    const u64 worst = clusters_first_bad(h, bad, tiles);
+    if (worst != ~0ull) {
+        char msg[200];
+        snprintf(msg, sizeof(msg), "clusters: S[%llu][%llu] is %s: %s linkage takes no such similarity", (unsigned long long)(worst / M),
+                 (unsigned long long)(worst % M), average ? "not finite" : "a NaN", average ? "average" : "complete");
+        east_throw(EAST_HIP_ERR_INVALID, msg);
+    }
+    Arena a = g.work.arena();
+    u32 *alive = a.alloc<u32>(M), *nn = a.alloc<u32>(M), *partner = a.alloc<u32>(M), *size0 = a.alloc<u32>(M), *size1 = a.alloc<u32>(M),
+        *ea = a.alloc<u32>(M), *eb = a.alloc<u32>(M), *ernd = a.alloc<u32>(M);
+    int32_t *ma = a.alloc<int32_t>(M), *mb = a.alloc<int32_t>(M);
+    double *nw = a.alloc<double>(M), *ew = a.alloc<double>(M), *mw = a.alloc<double>(M);
+    u32 *info = a.alloc<u32>(2);
+    std::vector<u32> ones(M, 1u);
+    HIP_CHECK(hipMemcpyAsync(alive, ones.data(), (size_t)M * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(hipMemcpyAsync(size0, ones.data(), (size_t)M * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(hipMemsetAsync(ea, 0xFF, (size_t)M * 4, h->stream));
+    const u32 wave_grid = ceil_div_u32(M, WAVES_PER_BLOCK);
+    const double fl = floor != floor ? LNK_NO_FLOOR : floor;
+    u32 host_info[2] = {0u, M};
+    u32 *size_in = size0, *size_out = size1;
+    // Three launches and one read-back a round.  The read-back stands between the pairing and the update, so a round that
+    // finds no pair at the floor launches no update; the next round's pick queues behind the update without a wait.
+    while (host_info[1] > 1u) {
+        if (g.rounds >= (i64)M) east_throw(EAST_HIP_ERR_INTERNAL, "clusters: the rounds do not end");
+        LAUNCH(ctx, lnk_best_kernel, wave_grid, (const double *)W, M, (const u32 *)alive, nw, nn);
+        LAUNCH(ctx, lnk_pair_kernel, 1, M, (u32)g.rounds, fl, alive, (const u32 *)nn, (const double *)nw, (const u32 *)size_in, size_out,
+               partner, ea, eb, ew, ernd, info);
+        HIP_CHECK(hipMemcpyAsync(host_info, info, 8, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+        g.launches += 2;
+        if (!host_info[0]) break;                                 // no pair reaches the floor: that round merged nothing and is not counted
+        LAUNCH(ctx, lnk_update_kernel, wave_grid, W, M, average ? 1u : 0u, (const u32 *)alive, (const u32 *)partner, (const u32 *)size_in);
+        g.launches++;
+        g.rounds++;
+        std::swap(size_in, size_out);
+    }
+    const u32 F = M - host_info[1];
+    if (F) {
+        LAUNCH(ctx, lnk_rank_kernel, ceil_div_u32(M, 64), M, (const u32 *)ea, (const u32 *)eb, (const double *)ew, (const u32 *)ernd, ma, mb, mw);
+        g.launches++;
+        b.fetch_merges(F, ma, mb, mw);
+    }
+    b.close(M, F, out);                                           // (the timer finishes before the guard frees the copy the launches read)
 }
 
-// Single linkage is the existing build; a floor keeps the merges that reach it, a prefix of the list.
+// ---- the build entry points, whatever the linkage -------------------------------------------------------------------------
+// Single linkage with a floor keeps the merges that reach it, a prefix of the list.
 static void clusters_build_linkage(east_hip_index *h, const double *S, u32 M, bool check, int32_t linkage, double floor, i64 *out)
 {
     if (linkage != EAST_HIP_LINKAGE_SINGLE) return linkage_build(h, S, M, check, linkage, floor, out);
@@ -377,46 +326,55 @@ static void linkage_known(east_hip_index *h, int32_t linkage)
     east_throw(EAST_HIP_ERR_INVALID, "clusters: unknown linkage (single = 0, complete = 1, average = 2)");
 }
 
+// The bodies of the build entry points; the two without a linkage are single linkage without a floor (a NaN).  What is
+// refused of the source or the size comes before consumer_begin: the last result stays fetchable.
+static void clusters_entry_resident(east_hip_index *h, int32_t source, int32_t linkage, double floor, i64 *out)
+{
+    if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
+    linkage_known(h, linkage);
+    const TableRef t = consumer_resident_square<ClustersState>(h, source, "clusters");
+    clusters_build_linkage(h, t.p, t.K, false, linkage, floor, out);
+}
+
+static void clusters_entry_host(east_hip_index *h, const double *matrix, int32_t m, int32_t linkage, double floor, i64 *out)
+{
+    if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
+    linkage_known(h, linkage);
+    if (m < 0 || (u32)m >= CLU_MAX_M || (m > 0 && !matrix)) east_throw(EAST_HIP_ERR_INVALID, "clusters: null matrix or bad size");
+    if (m == 0) {                                                 // (no members: nothing to upload, and no uploaded matrix left)
+        use_device(h);
+        consumer_begin<ClustersState>(h).table.withdraw();
+        return clusters_build_linkage(h, nullptr, 0, false, linkage, floor, out);
+    }
+    const TableRef t = consumer_upload<ClustersState>(h, matrix, m, m, "clusters: null matrix or bad size", "the clusters' matrix", [] {});
+    try {
+        clusters_build_linkage(h, t.p, t.K, true, linkage, floor, out);
+    } catch (...) {
+        consumer_peek<ClustersState>(h)->table.withdraw();       // (a matrix that was refused is no source either)
+        throw;
+    }
+}
+
 extern "C" {
+
+int east_hip_clusters_build_resident(east_hip_handle_t h, int32_t source, int64_t *out)
+{
+    return guarded([&] { clusters_entry_resident(h, source, EAST_HIP_LINKAGE_SINGLE, __builtin_nan(""), out); });
+}
+
+int east_hip_clusters_build_host(east_hip_handle_t h, const double *matrix, int32_t m, int64_t *out)
+{
+    return guarded([&] { clusters_entry_host(h, matrix, m, EAST_HIP_LINKAGE_SINGLE, __builtin_nan(""), out); });
+}
 
 int east_hip_clusters_build_resident_linkage(east_hip_handle_t h, int32_t source, int32_t linkage, double floor, int64_t *out)
 {
-    return guarded([&] {
-        if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
-        linkage_known(h, linkage);
-        if (source != EAST_HIP_GRAPH_SOURCE_SIMILARITY && source != EAST_HIP_GRAPH_SOURCE_RELATED &&
-            source != EAST_HIP_GRAPH_SOURCE_COSINE_TEXTS && source != EAST_HIP_GRAPH_SOURCE_OVERLAP && source != EAST_HIP_GRAPH_SOURCE_UPLOADED)
-            east_throw(EAST_HIP_ERR_INVALID, "clusters: the source is not a square matrix of members");
-        const TableRef t = consumer_resident<ClustersState>(h, source, "clusters", true);
-        if (t.directed)
-            east_throw(EAST_HIP_ERR_INVALID, source == EAST_HIP_GRAPH_SOURCE_OVERLAP
-                                                 ? "clusters: the overlap matrix is directed (build it with EAST_HIP_OVERLAP_SYMMETRIC)"
-                                                 : "clusters: the relatedness matrix is directed (build it with EAST_HIP_RELATED_SYMMETRIC)");
-        if (t.K != t.D) east_throw(EAST_HIP_ERR_INTERNAL, "clusters: the source matrix is not square");
-        clusters_build_linkage(h, t.p, t.K, false, linkage, floor, out);
-    });
+    return guarded([&] { clusters_entry_resident(h, source, linkage, floor, out); });
 }
 
 int east_hip_clusters_build_host_linkage(east_hip_handle_t h, const double *matrix, int32_t m, int32_t linkage, double floor, int64_t *out)
 {
-    return guarded([&] {
-        if (!h) east_throw(EAST_HIP_ERR_INVALID, "null handle");
-        linkage_known(h, linkage);
-        if (m < 0 || (u32)m >= CLU_MAX_M || (m > 0 && !matrix)) east_throw(EAST_HIP_ERR_INVALID, "clusters: null matrix or bad size");
-        if (m == 0) {                                             // (no members: nothing to upload, and no uploaded matrix left)
-            use_device(h);
-            consumer_begin<ClustersState>(h).table.withdraw();
-            clusters_build_linkage(h, nullptr, 0, false, linkage, floor, out);
-            return;
-        }
-        const TableRef t = consumer_upload<ClustersState>(h, matrix, m, m, "clusters: null matrix or bad size", "the clusters' matrix", [] {});
-        try {
-            clusters_build_linkage(h, t.p, t.K, true, linkage, floor, out);
-        } catch (...) {
-            consumer_peek<ClustersState>(h)->table.withdraw();   // (a matrix that was refused is no source either)
-            throw;
-        }
-    });
+    return guarded([&] { clusters_entry_host(h, matrix, m, linkage, floor, out); });
 }
 
 }  // extern "C"

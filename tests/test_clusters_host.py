@@ -375,3 +375,30 @@ def test_binding_against_the_header():
     kernel = open(os.path.join(ROOT, "ast-text-analysis_amd", "csrc", "clusters.h")).read()
     assert "SLOT_CLU" in kernel and "SLOT_CLU" in open(os.path.join(ROOT, "ast-text-analysis_amd", "csrc", "handle.h")).read()
     assert hip_backend.CLUSTERS_INFO_FIELDS == ("members", "merges", "rounds", "launches")
+
+
+def test_the_three_linkages_share_one_frame():
+    """clusters.h and linkage.h define the ten kernels; what single, complete and average linkage share is written once.  The
+    one exception is counted as such: the rank counting loop stands in both *_rank_kernel, because as one template over the slot
+    clu_rank_kernel measured about 1 % slower than its own body in three forms ("One frame for the three linkages")."""
+    csrc = os.path.join(ROOT, "ast-text-analysis_amd", "csrc")
+    both = open(os.path.join(csrc, "clusters.h")).read() + open(os.path.join(csrc, "linkage.h")).read()
+    for kernel in ("clu_best_kernel", "clu_pick_kernel", "clu_merge_kernel", "clu_rank_kernel", "clu_symmetry_kernel",
+                   "lnk_copy_kernel", "lnk_best_kernel", "lnk_pair_kernel", "lnk_update_kernel", "lnk_rank_kernel"):
+        assert len(re.findall(r"__global__ __launch_bounds__\(BLOCK\) void %s\(" % kernel, both)) == 1, kernel
+    assert both.count("for (u32 t = wv * 64u; t < wv * 64u + 64u; t++)") == 2, "the rank counting loop: the two rank kernels, nowhere else"
+    once = {"the row-maximum loop": "for (u32 j0 = 0; j0 < M; j0 += 64u * CLU_UNROLL)",
+            "the lanes' reduction of the row maximum": "ow == best && oj < best_j",
+            "the tile minimum": "lds8[wv] = worst",
+            "the tile read-back": "hipMemcpyAsync(host.data(), bad,",
+            "the limit of the tiles": "more tiles than one launch takes",
+            "the merge fetch": "hipMemcpyAsync(g.merge_w.data(), mw,",
+            "the closing of a build": "out[3] = g.launches",
+            "the upload": "consumer_upload<ClustersState>(",
+            "the resident front": "consumer_resident_square<ClustersState>("}
+    for what, line in once.items():
+        assert both.count(line) == 1, what
+    assert set(re.findall(r"EAST_HIP_GRAPH_SOURCE_\w+", both)) <= {"EAST_HIP_GRAPH_SOURCE_UPLOADED"}      # the frame knows the sources
+    for entry in ("east_hip_clusters_build_resident", "east_hip_clusters_build_host", "east_hip_clusters_build_resident_linkage",
+                  "east_hip_clusters_build_host_linkage"):
+        assert len(re.findall(r"\bint %s\(" % entry, both)) == 1, entry
