@@ -235,6 +235,7 @@ struct Knobs {
     i64 cosine_texts_batch = 0;                                         // east_hip_debug_set_text_similarity_batch (cosine_texts.h: 0 = COSTEXT_SCRATCH_BYTES of partial tiles)
     int terms_select = 0;                                               // east_hip_debug_set_terms_select (terms.h: 0 = the pre-selection, 1 = every entry is sorted)
     int overlap_route = 0;                                              // east_hip_debug_set_overlap_route (overlap.h: 0 = OVL_DEFAULT_ROUTE, 1 = the integer kernel, 2 = the f64 tile kernel)
+    int passages_route = 0;                                             // east_hip_debug_set_passages_route (passages.h: 0 = PAS_DEFAULT_ROUTE, 1 = the unit's text list, 2 = the text's unit list)
     i64 overlap_batch = 0;                                              // east_hip_debug_set_overlap_batch (overlap.h: 0 = OVL_SCRATCH_BYTES of partial tiles)
     int bm25_strip = 0;                                                 // east_hip_debug_set_bm25_strip (bm25.h: 0 = what the accumulators hold)
     u32 plan_epoch = 1;                                                 // bumped by the knobs that change what a build allocates

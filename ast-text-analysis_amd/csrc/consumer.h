@@ -1,6 +1,6 @@
 // consumer.h -- the host frame of the handle's consumers: the cosine term index, the keyphrase graph, the synonyms, the
 // ranking, the similarity, the text-to-text relatedness, the text-to-text cosine, the clusters, the extracted phrases,
-// the characteristic terms and the shingle overlap.
+// the characteristic terms, the shingle overlap and the shared passages.
 // A consumer is a struct of device buffers and results that the handle owns beside its arena, made by its first call.  The frame has
 // the state and its lifetime, the timer, the front of every entry point (consumer_begin, consumer_built, the two halves
 // of a *_build_resident / *_build_host pair), the table a source names (resolve_table), the M x M matrix of the consumers

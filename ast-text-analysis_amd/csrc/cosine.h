@@ -589,6 +589,12 @@ static void cos_withdraw_overlap(east_hip_index *h)
     if (Consumer *o = h->consumers[east_hip_index::SLOT_OVL]) o->withdraw();
 }
 
+// the shared passages (passages.h) are a function of the token sequence alone, as the overlap is
+static void cos_withdraw_passages(east_hip_index *h)
+{
+    if (Consumer *p = h->consumers[east_hip_index::SLOT_PAS]) p->withdraw();
+}
+
 static CosState &cos_built(east_hip_index *h) { return consumer_built<CosState>(h, "no cosine index has been built on this handle"); }
 
 // A ragged host array: n + 1 offsets into a payload of offsets[n] words, narrowed to 32 bits for the device.  bad: the
@@ -639,6 +645,7 @@ static void cos_build(east_hip_index *h, HostTexts in, const UnicodeTablesHost &
     cos_withdraw_phrases(h);
     cos_withdraw_terms(h);
     cos_withdraw_overlap(h);
+    cos_withdraw_passages(h);
     const u32 N = (u32)in.n_bytes, D = (u32)in.D;
     Stats stats;
 

@@ -451,3 +451,4 @@ double east_hip_last_score_ms(east_hip_handle_t h) { return h ? (double)h->last_
 #include "phrases.h"        // repeated phrases of the indexed texts as keyphrase candidates
 #include "terms.h"          // characteristic terms of texts and of groups of texts
 #include "overlap.h"        // shared-shingle overlap of the texts: resemblance and containment
+#include "passages.h"       // the shared passages of pairs of texts: which positions share which wording

@@ -119,9 +119,9 @@ struct east_hip_index {
     // (phrases.h) and the characteristic terms (terms.h).  Each owns its device allocations and is made by its first call; east_hip_reset and east_hip_destroy go over the array
     // (the tenth, SLOT_TERMS, is numbered behind SLOT_PHR but written behind the count: tests/test_phrases_host.py reads the
     // first line of the enum as it stood when the phrases were the last consumer; the eleventh, SLOT_OVL -- the shingle
-    // overlap, overlap.h -- follows it there)
-    enum { SLOT_COS, SLOT_GRAPH, SLOT_SYN, SLOT_TOP, SLOT_SIM, SLOT_REL, SLOT_COSTEXT, SLOT_CLU, SLOT_PHR, N_CONSUMERS = SLOT_PHR + 3,
-           SLOT_TERMS = SLOT_PHR + 1, SLOT_OVL = SLOT_PHR + 2 };
+    // overlap, overlap.h -- follows it there, and the twelfth, SLOT_PAS -- the shared passages, passages.h -- follows that)
+    enum { SLOT_COS, SLOT_GRAPH, SLOT_SYN, SLOT_TOP, SLOT_SIM, SLOT_REL, SLOT_COSTEXT, SLOT_CLU, SLOT_PHR, N_CONSUMERS = SLOT_PHR + 4,
+           SLOT_TERMS = SLOT_PHR + 1, SLOT_OVL = SLOT_PHR + 2, SLOT_PAS = SLOT_PHR + 3 };
     Consumer *consumers[N_CONSUMERS] = {};
     // the handle's own device allocations besides the arena: east_hip_destroy frees them, east_hip_reset the large ones
     // (a DevBuf has no destructor: the groups' forget() carries theirs over)

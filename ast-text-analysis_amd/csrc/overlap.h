@@ -14,6 +14,9 @@
 //     integers (route 2: cost_tile_kernel + cost_fold_kernel of cosine_texts.h on weights of 1.0, exact below 2^53)
 //   --ovl_finish_kernel: a workgroup per tile pair--> the quotients, self, NaN on the diagonal, the tile and its mirror
 //
+// The first two arrows -- the names, the units, the postings -- are ovl_names_postings, which the shared passages
+// (passages.h) run too.
+//
 // The tile kernel keeps the shape of cost_tile_kernel: a workgroup per (64 x 64 tile of text pairs, tile_a <= tile_b;
 // segment of COSTEXT_SEG units), a cursor per member found by binary search, the next chunk the one that holds the smallest
 // unit under any cursor, a chunk nobody holds never staged.  The chunk is OVL_CHUNK = 64 units wide and staged as 0/1 BYTES:
@@ -273,6 +276,84 @@ __global__ __launch_bounds__(BLOCK) void ovl_finish_kernel(const u32 *__restrict
 }
 
 // ============================================================================================================ host ==
+// ---- names and postings: steps 1 and 2, shared with the passages (passages.h) -------------------------------------------------
+struct OvlPostingRoom {     // where ovl_postings_kernel writes: first[T]; the postings' texts and units, P + 1 words each
+    u32 *first, *p_doc, *p_unit;
+};
+
+struct OvlNames {
+    PhrWork W;              // over the sorted pairs of level w (named only): ri, run_start, tflag, tx
+    PhrDomainIn din;        // the last level's domain (din.id_prev: the ids of level w - 1)
+    u32 dom = 0;            // the positions in it
+    int levels = 0, sr = 0; // the levels run; the sort's buffers that hold the sorted pairs
+    u32 named = 0;          // level w was reached and named
+    u32 U = 0, P = 0, runs = 0;     // the shared runs, their postings, all runs of level w
+    u32 *ux = nullptr, *px = nullptr;       // the units' and the postings' scans over the sorted pairs
+    OvlPostIn post = {};
+};
+
+// Levels 1 .. w - 1 with their survivors and level w named only (phr_level_step, min_count 2), the units' and the postings'
+// scans with their read-back, and the postings to the room that room(U, P) makes for them.  Every array comes out of `a`
+// (ctx.arena), 18 words and 24 bytes a kept token.
+template <class Room> static OvlNames ovl_names_postings(Ctx &ctx, Arena &a, const CosState &c, u32 w, Room room)
+{
+    const u32 T = c.n_kept, V = c.V;
+    const u32 *tok_term = c.tok_term, *tok_doc = c.tok_doc;
+    const size_t K1 = (size_t)T + 2;
+    OvlNames nm;
+    PhrLevel lv[2];
+    for (PhrLevel &l : lv) {
+        l.id = a.alloc<u32>(K1);
+        l.count = a.alloc<u32>(K1);
+        l.texts = a.alloc<u32>(K1);
+        l.first = a.alloc<u32>(K1);
+        l.open = a.alloc<u32>(K1);
+    }
+    PhrWork &W = nm.W;
+    W.dex = a.alloc<u32>(K1);
+    W.sb = sort_bufs_alloc<u64>(a, K1);
+    W.ri = a.alloc<u32>(K1);
+    W.run_start = a.alloc<u32>(K1);
+    W.tflag = a.alloc<u32>(K1);
+    W.tx = a.alloc<u32>(K1);
+    W.sx = a.alloc<u32>(K1);
+    W.term_bits = bit_width_u32(V ? V - 1u : 0u);
+    nm.ux = a.alloc<u32>(K1);
+    nm.px = a.alloc<u32>(K1);
+
+    // ---- 1. the names: levels 1 .. w - 1 with their survivors, level w named only
+    int cur = 0;
+    u32 dom = 0, n_below = 0;
+    PhrDomainIn din{tok_term, tok_doc, nullptr, 1u, T};
+    if (T) dom = device_scan_count(ctx, din, T, W.dex);
+    for (u32 n = 1; n <= w && dom; n++) {
+        const PhrLevel L = lv[cur], B = n > 1u ? lv[cur ^ 1] : PhrLevel{nullptr, nullptr, nullptr, nullptr, nullptr};
+        nm.levels = (int)n;
+        const PhrStep st = phr_level_step(ctx, din, dom, n_below, 2u, W, L, B, n < w);
+        if (n == w) { nm.named = 1u; nm.sr = st.r; break; }
+        if (!st.surv) break;                                  // (nothing occurs twice: no longer shingle does, all intersections are 0)
+        din = PhrDomainIn{tok_term, tok_doc, L.id, n + 1u, T};
+        n_below = st.surv;
+        dom = device_scan_count(ctx, din, T, W.dex);
+        cur ^= 1;
+    }
+    nm.din = din;
+    nm.dom = dom;
+
+    // ---- 2. the postings of the shared shingles, in (unit, text) order
+    nm.post = OvlPostIn{W.ri, W.run_start, W.tx, W.tflag};
+    if (nm.named) {
+        device_scan_with_total(ctx, OvlSharedIn{W.ri, W.run_start, W.tx}, dom, nm.ux);
+        device_scan_with_total(ctx, nm.post, dom, nm.px);
+        device_read_words(ctx, {{&nm.U, nm.ux + dom}, {&nm.P, nm.px + dom}, {&nm.runs, W.ri + dom - 1u}});
+    }
+    const OvlPostingRoom r = room(nm.U, nm.P);
+    if (nm.named)
+        LAUNCH(ctx, ovl_postings_kernel, ceil_div_u32(dom, BLOCK), nm.post, (const u32 *)nm.ux, (const u32 *)nm.px, (const u32 *)W.sb.vals[nm.sr], tok_doc,
+               dom, r.first, r.p_doc, r.p_unit);
+    return nm;
+}
+
 struct OverlapState : MatrixConsumer {       // per_member: self; count: shingles
     static constexpr int SLOT = east_hip_index::SLOT_OVL;
     bool symmetric = true;                  // the matrix is the symmetric form
@@ -301,7 +382,7 @@ static void overlap_build(east_hip_index *h, int32_t words, int32_t orientation,
     CosState *cp = consumer_peek<CosState>(h);
     if (!cp || !cp->valid) east_throw(EAST_HIP_ERR_NOT_BUILT, "overlap: no cosine index has been built on this handle");
     const CosState &c = *cp;
-    const u32 T = c.n_kept, V = c.V, D = c.n_docs, w = (u32)words;
+    const u32 T = c.n_kept, D = c.n_docs, w = (u32)words;
     if (D < 1) east_throw(EAST_HIP_ERR_INVALID, "overlap: the index holds no text");
     // (a text's shingle positions are among the collection's T positions)
     if (T >= 0x7FFFFFF0u) east_throw(EAST_HIP_ERR_INVALID, "overlap: a text may have 2^31 or more shingle positions");
@@ -323,77 +404,45 @@ static void overlap_build(east_hip_index *h, int32_t words, int32_t orientation,
     Stats stats;
     Ctx ctx = handle_ctx(h, &a, &stats);
     ConsumerTimer timer(h, g);
-    PhrLevel lv[2];
-    for (PhrLevel &l : lv) {
-        l.id = a.alloc<u32>(K1);
-        l.count = a.alloc<u32>(K1);
-        l.texts = a.alloc<u32>(K1);
-        l.first = a.alloc<u32>(K1);
-        l.open = a.alloc<u32>(K1);
-    }
-    PhrWork W;
-    W.dex = a.alloc<u32>(K1);
-    W.sb = sort_bufs_alloc<u64>(a, K1);
-    W.ri = a.alloc<u32>(K1);
-    W.run_start = a.alloc<u32>(K1);
-    W.tflag = a.alloc<u32>(K1);
-    W.tx = a.alloc<u32>(K1);
-    W.sx = a.alloc<u32>(K1);
-    W.term_bits = bit_width_u32(V ? V - 1u : 0u);
-    u32 *ux = a.alloc<u32>(K1), *px = a.alloc<u32>(K1), *first = a.alloc<u32>(K1), *nx = a.alloc<u32>(K1), *sh_x = a.alloc<u32>(K1),
-        *out_x = a.alloc<u32>(K1);
-
-    // ---- 1. the names: levels 1 .. w - 1 with their survivors, level w named only
-    int cur = 0, levels = 0, sr = 0;
-    u32 dom = 0, n_below = 0, named = 0;
-    PhrDomainIn din{tok_term, tok_doc, nullptr, 1u, T};
-    if (T) dom = device_scan_count(ctx, din, T, W.dex);
-    for (u32 n = 1; n <= w && dom; n++) {
-        const PhrLevel L = lv[cur], B = n > 1u ? lv[cur ^ 1] : PhrLevel{nullptr, nullptr, nullptr, nullptr, nullptr};
-        levels = (int)n;
-        const PhrStep st = phr_level_step(ctx, din, dom, n_below, 2u, W, L, B, n < w);
-        if (n == w) { named = 1u; sr = st.r; break; }
-        if (!st.surv) break;                                  // (nothing occurs twice: no longer shingle does, all intersections are 0)
-        din = PhrDomainIn{tok_term, tok_doc, L.id, n + 1u, T};
-        n_below = st.surv;
-        dom = device_scan_count(ctx, din, T, W.dex);
-        cur ^= 1;
-    }
-
-    // ---- 2. the postings of the shared shingles, in (unit, text) order
-    u32 U = 0, P = 0, runs = 0;
-    const OvlPostIn post{W.ri, W.run_start, W.tx, W.tflag};
-    if (named) {
-        device_scan_with_total(ctx, OvlSharedIn{W.ri, W.run_start, W.tx}, dom, ux);
-        device_scan_with_total(ctx, post, dom, px);
-        device_read_words(ctx, {{&U, ux + dom}, {&P, px + dom}, {&runs, W.ri + dom - 1u}});
-    }
-    const u32 NT = ceil_div_u32(D, SIM_TILE);
-    const u64 n_pairs = cost_pair_index(NT, NT, NT);
-    const u32 n_seg = ceil_div_u32(U, COSTEXT_SEG);
-    const bool integer = route == 1 || U == 0;                // (no unit: the zeros, whatever the route)
-    const size_t word_bytes = integer ? 4 : 8, tile_bytes = (size_t)n_pairs * OVL_TILE_WORDS * word_bytes;
-    u32 batch = kn.overlap_batch > 0 ? (u32)std::min<i64>(kn.overlap_batch, COSTEXT_MAX_BATCH)
+    u32 *first = a.alloc<u32>(K1), *nx = a.alloc<u32>(K1), *sh_x = a.alloc<u32>(K1), *out_x = a.alloc<u32>(K1);
+    std::vector<u32> pairs;                                   // (on its way up until the sizes' read-back)
+    u32 NT = 0, n_seg = 0, batch = 1, *doc_off = nullptr, *d_pairs = nullptr, *G = nullptr;
+    u64 n_pairs = 0;
+    bool integer = true;
+    double *dw = nullptr;
+    Arena pa;
+    SortBufs<u32> pb = {};
+    // ---- 1. the names; 2. the postings of the shared shingles, in (unit, text) order: the lambda makes their room
+    const OvlNames nm = ovl_names_postings(ctx, a, c, w, [&](u32 U, u32 P) {
+        NT = ceil_div_u32(D, SIM_TILE);
+        n_pairs = cost_pair_index(NT, NT, NT);
+        n_seg = ceil_div_u32(U, COSTEXT_SEG);
+        integer = route == 1 || U == 0;                       // (no unit: the zeros, whatever the route)
+        const size_t word_bytes = integer ? 4 : 8, tile_bytes = (size_t)n_pairs * OVL_TILE_WORDS * word_bytes;
+        batch = kn.overlap_batch > 0 ? (u32)std::min<i64>(kn.overlap_batch, COSTEXT_MAX_BATCH)
                                      : (u32)std::min<size_t>(std::max<size_t>(OVL_SCRATCH_BYTES / tile_bytes, 1), COSTEXT_MAX_BATCH);
-    batch = std::max(std::min(batch, n_seg), 1u);
-    const size_t P1 = (size_t)P + 2;
-    const size_t ops_bytes = 4 * align256(P1 * 4) + (integer ? 0 : align256(P1 * 8)) + align256(((size_t)D + 2) * 4) + align256((size_t)n_pairs * 4) +
-                             (integer ? align256((size_t)n_pairs * OVL_TILE_WORDS * 4) : 0) + P1 / 2 + ((size_t)4 << 20);
-    if (!g.ops.try_ensure(ops_bytes, h->stream)) ovl_oom("the postings and the integer tiles", (double)ops_bytes);
-    if (U && !g.scratch.try_ensure((size_t)batch * tile_bytes + 256, h->stream)) ovl_oom("a batch's partial tiles", (double)batch * (double)tile_bytes);
-    Arena pa = g.ops.arena();
-    SortBufs<u32> pb = sort_bufs_alloc<u32>(pa, P1);            // keys = the text, vals = the unit
-    u32 *doc_off = pa.alloc<u32>((size_t)D + 2), *d_pairs = pa.alloc<u32>((size_t)n_pairs);
-    double *dw = integer ? nullptr : pa.alloc<double>(P1);
-    u32 *G = integer ? pa.alloc<u32>((size_t)n_pairs * OVL_TILE_WORDS) : nullptr;
-    std::vector<u32> pairs;
-    pairs.reserve((size_t)n_pairs);
-    for (u32 ta = 0; ta < NT; ta++)
-        for (u32 tb = ta; tb < NT; tb++) pairs.push_back(ta << 16 | tb);
-    HIP_CHECK(hipMemcpyAsync(d_pairs, pairs.data(), pairs.size() * 4, hipMemcpyHostToDevice, h->stream));
-    if (named)
-        LAUNCH(ctx, ovl_postings_kernel, ceil_div_u32(dom, BLOCK), post, (const u32 *)ux, (const u32 *)px, (const u32 *)W.sb.vals[sr], tok_doc, dom,
-               first, pb.keys[0], pb.vals[0]);
+        batch = std::max(std::min(batch, n_seg), 1u);
+        const size_t P1 = (size_t)P + 2;
+        const size_t ops_bytes = 4 * align256(P1 * 4) + (integer ? 0 : align256(P1 * 8)) + align256(((size_t)D + 2) * 4) + align256((size_t)n_pairs * 4) +
+                                 (integer ? align256((size_t)n_pairs * OVL_TILE_WORDS * 4) : 0) + P1 / 2 + ((size_t)4 << 20);
+        if (!g.ops.try_ensure(ops_bytes, h->stream)) ovl_oom("the postings and the integer tiles", (double)ops_bytes);
+        if (U && !g.scratch.try_ensure((size_t)batch * tile_bytes + 256, h->stream)) ovl_oom("a batch's partial tiles", (double)batch * (double)tile_bytes);
+        pa = g.ops.arena();
+        pb = sort_bufs_alloc<u32>(pa, P1);                      // keys = the text, vals = the unit
+        doc_off = pa.alloc<u32>((size_t)D + 2);
+        d_pairs = pa.alloc<u32>((size_t)n_pairs);
+        dw = integer ? nullptr : pa.alloc<double>(P1);
+        G = integer ? pa.alloc<u32>((size_t)n_pairs * OVL_TILE_WORDS) : nullptr;
+        pairs.reserve((size_t)n_pairs);
+        for (u32 ta = 0; ta < NT; ta++)
+            for (u32 tb = ta; tb < NT; tb++) pairs.push_back(ta << 16 | tb);
+        HIP_CHECK(hipMemcpyAsync(d_pairs, pairs.data(), pairs.size() * 4, hipMemcpyHostToDevice, h->stream));
+        return OvlPostingRoom{first, pb.keys[0], pb.vals[0]};
+    });
+    const u32 U = nm.U, P = nm.P, runs = nm.runs, named = nm.named;
+    const int levels = nm.levels;
+    const PhrDomainIn din = nm.din;
+    u32 *ux = nm.ux;
 
     // ---- 3. the sizes
     const u32 *id_w = named && w > 1u ? din.id_prev : nullptr;

@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
 """keyphrases_table / keyphrases_graph (reference east/applications.py:11-149), keyphrases_top and keyphrases_similar;
-texts_related, texts_similar, texts_overlap, the clusters, keyphrases_extract and texts_terms."""
+texts_related, texts_similar, texts_overlap, texts_passages, the clusters, keyphrases_extract and texts_terms."""
 
 import inspect
 import os
@@ -701,6 +701,114 @@ def texts_overlap(texts, n=10, words=4, orientation="symmetric", overlap_thresho
     else:
         lists = _top_select(_overlap_on_host(texts.values(), measure.stopwords, words, orientation == "symmetric")[0], 1, n, threshold)
     return _top_named(lists, titles, titles)
+
+
+# ---- shared passages -----------------------------------------------------------------------------------------------------
+Passage = namedtuple("Passage", ("start", "words", "at", "text"))
+PassagePair = namedtuple("PassagePair", ("other", "value", "starts", "covered", "found", "passages"))
+
+
+def _passage_tokens(texts, stopwords):
+    """Per text its positions: the tokens of utils.tokenize(utils.prepare_text(text)) with at least 3 code points -> (the
+    words as they are, the same with None where the word is a stopword: a break)."""
+    kept = [[token for token in utils.tokenize(utils.prepare_text(text)) if len(token) >= 3] for text in texts]
+    return kept, [[None if token in stopwords else token for token in tokens] for tokens in kept]
+
+
+def _passages_of_pair(ta, tb, words, min_words, per_pair):
+    """The contract of include/east_hip.h ("Shared passages") in plain Python for one ordered pair: ta, tb = the positions
+    of a and of b (None: a break).  -> (starts, covered, found, [(start, words, at), ...]), positions relative to their text."""
+    first = {}
+    for j in range(len(tb) - words + 1):
+        g = tuple(tb[j:j + words])
+        if None not in g:
+            first.setdefault(g, j)
+    shared = [j for j in range(len(ta) - words + 1) if None not in ta[j:j + words] and tuple(ta[j:j + words]) in first]
+    covered, runs = set(), []
+    for j in shared:
+        covered.update(range(j, j + words))
+        if runs and runs[-1][1] == j:
+            runs[-1][1] = j + 1
+        else:
+            runs.append([j, j + 1])
+    found = sorted(((e - j + words - 1, j) for j, e in runs if e - j + words - 1 >= min_words), key=lambda p: (-p[0], p[1]))
+    kept = found[:per_pair] if per_pair else found
+    return len(shared), len(covered), len(found), [(j, n, first[tuple(ta[j:j + words])]) for n, j in kept]
+
+
+def _passages_arguments(words, min_words, per_pair):
+    min_words = words if min_words is None else min_words
+    if isinstance(min_words, bool) or int(min_words) != min_words or min_words < words:
+        raise ValueError("texts_passages: min_words must be an integer that is at least words (%d), not %r" % (words, min_words))
+    if isinstance(per_pair, bool) or int(per_pair) != per_pair or per_pair < 0:
+        raise ValueError("texts_passages: per_pair must be an integer that is not negative (0 keeps every passage), not %r" % (per_pair,))
+    return int(min_words), int(per_pair)
+
+
+def texts_passages(texts, n=10, words=4, min_words=None, per_pair=5, orientation="symmetric", overlap_threshold=None, pairs=None,
+                   similarity_measure=None, language=consts.Language.ENGLISH):
+    """The passages two texts share, WHICH words: for a text a and another text b the maximal stretches of a in which every
+    `words` consecutive words occur, in this order, somewhere in b (include/east_hip.h, "Shared passages").
+
+    :param texts: {text name: text}
+    :param n: by default every text is paired with the n others texts_overlap ranks for it -- with the same `words`,
+              `orientation`, `overlap_threshold`, measure and language, in the same order
+    :param words: the words of a shingle, 1 .. 8: the shortest stretch that counts as shared wording
+    :param min_words: only passages of at least this many words are listed (None: `words`)
+    :param per_pair: passages per pair at most, the longest first; 0 keeps all
+    :param pairs: [(name of a, name of b), ...] replaces the ranking: these pairs, in this order; a pair may repeat
+    :param similarity_measure: a relevance.CosineRelevanceMeasure, whose stopwords are the breaks (None:
+                               CosineRelevanceMeasure("words")); any other raises ValueError
+    :returns: {text name: [PassagePair(other, value, starts, covered, found, [Passage(start, words, at, text), ...]), ...]}:
+              `value` the overlap value of the ranking (None under `pairs=`); `starts` the positions of the text at which a
+              shingle of the other starts, `covered` the words of the text inside shared wording, `found` the passages of
+              min_words words or more; per passage `start` and `at` = where it starts in the text and where its first shingle
+              first starts in the other, both counted in the text's own kept tokens (at least 3 code points) from 0,
+              `words` its length and `text` its words joined by one space; longest first, then by start
+
+    Made on the device from the token sequence the term index keeps (csrc/passages.h) when the text titles are distinct and
+    EAST_HIP_PASSAGES is not `host`; in every other case on the host in plain Python from the same tokens, which then
+    touches no device.  The two paths give the SAME result.
+    """
+    words, measure = _overlap_arguments("texts_passages", words, orientation, similarity_measure)
+    min_words, per_pair = _passages_arguments(words, min_words, per_pair)
+    titles = list(texts.keys())
+    number = {title: d for d, title in enumerate(titles)}
+    if pairs is None:
+        _, n, threshold = _ranking_arguments("texts_passages", "text", n, overlap_threshold, "overlap")
+    else:
+        pairs = [tuple(pair) for pair in pairs]
+        for pair in pairs:
+            if len(pair) != 2 or pair[0] not in number or pair[1] not in number or pair[0] == pair[1]:
+                raise ValueError("texts_passages: a pair names two different texts of the collection, not %r" % (pair,))
+    if not titles:
+        return {}
+    on_device = _device_applies(measure, texts, None, "shared_passages", "EAST_HIP_PASSAGES")
+    if on_device:
+        measure.set_text_collection(list(texts.values()), language)
+    if pairs is None:
+        if on_device:
+            lists = _top_lists(measure.relevance_texts_overlap(n, threshold, words, orientation))
+        else:
+            lists = _top_select(_overlap_on_host(texts.values(), measure.stopwords, words, orientation == "symmetric")[0], 1, n, threshold)
+        numbered = [(a, b, value) for a, entries in enumerate(lists) for b, value in entries]
+        result = {title: [] for title in titles}
+    else:
+        numbered = [(number[a], number[b], None) for a, b in pairs]
+        result = {}
+    kept, positions = _passage_tokens(texts.values(), measure.stopwords)
+    if on_device:
+        found = measure.shared_passages([(a, b) for a, b, _ in numbered], words, min_words, per_pair)
+        base, off = found.text_start.tolist(), found.pair_off.tolist()
+        rows = list(zip(found.start.tolist(), found.words.tolist(), found.at.tolist()))
+        per_pair_rows = [(s, c, f, [(j - base[a], m, at - base[b]) for j, m, at in rows[off[i]:off[i + 1]]])
+                         for i, ((a, b, _), s, c, f) in enumerate(zip(numbered, found.starts.tolist(), found.covered.tolist(), found.found.tolist()))]
+    else:
+        per_pair_rows = [_passages_of_pair(positions[a], positions[b], words, min_words, per_pair) for a, b, _ in numbered]
+    for (a, b, value), (starts, covered, count, passages) in zip(numbered, per_pair_rows):
+        result.setdefault(titles[a], []).append(PassagePair(titles[b], value, starts, covered, count, [
+            Passage(j, m, at, " ".join(kept[a][j:j + m])) for j, m, at in passages]))
+    return result
 
 
 # ---- clusters ------------------------------------------------------------------------------------------------------------

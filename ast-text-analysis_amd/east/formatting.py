@@ -229,6 +229,43 @@ def phrases2xml(result):
     return "\n".join(lines) + "\n"
 
 
+def format_passages(result, format):
+    """Shared passages (applications.texts_passages: {text: [PassagePair(other, value, starts, covered, found, [Passage(start,
+    words, at, text)])]})."""
+    renderers = {"xml": passages2xml, "csv": passages2csv}
+    if format not in renderers:
+        raise Exception("Unknown passages format: '%s'. Please use one of: 'xml', 'csv'." % format)
+    return renderers[format](result)
+
+
+def _passage_value(value):
+    return "" if value is None else _SCORE % value
+
+
+def passages2xml(result):
+    """<passages> / <text name=..> / <text name=.. rank=.. value=.. starts=.. covered=.. found=..> / <passage start=.. words=..
+    at=..>text</passage>; texts sorted by name, the others in the order given, the passages longest first.  value is left
+    out where the pairs were named, not ranked."""
+    lines = ["<passages>"]
+    for text in sorted(result):
+        lines.append('  <text name="%s">' % text)
+        for rank, pair in enumerate(result[text], 1):
+            value = "" if pair.value is None else ' value="%s"' % _passage_value(pair.value)
+            lines.append('    <text name="%s" rank="%d"%s starts="%d" covered="%d" found="%d">' % (pair.other, rank, value, pair.starts, pair.covered, pair.found))
+            lines.extend('      <passage start="%d" words="%d" at="%d">%s</passage>' % (p.start, p.words, p.at, p.text) for p in pair.passages)
+            lines.append("    </text>")
+        lines.append("  </text>")
+    lines.append("</passages>")
+    return "\n".join(lines) + "\n"
+
+
+def passages2csv(result):
+    """One line per passage: "text","other",value,start,words,at,"passage"; in the order of passages2xml; value is empty
+    where the pairs were named, not ranked."""
+    return "".join("%s,%s,%s,%d,%d,%d,%s\n" % (_csv_quote(text), _csv_quote(pair.other), _passage_value(pair.value), p.start, p.words, p.at, _csv_quote(p.text))
+                   for text in sorted(result) for pair in result[text] for p in pair.passages)
+
+
 def format_terms(result, format):
     """Characteristic terms (applications.texts_terms: [TermGroup(names, [Term(text, value, texts, df)])])."""
     renderers = {"xml": terms2xml, "csv": terms2csv}

@@ -203,6 +203,12 @@ SIGNATURES = {
     "east_hip_last_overlap_ms": (ctypes.c_double, [ctypes.c_void_p]),
     "east_hip_debug_set_overlap_route": (ctypes.c_int, [ctypes.c_int]),
     "east_hip_debug_set_overlap_batch": (ctypes.c_int, [ctypes.c_int64]),
+    "east_hip_passages_build": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _c_i32p, _c_i32p,
+                                               ctypes.c_int64, _c_i64p]),
+    "east_hip_passages_fetch": (ctypes.c_int, [ctypes.c_void_p, _c_i64p, _c_i32p, _c_i32p, _c_i32p, _c_i32p, _c_i32p, _c_i32p, _c_i32p]),
+    "east_hip_passages_phases": (ctypes.c_int, [ctypes.c_void_p, _c_dblp]),
+    "east_hip_last_passages_ms": (ctypes.c_double, [ctypes.c_void_p]),
+    "east_hip_debug_set_passages_route": (ctypes.c_int, [ctypes.c_int]),
 }
 
 BUILD_INFO_FIELDS = ("n_total", "n_docs", "n_strings", "sigma_text", "bits_level0", "dc3_levels", "arena_bytes",
@@ -226,6 +232,8 @@ OVERLAP_DIRECTED, OVERLAP_SYMMETRIC = 0, 1  # EAST_HIP_OVERLAP_*
 OVERLAP_ORIENTATIONS = ("directed", "symmetric")
 OVERLAP_INFO_FIELDS = ("n_docs", "kept_tokens", "shingle_positions", "distinct_shingles", "shared_shingles", "postings", "segments",
                        "launches", "route", "levels", "tiles", "words", "operands_us", "product_us")          # east_hip_overlap_build: out
+PASSAGES_INFO_FIELDS = ("n_docs", "kept_tokens", "pairs", "shared_shingles", "postings", "bit_words", "shared_starts", "passages",
+                        "returned", "launches", "route", "levels")                                            # east_hip_passages_build: out
 TERMS_INFO_FIELDS = ("n_docs", "groups", "units", "postings", "entries", "passing", "sorted", "radix_passes", "launches",
                      "grouping_sort_skipped")                           # east_hip_terms_build: out
 CLUSTERS_INFO_FIELDS = ("members", "merges", "rounds", "launches")      # east_hip_clusters_build_*: out
@@ -476,6 +484,32 @@ class TermArrays(object):
 
     def __init__(self, members, count, unit, value, texts, df, info=None):
         self.members, self.count, self.unit, self.value, self.texts, self.df, self.info = members, count, unit, value, texts, df, info
+
+
+class PassageArrays(object):
+    """Shared passages as the device left them (include/east_hip.h, "Shared passages"): per pair `starts`, `covered`, `found`
+    (int32[pairs]) and `pair_off` (int64[pairs + 1]); per returned passage `start`, `words`, `at` (int32[pair_off[-1]],
+    collection positions, pair by pair, longest first); `text_start` (int32[D + 1]); `info` = {PASSAGES_INFO_FIELDS: value}."""
+    __slots__ = ("pair_off", "starts", "covered", "found", "start", "words", "at", "text_start", "info")
+
+
+def _passages(lib, h, pairs_a, pairs_b, words, min_words, per_pair):
+    pa, pb = np.ascontiguousarray(pairs_a, dtype=np.int32), np.ascontiguousarray(pairs_b, dtype=np.int32)
+    if pa.ndim != 1 or pa.shape != pb.shape:
+        raise ValueError("passages: pairs_a and pairs_b must be two lists of one length")
+    out = np.zeros(len(PASSAGES_INFO_FIELDS), dtype=np.int64)
+    _check(lib.east_hip_passages_build(h, int(words), int(min_words), int(per_pair), _ptr(pa, _c_i32p), _ptr(pb, _c_i32p), pa.size,
+                                       _ptr(out, _c_i64p)))
+    found = PassageArrays()
+    found.info = dict(zip(PASSAGES_INFO_FIELDS, (int(x) for x in out)))
+    n, R, D = pa.size, int(out[8]), int(out[0])
+    found.pair_off = np.zeros(n + 1, dtype=np.int64)
+    found.starts, found.covered, found.found = (np.zeros(n, dtype=np.int32) for _ in range(3))
+    found.start, found.words, found.at = (np.zeros(R, dtype=np.int32) for _ in range(3))
+    found.text_start = np.zeros(D + 1, dtype=np.int32)
+    _check(lib.east_hip_passages_fetch(h, _ptr(found.pair_off, _c_i64p), *[_ptr(x, _c_i32p) for x in (
+        found.starts, found.covered, found.found, found.start, found.words, found.at, found.text_start)]))
+    return found
 
 
 class PhraseArrays(object):
@@ -1085,6 +1119,22 @@ class HipCosineIndex(_ResidentTableConsumers):
 
     def last_overlap_ms(self):
         return float(self._lib.east_hip_last_overlap_ms(self._h))
+
+    # -- shared passages -----------------------------------------------------------
+    def passages(self, pairs_a, pairs_b, words=4, min_words=None, per_pair=5):
+        """The passages of text pairs_a[i] whose every `words` consecutive words occur in text pairs_b[i] (include/east_hip.h,
+        "Shared passages"): per pair the passages of min_words words or more (None: `words`), longest first, per_pair of
+        them at most (0: all) -> PassageArrays."""
+        return _passages(self._lib, self._h, pairs_a, pairs_b, words, words if min_words is None else min_words, per_pair)
+
+    def passages_phases_ms(self):
+        """(names and postings, the match kernel, runs + order + cut) of the last passages build, device ms."""
+        ms = np.zeros(3, dtype=np.float64)
+        _check(self._lib.east_hip_passages_phases(self._h, _ptr(ms, _c_dblp)))
+        return tuple(float(x) for x in ms)
+
+    def last_passages_ms(self):
+        return float(self._lib.east_hip_last_passages_ms(self._h))
 
     # -- characteristic terms ------------------------------------------------------
     def _characteristic_terms(self, tfidf, n, min_texts, groups, n_groups=None):

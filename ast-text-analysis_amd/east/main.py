@@ -39,6 +39,13 @@ README.rst:27-63; the shipped reference main crashes with a NameError, SURVEY.md
         -o directed: the containment |A n B| / |A| of the listing text in the listed one; exact integers and one division,
         on the device (csrc/overlap.h); with -j single|complete|average and (-r threshold | -k clusters | -f merges) the
         clusters of the symmetric matrix instead -- single linkage at a resemblance threshold: the near-duplicate groups
+    east [-x words] [-m min words] [-k passages per pair] [-n N] [-r threshold] [-o symmetric|directed] [-l language]
+         [-f xml|csv] texts passages <texts>
+        WHICH words they share: for every text and each of the N texts `texts overlap` ranks for it (same -x, -o, -r) the
+        passages of the text in which every -x (default 4, at most 8) consecutive words occur in the other, the longest
+        first; -m: only passages of that many words or more (default: -x); -k: that many passages a pair at most (default
+        5, 0 = all); per passage where it starts in the text, its words, and where its first -x words first start in the
+        other (positions count the words of 3 code points or more from 0); exact integers, on the device (csrc/passages.h)
     east [-s ast|cosine|bm25] [-j linkage] [-b text|keyphrase] [-r threshold | -k clusters] [-f xml|csv|merges] keyphrases clusters <keyphrases file> <texts>
         the same of the texts (-b text) or the keyphrases (-b keyphrase) by the profile cosines of `keyphrases similar`
     east [-n N] [-x max words] [-m min count] [-u min texts] [-l language] [-f txt|csv|xml] keyphrases extract <texts>
@@ -329,10 +336,12 @@ def _texts_main(opts, args, world, rank):
             print(line)
         return 1
 
-    if len(args) < 2 or args[1] not in ("related", "similar", "clusters", "terms", "overlap"):
-        return refuse("Invalid subcommand: '%s'. Please use one of: 'related', 'similar', 'clusters', 'terms', 'overlap'." % (args[1] if len(args) > 1 else ""))
+    if len(args) < 2 or args[1] not in ("related", "similar", "clusters", "terms", "overlap", "passages"):
+        return refuse("Invalid subcommand: '%s'. Please use one of: 'related', 'similar', 'clusters', 'terms', 'overlap', 'passages'." % (args[1] if len(args) > 1 else ""))
     if args[1] == "overlap":
         return _texts_overlap_main(opts, args, world, refuse)
+    if args[1] == "passages":
+        return _texts_passages_main(opts, args, world, refuse)
     if args[1] == "similar":
         return _texts_similar_main(opts, args, world, refuse)
     if args[1] == "terms":
@@ -568,6 +577,73 @@ def _texts_terms_main(opts, args, world, refuse):
                                          threshold, k, **linkage)
         print(formatting.format_terms(found, fmt))
     except (exceptions.EastException, applications.RefusedSimilarity) as e:     # (a missing stemmer, no device, a failed build ...): a message, not a traceback
+        print(e)
+        return 1
+    return 0
+
+
+def _texts_passages_main(opts, args, world, refuse):
+    """`east texts passages <texts>`: the passages every text shares with the -n texts `texts overlap` ranks for it.
+    Everything that cannot be done is refused with one line (refuse) before a file is read or a measure is made."""
+    if len(args) < 3:
+        return refuse('Invalid syntax. For text analysis, EAST should be called as:\n\n'
+                      '    east [options] texts passages "path/to/texts/dir"')
+    for key, line in (("-s", "Shared passages compare wording, not a relevance measure: -s %s is not supported."),
+                      ("-w", "Shared passages weigh no terms: -w %s is not supported."),
+                      ("-v", "Passages are made of words: -v %s is not supported."),
+                      ("-y", "Shared passages take no synonyms: -y is not supported."),
+                      ("-b", "Shared passages compare texts: -b %s is not supported."),
+                      ("-c", "Shared passages build no graph: -c %s is not supported."),
+                      ("-p", "Shared passages build no graph: -p %s is not supported."),
+                      ("-u", "Shared passages count no texts: -u %s is not supported (it belongs to `keyphrases extract`)."),
+                      ("-z", "Shared passages score no keyphrases: -z %s is not supported.")):
+        if key in opts:
+            return refuse(line % opts[key] if "%s" in line else line)
+    numbers = {}
+    for key, default, least, most, what in (("-x", "4", 1, applications.OVERLAP_MAX_WORDS, "number of words"),
+                                            ("-m", None, None, None, "least number of words of a passage"),
+                                            ("-k", "5", 0, None, "number of passages per pair")):
+        if key == "-m":
+            default, least = str(numbers["-x"]), numbers["-x"]
+        try:
+            numbers[key] = int(opts.get(key, default))
+        except ValueError:
+            numbers[key] = least - 1
+        if numbers[key] < least or (most is not None and numbers[key] > most):
+            bounds = "from %d to %d" % (least, most) if most is not None else "of at least %d" % least
+            return refuse("Invalid %s: '%s'. Please use an integer %s." % (what, opts[key], bounds))
+    orientation = opts.get("-o", "symmetric").lower()
+    if orientation not in ("symmetric", "directed"):
+        return refuse("Invalid orientation: '%s'. Please use one of: 'symmetric', 'directed'." % opts["-o"])
+    n, _, threshold, refusal = _top_options(opts)
+    if refusal:
+        return refuse(refusal.replace("relevance threshold", "overlap threshold"))
+    fmt = opts.get("-f", "xml").lower()
+    if fmt not in ("xml", "csv"):
+        return refuse("Unknown passages format: '%s'. Please use one of: 'xml', 'csv'." % opts["-f"])
+    if world > 1:
+        return refuse("Shared passages run on one device: a launcher with WORLD_SIZE=%d is not supported." % world)
+    if os.environ.get("EAST_HIP_FORCE_DIST") == "1":
+        return refuse("Shared passages run on one device: the collective path is not supported.")
+    devices = opts.get("-g", os.environ.get("EAST_HIP_DEVICES", "1"))
+    try:
+        n_ranks = int(devices)
+    except ValueError:
+        return refuse("Invalid number of GPUs: '%s'." % devices)
+    if n_ranks > 1:
+        return refuse("Shared passages run on one device: -g %d is not supported." % n_ranks)
+    language = opts.get("-l", consts.Language.ENGLISH)
+    try:
+        measure = relevance.CosineRelevanceMeasure(consts.VectorSpace.WORDS)
+        if measure.stopwords_source == "none":
+            sys.stderr.write("nltk's English stopword list is not available: no stopwords are removed.\n")
+        texts = _read_texts(args[2])
+        found = applications.texts_passages(texts, n, numbers["-x"], numbers["-m"], numbers["-k"], orientation, threshold, None, measure, language)
+        print(formatting.format_passages(found, fmt))
+    except exceptions.EastException as e:       # (no device, a failed build ...): a message, not a traceback
+        print(e)
+        return 1
+    except Exception as e:                      # (an unknown format)
         print(e)
         return 1
     return 0

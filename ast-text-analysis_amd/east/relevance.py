@@ -494,6 +494,13 @@ class CosineRelevanceMeasure(RelevanceMeasure):
         self.index.clusters_build(hip_backend.GRAPH_SOURCE_OVERLAP, linkage, floor)
         return self.index
 
+    def shared_passages(self, pairs, words=4, min_words=None, per_pair=5):
+        """For every (a, b) of `pairs` (text numbers of the indexed collection) the passages of a whose every `words`
+        consecutive words occur in b, longest first (include/east_hip.h, "Shared passages"; csrc/passages.h); after
+        set_text_collection.  Passages are made of words whatever the vector space.  -> hip_backend.PassageArrays."""
+        pairs = list(pairs)
+        return self.index.passages([a for a, _ in pairs], [b for _, b in pairs], words, min_words, per_pair)
+
     def extract_phrases(self, n=0, max_words=3, min_words=1, min_count=2, min_texts=1):
         """The repeated phrases of the indexed collection as keyphrase candidates, best first (include/east_hip.h, "Phrase
         extraction"; csrc/phrases.h); after set_text_collection, in the `words` space: a phrase is made of words, not of
@@ -682,6 +689,9 @@ class BM25RelevanceMeasure(CosineRelevanceMeasure):
 
     def relevance_overlap_clusters(self, words=4, linkage="single", floor=None):
         self._cosine_only("relevance_overlap_clusters")
+
+    def shared_passages(self, pairs, words=4, min_words=None, per_pair=5):
+        self._cosine_only("shared_passages")
 
     def unit_names(self):
         self._cosine_only("unit_names")

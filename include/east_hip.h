@@ -832,6 +832,66 @@ int east_hip_debug_set_overlap_route(int route);      /* 0: the default; 1: the 
 int east_hip_debug_set_overlap_batch(int64_t segments);
 
 /*
+ * Shared passages (`east texts passages`): WHICH WORDS two texts share -- after "Shingle overlap" has said that they share
+ * wording and how much.  Integers only: the device under either route, the host path of the Python package and any other
+ * exact count give the same numbers; there is no tolerance anywhere.  (How: csrc/passages.h)
+ *
+ * A cosine index has been built.  Tokens, positions, breaks, shingles and S_b are those of "Phrase extraction" and
+ * "Shingle overlap"; the width is w = `words`, 1 .. 8.  For an ordered pair of texts (a, b), a != b:
+ * A SHARED START of a in b is a shingle position j of a whose shingle is in S_b.
+ * A PASSAGE of a in b is a maximal run of shared starts at consecutive positions j, j + 1, .., j + m - 1: neither j - 1
+ * nor j + m is a shared start of a in b.  start = j, a collection position as `first` of the phrases is; words = m + w - 1,
+ * it covers the tokens [j, j + m + w - 1): every w consecutive words of a passage occur in b.  A passage holds no break and
+ * lies inside a -- by the shingle definition, not by an extra rule.  Two passages of one pair never share a start; their
+ * token ranges may overlap by up to w - 2 tokens.
+ * at = the smallest position in b at which the passage's first shingle starts.
+ * Per pair: starts = the number of shared starts; covered = |the union of [j, j + w) over the shared starts j|, the words of
+ * a that lie inside wording found in b; found = the number of passages with words >= min_words.
+ * Returned per pair are the passages with words >= min_words (w <= min_words), ordered by words descending, then start
+ * ascending -- a strict order; the first per_pair of them are kept, 0 keeps all.  Pairs come back in the order given;
+ * duplicate pairs are allowed and give the same result twice.
+ * The number of distinct shingles at the shared starts of (a, b) is I_ab of "Shingle overlap".
+ *
+ * Example.  w = 2, no stopwords, text 0 = `abc bcd cde def xyz bcd cde` (positions 0 .. 6), text 1 = `qqq bcd cde def rrr`
+ * (positions 7 .. 11).  Pair (0, 1): shared starts 1, 2, 5; passages (start, words, at) = (1, 3, 8) BCD CDE DEF, then
+ * (5, 2, 8) BCD CDE; starts 3, covered 5.  Pair (1, 0): shared starts 8, 9; passage (8, 3, 1); starts 2, covered 3.
+ *
+ * east_hip_passages_build: pair_a[n_pairs], pair_b[n_pairs] = the texts of every pair.  out (at least 12 entries): D; the
+ * kept tokens; the pairs; the shared shingles U (the units); their postings P; the 64-bit words of all pairs' rows (a row =
+ * one bit a position of a, ceil(len_a / 64) words); the shared starts over all pairs; the passages before the filter; the
+ * passages returned; the launches of this section's own kernels; the route taken (1 or 2); the naming levels run.
+ * east_hip_passages_fetch: pair_off[n_pairs + 1] = the prefix sum of the returned passages; starts, covered, found
+ * [n_pairs]; start, words, at [pair_off[n_pairs]], pair by pair in the contract's order; text_start[D + 1] = the first
+ * position of every text (and the number of positions behind the last), so a caller can make positions text-relative.
+ * Null outputs are skipped.
+ * east_hip_passages_phases: ms[3] = the device time of the last build up to the rows' offsets (names, postings, rows), of
+ * the match kernel (with the words' pairs), and from there on (runs, order, cut); they add up to east_hip_last_passages_ms.
+ * Errors: EAST_HIP_ERR_NOT_BUILT "passages: no cosine index has been built on this handle" for a build without an index,
+ * "no passages have been built on this handle" for a fetch without a result; EAST_HIP_ERR_INVALID, in lines that start
+ * with "passages: ", for words outside 1 .. 8, min_words < words, per_pair < 0, n_pairs < 0 or above 2^24, null pair_a or
+ * pair_b with n_pairs > 0, a null out, an index without a text, a pair with a == b or a text outside 0 .. D - 1 (named by
+ * its index in the list) -- all of these before anything is withdrawn: a refused call leaves the earlier result fetchable
+ * -- and for rows of 2^25 bit words or more; EAST_HIP_ERR_OOM "passages: ... of N pairs of D texts needs B bytes, which
+ * the device does not have".  n_pairs == 0, no shared shingle and a level that ends the naming early are results.
+ * Lifetime: a cosine build on the handle withdraws the result, east_hip_reset drops it; score calls and
+ * east_hip_cosine_set_classes leave it alone.  The buffers are the passages' own: a build disturbs neither the overlap
+ * matrix nor the extracted phrases.  The consumer offers no matrix: there is no graph source for it.
+ * east_hip_debug_set_passages_route: how "does b hold this shingle" is answered -- 0 the default, 1 a search of b in the
+ * shingle's own ascending list of texts, 2 a search of the shingle in b's ascending list of shingles (the operands of the
+ * overlap); anything else is EAST_HIP_ERR_INVALID.  The result does not depend on it.
+ * Memory: during a build 128 bytes a kept token; 4 bytes a position and 12 a posting of a shared shingle (28 more on route
+ * 2), 36 bytes a pair, 24 bytes a bit word, 16 bytes a passage before the filter, 24 one behind it, 12 one returned.
+ * Device time of the last build in milliseconds (its read-backs included), -1 before a build and after a failed one.
+ */
+int east_hip_passages_build(east_hip_handle_t h, int32_t words, int32_t min_words, int32_t per_pair,
+                            const int32_t *pair_a, const int32_t *pair_b, int64_t n_pairs, int64_t *out);
+int east_hip_passages_fetch(east_hip_handle_t h, int64_t *pair_off, int32_t *starts, int32_t *covered, int32_t *found,
+                            int32_t *start, int32_t *words, int32_t *at, int32_t *text_start);
+int east_hip_passages_phases(east_hip_handle_t h, double *ms);
+double east_hip_last_passages_ms(east_hip_handle_t h);
+int east_hip_debug_set_passages_route(int route);     /* 0: the default; 1: b in the shingle's texts; 2: the shingle in b's shingles */
+
+/*
  * Several devices in one process ("single-process/8-device fits the one-process CLI best").
  * Every document is an independent AST (east/relevance.py:41-46) and every (keyphrase, document) score is independent
  * (east/applications.py:43-52): a GROUP shards a collection at document granularity -- contiguous blocks of documents
