@@ -57,6 +57,7 @@ __global__ __launch_bounds__(BLOCK) void presence_kernel(const u32 *__restrict__
 #define FLAG_PLACE_FAIL 6        // the placement pass's "a repeat too long to order directly" (window_sort.h: fail), zeroed with the flags
 #define FLAG_KG_BAD 7            // the fused finish could not mark every k-gram bucket start (Ctx::kg_bad)
 #define FLAG_SAMPLE 8             // 17 words: sample_prefix_kernel's counts (dup2, dup4 for l = 1 .. 8) and the sample size
+#define FLAG_ANN_LISTED 25        // the ranks ann_wide_kernel decided: one add per run of tiles (the next build's block order, build.h)
 #define FLAG_WORDS 32
 #define STATUS_NO_TERMINATOR 1u
 #define STATUS_N_STRINGS 2u

@@ -8,6 +8,7 @@
 #include <chrono>
 
 static bool kgram_reserve(east_hip_index *h, u64 bins, u32 n_docs);      // (score_host.h: the build marks the score walk's k-gram tables)
+static bool kgram_finish_marked(east_hip_index *h, Ctx &ctx, u32 n_docs);   // (... and queues the launches that finish them)
 
 // min pyramid over the LCP table and the annotation table: the streaming pass decides all but the widest
 // intervals and writes pyramid levels 1 and 2 on the way, the upper levels follow, then the listed wide ones
@@ -33,8 +34,9 @@ static void annotate(east_hip_index *h, Ctx &ctx, u32 *listed_total = nullptr)
         LAUNCH(ctx, pyramid_level_kernel, ceil_div_u32(pyr_padded(pyr.len[l]), BLOCK), pyr.ptr[l - 1], pyr.len[l],
                pyr_padded(pyr.len[l]), (u32 *)pyr.ptr[l]);
     if (l < pyr.levels) LAUNCH(ctx, pyramid_top_kernel, 1, pyr, l);
+    // (the block order: ctx.ann_whole_grid -- build_common's choice from the last build's count, a test's from the knob)
     LAUNCH(ctx, ann_wide_kernel, ceil_div_u32(n_tiles, ANN_WIDE_RUN) * ANN_WIDE_SLICES, pyr, n, n_tiles, (const u32 *)wide_list,
-           (const u32 *)wide_count, h->ann, listed_total);
+           (const u32 *)wide_count, h->ann, listed_total ? listed_total : ctx.ann_listed, (int)ctx.ann_whole_grid);
     ar.release(mark);
 }
 
@@ -195,13 +197,18 @@ static void build_impl(east_hip_index *h, Ctx &ctx, const u32 *d_sym, u32 n, u32
     h->build_docs = n_docs;
 
     // ---- host-side small tables ---------------------------------------------
-    std::vector<u32> off32(2 * (size_t)n_docs + 1);       // the offsets, then n_strings: the device block's layout
+    // the offsets, then n_strings: the device block's layout, written straight into the handle's pinned block (behind the
+    // words the flags come back into; build_common has made room): no staging copy on the host.  It is queued here, in
+    // front of the fill -- behind the first streaming kernel it is a dispatch of its own between two kernels, which gains
+    // nothing on the 64 MiB document and costs builds of a few hundred microseconds 1 % (measured)
+    u32 *const off32 = ctx.dry ? nullptr : h->pin + FLAG_WORDS;
+    const size_t off32_words = 2 * (size_t)n_docs + 1;
     u32 longest_doc = ctx.dry ? n : 0;                    // (sizing run: as if one document held everything)
     if (!ctx.dry) {
         for (u32 d = 0; d <= n_docs; d++) off32[d] = (u32)doc_offsets[d];
         for (u32 d = 0; d < n_docs; d++) longest_doc = std::max(longest_doc, off32[d + 1] - off32[d]);
         for (u32 d = 0; d < n_docs; d++) off32[(size_t)n_docs + 1 + d] = (u32)n_strings[d];
-        HIP_CHECK(hipMemcpyAsync(h->doc_off, off32.data(), off32.size() * 4, hipMemcpyHostToDevice, ctx.stream));
+        HIP_CHECK(hipMemcpyAsync(h->doc_off, off32, off32_words * 4, hipMemcpyHostToDevice, ctx.stream));
     }
 
     const u32 gn = ceil_div_u32(n, BLOCK);
@@ -233,6 +240,7 @@ static void build_impl(east_hip_index *h, Ctx &ctx, const u32 *d_sym, u32 n, u32
     ctx.zeroed_word = ctx.dry ? nullptr : flags + FLAG_PLACE_FAIL;
     ctx.spec_fail = flags + FLAG_PLACE_FAIL;
     ctx.kg_bad = ctx.dry ? nullptr : flags + FLAG_KG_BAD;
+    ctx.ann_listed = ctx.dry ? nullptr : flags + FLAG_ANN_LISTED;
     {
         // ---- alphabet, dense remap ---------------------------------------------
         const size_t mark = ar.mark();
@@ -288,8 +296,8 @@ static void build_impl(east_hip_index *h, Ctx &ctx, const u32 *d_sym, u32 n, u32
             if (ctx.spec) {
                 sigma_t = spec_sigma;                        // (checked on the device; found out at the end of the build)
             } else {
-                u32 hf[FLAG_WORDS];
-                HIP_CHECK(hipMemcpyAsync(hf, flags, sizeof(hf), hipMemcpyDeviceToHost, ctx.stream));
+                u32 *const hf = h->pin;                       // (the pinned words the flags come back into at the end as well)
+                HIP_CHECK(hipMemcpyAsync(hf, flags, FLAG_WORDS * sizeof(u32), hipMemcpyDeviceToHost, ctx.stream));
                 HIP_CHECK(sync_stream(ctx.stream));
                 if (hf[FLAG_STATUS] & STATUS_NO_TERMINATOR)
                     east_throw(EAST_HIP_ERR_DOMAIN, tagged ? "a document does not end in a (tagged) string terminator"
@@ -357,7 +365,7 @@ static void build_impl(east_hip_index *h, Ctx &ctx, const u32 *d_sym, u32 n, u32
     prepare_ht_code(h, ctx, n, sigma_t, m_total);
     if ((h->use_s8 || ctx.dry) && ctx.knobs.window_sort) {       // (the sizing run prices it with 64-bit keys)
         DocKey docs;
-        if (n_docs > 1) { docs.doc_off = h->doc_off; docs.n_docs = n_docs; docs.bits = doc_bits; docs.h_doc_off = ctx.dry ? nullptr : off32.data(); }
+        if (n_docs > 1) { docs.doc_off = h->doc_off; docs.n_docs = n_docs; docs.bits = doc_bits; docs.h_doc_off = off32; }
         // the score walk's k-gram tables are marked off the sorted keys on the way (KgMark): as many levels
         // as a table of at most twice a document's size (and 1 GiB in all) has room for
         KgMark km;
@@ -482,6 +490,10 @@ static void finish_capped_lcp(east_hip_index *h, Ctx &ctx, u32 *counts_out = nul
     LAUNCH(ctx, lcp_phi_anchors_kernel, gn, (const uint8_t *)anchor, (const u32 *)count, n, apos);
     LAUNCH(ctx, lcp_phi_fill_kernel, gn, (const uint8_t *)anchor, (const u32 *)count, (const u32 *)apos, (const u32 *)rank, n, h->lcp);
     ar.release(mark);
+    // (the second annotation of the build: the grouped order unless the knob says otherwise -- this table lists every rank
+    // or close to it.  Its count comes on top of the first one's in the same word: build_common reads the word again and
+    // takes the difference -- no fill of one word on a path that small repetitive builds take)
+    ctx.ann_whole_grid = ctx.knobs.ann_wide_order == 2;
     annotate(h, ctx);
 }
 
@@ -630,12 +642,31 @@ static void build_common(east_hip_index *h, const u32 *sym, bool sym_on_host, i6
     // The build is queued WITHOUT waiting for the device wherever the previous build on this handle says what
     // to expect (alphabet size, no large tie groups): one read-back at the end finds out whether it was
     // right.  If not -- or on a handle's first build -- the build runs with its read-backs in place.
-    u32 flags[FLAG_WORDS] = {0};
+    // The flags come back into the handle's pinned block (pageable memory would be staged: a copy and a blit with the
+    // device idle), and the build waits for an event right behind that copy, not for the stream: where keyphrases are
+    // resident, the k-gram tables the build marked are finished behind the event, while the host reads the flags and
+    // returns (kgram_finish_marked, score_host.h: 11 us of launches off the score call's critical path; the same 11 us
+    // stand in front of whatever comes next where no score call follows).  They read the index alone -- the caller may
+    // reuse its symbol buffer as soon as the call returns -- and count as done only once the flags say the build stood.
+    ensure_pin(h, FLAG_WORDS + 2 * (size_t)n_docs + 1);
+    u32 *const flags = h->pin;
+    std::fill_n(flags, FLAG_WORDS, 0u);
+    // (other n_docs: the keyphrases go, below.  Under the library's profiler every call's report lists the launches that
+    // call needed: the tables stay with the score call, and the build waits for the whole stream before it collects)
+    const bool eager = kn.eager_kgram && !h->prof.enabled && h->kp.n_kp > 0 && h->n_docs == (u32)n_docs;
+    bool kg_queued = false;
     auto run = [&](bool spec, bool spec_rounds) -> bool {
         ctx.spec = spec;
         ctx.spec_rounds = spec && spec_rounds;
         ctx.plan = spec ? h->plan : SortPlan();          // (a build that waits for the alphabet plans from its own sample)
         ctx.did.first = FirstPassPlan();
+        // ann_wide_kernel's block order: whole-grid where the build before listed no more ranks than slice 0 of the
+        // average run takes in its first stretch (BLOCK entries per ANN_WIDE_RUN tiles), else -- and without a count -- grouped
+        ctx.ann_whole_grid = kn.ann_wide_order == 2 ||
+                             (kn.ann_wide_order == 0 && h->ann_hint.valid &&
+                              (u64)h->ann_hint.listed * ANN_WIDE_RUN <= (u64)h->ann_hint.n_tiles * ANN_WHOLE_GRID_MAX);
+        h->ann_order_used = ctx.ann_whole_grid ? 2 : 1;
+        kg_queued = false;
         try {
             build_impl(h, ctx, sym, n, (u32)n_docs, doc_offsets, n_strings, h->hint.sigma, tagged);
         } catch (const SpecAbort &) {
@@ -647,8 +678,13 @@ static void build_common(east_hip_index *h, const u32 *sym, bool sym_on_host, i6
             return false;
         }
         HIP_CHECK(hipEventRecord(h->ev1, h->stream));
-        HIP_CHECK(hipMemcpyAsync(flags, h->code_map + TEXT_SYMBOLS, sizeof(flags), hipMemcpyDeviceToHost, h->stream));
-        HIP_CHECK(sync_stream(h->stream));
+        HIP_CHECK(hipMemcpyAsync(flags, h->code_map + TEXT_SYMBOLS, FLAG_WORDS * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipEventRecord(h->ev_flags, h->stream));
+        // (h->kg.marked is this attempt's: build_impl resets it before anything is marked, so a repeat never queues the
+        // marks of the attempt before; `eager` itself holds for both attempts -- keyphrases and n_docs do not change in between)
+        if (eager) kg_queued = kgram_finish_marked(h, ctx, (u32)n_docs);
+        // (the library's profiler reads its events behind the build: the whole stream then)
+        HIP_CHECK(h->prof.enabled ? sync_stream(h->stream) : sync_event(h->ev_flags));
         return true;
     };
     HIP_CHECK(hipEventRecord(h->ev0, h->stream));
@@ -670,15 +706,25 @@ static void build_common(east_hip_index *h, const u32 *sym, bool sym_on_host, i6
     if (status & STATUS_NO_TERMINATOR)
         east_throw(EAST_HIP_ERR_DOMAIN, "a document does not end in a string terminator (>= U+0A00)");
     if (flags[FLAG_CAPPED] && !(status & STATUS_N_STRINGS)) {
+        const u32 listed_first = flags[FLAG_ANN_LISTED];     // (the second annotation adds its count to the same word)
         finish_capped_lcp(h, ctx);
         HIP_CHECK(hipEventRecord(h->ev1, h->stream));
+        HIP_CHECK(hipMemcpyAsync(flags + FLAG_ANN_LISTED, h->code_map + TEXT_SYMBOLS + FLAG_ANN_LISTED, sizeof(u32), hipMemcpyDeviceToHost, h->stream));
         HIP_CHECK(hipStreamSynchronize(h->stream));
+        flags[FLAG_ANN_LISTED] -= listed_first;
     }
     if (status & STATUS_N_STRINGS)
         east_throw(EAST_HIP_ERR_DOMAIN, tagged ? "n_strings does not match the tagged terminators found in a document"
                                                : "n_strings does not match the terminators found in a document "
                                                  "(text symbols must be < U+0A00 unless the terminators are tagged)");
     if (flags[FLAG_KG_BAD]) h->kg.marked = false;    // (the score side then builds its k-gram tables itself)
+    // (the tables queued behind the flags count only now that the build stands: a wrong guess's were overwritten by the
+    // repeat's marks, incomplete marks are built over by the score side)
+    h->kg.built = kg_queued && h->kg.marked;
+    h->kg_queued = kg_queued ? (h->kg.marked ? 1 : 2) : 0;
+    h->ann_hint.valid = true;
+    h->ann_hint.listed = flags[FLAG_ANN_LISTED];
+    h->ann_hint.n_tiles = ceil_div_u32(n, ANN_TILE);
     h->hint.valid = !tagged || h->sigma_hi == 0;
     h->hint.sigma = h->sigma_t;
     h->hint.window = h->stats.window_sorted != 0;

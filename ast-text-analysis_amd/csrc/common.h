@@ -238,6 +238,12 @@ struct Knobs {
     int passages_route = 0;                                             // east_hip_debug_set_passages_route (passages.h: 0 = PAS_DEFAULT_ROUTE, 1 = the unit's text list, 2 = the text's unit list)
     i64 overlap_batch = 0;                                              // east_hip_debug_set_overlap_batch (overlap.h: 0 = OVL_SCRATCH_BYTES of partial tiles)
     int bm25_strip = 0;                                                 // east_hip_debug_set_bm25_strip (bm25.h: 0 = what the accumulators hold)
+    // east_hip_debug_set_eager_kgram: the marked k-gram tables are finished behind the build's flags read-back
+    // (EAST_HIP_NO_EAGER_KGRAM: off from the start -- A/B timing of that part alone)
+    bool eager_kgram = getenv("EAST_HIP_NO_EAGER_KGRAM") == nullptr;
+    // east_hip_debug_set_ann_wide_order: 0 = by the last build's count, 1 = grouped, 2 = whole-grid
+    // (EAST_HIP_ANN_WIDE_ORDER=0/1/2: the same from the start, A/B timing; any other value is 0, as the setter refuses it)
+    int ann_wide_order = env_int("EAST_HIP_ANN_WIDE_ORDER", 0) == 1 ? 1 : env_int("EAST_HIP_ANN_WIDE_ORDER", 0) == 2 ? 2 : 0;
     u32 plan_epoch = 1;                                                 // bumped by the knobs that change what a build allocates
 };
 static Knobs g_knobs;
@@ -292,6 +298,8 @@ struct Ctx {
     // Speculative build: the first level's first radix pass as the build before ran it (FirstPassPlan), and -- where the
     // remap pass counted that pass's histogram ahead -- the counts for the sort to take (radix_sort.h: RsFirstHist)
     const struct RsFirstHist *first_hist = nullptr;
+    bool ann_whole_grid = false;    // ann_wide_kernel's block order: slice-major over the whole grid (a short list, tables.h), else grouped
+    u32 *ann_listed = nullptr;      // a zeroed word that takes the number of ranks ann_wide_kernel decides (FLAG_ANN_LISTED; a test's word)
     u32 *kg_bad = nullptr;      // raised by the fused finish when the k-gram marks it writes are incomplete (a bucket handed to the rounds)
     // What the sample of the build's own text says (sample_prefix_kernel; a handle's first build and every build that
     // waits for the alphabet): of sample_n consecutive suffixes, sample_dup2[l] / sample_dup4[l] share their first
@@ -351,6 +359,25 @@ static inline hipError_t sync_stream(hipStream_t stream)
         (void)hipGetLastError();
     }
     return hipStreamSynchronize(stream);
+}
+// The same for one event: the build's flags read-back is waited for on an event recorded right behind the copy, so that
+// work queued behind it (the k-gram tables, build.h) runs while the host reads the flags and returns.
+static inline hipError_t sync_event(hipEvent_t event)
+{
+    if (g_spin_sync) {
+        bool waited = false;
+        for (int i = 0; i < 20000; i++) {
+            const hipError_t e = hipEventQuery(event);
+            if (e == hipSuccess) {
+                if (waited) (void)hipGetLastError();
+                return hipSuccess;
+            }
+            if (e != hipErrorNotReady) return e;
+            waited = true;
+        }
+        (void)hipGetLastError();
+    }
+    return hipEventSynchronize(event);
 }
 
 static inline u32 ceil_div_u32(u64 a, u64 b) { return (u32)((a + b - 1) / b); }

@@ -135,6 +135,7 @@ static void debug_annotate(int device, const u32 *lcp, i64 n64, const i64 *doc_o
     u32 *listed = sc.arena.alloc<u32>(1);
     HIP_CHECK(hipMemsetAsync(listed, 0, 4, sc.stream));
     debug_table_handle(sc, h, lcp, n, doc_off, n_docs, n_strings);
+    sc.ctx.ann_whole_grid = knobs_snapshot().ann_wide_order == 2;       // (east_hip_debug_set_ann_wide_order; no build before: grouped)
     annotate(&h, sc.ctx, listed);
     HIP_CHECK(hipMemcpyAsync(ann_out, h.ann, (size_t)n * 4, hipMemcpyDeviceToHost, sc.stream));
     HIP_CHECK(hipMemcpyAsync(listed_out, listed, 4, hipMemcpyDeviceToHost, sc.stream));
@@ -757,6 +758,22 @@ int east_hip_debug_set_speculation(int enabled)
     // 0: every build waits for the alphabet and the placement counts; 1: the default; 2: as 1, the first radix pass's
     // histogram counted by a launch of its own (no presence_remap_hist_kernel)
     knobs_update([&](Knobs &k) { k.speculate = enabled != 0; k.first_hist = enabled != 2 && getenv("EAST_HIP_NO_FIRST_HIST") == nullptr; });
+    return EAST_HIP_OK;
+}
+
+int east_hip_debug_set_eager_kgram(int enabled)
+{
+    // 1 (default): a build with resident keyphrases finishes the k-gram tables it marked behind its flags read-back; 0: the
+    // first score call does
+    knobs_update([&](Knobs &k) { k.eager_kgram = enabled != 0; });
+    return EAST_HIP_OK;
+}
+
+int east_hip_debug_set_ann_wide_order(int order)
+{
+    // ann_wide_kernel's block order: 0 by the count of the build before, 1 grouped, 2 slice-major over the whole grid
+    if (order < 0 || order > 2) return EAST_HIP_ERR_INVALID;
+    knobs_update([&](Knobs &k) { k.ann_wide_order = order; });
     return EAST_HIP_OK;
 }
 

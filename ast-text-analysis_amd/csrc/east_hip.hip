@@ -117,6 +117,8 @@ void east_hip_destroy(east_hip_handle_t h)
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
+    if (h->ev_flags) (void)hipEventDestroy(h->ev_flags);
+    if (h->pin) (void)hipHostFree(h->pin);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     if (cur >= 0 && cur != h->device) (void)hipSetDevice(cur);
     delete h;
@@ -230,7 +232,8 @@ int east_hip_score_resident(east_hip_handle_t h, int normalized, double *d_out)
         if (d_out && !direct)
             HIP_CHECK(hipMemcpyAsync(d_out, h->kp.table, (size_t)h->kp.n_kp * h->n_docs * 8, hipMemcpyDeviceToDevice,
                                      h->stream));
-        HIP_CHECK(hipStreamSynchronize(h->stream));
+        // (polled, as the build's read-backs are: a sleeping waiter comes back tens of microseconds after a walk this short)
+        HIP_CHECK(sync_stream(h->stream));
         HIP_CHECK(hipEventElapsedTime(&h->last_score_ms, h->ev0, h->ev1));
     });
 }
@@ -335,6 +338,9 @@ int east_hip_reset(east_hip_handle_t h)
         // an index -- the sizing cache, the upload ring with bytes_refused, the Unicode tables, the alphabet guess --, only
         // ever advances (map_epoch) or reports the last call (last_*_ms, narrow_upload)
         h->plan = SortPlan();
+        h->ann_hint = east_hip_index::AnnHint();
+        h->ann_order_used = 0;
+        h->kg_queued = 0;
         h->kp.forget();
         h->kg.forget();
         h->ht.forget();
@@ -361,16 +367,17 @@ void *east_hip_stream(east_hip_handle_t h) { return h ? (void *)h->stream : null
 int east_hip_build_info(east_hip_handle_t h, int64_t *out, int32_t cap)
 {
     if (!h || !out) return EAST_HIP_ERR_INVALID;
-    const int64_t v[28] = {h->n, h->n_docs, h->m_total, h->sigma_t, h->bits0, h->stats.levels,
+    const int64_t v[31] = {h->n, h->n_docs, h->m_total, h->sigma_t, h->bits0, h->stats.levels,
                            (int64_t)h->arena.cap, (int64_t)h->arena.high, h->stats.radix_passes,
                            h->stats.radix_elems, h->stats.radix_elem_bytes, h->stats.radix_passes_u32,
                            h->stats.radix_elems_u32, h->stats.radix_passes_u64, h->stats.radix_elems_u64,
                            h->stats.levels_resolved, h->stats.merge_elems, h->stats.refine_rounds,
                            h->stats.window_sorted, h->stats.lds_sorted, h->stats.fused_finish, h->stats.first_kept,
                            h->stats.first_n, h->stats.ht_keys, h->stats.seg_sort, h->narrow_upload,
-                           h->stats.persist_rounds, h->stats.first_hist_fused};
-    for (int i = 0; i < 28 && i < cap; i++) out[i] = v[i];
-    return 28;
+                           h->stats.persist_rounds, h->stats.first_hist_fused, h->ann_order_used, h->kg_queued,
+                           h->ann_hint.valid ? (int64_t)h->ann_hint.listed : -1};
+    for (int i = 0; i < 31 && i < cap; i++) out[i] = v[i];
+    return 31;
 }
 
 int east_hip_profile_enable(east_hip_handle_t h, int on)

@@ -43,6 +43,22 @@ struct east_hip_index {
     // next_plan).  east_hip_reset forgets it: a plan is worth following only on the kind of text it was made on
     SortPlan plan;
     u32 build_docs = 0;          // documents of the build in progress (h->n_docs is set when it has succeeded)
+    // ... and how many ranks its ann_wide_kernel decided, of how many tiles: the next build's block order for that kernel
+    // (build.h: ann_order -- a short list takes the whole-grid order).  Either order is correct for any table; a stale
+    // hint costs time only.  east_hip_reset forgets it
+    struct AnnHint {
+        bool valid = false;
+        u32 listed = 0, n_tiles = 0;
+    } ann_hint;
+    int ann_order_used = 0;      // the last build's order: 1 grouped, 2 whole-grid (east_hip_build_info [28])
+    int kg_queued = 0;           // the last build queued the marked k-gram tables behind its flags read-back: 1, and 2 where the
+                                 // flags then said the marks were incomplete (FLAG_KG_BAD: the work is discarded) ([29])
+    // The build's small transfers go through one pinned block the handle owns (pageable memory is staged by the runtime: a
+    // copy and a blit on the critical path): FLAG_WORDS words the flags come back into, behind them the doc_off /
+    // n_strings upload in the device block's layout.  It grows with n_docs and is freed with the handle
+    u32 *pin = nullptr;
+    size_t pin_words = 0;
+    hipEvent_t ev_flags = nullptr;       // recorded right behind the flags copy: what the build waits for
     // the order-preserving variable-length code of the last build that made one (ht_code.h): device tables (own
     // allocation: 256 x u32 enc, 4096 x u16 dec), valid for text with `sigma` text symbols
     struct HtCode {
@@ -143,6 +159,22 @@ static void use_device(east_hip_index *h) { use_device_ordinal(h->device); }
 static void restore_device()
 {
     if (g_saved_device >= 0) { (void)hipSetDevice(g_saved_device); g_saved_device = -1; }
+}
+
+// the handle's pinned block with room for `words` words (what it held is lost when it grows)
+static void ensure_pin(east_hip_index *h, size_t words)
+{
+    if (!h->ev_flags) HIP_CHECK(hipEventCreateWithFlags(&h->ev_flags, hipEventDisableTiming));
+    if (words <= h->pin_words) return;
+    HIP_CHECK(hipStreamSynchronize(h->stream));      // (a copy out of the old block may still be queued)
+    if (h->pin) (void)hipHostFree(h->pin);
+    h->pin = nullptr;
+    h->pin_words = 0;
+    void *p = nullptr;
+    const size_t grown = std::max(words + words / 2, (size_t)1024);
+    HIP_CHECK(hipHostMalloc(&p, grown * sizeof(u32), hipHostMallocDefault));
+    h->pin = (u32 *)p;
+    h->pin_words = grown;
 }
 
 // a launch context on the handle's stream, timed by its profiler (arena, stats: what the caller's launches need of them)

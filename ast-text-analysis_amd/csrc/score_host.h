@@ -108,32 +108,42 @@ static bool kgram_reserve(east_hip_index *h, u64 bins, u32 n_docs)
     return h->kg.buf.try_ensure(bytes, h->stream);
 }
 
-// k-gram bucket tables of the current index (score.h); k = 0 when the alphabet is too wide
-static void ensure_kgram(east_hip_index *h, Ctx &ctx)
+// The tables the build marked (h->kg.marked), finished: a function of the index alone -- the marks and the document
+// table, nothing of the caller's.  n_docs: the index's documents (a build in progress queues this behind its flags
+// read-back, build.h, before h->n_docs is set).  false: nothing was marked, nothing queued
+static bool kgram_finish_marked(east_hip_index *h, Ctx &ctx, u32 n_docs)
 {
-    if (h->kg.built) return;
     if (h->kg.marked && h->kg.pairs) {
         // the pair layout: the last level stays as the build marked it (+ its end entries), the small table above it is filled
         const u32 bins3 = h->kg.bins / h->kg.A;
-        LAUNCH(ctx, kgram_pairs_end_kernel, ceil_div_u32(h->n_docs, BLOCK), (const u32 *)h->doc_off, h->n_docs, h->kg.bins, h->kg.buf.as<u32>());
-        LAUNCH(ctx, kgram_fill_kernel, h->n_docs, (const u32 *)h->doc_off, bins3, h->kg.kg3);
+        LAUNCH(ctx, kgram_pairs_end_kernel, ceil_div_u32(n_docs, BLOCK), (const u32 *)h->doc_off, n_docs, h->kg.bins, h->kg.buf.as<u32>());
+        LAUNCH(ctx, kgram_fill_kernel, n_docs, (const u32 *)h->doc_off, bins3, h->kg.kg3);
         // (levels 1 .. k - 2 as tables of their own: A + 1, A^2 + 1, ... entries per document)
         h->kg.up_stride = 0;
         u32 len = h->kg.A;
         for (int l = 1; l < h->kg.k - 1; l++) { h->kg.up_stride += len + 1; len *= h->kg.A; }
         if (h->kg.up_stride && h->kg.up)
-            LAUNCH(ctx, kgram_upper_kernel, h->n_docs, (const u32 *)h->kg.kg3, bins3, h->kg.A, h->kg.k - 1, h->kg.up_stride, h->kg.up);
-        h->kg.built = true;
-        return;
+            LAUNCH(ctx, kgram_upper_kernel, n_docs, (const u32 *)h->kg.kg3, bins3, h->kg.A, h->kg.k - 1, h->kg.up_stride, h->kg.up);
+        return true;
     }
     if (h->kg.marked) {
         // the build left the bucket starts in the table: suffix minimum per document, in chunks
         const u32 bins = h->kg.bins, n_chunks = ceil_div_u32(bins, KGF_CHUNK);
-        u32 *cmin = h->kg.buf.as<u32>() + (size_t)(bins + 1) * h->n_docs, *csuf = cmin + (size_t)n_chunks * h->n_docs;
-        LAUNCH(ctx, kgram_chunk_min_kernel, dim3(n_chunks, h->n_docs), h->kg.buf.as<const u32>(), bins, n_chunks, cmin);
-        LAUNCH(ctx, kgram_chunk_suffix_kernel, h->n_docs, (const u32 *)cmin, (const u32 *)h->doc_off, n_chunks, csuf);
-        LAUNCH(ctx, kgram_chunk_fill_kernel, dim3(n_chunks, h->n_docs), (const u32 *)csuf, (const u32 *)h->doc_off, bins,
+        u32 *cmin = h->kg.buf.as<u32>() + (size_t)(bins + 1) * n_docs, *csuf = cmin + (size_t)n_chunks * n_docs;
+        LAUNCH(ctx, kgram_chunk_min_kernel, dim3(n_chunks, n_docs), h->kg.buf.as<const u32>(), bins, n_chunks, cmin);
+        LAUNCH(ctx, kgram_chunk_suffix_kernel, n_docs, (const u32 *)cmin, (const u32 *)h->doc_off, n_chunks, csuf);
+        LAUNCH(ctx, kgram_chunk_fill_kernel, dim3(n_chunks, n_docs), (const u32 *)csuf, (const u32 *)h->doc_off, bins,
                n_chunks, h->kg.buf.as<u32>());
+        return true;
+    }
+    return false;
+}
+
+// k-gram bucket tables of the current index (score.h); k = 0 when the alphabet is too wide
+static void ensure_kgram(east_hip_index *h, Ctx &ctx)
+{
+    if (h->kg.built) return;
+    if (kgram_finish_marked(h, ctx, h->n_docs)) {
         h->kg.built = true;
         return;
     }

@@ -885,9 +885,11 @@ __global__ __launch_bounds__(BLOCK) void ann_stream_kernel(const u32 *__restrict
 #define ANN_WIDE_RUN 64                  // tiles per run: one wavefront scans their counts
 #define ANN_WIDE_SLICES 8                // workgroups per run
 #define ANN_WIDE_GROUP 8u                // runs per group of the block order = the XCDs workgroups are dealt over (not the slices)
+#define ANN_WHOLE_GRID_MAX BLOCK         // listed ranks per run up to which the whole-grid order is taken: slice 0's first stretch holds the average run's list
 __global__ __launch_bounds__(BLOCK) void ann_wide_kernel(Pyramid P, u32 n, u32 n_tiles, const u32 *__restrict__ wide_list,
                                                          const u32 *__restrict__ wide_count, u32 *__restrict__ ann,
-                                                         u32 *__restrict__ listed_total)      // != nullptr (tests): + the ranks that came through here
+                                                         u32 *__restrict__ listed_total,      // != nullptr: + the ranks that came through here (one add per run)
+                                                         int whole_grid)
 {
     __shared__ u32 off[ANN_WIDE_RUN + 1];
     const u32 *lcp = P.ptr[0];
@@ -895,11 +897,20 @@ __global__ __launch_bounds__(BLOCK) void ann_wide_kernel(Pyramid P, u32 n, u32 n
     // slice as blockIdx.x % 8 all of those sat on ONE XCD.  Slice-major inside groups of ANN_WIDE_GROUP runs (64 consecutive workgroups;
     // the last group: what is left): the slice-0 workgroups are 8 consecutive ones of every 64, one per XCD, and the eight
     // slices of a run still run side by side (slice-major over the whole grid starts them far apart: measured + 8 % where
-    // every rank is listed)
+    // every rank is listed).  whole_grid: that other order -- all slice-0 workgroups first, which is the
+    // faster one where the list is short (the build before says so, build.h: ann_order).  Both orders
+    // visit the same (run, slice) pairs.
     const u32 n_runs = gridDim.x / ANN_WIDE_SLICES;
-    const u32 group = blockIdx.x / (ANN_WIDE_GROUP * ANN_WIDE_SLICES), j = blockIdx.x % (ANN_WIDE_GROUP * ANN_WIDE_SLICES);
-    const u32 group_runs = min(ANN_WIDE_GROUP, n_runs - group * ANN_WIDE_GROUP);
-    const u32 tile0 = (group * ANN_WIDE_GROUP + j % group_runs) * ANN_WIDE_RUN, slice = j / group_runs;
+    u32 tile0, slice;
+    if (whole_grid) {
+        tile0 = (blockIdx.x % n_runs) * ANN_WIDE_RUN;
+        slice = blockIdx.x / n_runs;
+    } else {
+        const u32 group = blockIdx.x / (ANN_WIDE_GROUP * ANN_WIDE_SLICES), j = blockIdx.x % (ANN_WIDE_GROUP * ANN_WIDE_SLICES);
+        const u32 group_runs = min(ANN_WIDE_GROUP, n_runs - group * ANN_WIDE_GROUP);
+        tile0 = (group * ANN_WIDE_GROUP + j % group_runs) * ANN_WIDE_RUN;
+        slice = j / group_runs;
+    }
     if (threadIdx.x < ANN_WIDE_RUN) {
         const u32 t = tile0 + threadIdx.x;
         u32 inc = t < n_tiles ? wide_count[t] : 0u;

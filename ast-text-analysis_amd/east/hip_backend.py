@@ -74,6 +74,8 @@ SIGNATURES = {
     "east_hip_debug_set_persist": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "east_hip_debug_set_segmented_sort": (ctypes.c_int, [ctypes.c_int]),
     "east_hip_debug_set_speculation": (ctypes.c_int, [ctypes.c_int]),
+    "east_hip_debug_set_eager_kgram": (ctypes.c_int, [ctypes.c_int]),
+    "east_hip_debug_set_ann_wide_order": (ctypes.c_int, [ctypes.c_int]),
     "east_hip_debug_first_pass_hist": (ctypes.c_int, [ctypes.c_int, _c_u32p, ctypes.c_int64, _c_u32p, ctypes.c_int,
                                                       ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int,
                                                       ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint8), _c_u32p, _c_u32p,
@@ -216,7 +218,7 @@ BUILD_INFO_FIELDS = ("n_total", "n_docs", "n_strings", "sigma_text", "bits_level
                      "radix_passes_u32", "radix_elements_u32", "radix_passes_u64", "radix_elements_u64",
                      "dc3_levels_resolved", "merge_elements", "refine_rounds", "window_sorted", "lds_sorted",
                      "fused_finish", "first_kept", "first_n", "ht_keys", "seg_sort", "narrow_upload", "persist_rounds",
-                     "first_hist_fused")
+                     "first_hist_fused", "ann_wide_order", "kgram_queued", "ann_listed")
 COSINE_INFO_FIELDS = ("built", "n_docs", "kept_tokens", "words", "terms", "classes", "postings", "hash_attempts", "build_us",
                       "score_us")
 BM25_INFO_FIELDS = ("N", "avgdl", "k1", "b", "weights_computed")        # east_hip_bm25_info (k1, b: NaN while no weights are cached)

@@ -105,6 +105,10 @@ int east_hip_reset(east_hip_handle_t h);
  * and to BYTES (a quarter of the bytes) while every text symbol lies below 0xFF, as in ASCII word text: a
  * symbol that does not fit starts the upload over with 16-bit words, for that call and the handle's later ones;
  * tagged streams and small inputs take the plain 4-byte copy.
+ * When east_hip_build_device returns, every read of the caller's symbol buffer has completed: the caller may reuse or
+ * overwrite it at once.  The handle's stream may still hold work then -- the launches that finish the score walk's
+ * k-gram tables, queued behind the build's flags read-back when keyphrases are resident (east_hip_build_info [29]);
+ * they read the index alone, and every later call on the handle is ordered behind them (same stream, or it drains it).
  */
 /*
  * Which encoding east_hip_build / east_hip_build_device read on this handle (default: the reference's).
@@ -967,7 +971,12 @@ void *east_hip_stream(east_hip_handle_t h);
  * encoding, 4 Mi symbols or more), 2 when they went up as bytes (text below 0xFF),
  * [26] refinement rounds run inside one persistent launch (csrc/persist_rounds.h; they count in [17] too),
  * [27] 1 when the first radix pass's histogram was counted by the remap pass of a speculative build
- * (csrc/radix_sort.h: presence_remap_hist_kernel) and the sort took it.
+ * (csrc/radix_sort.h: presence_remap_hist_kernel) and the sort took it,
+ * [28] the block order of the annotation pass's ann_wide_kernel: 1 grouped, 2 slice-major over the whole grid (chosen
+ * from the count of the build before, east_hip_debug_set_ann_wide_order), [29] 1 when the build queued the score
+ * walk's k-gram tables behind its flags read-back (keyphrases resident, marks written; east_hip_debug_set_eager_kgram),
+ * 2 when it did and the flags then said the marks were incomplete: that work is discarded, the score side builds the tables,
+ * [30] the ranks ann_wide_kernel decided in the last build (what the next build's order is chosen from; -1: none yet).
  */
 int east_hip_build_info(east_hip_handle_t h, int64_t *out, int32_t cap);
 
@@ -1051,6 +1060,16 @@ int east_hip_debug_set_lds_rounds(int enabled);   /* 0 / 1 (default: the in-LDS 
  * of what the build before found, and checked by the one read-back at their end; 2 = as 1, but
  * the first radix pass's histogram is counted by a launch of its own, not by the remap pass. */
 int east_hip_debug_set_speculation(int enabled);
+/* Test knob: 1 (default) = a build on a handle with resident keyphrases (east_hip_set_keyphrases, same number of
+ * documents) queues the launches that finish the k-gram tables it marked behind its flags read-back, so that they run
+ * while the host reads the flags and returns; the handle counts them as done only once the flags say the build stood.
+ * 0 = the first score call behind the build queues them, as every other kind of k-gram table.  Same tables either way. */
+int east_hip_debug_set_eager_kgram(int enabled);
+/* Test knob: the block order of ann_wide_kernel (csrc/tables.h) -- 0 (default) = from the number of ranks the build
+ * before on the handle listed: slice-major over the whole grid where the list is short, else (and on a first build,
+ * after east_hip_reset, in the second annotation of a capped build) grouped; 1 = grouped; 2 = whole-grid, also in
+ * east_hip_debug_annotate.  Both orders give the same table.  Other values: EAST_HIP_ERR_INVALID. */
+int east_hip_debug_set_ann_wide_order(int order);
 /* Kernel-level test of the remap pass that counts the first radix histogram (csrc/radix_sort.h:
  * presence_remap_hist_kernel): n host symbols go through code_map (2 560 words: code point -> byte) (a) in that kernel and
  * (b) through remap_bytes_kernel + presence_kernel + radix_hist_kernel on window keys of key_bytes (4 / 8) x 8 bits --
